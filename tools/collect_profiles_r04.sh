@@ -20,11 +20,11 @@ import json,sys
 l=[x for x in open('$1') if x.startswith('{')]
 j=json.loads(l[-1]); j['evidence_commit']='$COMMIT'
 print(json.dumps(j))" > $2; }
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/b1.out 2> $O/b1.err && line $O/b1.out $O/r04_bench_driver_form.json
-python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/b2.out 2> $O/b2.err && line $O/b2.out $O/r04_bench_driver_form_rerun.json
-python bench.py --steps 100 --warmup 5 --no-cpu-baseline > $O/b3.out 2> $O/b3.err && line $O/b3.out $O/r04_bench_100_steps.json
-python bench.py --steps 100 --warmup 5 --no-cpu-baseline --schedule pipeline > $O/b4.out 2> $O/b4.err && line $O/b4.out $O/r04_bench_two_stage.json
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --in-flight 1 --schedule pipeline > $O/b5.out 2> $O/b5.err && line $O/b5.out $O/r04_bench_in_flight_1.json
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/b1.out 2> $O/b1.err && line $O/b1.out $O/r04_bench_driver_form.json
+python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $O/b2.out 2> $O/b2.err && line $O/b2.out $O/r04_bench_driver_form_rerun.json
+python bench.py --steps 100 --warmup 5 --full --no-cpu-baseline > $O/b3.out 2> $O/b3.err && line $O/b3.out $O/r04_bench_100_steps.json
+python bench.py --steps 100 --warmup 5 --full --no-cpu-baseline --schedule pipeline > $O/b4.out 2> $O/b4.err && line $O/b4.out $O/r04_bench_two_stage.json
+python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --in-flight 1 --schedule pipeline > $O/b5.out 2> $O/b5.err && line $O/b5.out $O/r04_bench_in_flight_1.json
 echo "bench done $SECONDS s"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d $O/kt_default --output-format csv -- python3 $R/bench.py --no-cpu-baseline --timed-only --steps 100 > $O/kt_default.log 2>&1

@@ -34,7 +34,7 @@ bench)
   for rnd in 1 2; do
     for tc in 0 32; do
       for st in "--steps 20 --warmup 5" "--steps 100 --warmup 5"; do
-        timeout -k 10 300 python bench.py --gpus 1 $st --no-cpu-baseline --tail-cus $tc 2>&1 | tail -1 | python -c "
+        timeout -k 10 300 python bench.py --gpus 1 $st --full --no-cpu-baseline --tail-cus $tc 2>&1 | tail -1 | python -c "
 import sys, json
 j = json.loads(sys.stdin.readline())
 r = j['roofline']
