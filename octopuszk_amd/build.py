@@ -18,6 +18,11 @@ LIB = os.path.join(HERE, "libozk_hip.so")
 HIP_SOURCES = ["msm_var.hip", "msm_var_g2.hip", "msm_fixed.hip", "fft.hip", "host_ctx.hip"]
 HEADERS = ["consts_gen.h", "mad_chain_gen.h", "fp29.cuh", "fq2.cuh", "ec.cuh", "quad.cuh", "curve.cuh", "msm_var.cuh", "msm_var_driver.cuh", "glv.cuh", "ozk_common.h", "host_ctx.h", "pin_cache.h",
            os.path.join("..", "..", "include", "ozk.h")]
+# hipcc flags of every device translation unit (after the hipcc path); the test harness tests/native/devcheck.hip
+# is compiled with the same list, so that it runs the arithmetic exactly as the library compiles it
+HIPCC_FLAGS = ["-std=c++17", "-O3", "--offload-arch=gfx950", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result",
+               "-Wno-pass-failed"]
+
 JNI_LIBS = {
     "libAlgebraMSMVariableBaseMSM.so": "jni_var_msm.c",
     "libAlgebraMSMFixedBaseMSM.so": "jni_fixed_msm.c",
@@ -49,8 +54,7 @@ def build(force=False, verbose=True):
         # one object per translation unit, compiled in parallel, then one device link
         objdir = os.path.join(HERE, "_obj")
         os.makedirs(objdir, exist_ok=True)
-        common = [hipcc(), "-std=c++17", "-O3", "--offload-arch=gfx950", "-fPIC", "-fno-gpu-rdc",
-                  "-Wno-unused-result", "-Wno-pass-failed"] + defs
+        common = [hipcc()] + HIPCC_FLAGS + defs
         procs, objs = [], []
         for src in srcs:
             obj = os.path.join(objdir, os.path.basename(src) + ".o")

@@ -413,11 +413,14 @@ OZK_HD auto sub(const Fe<P, B1>& a, const Fe<P, B2>& b) {
   return r;
 }
 
+// bound of K p - b, K = B2 / 16 + 1: b = 0 gives K p itself, so K p + p / 16 (every formula that sizes a product with
+// a negated factor uses this)
+constexpr int neg_bound(int B2) { return 16 * (B2 / 16 + 1) + 1; }
 template <class P, int B2>
 OZK_HD auto neg(const Fe<P, B2>& b) {
   constexpr int K = B2 / 16 + 1;
   static_assert(K <= FE_MAXK, "sub bias table too small");
-  Fe<P, 16 * K> r;
+  Fe<P, neg_bound(B2)> r;
 #pragma unroll
   for (int i = 0; i < 9; i++) r.l[i] = P::BIAS[K][i] - b.l[i];
   fe_carry(r);
@@ -428,7 +431,7 @@ OZK_HD auto neg(const Fe<P, B2>& b) {
 // subtraction of the two reduced products (the Y3 of every addition / doubling formula in ec.cuh)
 template <class P, int B1, int B2, int B3, int B4>
 OZK_HD auto mulsub(const Fe<P, B1>& a, const Fe<P, B2>& b, const Fe<P, B3>& c, const Fe<P, B4>& d) {
-  if constexpr ((long long)B1 * B2 + 16LL * (B3 / 16 + 1) * B4 <= (long long)MONT_SLACK * 256) {
+  if constexpr ((long long)B1 * B2 + (long long)neg_bound(B3) * B4 <= (long long)MONT_SLACK * 256) {
     return mul2(a, b, neg(c), d);
   } else {
     return sub(mul(a, b), mul(c, d));
@@ -469,7 +472,7 @@ template <class P, int B2>
 OZK_HD auto neg_nc(const Fe<P, B2>& b) {
   constexpr int K = B2 / 16 + 1;
   static_assert(K <= FE_MAXK, "sub bias table too small");
-  FeL<P, 16 * K, 4> r;
+  FeL<P, neg_bound(B2), 4> r;
 #pragma unroll
   for (int i = 0; i < 9; i++) r.l[i] = P::BIAS[K][i] - b.l[i];
   return r;

@@ -58,7 +58,7 @@ OZK_HD auto sub(const Fe2<B1>& a, const Fe2<B2>& b) {
 }
 template <int B2>
 OZK_HD auto neg(const Fe2<B2>& b) {
-  Fe2<16 * (B2 / 16 + 1)> r;
+  Fe2<neg_bound(B2)> r;
   r.c0 = neg(b.c0);
   r.c1 = neg(b.c1);
   return r;
@@ -92,7 +92,7 @@ OZK_HD bool is_zero(const Fe2<B>& a) {  // Fp2.java:78-80
 
 // bounds for which a0 b0 + (-a1) b1 (the larger of the two dual products) meets the Montgomery precondition
 constexpr bool lazy_ok(int B1, int B2) {
-  return (long long)B1 * B2 + 16LL * (B1 / 16 + 1) * B2 <= (long long)MONT_SLACK * 256;
+  return (long long)B1 * B2 + (long long)neg_bound(B1) * B2 <= (long long)MONT_SLACK * 256;
 }
 
 // (a0 + a1 u)(b0 + b1 u) = (a0 b0 - a1 b1) + (a0 b1 + a1 b0) u.  Same values as Fp2.java:59-72 (which
@@ -113,7 +113,7 @@ OZK_HD Fe2<32> mul(const Fe2<B1>& a_in, const Fe2<B2>& b_in) {
 //   c0 = a0 b0 + (-a1) b1 + (-c0) d0 + c1 d1,   c1 = a0 b1 + a1 b0 + (-c0) d1 + (-c1) d0
 template <int B1, int B2, int B3, int B4>
 OZK_HD auto mulsub(const Fe2<B1>& a, const Fe2<B2>& b, const Fe2<B3>& c, const Fe2<B4>& d) {
-  constexpr long long N1 = 16LL * (B1 / 16 + 1), N3 = 16LL * (B3 / 16 + 1);
+  constexpr long long N1 = neg_bound(B1), N3 = neg_bound(B3);
   constexpr long long BB0 = (long long)B1 * B2 + N1 * B2 + N3 * B4 + (long long)B3 * B4;
   constexpr long long BB1 = 2LL * B1 * B2 + 2 * N3 * B4;
   constexpr long long BB = BB0 > BB1 ? BB0 : BB1;
@@ -154,7 +154,7 @@ OZK_HD Fe2<32> sqr_lz(const Fe2<B1>& a) {
 }
 template <int B1, int B2, int B3, int B4>
 OZK_HD auto mulsub_lz(const Fe2<B1>& a, const Fe2<B2>& b, const Fe2<B3>& c, const Fe2<B4>& d) {
-  constexpr long long N1 = 16LL * (B1 / 16 + 1), N3 = 16LL * (B3 / 16 + 1);
+  constexpr long long N1 = neg_bound(B1), N3 = neg_bound(B3);
   constexpr long long BB0 = (long long)B1 * B2 + N1 * B2 + N3 * B4 + (long long)B3 * B4;
   constexpr long long BB1 = 2LL * B1 * B2 + 2 * N3 * B4;
   constexpr long long BB = BB0 > BB1 ? BB0 : BB1;
@@ -362,7 +362,7 @@ __device__ __forceinline__ auto sub(const Fe2L<B1>& a, const Fe2L<B2>& b) {
 }
 template <int B2>
 __device__ __forceinline__ auto neg(const Fe2L<B2>& b) {
-  Fe2L<16 * (B2 / 16 + 1)> r;
+  Fe2L<neg_bound(B2)> r;
   r.c0 = neg(b.c0);
   r.c1 = neg(b.c1);
   return r;

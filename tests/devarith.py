@@ -1,0 +1,320 @@
+"""Driver, input builders and exact-integer expectations for tests/native/devcheck.hip (the device arithmetic
+conformance harness).  Shared by test_device_arith_cpu.py (builds the harness, checks the builders) and
+test_device_arith_gpu.py (runs it).
+
+Every operand is a raw 9-limb record (limbs 0..7 of 29 bits, limb 8 the rest) of an integer that respects its
+type's invariant: value < B p / 16 and limbs 0..7 < LU 2^28 (LU = 2: normalised).  The values are built so that
+they reach those limits: 0, 1, p - 1, every k p and k p +- 1 below the bound, the largest value below it, the
+"all limbs maximal" vector and random values over the range, a quarter of them in its top percent."""
+import ctypes
+import os
+import random
+import subprocess
+
+import numpy as np
+
+from oracle import bn254 as o
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+SRC = os.path.join(HERE, "native", "devcheck.hip")
+LIB = os.path.join(HERE, "native", "_devcheck.so")
+CSRC = os.path.join(ROOT, "octopuszk_amd", "csrc")
+DEPS = [SRC] + [os.path.join(CSRC, f) for f in ("fp29.cuh", "fq2.cuh", "ec.cuh", "quad.cuh", "curve.cuh",
+                                                 "consts_gen.h", "mad_chain_gen.h")]
+
+W = 29
+MASK = (1 << W) - 1
+RBITS = 261                       # Montgomery radix 2^261
+FIELDS = {0: o.Q, 1: o.R, 2: o.Q}  # devcheck field index -> modulus (2: Fq2 and the group laws over Fq)
+
+
+def build(force=False):
+    """cross-compile the harness for gfx950 with the library's flags; rebuilt only when missing or stale"""
+    from octopuszk_amd import build as b
+    if force or b._newer(LIB, DEPS):
+        subprocess.check_call([b.hipcc()] + b.HIPCC_FLAGS + ["-shared", "-o", LIB, SRC])
+    return LIB
+
+
+_lib = None
+
+
+def load():
+    global _lib
+    if _lib is None:
+        # torch first: device pointers from torch are valid only in the HIP runtime torch loaded, and a second
+        # runtime pulled in by this library would leave torch without a device (octopuszk_amd/lib.py load())
+        import torch  # noqa: F401
+        _lib = ctypes.CDLL(build())
+        _lib.dc_run.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                ctypes.c_void_p]
+        _lib.dc_info.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
+    return _lib
+
+
+class OpInfo:
+    def __init__(self, field, idx, name, v):
+        self.field, self.idx, self.name = field, idx, name
+        self.group, nin, nout, self.kp = v[0], v[1], v[2], v[3]
+        self.ins = list(zip(v[4:4 + nin], v[4 + nin:4 + 2 * nin]))             # (B, LU) per operand element
+        self.outs = list(zip(v[4 + 2 * nin:4 + 2 * nin + nout], v[4 + 2 * nin + nout:4 + 2 * nin + 2 * nout]))
+
+    @property
+    def id(self):
+        return "%s:%s(%s)" % ("fq fr ext".split()[self.field], self.name,
+                              ",".join("%d" % b if lu == 2 else "%d/L%d" % (b, lu) for b, lu in self.ins))
+
+
+def ops(lib, field):
+    out = []
+    for i in range(lib.dc_count(field)):
+        name = ctypes.create_string_buffer(64)
+        v = (ctypes.c_int * 128)()
+        assert lib.dc_info(field, i, name, v) == 0
+        out.append(OpInfo(field, i, name.value.decode(), list(v)))
+    return out
+
+
+# ---------------------------------------------------------------- values <-> limbs
+def to_limbs(v):
+    return [(v >> (W * i)) & MASK for i in range(8)] + [v >> (8 * W)]
+
+
+def from_limbs(l):
+    return sum(int(x) << (W * i) for i, x in enumerate(l))
+
+
+def vmax(B, p):
+    """largest integer below B p / 16"""
+    return (B * p - 1) // 16
+
+
+def maximal(B, LU, p):
+    """limbs 0..7 at their limit LU 2^28 - 1, limb 8 the largest the value bound allows (None if none does)"""
+    lo = [LU * (1 << 28) - 1] * 8
+    base = from_limbs(lo + [0])
+    top = (vmax(B, p) - base) >> (8 * W)
+    return lo + [top] if top >= 0 else None
+
+
+def spread(v, LU, rng):
+    """the same integer with limbs 0..7 pushed up to < LU 2^28 by borrowing from the limb above"""
+    l = to_limbs(v)
+    cap = LU * (1 << 28) - 1
+    for i in range(7, -1, -1):
+        t = min((cap - l[i]) >> W, l[i + 1])
+        if t > 0:
+            t = rng.choice((t, rng.randrange(t + 1)))
+            l[i] += t << W
+            l[i + 1] -= t
+    return l
+
+
+def check_limbs(l, B, LU, p):
+    """the type invariant of one record"""
+    return all(0 <= x < LU << 28 for x in l[:8]) and 0 <= l[8] < 1 << 32 and 16 * from_limbs(l) < B * p
+
+
+def edge_values(B, p):
+    """integers below B p / 16 where arithmetic on bounded values goes wrong"""
+    hi = vmax(B, p)
+    vals = {0, 1, 2, p - 1, hi, hi - 1, (hi + 1) // 2}
+    for k in range(0, (B + 15) // 16 + 1):
+        for d in (-1, 0, 1):
+            vals.add(k * p + d)
+    # where reduce_q's quotient estimate steps: multiples of (p >> 232) + 1 in the top limb
+    D = ((p >> 232) + 1) << 232
+    for k in range(1, hi // D + 1):
+        for d in (-1, 0, 1):
+            vals.add(k * D + d)
+    return sorted(v for v in vals if 0 <= v <= hi)
+
+
+def element_records(B, LU, p, n, rng):
+    """n limb records for one operand of bound (B, LU): the edge values (normalised and, for loose types, spread),
+    the maximal vector, then random values (a quarter of them in the top percent of the range)"""
+    hi = vmax(B, p)
+    recs = [to_limbs(v) for v in edge_values(B, p)]
+    m = maximal(B, LU, p)
+    if m is not None:
+        recs.append(m)
+    if LU > 2:
+        recs += [spread(v, LU, rng) for v in edge_values(B, p)]
+    recs = recs[:n]
+    while len(recs) < n:
+        r = rng.random()
+        v = hi - rng.randrange(hi // 100) if r < 0.25 else rng.randrange(hi + 1)
+        recs.append(spread(v, LU, rng) if LU > 2 and rng.random() < 0.75 else to_limbs(v))
+    return recs
+
+
+def wire_records(p, n, rng):
+    """8-word wire values anywhere below 2^256 (limb record: words 0..7, word 8 unused)"""
+    top = (1 << 256) - 1
+    vals = [0, 1, p - 1, p, p + 1, top, top - 1, 1 << 255, (1 << 232) - 1, 1 << 232]
+    vals += [k * p + d for k in range(2, top // p + 1) for d in (-1, 0, 1) if k * p + d <= top]
+    vals = vals[:n]
+    while len(vals) < n:
+        vals.append(top - rng.randrange(1 << 240) if rng.random() < 0.25 else rng.randrange(top + 1))
+    return [[(v >> (32 * i)) & 0xffffffff for i in range(8)] + [0] for v in vals]
+
+
+def operand_sets(op, n, seed):
+    """per operand element a list of n records; the first operands' edge values are crossed with each other"""
+    rng = random.Random(seed)
+    p = FIELDS[op.field]
+    cols = []
+    for k, (B, LU) in enumerate(op.ins):
+        if B == -2:
+            cols.append(wire_records(p, n, rng))
+        elif B == 0:
+            cols.append([[rng.randrange(2)] + [0] * 8 for _ in range(n)])
+        else:
+            cols.append(element_records(B, LU, p, n, rng))
+    nedge = [len(edge_values(B, p)) + 1 + (len(edge_values(B, p)) if LU > 2 else 0) if B > 0 else 0
+             for B, LU in op.ins]
+    if len(cols) >= 2 and nedge[0] and nedge[1]:
+        # every operand's edge values first (shorter lists repeat), then edges x edges of the first two operands
+        # as far as half of n allows, then the random values
+        E = max(nedge)
+        head = [[c[i % ne] for i in range(E)] if ne else c[:E] for c, ne in zip(cols, nedge)]
+        cross = [(a, b) for a in cols[0][:nedge[0]] for b in cols[1][:nedge[1]]]
+        rng.shuffle(cross)
+        cross = cross[:max(0, n // 2 - E)]
+        mid = [[a for a, _ in cross], [b for _, b in cross]] + [[rng.choice(c) for _ in cross] for c in cols[2:]]
+        cols = [(h + m + c[ne:])[:n] for h, m, c, ne in zip(head, mid, cols, nedge)]
+    if all(B > 0 for B, _ in op.ins):
+        # the corners first: every operand at its maximal vector (the largest column sums) or at the largest value
+        # below its bound (the largest output value), the first two operands in all four combinations
+        M = [maximal(B, LU, p) or to_limbs(vmax(B, p)) for B, LU in op.ins]
+        H = [to_limbs(vmax(B, p)) for B, _ in op.ins]
+        corners = []
+        for a, b in ((M, M), (H, H), (M, H), (H, M)):
+            corners.append([a[0]] + ([b[1]] if len(op.ins) > 1 else []) + a[2:])
+        cols = [[row[k] for row in corners] + c[:n - len(corners)] for k, c in enumerate(cols)]
+    return cols
+
+
+# ---------------------------------------------------------------- expected values (exact integers)
+def field_expect(op, vals):
+    """(expected value, exact?) of a one-element field operation on operand values vals"""
+    p = FIELDS[op.field]
+    ri = pow(1 << RBITS, -1, p)
+    n, v = op.name, vals
+    if n == "mul":
+        return v[0] * v[1] * ri % p, False
+    if n == "sqr":
+        return v[0] * v[0] * ri % p, False
+    if n == "mul2":
+        return (v[0] * v[1] + v[2] * v[3]) * ri % p, False
+    if n == "mul4":
+        return (v[0] * v[1] + v[2] * v[3] + v[4] * v[5] + v[6] * v[7]) * ri % p, False
+    if n == "mulsub":
+        return (v[0] * v[1] - v[2] * v[3]) * ri % p, False
+    if n == "add":
+        return (v[0] + v[1]) % p, False
+    if n == "dbl":
+        return 2 * v[0] % p, False
+    if n == "sub":
+        return (v[0] - v[1]) % p, False
+    if n == "neg":
+        return -v[0] % p, False
+    if n == "sub_sub2":
+        return (v[0] - v[1] - 2 * v[2]) % p, False
+    if n in ("reduce_to", "normalise"):
+        return v[0] % p, False
+    if n == "csub":
+        K = op.kp
+        return (v[0] - K * p if v[0] >= K * p else v[0]), True
+    if n == "reduce_q":                            # the documented quotient floor(top / (ptop + 1)), exactly
+        return v[0] - ((v[0] >> 232) // ((p >> 232) + 1)) * p, True
+    if n in ("canonical", "canonical_q"):
+        return v[0] % p, True
+    if n in ("unpack", "pack"):
+        return v[0], True
+    if n == "inv":
+        return (pow(v[0], -1, p) * pow(1 << RBITS, 2, p) % p if v[0] % p else 0), False
+    if n == "is_zero":
+        return int(v[0] % p == 0), True
+    if n == "eq":
+        return int((v[0] - v[1]) % p == 0), True
+    raise KeyError(n)
+
+
+# ---- Fq2 and curve points in the Montgomery domain (the device holds x R mod p, plus multiples of p)
+Q = o.Q
+RQ = (1 << RBITS) % Q
+RQI = pow(1 << RBITS, -1, Q)
+
+
+def fq2_expect(name, v):
+    """v: operand elements as integers (two per Fq2 value); result components"""
+    F = o.Fq2Ops
+
+    def el(k):
+        return (v[2 * k] % Q, v[2 * k + 1] % Q)
+
+    def mont(a):            # the product of two Montgomery values carries one R^-1
+        return (a[0] * RQI % Q, a[1] * RQI % Q)
+    if name == "fq2_mul":
+        return mont(F.mul(el(0), el(1)))
+    if name == "fq2_sqr":
+        return mont(F.sqr(el(0)))
+    if name == "fq2_mulsub":
+        return mont(F.sub(F.mul(el(0), el(1)), F.mul(el(2), el(3))))
+    if name == "fq2_sub_sub2":
+        a, b, c = el(0), el(1), el(2)
+        return F.sub(F.sub(a, b), F.add(c, c))
+    raise KeyError(name)
+
+
+def demont(x, F):
+    return x * RQI % Q if F is o.FqOps else (x[0] * RQI % Q, x[1] * RQI % Q)
+
+
+def tomont(x, F):
+    return x * RQ % Q if F is o.FqOps else (x[0] * RQ % Q, x[1] * RQ % Q)
+
+
+def affine_of_jac(C, X, Y, Z):
+    """Montgomery Jacobian coordinates (any representatives) -> oracle affine point, None for infinity"""
+    F = C.F
+    X, Y, Z = (demont(c, F) for c in (X, Y, Z))
+    if F.is_zero(Z):
+        return None
+    zi = F.inv(Z)
+    return (F.mul(X, F.sqr(zi)), F.mul(Y, F.mul(F.sqr(zi), zi)))
+
+
+def affine_of_xyzz(C, X, Y, ZZ, ZZZ):
+    F = C.F
+    X, Y, ZZ, ZZZ = (demont(c, F) for c in (X, Y, ZZ, ZZZ))
+    if F.is_zero(ZZ):
+        return None
+    return (F.mul(X, F.inv(ZZ)), F.mul(Y, F.inv(ZZZ)))
+
+
+def oracle_affine(C, P):
+    if C.is_zero(P):
+        return None
+    a = C.to_affine(P)
+    return (a[0], a[1])
+
+
+def random_points(C, n, seed):
+    """n distinct affine points (oracle Jacobian form, Z = 1)"""
+    rng = random.Random(seed)
+    P = C.mul(C.one, rng.randrange(1, o.R))
+    step = C.mul(C.one, rng.randrange(1, o.R))
+    out = []
+    for _ in range(n):
+        a = C.to_affine(P)
+        out.append(a)
+        P = C.add(P, step)
+    return out
+
+
+def comps(x, F):
+    """coordinate -> list of base-field integers"""
+    return [x] if F is o.FqOps else [x[0], x[1]]

@@ -130,6 +130,45 @@ def test_fft_every_pass_plan_gives_the_oracle_bytes(knobs, monkeypatch):
         L.ozk_tuning_reload()
 
 
+@pytest.mark.parametrize("knobs", [{}, {"OZK_FFT_PLAN": "0"}, {"OZK_FFT_KS": "9,4,7"}],
+                         ids=lambda k: "_".join("%s%s" % (a[8:], b) for a, b in k.items()) or "default")
+@pytest.mark.parametrize("kind", ["all_r-1", "alternating_0_r-1", "all_2^253-1", "one_r-1"])
+def test_fft_extreme_inputs_give_the_oracle_bytes(kind, knobs, monkeypatch):
+    """Inputs that drive the uncarried butterfly values (fft.hip fft_stage2: LDS values < 1.5 x 2^30, b1 < 2.5 x 2^30)
+    toward their maxima on every element, which uniform data reaches only by chance; same sizes and plans as
+    above, byte for byte against the C oracle"""
+    import ctypes
+    import numpy as np
+    from octopuszk_amd import lib
+    L = lib.load()
+    for k, v in knobs.items():
+        monkeypatch.setenv(k, v)
+    L.ozk_tuning_reload()
+    top = np.frombuffer((o.R - 1).to_bytes(32, "little"), dtype=np.uint8)
+    big = np.frombuffer(((1 << 253) - 1).to_bytes(32, "little"), dtype=np.uint8)
+    try:
+        for logn in (10, 12, 14, 15, 17, 18, 19, 20):
+            n = 1 << logn
+            a = np.zeros((n, 32), dtype=np.uint8)
+            if kind == "all_r-1":
+                a[:] = top
+            elif kind == "alternating_0_r-1":
+                a[1::2] = top
+            elif kind == "all_2^253-1":
+                a[:] = big
+            else:
+                a[(n * 5) // 7] = top
+            w = o.to_le32(o.fr_root_of_unity(n))
+            out = ctypes.create_string_buffer(64 * n)
+            lib.check(L.ozk_fft_host(a.ctypes.data_as(ctypes.c_void_p), n, ctypes.cast(ctypes.c_char_p(w), ctypes.c_void_p), 0,
+                                     ctypes.cast(out, ctypes.c_void_p)))
+            assert out.raw == coracle.fft_fr(a.tobytes(), n, w), (kind, knobs, logn)
+    finally:
+        for k in knobs:
+            monkeypatch.delenv(k)
+        L.ozk_tuning_reload()
+
+
 def test_fft_plan_cache_many_domains_from_many_threads():
     """the plan cache handed out raw pointers into four process-wide slots.  Nine domains (more than the
     four plans a device keeps) cycled from six host threads at once — every call must return what the same call
