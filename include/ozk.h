@@ -213,6 +213,12 @@ int ozk_var_msm_tail_dev(int32_t n, int32_t type, void* d_tail, size_t tail_byte
  * reduce(GroupT::add) of VariableBaseMSM.java:777-783 after the RCCL all-gather. */
 int ozk_points_sum_dev(const void* d_points, int32_t k, int32_t type, void* d_out, void* stream);
 
+/* The sharded Groth16 proof from the gathered per-rank partials (zksnark.ShardedProver): d_records holds `world`
+ * records of 768 B, A_r (G1, 192) | B_r (G2, 384) | C_r (G1, 192) in wire-out format, in rank order; d_proof receives
+ * A | B | C (768 B), each part the normalised sum over the ranks (infinity as (0, 1, 0)) — the bytes three
+ * ozk_points_sum_dev calls would write.  One launch, the three sums on their own waves.  world < 1: OZK_E_INVALID. */
+int ozk_groth16_combine_dev(const void* d_records, int32_t world, void* d_proof, void* stream);
+
 /* Measurement hooks (bench.py): timing of the dominant kernel (the level-1 bucket accumulation,
  * k_segreduce<.., true>) per launch.  ozk_prof_enable(2): the kernel's own waves stamp the device's constant-rate
  * clock (first wave start -> last wave end), which leaves the schedule untouched; ozk_prof_enable(1): HIP start /

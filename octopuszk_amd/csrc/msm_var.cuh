@@ -1431,7 +1431,7 @@ __global__ void __launch_bounds__(256) k_bucket_combine(SliceBuckets t, int K, u
 // affine-normalise and emit the reference's return layout: per Fq value 64 B LE, upper
 // 32 B zero (VariableBaseMSM.cu:1655-1659); infinity -> (0, 1, 0) (BNG1.java:163-172).
 template <class CV>
-__device__ void write_normalised(const Jac<CV>& r, u32* out) {
+__device__ __forceinline__ void write_normalised_inline(const Jac<CV>& r, u32* out) {
   using EA = typename CV::EA;
   using ET = ElemTraits<EA>;
   constexpr int OW = 2 * ET::WORDS;  // wire-out words per coordinate
@@ -1446,6 +1446,11 @@ __device__ void write_normalised(const Jac<CV>& r, u32* out) {
     ET::to_wire_out(EA(reduce_to<17>(mul(r.Y, mul(zi2, zi)))), out + OW);
     ET::to_wire_out(EA(el_one(r.X)), out + 2 * OW);
   }
+}
+// (the out-of-line form the existing kernels call; k_groth16_combine inlines the body so that it needs no call stack)
+template <class CV>
+__device__ void write_normalised(const Jac<CV>& r, u32* out) {
+  write_normalised_inline<CV>(r, out);
 }
 
 // A_w holds S_w (one element per window after the last wsum level, with 2^g * 0 * R = 0).
@@ -1535,6 +1540,45 @@ __global__ void __launch_bounds__(64) k_points_sum(const u32* __restrict__ pts, 
     r = jac_add(r, q);
   }
   write_normalised<CV>(r, out);
+}
+
+// one lane: the sum of k AFFINE-NORMALISED points in wire-out format ((x, y, 1), or (0, 1, 0) for infinity),
+// `stride_words` apart, by mixed additions (the Z of the inputs is 1: fewer products and fewer live registers
+// than jac_add, which the G2 instance needs to stay out of scratch), normalised to `out`
+template <class CV>
+__device__ __forceinline__ void affine_sum_lane(const u32* pts, int k, int stride_words, u32* out) {
+  using EA = typename CV::EA;
+  using ET = ElemTraits<EA>;
+  constexpr int OW = 2 * ET::WORDS;
+  Jac<CV> r = jac_infinity<CV>();
+  for (int i = 0; i < k; i++) {
+    const u32* p = pts + (size_t)i * stride_words;
+    if (is_zero(ET::from_wire_out(p + 2 * OW))) continue;   // infinity
+    Aff<EA> q;
+    q.x = ET::from_wire_out(p);
+    q.y = ET::from_wire_out(p + OW);
+    r = jac_madd(r, q);
+  }
+  write_normalised_inline<CV>(r, out);
+}
+
+// The sharded Groth16 proof from the `world` gathered per-rank records A_r (G1, 192 B) | B_r (G2, 384 B) |
+// C_r (G1, 192 B) in wire-out format: three independent sums, one per workgroup, so the G2 sum (the longest:
+// Fq2 additions and an Fq2 inversion) and the two G1 sums run side by side on their own waves.  Each sum is
+// serial over the records: world is small (one record per GPU) and the normalising inversion costs more than the
+// world - 1 additions.  Output: A | B | C, 768 B, the layout of the input records.
+template <class C1, class C2>
+__global__ void __launch_bounds__(64) k_groth16_combine(const u32* __restrict__ rec, int world, u32* __restrict__ proof) {
+  constexpr int REC_WORDS = 768 / 4, B_OFF = 192 / 4, C_OFF = 576 / 4;
+  rec += opaque_zero();
+  const int part = blockIdx.x;   // 0: A, 1: B, 2: C
+  if (threadIdx.x != 0) return;
+  if (part == 1) {
+    affine_sum_lane<C2>(rec + B_OFF, world, REC_WORDS, proof + B_OFF);
+  } else {
+    const int off = part == 0 ? 0 : C_OFF;
+    affine_sum_lane<C1>(rec + off, world, REC_WORDS, proof + off);
+  }
 }
 
 // ------------------------------------------------------------------ synthetic bases

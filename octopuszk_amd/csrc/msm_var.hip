@@ -729,6 +729,19 @@ int ozk_points_sum_dev(const void* d_points, int32_t k, int32_t type, void* d_ou
   return points_sum_strided(d_points, k, type, type == OZK_G1 ? 192 : 384, d_out, (hipStream_t)stream);
 }
 
+int ozk_groth16_combine_dev(const void* d_records, int32_t world, void* d_proof, void* stream) {
+  hip_clear_stale();   // (ozk_common.h: a stale error of the calling thread is not this call's)
+  if (!d_records || !d_proof || world < 1) return fail(OZK_E_INVALID, "bad argument");
+#if defined(OZK_WITH_G2)
+  hipLaunchKernelGGL((k_groth16_combine<G1Cfg, G2Cfg>), dim3(3), dim3(64), 0, (hipStream_t)stream,
+                     (const u32*)d_records, (int)world, (u32*)d_proof);
+  OZK_HIP(hipGetLastError());
+  return OZK_OK;
+#else
+  return fail(OZK_E_INVALID, "G2 not built");
+#endif
+}
+
 int ozk_gen_bases_dev(uint64_t seed, int32_t n, int32_t type, void* d_out_wire, void* stream) {
   hip_clear_stale();   // (ozk_common.h: a stale error of the calling thread is not this call's)
   if (!d_out_wire || n <= 0) return fail(OZK_E_INVALID, "bad argument");

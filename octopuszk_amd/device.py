@@ -323,6 +323,20 @@ def points_sum(d_points, k, type_=1):
     return out
 
 
+def groth16_combine(d_records, world):
+    """The sharded Groth16 proof (zksnark.ShardedProver) from `world` gathered 768-byte partials A_r | B_r | C_r in
+    one launch (ozk_groth16_combine_dev) -> zksnark.Proof of wire-out bytes.  Synchronises the current stream."""
+    from .zksnark import Proof
+    L = _lib.load()
+    if d_records.numel() != world * 768:
+        raise ValueError("%d bytes are not %d records of 768" % (d_records.numel(), world))
+    d_records = d_records.contiguous()
+    out = torch.zeros(768, dtype=torch.uint8, device=d_records.device)
+    _lib.check(L.ozk_groth16_combine_dev(_ptr(d_records), world, _ptr(out), _stream()))
+    raw = bytes(out.cpu().numpy())
+    return Proof(raw[:192], raw[192:576], raw[576:])
+
+
 SPLITMIX_MASK = (1 << 64) - 1
 
 

@@ -9,8 +9,12 @@ partials with the HIP point-sum kernel.  RCCL has no elliptic-curve reduction op
 the "all-reduce" is all-gather + local sum; the message is < 4 KiB, i.e. latency-bound, and
 there is no other data-path collective.
 """
+import time
+
 import torch
 import torch.distributed as dist
+
+from .device import groth16_combine
 
 
 def shard_range(n: int, rank: int, world: int):
@@ -26,6 +30,15 @@ def all_gather_partials(partial: torch.Tensor, group=None) -> torch.Tensor:
     out = torch.empty(world * partial.numel(), dtype=torch.uint8, device=partial.device)
     dist.all_gather_into_tensor(out, partial.contiguous(), group=group)
     return out
+
+
+def all_gather_partials_host(partial: torch.Tensor, group=None) -> torch.Tensor:
+    """all_gather_partials through host memory, for gloo (ranks sharing one device: RCCL refuses two ranks on a
+    device) -> the gathered records back on the partial's device."""
+    world = dist.get_world_size(group)
+    out = [torch.empty(partial.numel(), dtype=torch.uint8) for _ in range(world)]
+    dist.all_gather(out, partial.cpu().contiguous(), group=group)
+    return torch.cat(out).to(partial.device)
 
 
 def distributed_var_msm(local_partial_fn, sum_fn, type_: int = 1, group=None, always_collective=False) -> torch.Tensor:
@@ -71,3 +84,33 @@ def gpu_var_double_msm(ws_g1, ws_g2, d_bases_g1, d_bases_g2, d_scalars, group=No
         return torch.cat([ws_g1.run(d_bases_g1, d_scalars).view(-1), ws_g2.run(d_bases_g2, d_scalars).view(-1)])
 
     return distributed_var_double_msm(local, dev.points_sum, group)
+
+
+def distributed_prove(prover, primary, auxiliary, seed, group=None, gather=all_gather_partials,
+                      combine=groth16_combine, timing=None, full_bytes=None):
+    """DistributedProver.prove (DistributedProver.java:89-146) over zksnark.ShardedProver ranks: rank 0's seed is
+    broadcast (every rank derives the same r and s from it), every rank builds its 768-byte partial
+    (prover.prove_partial), ONE all-gather of the partials, then combine(gathered, world) -> zksnark.Proof (on the
+    GPU: device.groth16_combine, one launch).  Without a process group, or in a world of one, the single record is
+    combined.  Tests inject host stand-ins for gather and combine.  `timing` (optional dict) receives
+    prover.prove_partial's stage times and the wall times of the exchange and of the combine; `full_bytes`: the
+    assignment already marshalled (zksnark.assignment_bytes), as SerialProver.prove takes it."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    if prover.world != world or (world > 1 and prover.rank != dist.get_rank(group)):
+        raise ValueError("prover is rank %d of %d, the process group rank %d of %d"
+                         % (prover.rank, prover.world, dist.get_rank(group) if world > 1 else 0, world))
+    if world > 1:
+        box = [seed]
+        dist.broadcast_object_list(box, group=group, group_src=0)
+        seed = box[0]
+    rec = prover.prove_partial(primary, auxiliary, seed, timing=timing, full_bytes=full_bytes)
+    t0 = time.perf_counter()
+    gathered = gather(rec, group) if world > 1 else rec
+    if timing is not None and gathered.is_cuda:
+        torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    proof = combine(gathered, world)
+    t2 = time.perf_counter()
+    if timing is not None:
+        timing.update({"exchange_ms": (t1 - t0) * 1e3, "combine_ms": (t2 - t1) * 1e3})
+    return proof

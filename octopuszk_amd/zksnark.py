@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .distributed import shard_range
 from .fft import FR, FR_MULT_GEN, root_of_unity
 from .fixed_base_msm import G1_WINDOW_TABLE, G2_WINDOW_TABLE, get_window_size
 
@@ -871,5 +872,202 @@ class SerialProver:
 
     def coefficients_h(self):
         """coefficientsH of the last prove() (m + 1 ints), for checks."""
+        raw = bytes(self.d_h.cpu().numpy())
+        return [int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(self.m + 1)]
+
+
+# ---------------------------------------------------------------------------- sharded prover
+RECORD_BYTES = 768   # a rank's partial: A_r (G1, 192) | B_r (G2, 384) | C_r (G1, 192), wire-out
+
+
+def shard_plan(nv: int, m: int, nw: int, rank: int, world: int):
+    """The slices [lo, hi) rank `rank` of `world` owns of the five MSMs of a proof, as SerialProver lays them out:
+    A, B1 and B2 over query A / query B ++ [alpha or beta, delta] (nv + 2 pairs), L over deltaABC (nw), H over
+    query H (m + 1)."""
+    ab = shard_range(nv + 2, rank, world)
+    return {"A": ab, "B1": ab, "B2": ab, "L": shard_range(nw, rank, world), "H": shard_range(m + 1, rank, world)}
+
+
+def c_share_scalars(r: int, s: int, rank: int):
+    """The scalars of a rank's 3-term MSM over [A_r, B1_r, deltaG1]: s A_r + r B1_r, and the -rs delta of
+    SerialProver.java:114 on rank 0 only, so that the ranks' shares sum to SerialProver's."""
+    return [s, r, (FR - r * s % FR) % FR if rank == 0 else 0]
+
+
+def _rows(parts, lo, hi, row_bytes):
+    """rows [lo, hi) of the concatenation of `parts` (uint8 tensors of row_bytes-byte rows), without building the
+    whole concatenation"""
+    out, base = [], 0
+    for t in parts:
+        n = t.numel() // row_bytes
+        a, b = max(lo - base, 0), min(hi - base, n)
+        if a < b:
+            out.append(t[a * row_bytes:b * row_bytes])
+        base += n
+    return torch.cat(out)
+
+
+def _prepared_bytes(n, type_):
+    return int(_lib.load().ozk_var_msm_prepared_bytes(n, type_))
+
+
+class ShardedProver:
+    """Rank `rank` of a Groth16 prover sharded over `world` GPUs (DistributedProver.java:89-146 with its
+    distributedMSM / distributedDoubleMSM): the prover's scalars are linear in the key, so each rank finishes its
+    share of every proof element over its slices of the key (shard_plan) before any exchange, and sends one
+    768-byte record; the proof is the sum of the records (distributed.distributed_prove, device.groth16_combine).
+    Only this rank's slices are prepared (key_bytes: this rank's prepared-key bytes against SerialProver's).
+    The witness map runs on every rank (a replica: DESIGN.md section 7)."""
+
+    def __init__(self, pk: ProvingKey, rank: int, world: int):
+        L = _lib.load()
+        r1cs = pk.r1cs
+        self.rank, self.world = rank, world
+        self.ni, self.nv = r1cs.num_inputs, r1cs.num_variables
+        self.nw = self.nv - self.ni
+        self.m = lowest_power_of_two(r1cs.num_constraints + self.ni)
+        nv, nw, m = self.nv, self.nw, self.m
+        assert pk.query_h.numel() == (m + 1) * 96 and pk.query_a.numel() == nv * 96
+        if not 0 <= rank < world:
+            raise ValueError("rank %d outside a world of %d" % (rank, world))
+        if world > min(nv + 2, nw, m + 1):
+            raise ValueError("a world of %d leaves a rank an empty slice (slice lengths nv + 2 = %d, nw = %d, m + 1 = %d)"
+                             % (world, nv + 2, nw, m + 1))
+        self.plan = plan = shard_plan(nv, m, nw, rank, world)
+        self.n = {k: hi - lo for k, (lo, hi) in plan.items()}
+
+        def prep(parts, key, row_bytes, type_):
+            lo, hi = plan[key]
+            nb = _prepared_bytes(hi - lo, type_)
+            out = torch.empty(nb, dtype=torch.uint8, device="cuda")
+            _lib.check(L.ozk_var_msm_prepare_dev(_ptr(_rows(parts, lo, hi, row_bytes)), hi - lo, type_, _ptr(out), nb,
+                                                 _stream()))
+            torch.cuda.current_stream().synchronize()   # the concatenated slice dies here
+            return out
+
+        self.qa = prep((pk.query_a, pk.alpha_g1, pk.delta_g1), "A", 96, 1)
+        self.qb1 = prep((pk.query_b_g1, pk.beta_g1, pk.delta_g1), "B1", 96, 1)
+        self.qb2 = prep((pk.query_b_g2, pk.beta_g2, pk.delta_g2), "B2", 192, 2)
+        self.dabc = prep((pk.delta_abc_g1,), "L", 96, 1)
+        self.qh = prep((pk.query_h,), "H", 96, 1)
+        self.delta_g1 = pk.delta_g1.clone()
+        self.key_bytes = {
+            "rank": sum(int(t.numel()) for t in (self.qa, self.qb1, self.qb2, self.dabc, self.qh)),
+            "serial": (2 * _prepared_bytes(nv + 2, 1) + _prepared_bytes(nv + 2, 2) + _prepared_bytes(nw, 1)
+                       + _prepared_bytes(m + 1, 1))}
+        n_ab, n_l, n_h = self.n["A"], self.n["L"], self.n["H"]
+        # the streams and the pipeline of SerialProver, sized to this rank's slices
+        three = os.environ.get("OZK_PROVER_PIPE3", "1") == "1"
+        ts = int(os.environ.get("OZK_PROVER_TAIL_STREAMS", "1"))
+        sizes = [n_ab, n_h, n_l]
+        self.pipe = _G1Pipeline3(sizes, tail_streams=ts) if three else _G1Pipeline(sizes)
+        self.g2_ws_bytes = int(L.ozk_var_msm_head_workspace_bytes(n_ab, 2))
+        self.g2_ws = torch.empty(self.g2_ws_bytes, dtype=torch.uint8, device="cuda")
+        self.g2_tail_bytes = int(L.ozk_var_msm_tail_bytes(n_ab, 2))
+        self.g2_tail = torch.empty(self.g2_tail_bytes, dtype=torch.uint8, device="cuda")
+        self.s_g2 = torch.cuda.Stream()
+        self.s_fin = torch.cuda.Stream(priority=-1)
+        self.fin_ws_bytes = int(L.ozk_var_msm_workspace_bytes(3, 1))
+        self.fin_ws = torch.empty(self.fin_ws_bytes, dtype=torch.uint8, device="cuda")
+        self.q_ws_bytes = int(L.ozk_qap_witness_workspace_bytes(m))
+        self.q_ws = torch.empty(self.q_ws_bytes, dtype=torch.uint8, device="cuda")
+        self.d_h = torch.empty((m + 1) * 32, dtype=torch.uint8, device="cuda")
+        self.o1 = torch.zeros(4, 192, dtype=torch.uint8, device="cuda")   # B1_r, L_r, H_r, C's 3-term share
+        self.r1cs_dev = R1CSDevice(r1cs)
+        self.omega = ctypes.create_string_buffer(root_of_unity(m).to_bytes(32, "little"), 32)
+        self.g = ctypes.create_string_buffer(FR_MULT_GEN.to_bytes(32, "little"), 32)
+        torch.cuda.synchronize()
+
+    def close(self):
+        self.pipe.close()
+
+    def prove_partial(self, primary, auxiliary, seed: int = SEED, timing=None, full_bytes=None) -> torch.Tensor:
+        """This rank's 768-byte record A_r | B_r | C_r (uint8 tensor in HBM, complete on return) with
+        C_r = L_r + H_r + s A_r + r B1_r (- rs deltaG1 on rank 0).  `timing` (optional dict) receives the stage
+        times of the device work from its start: witness map done, L and H MSMs done, record done."""
+        L = _lib.load()
+        ni, m, nv = self.ni, self.m, self.nv
+        (lo, hi), (llo, lhi), (hlo, hhi) = self.plan["A"], self.plan["L"], self.plan["H"]
+        n_ab, n_l, n_h = hi - lo, lhi - llo, hhi - hlo
+        t0 = time.perf_counter()
+        if full_bytes is None:
+            full_bytes = assignment_bytes(list(primary) + list(auxiliary))
+        assert full_bytes.size == nv * 32
+        r = fr_random(seed)                                      # SerialProver.java:58-59
+        s = fr_random(seed)
+        d_full = torch.from_numpy(full_bytes).cuda()
+        tails = _dev_bytes(_le32([1, r, 1, s] + c_share_scalars(r, s, self.rank)))
+        d_sc_r = torch.cat((d_full, tails[:64]))[32 * lo:32 * hi]        # (z ++ [1, r]) over this rank's slice
+        d_sc_s = torch.cat((d_full, tails[64:128]))[32 * lo:32 * hi]     # (z ++ [1, s])
+        d_aux = d_full[32 * (ni + llo):32 * (ni + lhi)]
+        d_fin_sc = tails[128:]
+        rec = torch.zeros(RECORD_BYTES, dtype=torch.uint8, device="cuda")
+        main = torch.cuda.current_stream()
+        ev = (lambda: torch.cuda.Event(enable_timing=True)) if timing is not None else None
+        if ev:
+            t_start = ev()
+            t_start.record(main)
+        ready = torch.cuda.Event()
+        ready.record(main)
+        o1 = self.o1
+        # B_r in G2 first, on its own stream (SerialProver.prove)
+        self.s_g2.wait_event(ready)
+        with torch.cuda.stream(self.s_g2):
+            _lib.check(L.ozk_var_msm_head_prepared_dev(_ptr(self.qb2), _ptr(d_sc_s), n_ab, 2, _ptr(self.g2_ws),
+                                                       self.g2_ws_bytes, _ptr(self.g2_tail), self.g2_tail_bytes, _stream(),
+                                                       None))
+            _lib.check(L.ozk_var_msm_tail_mode_dev(n_ab, 2, _ptr(self.g2_tail), self.g2_tail_bytes, _ptr(rec[192:576]),
+                                                   _stream(), None, 1))
+            g2_done = torch.cuda.Event()
+            g2_done.record(self.s_g2)
+        # the witness map, whole, on the priority stream: coefficientsH of every rank are the same
+        self.s_fin.wait_event(ready)
+        with torch.cuda.stream(self.s_fin):
+            d_ev = self.r1cs_dev.evaluate(d_full)
+            _lib.check(L.ozk_qap_witness_dev(_ptr(d_ev[0]), _ptr(d_ev[1]), _ptr(d_ev[2]), m, ctypes.cast(self.omega, ctypes.c_void_p),
+                                             ctypes.cast(self.g, ctypes.c_void_p), _ptr(self.d_h), _ptr(self.q_ws),
+                                             self.q_ws_bytes, _stream()))
+            h_ready = torch.cuda.Event()
+            h_ready.record(self.s_fin)
+            if ev:
+                t_map = ev()
+                t_map.record(self.s_fin)
+        p = self.pipe
+        ev_a = p.submit(self.qa, d_sc_r, n_ab, rec[:192])
+        ev_b = p.submit(self.qb1, d_sc_s, n_ab, o1[0])
+        self.s_fin.wait_event(ev_a)
+        self.s_fin.wait_event(ev_b)
+        ev_l = p.submit(self.dabc, d_aux, n_l, o1[1])
+        main.wait_event(h_ready)
+        ev_h = p.submit(self.qh, self.d_h[32 * hlo:32 * hhi], n_h, o1[2], last=True)
+        with torch.cuda.stream(self.s_fin):
+            fin_bases = torch.cat((wire_out_to_in(rec[:192], 1), wire_out_to_in(o1[0], 1), self.delta_g1))
+            _lib.check(L.ozk_var_msm_dev(_ptr(fin_bases), _ptr(d_fin_sc), 3, 1, _ptr(o1[3]), _ptr(self.fin_ws),
+                                         self.fin_ws_bytes, _stream()))
+            fin_done = torch.cuda.Event()
+            fin_done.record(self.s_fin)
+        main.wait_event(ev_l)
+        main.wait_event(ev_h)
+        if ev:
+            t_msm = ev()
+            t_msm.record(main)
+        main.wait_event(fin_done)
+        # C_r = L_r + H_r + (s A_r + r B1_r [- rs delta])
+        _lib.check(L.ozk_points_sum_dev(_ptr(o1[1:4]), 3, 1, _ptr(rec[576:]), int(main.cuda_stream)))
+        main.wait_event(g2_done)
+        if ev:
+            t_end = ev()
+            t_end.record(main)
+        torch.cuda.synchronize()
+        self._keep = (d_full, tails, d_sc_r, d_sc_s, fin_bases, d_ev)
+        if timing is not None:
+            timing.update({"witness_map_done_ms": t_start.elapsed_time(t_map),
+                           "lh_msm_done_ms": t_start.elapsed_time(t_msm),
+                           "record_done_ms": t_start.elapsed_time(t_end),
+                           "partial_wall_ms": (time.perf_counter() - t0) * 1e3})
+        return rec
+
+    def coefficients_h(self):
+        """coefficientsH of the last prove_partial() (m + 1 ints), for checks."""
         raw = bytes(self.d_h.cpu().numpy())
         return [int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(self.m + 1)]
