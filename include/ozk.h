@@ -363,6 +363,33 @@ int ozk_qap_witness_dev(const void* d_A, const void* d_B, const void* d_C, int32
                         const uint8_t* g_host32, void* d_H, void* d_workspace, size_t workspace_bytes,
                         void* stream);
 
+/* The BN254a optimal-ate pairing and the Groth16 verifier (BNPairing.java, zkSNARK/Verifier.java:24-59), one pairing
+ * per lane.  No JNI native: the reference's verifier is Java.
+ *
+ * Formats.  Pairing inputs are wire-in points (G1 96 B, G2 192 B, any Z); they are normalised as toAffineCoordinates
+ * does, a point at infinity (Z = 0) becoming (0, 1, 0) (BNG1.java:163-172, BNG2.java:168-177), and the Java's
+ * arithmetic then runs on those coordinates: P at infinity gives the Java's value; Q at infinity makes the Miller
+ * value zero, where the Java throws, and gives 384 zero bytes.  GT values are 384 B: twelve 32-byte little-endian canonical Fq values in the Java's nesting order
+ * c0.c0.c0, c0.c0.c1, c0.c1.c0, c0.c1.c1, c0.c2.c0, c0.c2.c1, c1.c0.c0, ..., c1.c2.c1
+ * (Fq12 = Fq6[w]/(w^2 - v), Fq6 = Fq2[v]/(v^3 - (9 + u)), Fq2 = Fq[u]/(u^2 + 1)).
+ *
+ *   ozk_pairing_g2_prepared_bytes  bytes of the line coefficients of n G2 points (102 triples of Fq2, ~22 KB each)
+ *   ozk_pairing_g2_prepare_dev     precomputeG2 of n wire-in G2 points into d_prep (opaque layout)
+ *   ozk_reduced_pairing_dev        d_gt[i] = reducedPairing(P_i, Q_i) for n pairs; d_q_or_prep holds n wire-in G2
+ *                                  points (prepared = 0) or n prepared points (prepared = 1)
+ *   ozk_groth16_verify_dev         k proofs: d_proofs k x 768 B records A | B | C in wire-out format (the layout of
+ *                                  ozk_groth16_combine_dev), d_abc k x 192 B wire-out evaluationABC points,
+ *                                  d_alpha_beta one GT value, d_gamma_prep / d_delta_prep one prepared point each;
+ *                                  d_ok[j] = 1 when Verifier.verify would return true, else 0 (also when a Miller
+ *                                  value is zero, where the Java throws instead of returning)
+ * n or k <= 0: OZK_E_INVALID.  Asynchronous on `stream`. */
+size_t ozk_pairing_g2_prepared_bytes(int32_t n);
+int ozk_pairing_g2_prepare_dev(const void* d_q, int32_t n, void* d_prep, size_t prep_bytes, void* stream);
+int ozk_reduced_pairing_dev(const void* d_p, const void* d_q_or_prep, int32_t prepared, int32_t n, void* d_gt,
+                            void* stream);
+int ozk_groth16_verify_dev(const void* d_alpha_beta, const void* d_gamma_prep, const void* d_delta_prep,
+                           const void* d_proofs, const void* d_abc, int32_t k, int32_t* d_ok, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,10 @@ _SIGS = {
     "ozk_qap_witness_host": (ctypes.c_int, [vp, vp, vp, i32, vp, vp, i32, vp]),
     "ozk_qap_witness_workspace_bytes": (sz, [i32]),
     "ozk_qap_witness_dev": (ctypes.c_int, [vp, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
+    "ozk_pairing_g2_prepared_bytes": (sz, [i32]),
+    "ozk_pairing_g2_prepare_dev": (ctypes.c_int, [vp, i32, vp, sz, vp]),
+    "ozk_reduced_pairing_dev": (ctypes.c_int, [vp, vp, i32, i32, vp, vp]),
+    "ozk_groth16_verify_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, i32, vp, vp]),
 }
 
 

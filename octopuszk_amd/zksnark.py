@@ -1071,3 +1071,67 @@ class ShardedProver:
         """coefficientsH of the last prove_partial() (m + 1 ints), for checks."""
         raw = bytes(self.d_h.cpu().numpy())
         return [int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(self.m + 1)]
+
+
+# ---------------------------------------------------------------------------- verification (pairing.py)
+class VerificationKey:
+    """zk_proof_systems/zkSNARK/objects/VerificationKey.java: alphaG1betaG2 (GT, 384 B), gammaG2, deltaG2 (wire-in
+    G2) and gammaABC (wire-in G1, one point per primary input), all in HBM; gamma and delta are also kept prepared
+    (their Miller-loop line coefficients, computed once per key)."""
+
+    def __init__(self, alpha_g1_beta_g2, gamma_g2, delta_g2, gamma_abc_g1):
+        from . import pairing as _pairing
+        self.alpha_g1_beta_g2 = alpha_g1_beta_g2
+        self.gamma_g2, self.delta_g2, self.gamma_abc_g1 = gamma_g2, delta_g2, gamma_abc_g1
+        self.num_inputs = gamma_abc_g1.numel() // 96
+        self.gamma_prep = _pairing.prepare_g2(gamma_g2)
+        self.delta_prep = _pairing.prepare_g2(delta_g2)
+        self._msm = None
+
+    def evaluation_abc(self, primary) -> torch.Tensor:
+        """sum primary_i gammaABC_i (Verifier.java:45-47, VariableBaseMSM.serialMSM) through the variable-base MSM;
+        192-byte wire-out point, asynchronous on the current stream"""
+        from . import device as _device
+        if len(primary) != self.num_inputs:
+            raise ValueError("%d primary inputs for a key of %d" % (len(primary), self.num_inputs))
+        if self._msm is None:
+            self._msm = _device.VarMsmWorkspace(self.num_inputs, 1)
+        return self._msm.run(self.gamma_abc_g1, _dev_bytes(_le32(primary))).clone()
+
+
+def verification_key(crs: CRS) -> VerificationKey:
+    """The verification key of a CRS from serial_setup_generate (SerialSetup.java:159-164): alphaG1betaG2 =
+    reducedPairing(alphaG1, betaG2) computed on the device."""
+    from . import pairing as _pairing
+    pk = crs.proving_key
+    alpha_beta = _pairing.reduced_pairing(pk.alpha_g1, pk.beta_g2)
+    return VerificationKey(alpha_beta, crs.gamma_g2, pk.delta_g2, crs.gamma_abc_g1)
+
+
+def proof_record(proof: Proof) -> bytes:
+    """A | B | C, 768 bytes of wire-out (the layout of ozk_groth16_combine_dev)"""
+    return bytes(proof.g_a) + bytes(proof.g_b) + bytes(proof.g_c)
+
+
+class Verifier:
+    """Verifier.verify (zkSNARK/Verifier.java:24-59) on the device.  A proof is accepted exactly when
+    e(A, B) == alphaG1betaG2 e(evaluationABC, gamma) e(C, delta), the Java's boolean; no on-curve or subgroup check
+    of the proof points (the Java does none)."""
+
+    @staticmethod
+    def verify(vk: VerificationKey, primary, proof: Proof) -> bool:
+        return Verifier.verify_batch(vk, [primary], [proof])[0]
+
+    @staticmethod
+    def verify_batch(vk: VerificationKey, primaries, proofs) -> list:
+        """k proofs in one launch pair (the three Miller loops of every proof, then one final exponentiation per
+        proof); evaluationABC is one variable-base MSM per proof."""
+        from . import pairing as _pairing
+        if len(primaries) != len(proofs) or not proofs:
+            raise ValueError("one primary input per proof, at least one proof")
+        for primary in primaries:
+            assert primary[0] % FR == 1   # Verifier.java:31-32
+        abc = torch.cat([vk.evaluation_abc(primary) for primary in primaries])
+        recs = _dev_bytes(b"".join(proof_record(p) for p in proofs))
+        ok = _pairing.groth16_verify(vk.alpha_g1_beta_g2, vk.gamma_prep, vk.delta_prep, recs, abc)
+        return [bool(v) for v in ok.cpu().tolist()]
