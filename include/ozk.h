@@ -390,6 +390,38 @@ int ozk_reduced_pairing_dev(const void* d_p, const void* d_q_or_prep, int32_t pr
 int ozk_groth16_verify_dev(const void* d_alpha_beta, const void* d_gamma_prep, const void* d_delta_prep,
                            const void* d_proofs, const void* d_abc, int32_t k, int32_t* d_ok, void* stream);
 
+/* Products of pairings, GT powers and randomized batch verification of Groth16 proofs.
+ *
+ *   ozk_pairing_product_dev     d_gt (one GT value) = FE(prod_i ML(P_i, Q_i)) = prod_i reducedPairing(P_i, Q_i) for n
+ *                               pairs in the formats of ozk_reduced_pairing_dev (a Q at infinity: 384 zero bytes)
+ *   ozk_gt_pow_dev              d_out[i] = d_gt[i]^e_i for n GT values; d_exp holds n 32-byte little-endian integers
+ *                               (any 256-bit value).  The inputs must lie in GT (results of reduced pairings): the
+ *                               exponentiation squares with the cyclotomic squaring.
+ *   ozk_groth16_wellformed_dev  d_flags[j] = 1 when proof j (768 B record A | B | C, wire-out) is well-formed: every
+ *                               coordinate canonical (< q, upper 32 bytes zero), A and C on the curve with Z != 0
+ *                               (G1 has cofactor 1), B on the twist with Z != 0 and [r]B = O; else 0
+ *   ozk_groth16_verify_rlc_dev  k proofs as one check: d_gamma_abc the key's n wire-in gammaABC points (96 B each),
+ *                               d_proofs k records, d_inputs k rows of n 32-byte little-endian primary inputs (taken
+ *                               mod r), d_r k 32-byte weights.  Proof j is covered when it is well-formed and
+ *                               0 < r_j < 2^128 (d_covered[j] = 1, else 0).  With s_i = sum_j r_j x_ji mod r over the
+ *                               covered proofs, ABC* = sum_i s_i gammaABC_i, C* = sum_j r_j C_j and S = sum_j r_j:
+ *                               *d_verdict = 1 when FE(prod_j ML(r_j A_j, B_j) (ML(ABC*, gamma) ML(C*, delta))^-1)
+ *                               == alphaBeta^S, 0 when not (some covered proof fails Verifier.verify), -1 when the
+ *                               check declines (ABC* or C* at infinity, e.g. no proof covered, or a zero Miller
+ *                               value).  With the r_j uniform in [1, 2^128) and unknown to the prover, a verdict of 1
+ *                               is wrong with probability at most 1 / (2^128 - 1).  Uncovered proofs are not judged.
+ *                               stage_ms: nullptr, or five floats that receive the stage times (combination, MSMs,
+ *                               Miller loops, product tree, final exponentiation); the call then waits for the stream.
+ * n or k <= 0: OZK_E_INVALID.  Otherwise asynchronous on `stream`. */
+int ozk_pairing_product_dev(const void* d_p, const void* d_q_or_prep, int32_t prepared, int32_t n, void* d_gt,
+                            void* stream);
+int ozk_gt_pow_dev(const void* d_gt, const void* d_exp, int32_t n, void* d_out, void* stream);
+int ozk_groth16_wellformed_dev(const void* d_proofs, int32_t k, int32_t* d_flags, void* stream);
+int ozk_groth16_verify_rlc_dev(const void* d_alpha_beta, const void* d_gamma_prep, const void* d_delta_prep,
+                               const void* d_gamma_abc, int32_t n, const void* d_proofs, const void* d_inputs,
+                               const void* d_r, int32_t k, int32_t* d_covered, int32_t* d_verdict, float* stage_ms,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,10 +5,13 @@
 //   k_miller        millerLoop (BNPairing.java:236-276) over prepared coefficients, or with the G2 steps inline
 //   k_final_exp     finalExponentiation (BNPairing.java:333-336) -> GT wire bytes
 //   k_verify_final  per proof FE(ML(A,B) (ML(ABC,gamma) ML(C,delta))^-1) == alphaG1betaG2
+//   batch_verify.cuh  randomized batch verification of K proofs as one check, products of pairings, GT powers
 //
 // A Miller value f lives in one lane's registers (108 VGPRs); the kernels are launched one wave per workgroup with
 // __launch_bounds__(64) so the compiler may use the whole register file.  The Miller values between the loop and
 // the final exponentiation go through HBM (432 B per pair), which keeps the two register budgets apart.
+#include <algorithm>
+
 #include "ozk_common.h"
 #include "curve.cuh"
 #include "fq12.cuh"
@@ -184,6 +187,28 @@ __global__ __launch_bounds__(64) void k_verify_final(const u32* __restrict__ f_i
 constexpr size_t PREP_BYTES = (size_t)pc::ATE_STEPS * ELL_WORDS * 4;
 constexpr size_t F12_BYTES = (size_t)FE12_WORDS * 4;
 constexpr int MAX_N = 1 << 24;   // (indices are 64-bit; this only rejects absurd counts)
+constexpr int PROD_CHUNK = 16;   // Miller values multiplied per lane at each level of the product tree
+
+}  // namespace ozk
+
+#include "batch_verify.cuh"
+
+namespace ozk {
+
+// the product of the n Miller values in d_f (stride n) into d_out (one value), through d_tmp (ceil(n / 16) values)
+static hipError_t f12_product(u32* d_f, int n, u32* d_tmp, u32* d_out, hipStream_t s) {
+  u32* src = d_f;
+  while (n > 1) {
+    const int m = (n + PROD_CHUNK - 1) / PROD_CHUNK;
+    u32* dst = m == 1 ? d_out : (src == d_tmp ? d_f : d_tmp);
+    hipLaunchKernelGGL(k_f12_prod, dim3((m + 63) / 64), dim3(64), 0, s, (const u32*)src, n, PROD_CHUNK, dst);
+    src = dst;
+    n = m;
+  }
+  return src != d_out ? hipMemcpyAsync(d_out, src, F12_BYTES, hipMemcpyDeviceToDevice, s) : hipSuccess;
+}
+
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace ozk
 
@@ -236,6 +261,128 @@ int ozk_groth16_verify_dev(const void* d_alpha_beta, const void* d_gamma_prep, c
   OZK_HIP(hipFreeAsync(d_f, s));
   OZK_HIP(e);
   return OZK_OK;
+}
+
+int ozk_pairing_product_dev(const void* d_p, const void* d_q_or_prep, int32_t prepared, int32_t n, void* d_gt,
+                            void* stream) {
+  hip_clear_stale();
+  if (!d_p || !d_q_or_prep || !d_gt || n <= 0 || n > MAX_N) return fail(OZK_E_INVALID, "bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  const int m = (n + PROD_CHUNK - 1) / PROD_CHUNK;
+  u32* d_f = nullptr;
+  OZK_HIP(hipMallocAsync((void**)&d_f, ((size_t)n + m + 1) * F12_BYTES, s));
+  u32* d_tmp = d_f + (size_t)n * FE12_WORDS;
+  u32* d_prod = d_tmp + (size_t)m * FE12_WORDS;
+  hipLaunchKernelGGL(k_miller, dim3((n + 63) / 64), dim3(64), 0, s, (const u32*)d_p, (const u32*)d_q_or_prep,
+                     (int)(prepared != 0), (int)n, d_f);
+  hipError_t e = f12_product(d_f, n, d_tmp, d_prod, s);
+  hipLaunchKernelGGL(k_final_exp, dim3(1), dim3(64), 0, s, (const u32*)d_prod, 1, (u32*)d_gt);
+  if (e == hipSuccess) e = hipGetLastError();
+  OZK_HIP(hipFreeAsync(d_f, s));
+  OZK_HIP(e);
+  return OZK_OK;
+}
+
+int ozk_gt_pow_dev(const void* d_gt, const void* d_exp, int32_t n, void* d_out, void* stream) {
+  hip_clear_stale();
+  if (!d_gt || !d_exp || !d_out || n <= 0 || n > MAX_N) return fail(OZK_E_INVALID, "bad argument");
+  hipLaunchKernelGGL(k_gt_pow, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, (const u32*)d_gt,
+                     (const u32*)d_exp, (int)n, (u32*)d_out);
+  OZK_HIP(hipGetLastError());
+  return OZK_OK;
+}
+
+int ozk_groth16_wellformed_dev(const void* d_proofs, int32_t k, int32_t* d_flags, void* stream) {
+  hip_clear_stale();
+  if (!d_proofs || !d_flags || k <= 0 || k > MAX_N) return fail(OZK_E_INVALID, "bad argument");
+  hipLaunchKernelGGL(k_wellformed, dim3((k + 63) / 64), dim3(64), 0, (hipStream_t)stream, (const u32*)d_proofs,
+                     (int)k, d_flags);
+  OZK_HIP(hipGetLastError());
+  return OZK_OK;
+}
+
+int ozk_groth16_verify_rlc_dev(const void* d_alpha_beta, const void* d_gamma_prep, const void* d_delta_prep,
+                               const void* d_gamma_abc, int32_t n, const void* d_proofs, const void* d_inputs,
+                               const void* d_r, int32_t k, int32_t* d_covered, int32_t* d_verdict, float* stage_ms,
+                               void* stream) {
+  hip_clear_stale();
+  if (!d_alpha_beta || !d_gamma_prep || !d_delta_prep || !d_gamma_abc || !d_proofs || !d_inputs || !d_r ||
+      !d_covered || !d_verdict || n <= 0 || n > MAX_N || k <= 0 || k > MAX_N)
+    return fail(OZK_E_INVALID, "bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t ws_bytes = std::max(ozk_var_msm_workspace_bytes(n, OZK_G1), ozk_var_msm_workspace_bytes(k, OZK_G1));
+  if (ws_bytes == 0) return fail(OZK_E_INVALID, "MSM workspace size query failed");
+  const int nb = (k + 63) / 64, m = (k + PROD_CHUNK - 1) / PROD_CHUNK;
+  // one allocation, carved: wf, C* bases, C* scalars, s_j | S, ABC*, C*, status, Miller values, tree, key values,
+  // alphaBeta^S, product, MSM workspace
+  const size_t sz[] = {(size_t)k * 4, (size_t)k * 96, (size_t)k * 32, ((size_t)n + 1) * 32, 192, 192, 8,
+                       (size_t)k * F12_BYTES, (size_t)m * F12_BYTES, 2 * F12_BYTES, F12_BYTES, F12_BYTES, ws_bytes};
+  constexpr int NP = sizeof(sz) / sizeof(sz[0]);
+  size_t off[NP], total = 0;
+  for (int i = 0; i < NP; i++) {
+    off[i] = total;
+    total += align256(sz[i]);
+  }
+  uint8_t* base = nullptr;
+  OZK_HIP(hipMallocAsync((void**)&base, total, s));
+  int32_t* d_wf = (int32_t*)(base + off[0]);
+  u32* d_cb = (u32*)(base + off[1]);
+  u32* d_cs = (u32*)(base + off[2]);
+  u32* d_s = (u32*)(base + off[3]);
+  u32* d_abc = (u32*)(base + off[4]);
+  u32* d_cstar = (u32*)(base + off[5]);
+  int32_t* d_status = (int32_t*)(base + off[6]);
+  u32* d_f = (u32*)(base + off[7]);
+  u32* d_tmp = (u32*)(base + off[8]);
+  u32* d_key = (u32*)(base + off[9]);
+  u32* d_pow = (u32*)(base + off[10]);
+  u32* d_prod = (u32*)(base + off[11]);
+  void* d_ws = base + off[12];
+
+  // stage_ms != nullptr: five stage times (combination, MSMs, Miller loops, product tree, final exponentiation),
+  // taken with events; the call then waits for the stream
+  hipEvent_t ev[6] = {};
+  int rc = OZK_OK;
+  hipError_t e = hipSuccess;
+  if (stage_ms)
+    for (int i = 0; i < 6 && e == hipSuccess; i++) e = hipEventCreate(&ev[i]);
+  auto mark = [&](int i) {
+    if (stage_ms && e == hipSuccess) e = hipEventRecord(ev[i], s);
+  };
+  mark(0);
+  hipLaunchKernelGGL(k_wellformed, dim3(nb), dim3(64), 0, s, (const u32*)d_proofs, (int)k, d_wf);
+  hipLaunchKernelGGL(k_rlc_inputs, dim3(nb), dim3(64), 0, s, (const u32*)d_proofs, (const u32*)d_r,
+                     (const int32_t*)d_wf, (int)k, d_cb, d_cs, d_covered);
+  hipLaunchKernelGGL(k_rlc_combine, dim3(n + 1), dim3(256), 0, s, (const u32*)d_inputs, (const u32*)d_r,
+                     (const int32_t*)d_covered, (int)k, (int)n, d_s);
+  mark(1);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) rc = ozk_var_msm_dev(d_gamma_abc, d_s, n, OZK_G1, d_abc, d_ws, ws_bytes, s);
+  if (e == hipSuccess && rc == OZK_OK) rc = ozk_var_msm_dev(d_cb, d_cs, k, OZK_G1, d_cstar, d_ws, ws_bytes, s);
+  mark(2);
+  if (e == hipSuccess && rc == OZK_OK) {
+    hipLaunchKernelGGL(k_rlc_miller, dim3(RLC_KEY_BLOCKS + nb), dim3(64), 0, s, (const u32*)d_proofs,
+                       (const u32*)d_r, (const int32_t*)d_covered, (int)k, (const u32*)d_abc, (const u32*)d_cstar,
+                       (const u32*)d_gamma_prep, (const u32*)d_delta_prep, (const u32*)d_alpha_beta,
+                       (const u32*)(d_s + 8L * n), d_f, d_key, d_pow, d_status);
+    mark(3);
+    e = f12_product(d_f, k, d_tmp, d_prod, s);
+    mark(4);
+    hipLaunchKernelGGL(k_rlc_final, dim3(1), dim3(64), 0, s, (const u32*)d_prod, (const u32*)d_key,
+                       (const u32*)d_pow, (const int32_t*)d_status, d_verdict);
+    mark(5);
+    if (e == hipSuccess) e = hipGetLastError();
+  }
+  if (stage_ms && e == hipSuccess && rc == OZK_OK) {
+    e = hipEventSynchronize(ev[5]);
+    for (int i = 0; i < 5 && e == hipSuccess; i++) e = hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]);
+  }
+  for (int i = 0; i < 6; i++)
+    if (ev[i]) (void)hipEventDestroy(ev[i]);
+  const hipError_t ef = hipFreeAsync(base, s);
+  OZK_HIP(e);
+  OZK_HIP(ef);
+  return rc;
 }
 
 }  // extern "C"

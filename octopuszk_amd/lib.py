@@ -96,6 +96,10 @@ _SIGS = {
     "ozk_pairing_g2_prepare_dev": (ctypes.c_int, [vp, i32, vp, sz, vp]),
     "ozk_reduced_pairing_dev": (ctypes.c_int, [vp, vp, i32, i32, vp, vp]),
     "ozk_groth16_verify_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, i32, vp, vp]),
+    "ozk_pairing_product_dev": (ctypes.c_int, [vp, vp, i32, i32, vp, vp]),
+    "ozk_gt_pow_dev": (ctypes.c_int, [vp, vp, i32, vp, vp]),
+    "ozk_groth16_wellformed_dev": (ctypes.c_int, [vp, i32, vp, vp]),
+    "ozk_groth16_verify_rlc_dev": (ctypes.c_int, [vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
 }
 
 

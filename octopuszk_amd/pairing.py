@@ -5,6 +5,8 @@ Points are device tensors of uint8 in the natives' wire-in format (G1 n x 96 B, 
 Z = 0 and is normalised to (0, 1, 0) as toAffineCoordinates does).  GT values are n x 384 B: twelve 32-byte
 little-endian canonical Fq values in the order c0.c0.c0, c0.c0.c1, c0.c1.c0, ..., c1.c2.c1.
 """
+import ctypes
+
 import torch
 
 from . import lib as _lib
@@ -78,3 +80,79 @@ def groth16_verify(alpha_beta, gamma_prep: PreparedG2, delta_prep: PreparedG2, d
     _lib.check(L.ozk_groth16_verify_dev(_ptr(alpha_beta), _ptr(gamma_prep.data), _ptr(delta_prep.data),
                                         _ptr(d_proofs), _ptr(d_abc), k, _ptr(ok), _stream()))
     return ok
+
+
+def pairing_product(p_batch, q_batch) -> torch.Tensor:
+    """prod_i e(P_i, Q_i) as one GT value (384 B): the n Miller values multiplied, then one final exponentiation.
+    Inputs as for reduced_pairing.  Asynchronous on the current stream."""
+    L = _lib.load()
+    p_batch = p_batch.contiguous()
+    n = _count(p_batch, G1_BYTES, "P")
+    if isinstance(q_batch, PreparedG2):
+        prepared, q = 1, q_batch.data
+        nq = q_batch.n
+    else:
+        prepared, q = 0, q_batch.contiguous()
+        nq = _count(q, G2_BYTES, "Q")
+    if nq != n:
+        raise ValueError("%d G1 points against %d G2 points" % (n, nq))
+    out = torch.empty(GT_BYTES, dtype=torch.uint8, device=p_batch.device)
+    _lib.check(L.ozk_pairing_product_dev(_ptr(p_batch), _ptr(q), prepared, n, _ptr(out), _stream()))
+    return out
+
+
+def gt_pow(gt_batch, exponents) -> torch.Tensor:
+    """gt_i^e_i for n GT values (n x 384 B, results of reduced pairings) and n integers 0 <= e_i < 2^256, given as a
+    list of ints or an n x 32-byte little-endian uint8 CUDA tensor.  Asynchronous on the current stream."""
+    L = _lib.load()
+    gt_batch = gt_batch.contiguous()
+    n = _count(gt_batch, GT_BYTES, "GT")
+    if not isinstance(exponents, torch.Tensor):
+        exponents = list(exponents)
+        if any(not 0 <= int(e) < 1 << 256 for e in exponents):
+            raise ValueError("exponents must lie in [0, 2^256)")
+        raw = b"".join(int(e).to_bytes(32, "little") for e in exponents)
+        exponents = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(gt_batch.device) if raw else \
+            torch.empty(0, dtype=torch.uint8, device=gt_batch.device)
+    exponents = exponents.contiguous()
+    if _count(exponents, 32, "exponents") != n:
+        raise ValueError("one exponent per GT value")
+    out = torch.empty_like(gt_batch)
+    _lib.check(L.ozk_gt_pow_dev(_ptr(gt_batch), _ptr(exponents), n, _ptr(out), _stream()))
+    return out
+
+
+def wellformed(d_proofs) -> torch.Tensor:
+    """k flags (int32, 1 = well-formed) of k 768-byte proof records A | B | C (wire-out): every coordinate canonical,
+    A and C on the curve, B on the twist and in the order-r subgroup, no point at infinity.  Asynchronous."""
+    L = _lib.load()
+    d_proofs = d_proofs.contiguous()
+    k = _count(d_proofs, 768, "proofs")
+    flags = torch.empty(k, dtype=torch.int32, device=d_proofs.device)
+    _lib.check(L.ozk_groth16_wellformed_dev(_ptr(d_proofs), k, _ptr(flags), _stream()))
+    return flags
+
+
+def groth16_verify_rlc(alpha_beta, gamma_prep: PreparedG2, delta_prep: PreparedG2, gamma_abc, d_proofs, d_inputs,
+                       d_r, stage_ms=None):
+    """The randomized batch check of ozk_groth16_verify_rlc_dev over k records, k x n primary inputs and k weights
+    (32-byte little-endian each).  Returns (verdict, covered): an int32 tensor of one value (1 accepted, 0 rejected,
+    -1 declined) and k int32 flags (1 = the proof entered the check).  stage_ms: None, or a list that receives the
+    five stage times in ms (the call then waits for the stream)."""
+    L = _lib.load()
+    d_proofs, d_inputs, d_r = d_proofs.contiguous(), d_inputs.contiguous(), d_r.contiguous()
+    k = _count(d_proofs, 768, "proofs")
+    n = _count(gamma_abc, G1_BYTES, "gammaABC")
+    if _count(d_inputs, 32 * n, "inputs") != k or _count(d_r, 32, "weights") != k:
+        raise ValueError("one row of %d inputs and one weight per proof" % n)
+    if gamma_prep.n != 1 or delta_prep.n != 1 or alpha_beta.numel() != GT_BYTES:
+        raise ValueError("one prepared gamma, one prepared delta and one GT value")
+    covered = torch.empty(k, dtype=torch.int32, device=d_proofs.device)
+    verdict = torch.empty(1, dtype=torch.int32, device=d_proofs.device)
+    times = (ctypes.c_float * 5)() if stage_ms is not None else None
+    _lib.check(L.ozk_groth16_verify_rlc_dev(_ptr(alpha_beta), _ptr(gamma_prep.data), _ptr(delta_prep.data),
+                                            _ptr(gamma_abc), n, _ptr(d_proofs), _ptr(d_inputs), _ptr(d_r), k,
+                                            _ptr(covered), _ptr(verdict), times, _stream()))
+    if stage_ms is not None:
+        stage_ms[:] = [float(t) for t in times]
+    return verdict, covered

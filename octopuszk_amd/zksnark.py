@@ -26,6 +26,8 @@ Proof elements are returned in the wire-out format of the variable-base natives 
 """
 import ctypes
 import os
+import random
+import secrets
 import time
 
 import numpy as np
@@ -1113,6 +1115,27 @@ def proof_record(proof: Proof) -> bytes:
     return bytes(proof.g_a) + bytes(proof.g_b) + bytes(proof.g_c)
 
 
+def _pack_primaries(primaries, n):
+    """one 32n-byte row (inputs mod r, little-endian) per primary input, validated as Verifier.java:31-32 asserts.
+    A row object that recurs is packed once.  The cache holds the row object itself, so that its id cannot be reused
+    by a later row while the cache lives (rows may be temporaries, e.g. the rows of a numpy object array)."""
+    packed = {}
+    rows = []
+    for primary in primaries:
+        hit = packed.get(id(primary))
+        if hit is not None and hit[0] is primary:
+            rows.append(hit[1])
+            continue
+        if len(primary) != n:
+            raise ValueError("%d primary inputs for a key of %d" % (len(primary), n))
+        if int(primary[0]) % FR != 1:
+            raise ValueError("primary[0] must be 1")
+        row = b"".join((int(v) % FR).to_bytes(32, "little") for v in primary)
+        packed[id(primary)] = (primary, row)
+        rows.append(row)
+    return rows
+
+
 class Verifier:
     """Verifier.verify (zkSNARK/Verifier.java:24-59) on the device.  A proof is accepted exactly when
     e(A, B) == alphaG1betaG2 e(evaluationABC, gamma) e(C, delta), the Java's boolean; no on-curve or subgroup check
@@ -1135,3 +1158,66 @@ class Verifier:
         recs = _dev_bytes(b"".join(proof_record(p) for p in proofs))
         ok = _pairing.groth16_verify(vk.alpha_g1_beta_g2, vk.gamma_prep, vk.delta_prep, recs, abc)
         return [bool(v) for v in ok.cpu().tolist()]
+
+    @staticmethod
+    def _rlc(vk: VerificationKey, primaries, proofs, seed, stage_ms=None):
+        """The randomized check over the well-formed proofs: (verdict, covered flags), verdict 1 / 0 / -1 as
+        ozk_groth16_verify_rlc_dev returns it."""
+        from . import pairing as _pairing
+        if len(primaries) != len(proofs) or not proofs:
+            raise ValueError("one primary input per proof, at least one proof")
+        rows = _pack_primaries(primaries, vk.num_inputs)
+        rng = random.Random(seed) if seed is not None else secrets.SystemRandom()
+        weights = b"".join((rng.randrange(1, 1 << 128)).to_bytes(32, "little") for _ in proofs)
+        t0 = time.perf_counter()
+        recs = _dev_bytes(b"".join(proof_record(p) for p in proofs))
+        d_inputs = _dev_bytes(b"".join(rows))
+        d_r = _dev_bytes(weights)
+        if stage_ms is not None:
+            torch.cuda.synchronize()
+            stage_ms["upload"] = (time.perf_counter() - t0) * 1e3
+            times = []
+        else:
+            times = None
+        verdict, covered = _pairing.groth16_verify_rlc(vk.alpha_g1_beta_g2, vk.gamma_prep, vk.delta_prep,
+                                                       vk.gamma_abc_g1, recs, d_inputs, d_r, times)
+        if stage_ms is not None:
+            stage_ms.update(zip(("combination", "msms", "miller", "product", "final_exp"), times))
+        return int(verdict.item()), [bool(c) for c in covered.cpu().tolist()]
+
+    @staticmethod
+    def verify_all(vk: VerificationKey, primaries, proofs, *, seed=None, stage_ms=None) -> bool:
+        """True exactly when every proof passes (the Java's verify on each), for a batch of any size at the cost of
+        about one pairing check: a random linear combination of the equations of the well-formed proofs, with
+        weights r_i uniform in [1, 2^128), is checked once (ozk_groth16_verify_rlc_dev); the other proofs, or all of
+        them if the check declines, go through verify_batch.  A wrong True has probability at most 1 / (2^128 - 1)
+        over the weights.
+
+        The weights come from `secrets` unless `seed` is given.  A seeded batch is reproducible, and therefore
+        UNSOUND against anyone who knows the seed: they can build invalid proofs whose errors cancel in the
+        combination.  Use a seed for tests only.  stage_ms: None, or a dict that receives the stage times in ms."""
+        primaries, proofs = list(primaries), list(proofs)
+        verdict, covered = Verifier._rlc(vk, primaries, proofs, seed, stage_ms)
+        if verdict == 0:
+            return False
+        rest = [i for i in range(len(proofs)) if verdict < 0 or not covered[i]]
+        if not rest:
+            return True
+        return all(Verifier.verify_batch(vk, [primaries[i] for i in rest], [proofs[i] for i in rest]))
+
+    @staticmethod
+    def verify_batch_rlc(vk: VerificationKey, primaries, proofs, *, seed=None) -> list:
+        """The verdicts of verify_batch, found with the randomized check first: when it accepts, every well-formed
+        proof gets True and only the others go through verify_batch; when it rejects or declines, the whole batch
+        does.  Weights and `seed` as in verify_all (a seeded batch is unsound against anyone who knows the seed)."""
+        primaries, proofs = list(primaries), list(proofs)
+        verdict, covered = Verifier._rlc(vk, primaries, proofs, seed)
+        if verdict != 1:
+            return Verifier.verify_batch(vk, primaries, proofs)
+        out = [True] * len(proofs)
+        rest = [i for i in range(len(proofs)) if not covered[i]]
+        if rest:
+            for i, v in zip(rest, Verifier.verify_batch(vk, [primaries[i] for i in rest], [proofs[i] for i in rest])):
+                out[i] = v
+        return out
+

@@ -5,7 +5,10 @@
 
   * reduced pairings / s at n = 1, 1024, 65536 (random pairs, G2 steps inline; median of a few runs);
   * one 2^10-constraint proof (15 inputs): Verifier.verify latency, with the evaluationABC MSM shown separately;
-  * Verifier.verify_batch proofs / s at K = 64, 4096 (the ABC MSMs, one per proof, included and shown apart).
+  * Verifier.verify_batch proofs / s at K = 64, 4096 (the ABC MSMs, one per proof, included and shown apart);
+  * Verifier.verify_all and verify_batch_rlc (the randomized batch check) at K = 1, 64, 4096, 65536, with the stage
+    split of verify_all (upload, combination, MSMs, Miller loops, product tree, final exponentiation), repeated
+    copies of the one proof.  `rlc_floor_ok`: verify_all at K = 4096 within 150 ms and >= 20x verify_batch's rate.
 The floor the issue sets is 1 M reduced pairings / s at n = 65536; `floor_ok` reports it.  The counted figures are
 the Fq multiplications per reduced pairing taken from the code."""
 import json
@@ -72,6 +75,22 @@ def main():
         t_abc = _timed(lambda: [vk.evaluation_abc(p) for p in prims], 1)
         batch[str(k)] = {"ms": round(t * 1e3, 2), "proofs_per_s": round(k / t, 1), "abc_msm_ms": round(t_abc * 1e3, 2)}
     out["verify_batch"] = batch
+    rlc = {}
+    for k in ([1, 64] if quick else [1, 64, 4096, 65536]):
+        prims, proofs = [primary] * k, [proof] * k
+        assert z.Verifier.verify_all(vk, prims, proofs)
+        t_all = _timed(lambda: z.Verifier.verify_all(vk, prims, proofs), 3)
+        t_rlc = _timed(lambda: z.Verifier.verify_batch_rlc(vk, prims, proofs), 3)
+        stages = {}
+        z.Verifier.verify_all(vk, prims, proofs, stage_ms=stages)
+        rlc[str(k)] = {"verify_all_ms": round(t_all * 1e3, 2), "verify_all_proofs_per_s": round(k / t_all, 1),
+                       "verify_batch_rlc_ms": round(t_rlc * 1e3, 2),
+                       "stages_ms": {n: round(v, 3) for n, v in stages.items()}}
+    out["verify_all"] = rlc
+    if not quick:
+        t = rlc["4096"]["verify_all_ms"]
+        out["rlc_speedup_4096"] = round(rlc["4096"]["verify_all_proofs_per_s"] / batch["4096"]["proofs_per_s"], 1)
+        out["rlc_floor_ok"] = t <= 150 and out["rlc_speedup_4096"] >= 20
     print(json.dumps(out))
 
 
