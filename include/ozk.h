@@ -422,6 +422,48 @@ int ozk_groth16_verify_rlc_dev(const void* d_alpha_beta, const void* d_gamma_pre
                                const void* d_r, int32_t k, int32_t* d_covered, int32_t* d_verdict, float* stage_ms,
                                void* stream);
 
+/* BACE: batch arithmetic-circuit evaluation (the reference's bace/ package).  An instance is a
+ * row of n inputs; d_inputs holds N instances row-major (value i n + j is input j of instance i), 32-byte
+ * little-endian values (taken mod r).  N is a power of two, D = lowestPowerOfTwo(deg N) with N <= D <= 2^28, n <= 65535.
+ * BACE programs (host memory, checked record by record before anything is enqueued): n_ops records of four int32
+ * {op, dst, a, b}, run in order at every point:
+ *     op 0 INPUT  slot[dst] = input a (0 <= a < n)        op 1 CONST  slot[dst] = consts[a] (0 <= a < n_consts)
+ *     op 2 ADD    slot[dst] = slot[a] + slot[b]           op 3 MUL    slot[dst] = slot[a] * slot[b]
+ * with 0 <= dst, a, b < n_slots; the value of the last record is the circuit's output.  consts: n_consts 32-byte LE
+ * values (host memory).  Slots beyond OZK_BACE_LDS_SLOTS (default 16, at most 28; read once, ozk_tuning_reload) live
+ * in the workspace, so query the workspace size after any change of that knob.
+ *   ozk_bace_prove_dev        Prover.computeProof: d_proof = the D coefficients (D x 32 B, canonical) of
+ *                             R(z) = C(beta_1(z), ..., beta_n(z)), beta_j the interpolant of column j on the N-point
+ *                             domain.  Workspace: ozk_bace_workspace_bytes(n, N, D, n_ops, n_slots, n_consts).
+ *   ozk_bace_evaluate_dev     NaiveEvaluator.getResult: d_out[i] = C(row i) for `rows` rows of n inputs (rows x 32 B).
+ *                             Workspace: ozk_bace_evaluate_workspace_bytes(rows, n_ops, n_slots, n_consts).
+ *   ozk_bace_columns_at_dev   d_out[j] = beta_j(r) for the n columns (n x 32 B); r: 32-byte LE host value (mod r).
+ *                             Workspace: ozk_bace_workspace_bytes(n, N, N, 0, 0, 0).
+ *   ozk_bace_result_dev       Verifier.getResult: d_out[i] = proof(omega_N^i), i < N (N x 32 B) for a proof of D
+ *                             coefficients: the proof folded mod z^N - 1, then one transform of size N.
+ *                             Workspace: ozk_bace_workspace_bytes(1, N, N, 0, 0, 0).
+ *   ozk_fr_poly_eval_dev      d_out[y] = sum_i c_yi r^i for npolys polynomials of len coefficients each (canonical,
+ *                             32-byte LE), polynomial y at d_coeffs + 32 y poly_stride bytes.  Workspace:
+ *                             ozk_fr_poly_eval_workspace_bytes(npolys).
+ * A size function returns 0 for a shape it rejects; the entry points return OZK_E_INVALID for it (N not a power of two,
+ * D < N, D > 2^28, a malformed program, a short workspace).  All calls are asynchronous on `stream`. */
+size_t ozk_bace_workspace_bytes(int32_t n, int32_t N, int32_t D, int32_t n_ops, int32_t n_slots, int32_t n_consts);
+size_t ozk_bace_evaluate_workspace_bytes(int32_t rows, int32_t n_ops, int32_t n_slots, int32_t n_consts);
+int ozk_bace_prove_dev(const void* d_inputs, int32_t n, int32_t N, const int32_t* program, int32_t n_ops,
+                       int32_t n_slots, const uint8_t* consts, int32_t n_consts, int32_t D, void* d_proof,
+                       void* d_workspace, size_t workspace_bytes, void* stream);
+int ozk_bace_evaluate_dev(const void* d_inputs, int32_t n, int32_t rows, const int32_t* program, int32_t n_ops,
+                          int32_t n_slots, const uint8_t* consts, int32_t n_consts, void* d_out, void* d_workspace,
+                          size_t workspace_bytes, void* stream);
+int ozk_bace_columns_at_dev(const void* d_inputs, int32_t n, int32_t N, const uint8_t* r_host32, void* d_out,
+                            void* d_workspace, size_t workspace_bytes, void* stream);
+int ozk_bace_result_dev(const void* d_proof, int32_t D, int32_t N, void* d_out, void* d_workspace,
+                        size_t workspace_bytes, void* stream);
+size_t ozk_fr_poly_eval_workspace_bytes(int32_t npolys);
+int ozk_fr_poly_eval_dev(const void* d_coeffs, int32_t npolys, int32_t len, int64_t poly_stride,
+                         const uint8_t* r_host32, void* d_out, void* d_workspace, size_t workspace_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,8 @@ struct PassArgs {
   int pyr;          // 1: twiddles from the pyramid's levels (default), 0: from level 0 with a stride
   const u32* scale; // LAST pass only, or null: out[i] is multiplied by scale[i] (n x 8 words, Montgomery form) on its
                     // way out — the coset / 1-over-m scalings of the witness map ride on the transform before them
+  size_t in_cs, out_cs;   // batched transforms (bace.cuh): column blockIdx.y reads at in + y in_cs, writes at
+                          // out + y out_cs (words); one column (gridDim.y = 1) reads and writes at offset 0
 };
 
 // omega^(j 2^s): entry j of level s of the pyramid
@@ -171,7 +173,7 @@ __device__ __forceinline__ void gload(const PassArgs& a, int T, int logT, u32 mi
   const u32 i = tile_index<FIRST>(a, blockIdx.x, T, logT, mid, ul);
   u32 src = i;
   if (FIRST) src = __brev(i) >> (32 - a.logn);
-  const uint4* sp = reinterpret_cast<const uint4*>(a.in + (size_t)src * 8);
+  const uint4* sp = reinterpret_cast<const uint4*>(a.in + (size_t)blockIdx.y * a.in_cs + (size_t)src * 8);
   v0 = sp[0];
   v1 = sp[1];
 }
@@ -189,7 +191,7 @@ __device__ __forceinline__ void gstore(const PassArgs& a, int T, int logT, u32 m
   if constexpr (LAST != 0) {
     if constexpr (LAST == 2) pack(canonical(mul(v, ElemTraits<Fe<FrP, 16>>::load(a.scale + (size_t)i * 8))), o);
     else pack(canonical_q(v), o);
-    uint4* dst = reinterpret_cast<uint4*>(a.out + (size_t)i * a.out_stride);
+    uint4* dst = reinterpret_cast<uint4*>(a.out + (size_t)blockIdx.y * a.out_cs + (size_t)i * a.out_stride);
     dst[0] = make_uint4(o[0], o[1], o[2], o[3]);
     dst[1] = make_uint4(o[4], o[5], o[6], o[7]);
     if (a.out_stride == 16) {
@@ -198,7 +200,7 @@ __device__ __forceinline__ void gstore(const PassArgs& a, int T, int logT, u32 m
     }
   } else {
     pack(reduce_q(v), o);
-    uint4* dst = reinterpret_cast<uint4*>(a.out + (size_t)i * 8);
+    uint4* dst = reinterpret_cast<uint4*>(a.out + (size_t)blockIdx.y * a.out_cs + (size_t)i * 8);
     dst[0] = make_uint4(o[0], o[1], o[2], o[3]);
     dst[1] = make_uint4(o[4], o[5], o[6], o[7]);
   }
@@ -506,12 +508,15 @@ static void fft_build_twiddles(const u32* d_omega, int n, u32* small, u32* tw, h
 
 // the transform proper: d_in (n x 8 words) -> d_out (n x out_stride words), in place allowed only
 // through the two ping-pong buffers (d_out may be one of them only if it is not read by the last pass)
+// batch > 1 (the tiled transform only): `batch` independent columns, column c from d_in + c in_cs to d_out + c out_cs
+// (words), one launch per pass for all of them; the ping-pong buffers then hold batch x n x 8 words each
 static int fft_core(const u32* d_in, int n, const u32* tw, u32* d_out, int out_stride, u32* buf0, u32* buf1,
-                    hipStream_t st, const u32* scale = nullptr) {
+                    hipStream_t st, const u32* scale = nullptr, int batch = 1, size_t in_cs = 0, size_t out_cs = 0) {
   hip_clear_stale();   // (ozk_common.h: a stale error of the calling thread is not this call's)
   const int logn = ilog2((uint32_t)n);
   if (n < FFT_TILE_SMALL) {
     if (scale) return fail(OZK_E_INTERNAL, "output scaling needs the tiled transform");
+    if (batch != 1) return fail(OZK_E_INTERNAL, "batched transforms below %d elements go through bace.cuh", FFT_TILE_SMALL);
     hipLaunchKernelGGL(k_fft_small, dim3(1), dim3(FFT_THREADS), 0, st, d_in, d_out, tw, n, logn, buf0, out_stride);
     OZK_HIP(hipGetLastError());
     return OZK_OK;
@@ -574,15 +579,17 @@ static int fft_core(const u32* d_in, int n, const u32* tw, u32* d_out, int out_s
     a.K = K;
     a.pyr = env_int("OZK_FFT_TW_PYRAMID", 1) != 0;
     a.scale = last ? scale : nullptr;
-    const int tiles = n / tile;
+    a.in_cs = pass == 0 ? in_cs : (size_t)n * 8;
+    a.out_cs = last ? out_cs : (size_t)n * 8;
+    const dim3 tiles(n / tile, batch);
     const int mode = !last ? 0 : (a.scale ? 2 : 1);
 #define OZK_FFT_LAUNCH(F, MODE)                                                                                          \
   do {                                                                                                                   \
     if (K >= 3 && (K & 1))                                                                                               \
-      hipLaunchKernelGGL((k_fft_pass<F, FFT_TILE_SMALL, MODE, true>), dim3(tiles), dim3(FFT_TILE_SMALL / 4), lds_bytes,  \
+      hipLaunchKernelGGL((k_fft_pass<F, FFT_TILE_SMALL, MODE, true>), tiles, dim3(FFT_TILE_SMALL / 4), lds_bytes,        \
                          st, a);                                                                                         \
     else                                                                                                                 \
-      hipLaunchKernelGGL((k_fft_pass<F, FFT_TILE_SMALL, MODE, false>), dim3(tiles), dim3(FFT_TILE_SMALL / 4), lds_bytes, \
+      hipLaunchKernelGGL((k_fft_pass<F, FFT_TILE_SMALL, MODE, false>), tiles, dim3(FFT_TILE_SMALL / 4), lds_bytes,       \
                          st, a);                                                                                         \
   } while (0)
     if (pass == 0) {
@@ -1478,3 +1485,5 @@ int ozk_fft_compact_host(const uint8_t* in, int32_t n, const uint8_t* omega, int
 }
 
 }  // extern "C"
+
+#include "bace.cuh"

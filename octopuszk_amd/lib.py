@@ -100,6 +100,14 @@ _SIGS = {
     "ozk_gt_pow_dev": (ctypes.c_int, [vp, vp, i32, vp, vp]),
     "ozk_groth16_wellformed_dev": (ctypes.c_int, [vp, i32, vp, vp]),
     "ozk_groth16_verify_rlc_dev": (ctypes.c_int, [vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "ozk_bace_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
+    "ozk_bace_evaluate_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "ozk_bace_prove_dev": (ctypes.c_int, [vp, i32, i32, vp, i32, i32, vp, i32, i32, vp, vp, sz, vp]),
+    "ozk_bace_evaluate_dev": (ctypes.c_int, [vp, i32, i32, vp, i32, i32, vp, i32, vp, vp, sz, vp]),
+    "ozk_bace_columns_at_dev": (ctypes.c_int, [vp, i32, i32, vp, vp, vp, sz, vp]),
+    "ozk_bace_result_dev": (ctypes.c_int, [vp, i32, i32, vp, vp, sz, vp]),
+    "ozk_fr_poly_eval_workspace_bytes": (sz, [i32]),
+    "ozk_fr_poly_eval_dev": (ctypes.c_int, [vp, i32, i32, ctypes.c_int64, vp, vp, vp, sz, vp]),
 }
 
 
