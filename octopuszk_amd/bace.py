@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .device import _ptr, _stream
 from .fft import FR
 from .zksnark import fr_random, lowest_power_of_two
 
@@ -195,14 +196,6 @@ class Circuit:
 
 
 # ---------------------------------------------------------------------------------------------- device helpers
-def _ptr(t):
-    return int(t.data_ptr())
-
-
-def _stream():
-    return int(torch.cuda.current_stream().cuda_stream)
-
-
 def _le32(values) -> bytes:
     return b"".join((int(v) % FR).to_bytes(32, "little") for v in values)
 

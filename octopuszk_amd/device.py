@@ -17,6 +17,28 @@ def _stream():
     return int(torch.cuda.current_stream().cuda_stream)
 
 
+def prepare_bases(d_bases, n, type_):
+    """Affine Montgomery records of the `n` bases `d_bases` (wire format) for the *_prepared_dev entry points
+    (submit(..., prepared=True)): done once per proving key, skips the conversion kernel in every MSM.
+    Asynchronous on the current stream."""
+    L = _lib.load()
+    nbytes = int(L.ozk_var_msm_prepared_bytes(n, type_))
+    out = torch.empty(nbytes, dtype=torch.uint8, device=d_bases.device)
+    _lib.check(L.ozk_var_msm_prepare_dev(_ptr(d_bases), n, type_, _ptr(out), nbytes, _stream()))
+    return out
+
+
+def _close_on_del(self):
+    # never call into HIP while the interpreter (and possibly the HIP runtime) is being torn down
+    # (`sys` is a module-level import: an import statement here fails during interpreter shutdown)
+    if sys is None or sys.is_finalizing():
+        return
+    try:
+        self.close()
+    except Exception:
+        pass
+
+
 class VarMsmWorkspace:
     """Pre-allocated workspace + output for repeated device-resident MSMs of size n.
 
@@ -85,24 +107,10 @@ class VarMsmPipeline:
                 L.ozk_order_event_destroy(ev)
             self.levels_done = []
 
-    def __del__(self):
-        # never call into HIP while the interpreter (and possibly the HIP runtime) is being torn down
-        # (`sys` is a module-level import: an import statement here fails during interpreter shutdown)
-        if sys is None or sys.is_finalizing():
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
+    __del__ = _close_on_del
 
     def prepare(self, d_bases):
-        """Affine Montgomery records of `d_bases` (wire format) for submit(..., prepared=True): done once
-        per proving key, skips the conversion kernel in every MSM."""
-        L = _lib.load()
-        nbytes = int(L.ozk_var_msm_prepared_bytes(self.n, self.type))
-        out = torch.empty(nbytes, dtype=torch.uint8, device=d_bases.device)
-        _lib.check(L.ozk_var_msm_prepare_dev(_ptr(d_bases), self.n, self.type, _ptr(out), nbytes, _stream()))
-        return out
+        return prepare_bases(d_bases, self.n, self.type)
 
     def submit(self, d_bases, d_scalars, prepared=False):
         L = _lib.load()
@@ -197,11 +205,7 @@ class VarMsmPipeline3:
                 L.ozk_stream_destroy(h)
             self._owned = []
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    __del__ = _close_on_del
 
     def _check_stream(self, main):
         if self.tail_cus > 0 and int(main.cuda_stream) == 0:
@@ -209,57 +213,12 @@ class VarMsmPipeline3:
                                "streams and would serialise against it; submit under torch.cuda.stream(<a stream>)")
 
     def prepare(self, d_bases):
-        L = _lib.load()
-        nbytes = int(L.ozk_var_msm_prepared_bytes(self.n, self.type))
-        out = torch.empty(nbytes, dtype=torch.uint8, device=d_bases.device)
-        _lib.check(L.ozk_var_msm_prepare_dev(_ptr(d_bases), self.n, self.type, _ptr(out), nbytes, _stream()))
-        return out
-
-    def _submit_split(self, d_bases, d_scalars, prepared, last):
-        """submit() with the accumulate stage in two parts: sorted set s and accumulate scratch s are free again once
-        the REST of MSM k has run — on the tail stream, which is where accum_done[s] is recorded."""
-        L = _lib.load()
-        k = self.count
-        s, slot = k % 2, k % self.depth
-        main = torch.cuda.current_stream()
-        self._check_stream(main)
-        self._inputs = (d_bases, d_scalars)
-        if k >= 2:
-            main.wait_event(self.accum_done[s])
-        sort = L.ozk_var_msm_sort_prepared_dev if prepared else L.ozk_var_msm_sort_dev
-        _lib.check(sort(_ptr(d_bases), _ptr(d_scalars), self.n, self.type, _ptr(self.sorted[s]), self.sorted_bytes,
-                        _ptr(self.sort_ws), self.sort_ws_bytes, int(main.cuda_stream)))
-        self.sort_done[s].record(main)
-        self.acc.wait_event(self.sort_done[s])   # (ordered after rest(k - 2) through the sort's wait above)
-        if k >= self.depth:
-            self.acc.wait_event(self.tail_done[slot])
-        args = (_ptr(d_bases) if prepared else None, self.n, self.type, _ptr(self.sorted[s]), self.sorted_bytes,
-                _ptr(self.accum_ws2[s]), self.accum_ws_bytes, _ptr(self.tails[slot]), self.tail_bytes)
-        _lib.check(L.ozk_var_msm_accum_part_dev(*args, int(self.acc.cuda_stream), 1))
-        self.l1_done[s].record(self.acc)
-        T = self.tail_st[k % len(self.tail_st)]
-        R = self.rest_st or T     # (the rest on a stream of its own when the tail streams are confined to a few CUs)
-        R.wait_event(self.l1_done[s])
-        _lib.check(L.ozk_var_msm_accum_part_dev(*args, int(R.cuda_stream), 2))
-        self.accum_done[s].record(R)
-        if R is not T:
-            T.wait_event(self.accum_done[s])
-        if last:
-            _lib.check(L.ozk_var_msm_tail_mode_dev(self.n, self.type, _ptr(self.tails[slot]), self.tail_bytes,
-                                                   _ptr(self.outs[slot]), int(T.cuda_stream), None, 0))
-        else:
-            _lib.check(L.ozk_var_msm_tail_dev(self.n, self.type, _ptr(self.tails[slot]), self.tail_bytes,
-                                              _ptr(self.outs[slot]), int(T.cuda_stream)))
-        self.tail_done[slot].record(T)
-        self.count += 1
-        return k
+        return prepare_bases(d_bases, self.n, self.type)
 
     def submit(self, d_bases, d_scalars, prepared=False, last=False):
         """last=True: the caller knows that no MSM follows this one (the end of a burst, a prover's final MSM): its
         tail then runs with the chip to itself and takes the LATENCY shape of the window sums (fused first level +
         wave levels: ~40 dependent additions shorter) instead of the throughput shape the overlapped tails use."""
-        if self.split:
-            return self._submit_split(d_bases, d_scalars, prepared, last)
         L = _lib.load()
         k = self.count
         s, slot = k % 2, k % self.depth
@@ -267,7 +226,7 @@ class VarMsmPipeline3:
         self._check_stream(main)
         self._inputs = (d_bases, d_scalars)
         if k >= 2:
-            main.wait_event(self.accum_done[s])        # sorted set s is free again
+            main.wait_event(self.accum_done[s])        # sorted set s (and, split, accumulate scratch s) is free again
         sort = L.ozk_var_msm_sort_prepared_dev if prepared else L.ozk_var_msm_sort_dev
         _lib.check(sort(_ptr(d_bases), _ptr(d_scalars), self.n, self.type, _ptr(self.sorted[s]), self.sorted_bytes,
                         _ptr(self.sort_ws), self.sort_ws_bytes, int(main.cuda_stream)))
@@ -275,18 +234,30 @@ class VarMsmPipeline3:
         self.acc.wait_event(self.sort_done[s])
         if k >= self.depth:
             self.acc.wait_event(self.tail_done[slot])  # the tail that last used this slot's buffers
-        if prepared:
-            _lib.check(L.ozk_var_msm_accum_prepared_dev(_ptr(d_bases), self.n, self.type, _ptr(self.sorted[s]),
-                                                        self.sorted_bytes, _ptr(self.accum_ws), self.accum_ws_bytes,
-                                                        _ptr(self.tails[slot]), self.tail_bytes,
-                                                        int(self.acc.cuda_stream)))
-        else:
-            _lib.check(L.ozk_var_msm_accum_dev(self.n, self.type, _ptr(self.sorted[s]), self.sorted_bytes,
-                                               _ptr(self.accum_ws), self.accum_ws_bytes, _ptr(self.tails[slot]),
-                                               self.tail_bytes, int(self.acc.cuda_stream)))
-        self.accum_done[s].record(self.acc)
         T = self.tail_st[k % len(self.tail_st)]
-        T.wait_event(self.accum_done[s])
+        accum_ws = self.accum_ws2[s] if self.split else self.accum_ws
+        args = (self.n, self.type, _ptr(self.sorted[s]), self.sorted_bytes, _ptr(accum_ws), self.accum_ws_bytes,
+                _ptr(self.tails[slot]), self.tail_bytes)
+        if self.split:
+            # the accumulate stage in two parts: sorted set s and accumulate scratch s are free again once the REST of
+            # MSM k has run, which is where accum_done[s] is recorded (the next accumulate on scratch s is ordered
+            # after it through the sort's wait above)
+            bases = _ptr(d_bases) if prepared else None
+            _lib.check(L.ozk_var_msm_accum_part_dev(bases, *args, int(self.acc.cuda_stream), 1))
+            self.l1_done[s].record(self.acc)
+            R = self.rest_st or T     # (the rest on a stream of its own when the tail streams are confined to a few CUs)
+            R.wait_event(self.l1_done[s])
+            _lib.check(L.ozk_var_msm_accum_part_dev(bases, *args, int(R.cuda_stream), 2))
+            self.accum_done[s].record(R)
+            if R is not T:
+                T.wait_event(self.accum_done[s])
+        else:
+            if prepared:
+                _lib.check(L.ozk_var_msm_accum_prepared_dev(_ptr(d_bases), *args, int(self.acc.cuda_stream)))
+            else:
+                _lib.check(L.ozk_var_msm_accum_dev(*args, int(self.acc.cuda_stream)))
+            self.accum_done[s].record(self.acc)
+            T.wait_event(self.accum_done[s])
         if last:
             _lib.check(L.ozk_var_msm_tail_mode_dev(self.n, self.type, _ptr(self.tails[slot]), self.tail_bytes,
                                                    _ptr(self.outs[slot]), int(T.cuda_stream), None, 0))

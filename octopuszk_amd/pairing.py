@@ -10,16 +10,9 @@ import ctypes
 import torch
 
 from . import lib as _lib
+from .device import _ptr, _stream
 
 G1_BYTES, G2_BYTES, GT_BYTES = 96, 192, 384
-
-
-def _ptr(t):
-    return int(t.data_ptr())
-
-
-def _stream():
-    return int(torch.cuda.current_stream().cuda_stream)
 
 
 def _count(t, rec, what):

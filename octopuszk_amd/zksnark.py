@@ -21,6 +21,9 @@ of A_i(t), B_i(t), C_i(t)), and device buffers for everything else:
     two streams, G2 on a third — and the proof is assembled on the device (ozk_points_sum_dev and one
     3-term MSM, s A + r B1 - r s delta, on a fourth stream behind the long MSMs) from the MSM results.
 
+The prover's schedule exists once, in ShardedProver (one rank's slices of the key, one 768-byte record A | B | C per
+proof); SerialProver is its rank 0 of a world of one, whose record is the proof.
+
 Proof elements are returned in the wire-out format of the variable-base natives (affine-normalised,
 64-byte little-endian coordinates).  There is no CPU fallback: without the HIP library nothing here works.
 """
@@ -34,6 +37,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .device import _ptr, _stream, prepare_bases
 from .distributed import shard_range
 from .fft import FR, FR_MULT_GEN, root_of_unity
 from .fixed_base_msm import G1_WINDOW_TABLE, G2_WINDOW_TABLE, get_window_size
@@ -91,14 +95,6 @@ def _upload(a: np.ndarray) -> torch.Tensor:
 
 def _dev_bytes(b: bytes) -> torch.Tensor:
     return _upload(np.frombuffer(b, dtype=np.uint8))
-
-
-def _ptr(t):
-    return int(t.data_ptr())
-
-
-def _stream():
-    return int(torch.cuda.current_stream().cuda_stream)
 
 
 def g1_wire(P) -> bytes:
@@ -216,6 +212,34 @@ def assignment_bytes(full) -> np.ndarray:
     return np.frombuffer(_le32(full), dtype=np.uint8).copy()
 
 
+class _CsrDevice:
+    """A sparse matrix resident in HBM as CSR: u32 row offsets and column indices, optional 32-byte coefficients
+    (None: every coefficient is one) and the list of the rows longer than 64 terms, which the kernels of
+    ozk_r1cs_evaluate_dev / ozk_sparse_mat_vec_dev reduce in a pass of their own."""
+
+    def __init__(self, ptr, idx, val):
+        assert ptr[-1] == len(idx) < 1 << 32
+        long_rows = np.nonzero(np.diff(ptr) > 64)[0].astype(np.uint32)
+        self.rows, self.n_long = len(ptr) - 1, len(long_rows)
+        self.ptr = _upload(ptr.astype(np.uint32).view(np.uint8))
+        self.idx = _upload(idx.astype(np.uint32).view(np.uint8))
+        self.coeff = None if val is None else _dev_bytes(_le32(int(v) % FR for v in val))
+        self.long = _upload(long_rows.view(np.uint8)) if self.n_long else None
+
+    @staticmethod
+    def workspace(mats):
+        """scratch that serves any one of `mats` at a time"""
+        nbytes = int(_lib.load().ozk_r1cs_evaluate_workspace_bytes(max(mat.n_long for mat in mats)))
+        return torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+
+    def apply(self, fn, d_vec, d_out, ws):
+        """d_out = this matrix times d_vec through `fn` (ozk_r1cs_evaluate_dev or ozk_sparse_mat_vec_dev: one
+        signature); asynchronous on the current stream"""
+        opt = lambda t: None if t is None else _ptr(t)
+        _lib.check(fn(_ptr(self.ptr), _ptr(self.idx), opt(self.coeff), _ptr(d_vec), self.rows, opt(self.long),
+                      self.n_long, _ptr(d_out), _ptr(ws), ws.numel(), _stream()))
+
+
 class R1CSDevice:
     """The three constraint matrices resident in HBM as CSR (u32 row offsets / variable indices, optional 32-byte
     coefficients), with the rows R1CStoQAPWitness adds: A gets `input_i * 0 = 0` rows behind the constraints
@@ -234,26 +258,17 @@ class R1CSDevice:
                 if val is not None:
                     val = np.concatenate((val, np.ones(ni, dtype=object)))
             ptr = np.concatenate((ptr, np.full(m + 1 - len(ptr), ptr[-1], dtype=np.int64)))
-            assert len(ptr) == m + 1 and ptr[-1] == len(idx) < 1 << 32
-            long_rows = np.nonzero(np.diff(ptr) > 64)[0].astype(np.uint32)
-            d = dict(ptr=_upload(ptr.astype(np.uint32).view(np.uint8)),
-                     idx=_upload(idx.astype(np.uint32).view(np.uint8)),
-                     coeff=None if val is None else _dev_bytes(_le32(int(v) % FR for v in val)),
-                     long=_upload(long_rows.view(np.uint8)) if len(long_rows) else None,
-                     n_long=len(long_rows))
-            self.mats.append(d)
+            assert len(ptr) == m + 1
+            self.mats.append(_CsrDevice(ptr, idx, val))
         self.out = [torch.empty(m * 32, dtype=torch.uint8, device="cuda") for _ in range(3)]
-        self.ws_bytes = int(_lib.load().ozk_r1cs_evaluate_workspace_bytes(max(d["n_long"] for d in self.mats)))
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device="cuda")
+        self.ws = _CsrDevice.workspace(self.mats)
 
     def evaluate(self, d_full):
         """d_full: the assignment in HBM (num_variables x 32 B).  Asynchronous on the current stream; returns the
         three evaluation vectors (m x 32 B each)."""
-        L = _lib.load()
-        for d, out in zip(self.mats, self.out):
-            _lib.check(L.ozk_r1cs_evaluate_dev(_ptr(d["ptr"]), _ptr(d["idx"]), _ptr(d["coeff"]) if d["coeff"] is not None else None,
-                                               _ptr(d_full), self.m, _ptr(d["long"]) if d["long"] is not None else None,
-                                               d["n_long"], _ptr(out), _ptr(self.ws), self.ws_bytes, _stream()))
+        fn = _lib.load().ozk_r1cs_evaluate_dev
+        for mat, out in zip(self.mats, self.out):
+            mat.apply(fn, d_full, out, self.ws)
         return self.out
 
 
@@ -364,17 +379,9 @@ class R1CSTransposedDevice:
                     val = np.concatenate((val, np.ones(ni, dtype=object)))
             order = np.argsort(cols, kind="stable")
             ptr = np.concatenate(([0], np.cumsum(np.bincount(cols, minlength=nv))))
-            idx = rows[order]
-            assert len(ptr) == nv + 1 and ptr[-1] == len(idx) < 1 << 32
-            long_rows = np.nonzero(np.diff(ptr) > 64)[0].astype(np.uint32)
-            self.mats.append(dict(
-                ptr=_upload(ptr.astype(np.uint32).view(np.uint8)),
-                idx=_upload(idx.astype(np.uint32).view(np.uint8)),
-                coeff=None if val is None else _dev_bytes(_le32(int(v) % FR for v in val[order])),
-                long=_upload(long_rows.view(np.uint8)) if len(long_rows) else None,
-                n_long=len(long_rows)))
-        self.ws_bytes = int(_lib.load().ozk_r1cs_evaluate_workspace_bytes(max(d["n_long"] for d in self.mats)))
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device="cuda")
+            assert len(ptr) == nv + 1
+            self.mats.append(_CsrDevice(ptr, rows[order], None if val is None else val[order]))
+        self.ws = _CsrDevice.workspace(self.mats)
 
 
 class QAPRelationDevice:
@@ -416,11 +423,9 @@ def r1cs_to_qap_relation_dev(r1cs: R1CSRelation, t: int, transposed: R1CSTranspo
     _lib.check(L.ozk_qap_lagrange_dev(ctypes.cast(tb, ctypes.c_void_p), ctypes.cast(ob, ctypes.c_void_p), m, _ptr(d_lag),
                                       _ptr(d_zt), _ptr(ws), wsb, st))
     outs = []
-    for d in T.mats:
+    for mat in T.mats:
         out = torch.empty(nv * 32, dtype=torch.uint8, device="cuda")
-        _lib.check(L.ozk_sparse_mat_vec_dev(_ptr(d["ptr"]), _ptr(d["idx"]), _ptr(d["coeff"]) if d["coeff"] is not None else None,
-                                            _ptr(d_lag), nv, _ptr(d["long"]) if d["long"] is not None else None,
-                                            d["n_long"], _ptr(out), _ptr(T.ws), T.ws_bytes, st))
+        mat.apply(L.ozk_sparse_mat_vec_dev, d_lag, out, T.ws)
         outs.append(out)
     q.d_At, q.d_Bt, q.d_Ct = outs
     q.d_Ht = torch.empty((m + 1) * 32, dtype=torch.uint8, device="cuda")
@@ -437,10 +442,6 @@ def r1cs_to_qap_relation_dev(r1cs: R1CSRelation, t: int, transposed: R1CSTranspo
 
 
 # ---------------------------------------------------------------------------- fixed-base batches on the device
-def _num_windows(scalar_size, window_size):
-    return scalar_size // window_size if scalar_size % window_size == 0 else scalar_size // window_size + 1
-
-
 def batch_msm_dev(scalar_size: int, window_size: int, base_wire: bytes, scalars, type_: int) -> torch.Tensor:
     """FixedBaseMSM.batchMSM (FixedBaseMSM.java:186-315) with the result left in HBM in the variable-base
     wire-in format: uint8 tensor n x 96 (G1) / n x 192 (G2)."""
@@ -598,9 +599,9 @@ class _G1Pipeline:
     stream, each tail on a side stream out of its own tail buffer (device.VarMsmPipeline generalised to a
     length per submission)."""
 
-    def __init__(self, sizes, depth=2):
+    def __init__(self, sizes, depth=2, last_lone=True):
         L = _lib.load()
-        self.depth = depth
+        self.depth, self.last_lone = depth, last_lone
         self.ws_bytes = max(int(L.ozk_var_msm_head_workspace_bytes(n, 1)) for n in sizes)
         self.tail_bytes = max(int(L.ozk_var_msm_tail_bytes(n, 1)) for n in sizes)
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device="cuda")
@@ -628,7 +629,7 @@ class _G1Pipeline:
         main = torch.cuda.current_stream()
         if self.count >= self.depth:
             main.wait_event(self.tail_done[slot])
-        if last and os.environ.get("OZK_PROVER_LAST_LONE", "1") != "0":
+        if last and self.last_lone:
             _lib.check(L.ozk_var_msm_prepared_dev(_ptr(d_prepared), _ptr(d_scalars), n, 1, _ptr(out), _ptr(self.full_ws),
                                                   self.full_ws_bytes, int(main.cuda_stream)))
             self.tail_done[slot].record(main)
@@ -661,9 +662,9 @@ class _G1Pipeline3:
     caller's stream, its bucket ACCUMULATION on a second, its TAIL on a third / fourth — so the sort of MSM k + 1 runs
     beside the accumulation of MSM k instead of after it.  Same interface as _G1Pipeline."""
 
-    def __init__(self, sizes, depth=4, tail_streams=2):
+    def __init__(self, sizes, depth=4, tail_streams=2, last_lone=True):
         L = _lib.load()
-        self.depth = depth
+        self.depth, self.last_lone = depth, last_lone
         sb = swb = awb = 0
         for n in sizes:
             a, b, c = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
@@ -688,7 +689,7 @@ class _G1Pipeline3:
         k = self.count
         s, slot = k % 2, k % self.depth
         main = torch.cuda.current_stream()
-        if last and os.environ.get("OZK_PROVER_LAST_LONE", "1") != "0":
+        if last and self.last_lone:
             # the whole MSM on the accumulate stream, behind the accumulations already queued (see _G1Pipeline.submit)
             ready = torch.cuda.Event()
             ready.record(main)
@@ -725,6 +726,17 @@ class _G1Pipeline3:
         pass
 
 
+def _g1_pipeline(sizes):
+    """The prover's G1 pipeline as the environment selects it: three-stage by default, one tail stream (a
+    2^20-constraint proof: 15.6-15.7 ms against 15.9 with the two-stage pipeline of round 2, OZK_PROVER_PIPE3=0; two
+    tail streams, OZK_PROVER_TAIL_STREAMS=2, measure the same as one); OZK_PROVER_LAST_LONE=0 sends the last MSM
+    through the stages like the others."""
+    lone = os.environ.get("OZK_PROVER_LAST_LONE", "1") != "0"
+    if os.environ.get("OZK_PROVER_PIPE3", "1") == "1":
+        return _G1Pipeline3(sizes, tail_streams=int(os.environ.get("OZK_PROVER_TAIL_STREAMS", "1")), last_lone=lone)
+    return _G1Pipeline(sizes, last_lone=lone)
+
+
 class Proof:
     """zk_proof_systems/zkSNARK/objects/Proof.java: gA (G1), gB (G2), gC (G1) — wire-out bytes."""
 
@@ -732,158 +744,11 @@ class Proof:
         self.g_a, self.g_b, self.g_c = a, b, c
 
 
-class SerialProver:
-    """SerialProver.prove (SerialProver.java:26-119) over a proving key resident in HBM.  Construct once per
-    key (prepares the bases), call prove() per witness."""
-
-    def __init__(self, pk: ProvingKey):
-        L = _lib.load()
-        self.pk = pk
-        r1cs = pk.r1cs
-        self.ni, self.nv = r1cs.num_inputs, r1cs.num_variables
-        self.nw = self.nv - self.ni
-        self.m = lowest_power_of_two(r1cs.num_constraints + self.ni)
-        ni, nw, m = self.ni, self.nw, self.m
-        assert pk.query_h.numel() == (m + 1) * 96 and pk.query_a.numel() == self.nv * 96
-
-        def prep(d_bases, n, type_):
-            nb = int(L.ozk_var_msm_prepared_bytes(n, type_))
-            out = torch.empty(nb, dtype=torch.uint8, device="cuda")
-            _lib.check(L.ozk_var_msm_prepare_dev(_ptr(d_bases), n, type_, _ptr(out), nb, _stream()))
-            return out
-
-        # A = alpha + sum z_i A_i(t) + r delta (SerialProver.java:76-79,105): the Java sums a primary-input MSM,
-        # an auxiliary-input MSM, alpha and r delta; here ONE MSM over query A ++ [alphaG1, deltaG1] with scalars
-        # z ++ [1, r] — the same group element, hence the same affine bytes, without the two short MSMs (each of
-        # which costs a whole latency-bound tail) and four additions.  B likewise with beta, delta and s (:82-88,108-110).
-        cat = torch.cat
-        self.qa = prep(cat((pk.query_a, pk.alpha_g1, pk.delta_g1)), self.nv + 2, 1)
-        self.qb1 = prep(cat((pk.query_b_g1, pk.beta_g1, pk.delta_g1)), self.nv + 2, 1)
-        self.qb2 = prep(cat((pk.query_b_g2, pk.beta_g2, pk.delta_g2)), self.nv + 2, 2)
-        self.qh = prep(pk.query_h, m + 1, 1)
-        self.dabc = prep(pk.delta_abc_g1, nw, 1)
-        torch.cuda.synchronize()
-        # three-stage by default, one tail stream (a 2^20-constraint proof: 15.6-15.7 ms against 15.9 with the two-stage
-        # pipeline of round 2, OZK_PROVER_PIPE3=0; two tail streams measure the same as one)
-        three = os.environ.get("OZK_PROVER_PIPE3", "1") == "1"
-        ts = int(os.environ.get("OZK_PROVER_TAIL_STREAMS", "1"))
-        self.pipe = _G1Pipeline3([self.nv + 2, m + 1, nw], tail_streams=ts) if three else _G1Pipeline([self.nv + 2, m + 1, nw])
-        self.g2_ws_bytes = int(L.ozk_var_msm_head_workspace_bytes(self.nv + 2, 2))
-        self.g2_ws = torch.empty(self.g2_ws_bytes, dtype=torch.uint8, device="cuda")
-        self.g2_tail_bytes = int(L.ozk_var_msm_tail_bytes(self.nv + 2, 2))
-        self.g2_tail = torch.empty(self.g2_tail_bytes, dtype=torch.uint8, device="cuda")
-        self.s_g2 = torch.cuda.Stream()
-        # witness map + C's share: dispatched ahead of the MSMs that do not depend on them (the H MSM waits for the map)
-        self.s_fin = torch.cuda.Stream(priority=-1)
-        self.fin_ws_bytes = int(L.ozk_var_msm_workspace_bytes(3, 1))
-        self.fin_ws = torch.empty(self.fin_ws_bytes, dtype=torch.uint8, device="cuda")
-        self.q_ws_bytes = int(L.ozk_qap_witness_workspace_bytes(m))
-        self.q_ws = torch.empty(self.q_ws_bytes, dtype=torch.uint8, device="cuda")
-        self.d_h = torch.empty((m + 1) * 32, dtype=torch.uint8, device="cuda")
-        # results: G1 MSM outputs (192 B each) and G2 outputs (384 B)
-        self.o1 = torch.zeros(5, 192, dtype=torch.uint8, device="cuda")   # A, B1, deltaABC, H, C's share
-        self.o2 = torch.zeros(1, 384, dtype=torch.uint8, device="cuda")   # B
-        self.r1cs_dev = R1CSDevice(r1cs)   # the constraint matrices, uploaded once per key
-        self.omega = ctypes.create_string_buffer(root_of_unity(m).to_bytes(32, "little"), 32)
-        self.g = ctypes.create_string_buffer(FR_MULT_GEN.to_bytes(32, "little"), 32)
-
-    def close(self):
-        self.pipe.close()
-
-    def prove(self, primary, auxiliary, seed: int = SEED, timing=None, full_bytes=None) -> Proof:
-        """`full_bytes` (optional): the assignment primary ++ auxiliary already marshalled (assignment_bytes) —
-        what a caller that keeps its witness as bytes hands over; otherwise it is marshalled here."""
-        L = _lib.load()
-        pk, ni, nw, m = self.pk, self.ni, self.nw, self.m
-        T = {}
-        t0 = time.perf_counter()
-        if full_bytes is None:
-            full_bytes = assignment_bytes(list(primary) + list(auxiliary))
-        assert full_bytes.size == self.nv * 32
-        T["marshal_assignment_host_ms"] = (time.perf_counter() - t0) * 1e3
-        r = fr_random(seed)                                      # SerialProver.java:58-59
-        s = fr_random(seed)
-        t1 = time.perf_counter()
-        d_full = torch.from_numpy(full_bytes).cuda()
-        tails = _dev_bytes(_le32([1, r, 1, s, s, r, (FR - r * s % FR) % FR]))
-        d_aux = d_full[ni * 32:]
-        d_full_r = torch.cat((d_full, tails[:64]))               # z ++ [1, r]
-        d_full_s = torch.cat((d_full, tails[64:128]))            # z ++ [1, s]
-        d_fin_sc = tails[128:]                                   # [s, r, -rs]
-        torch.cuda.synchronize()
-        T["upload_ms"] = (time.perf_counter() - t1) * 1e3
-        t2 = time.perf_counter()
-        main = torch.cuda.current_stream()
-        ready = torch.cuda.Event()
-        ready.record(main)
-        o1, o2 = self.o1, self.o2
-        nv = self.nv
-        # B in G2 (doubleMSM, SerialProver.java:82-88): own stream, nothing to wait for but the uploads.  Issued
-        # first: its tail is the longest latency-bound chain of the proof and hides under the G1 accumulations.
-        self.s_g2.wait_event(ready)
-        with torch.cuda.stream(self.s_g2):
-            _lib.check(L.ozk_var_msm_head_prepared_dev(_ptr(self.qb2), _ptr(d_full_s), nv + 2, 2, _ptr(self.g2_ws),
-                                                       self.g2_ws_bytes, _ptr(self.g2_tail), self.g2_tail_bytes, _stream(),
-                                                       None))
-            _lib.check(L.ozk_var_msm_tail_mode_dev(nv + 2, 2, _ptr(self.g2_tail), self.g2_tail_bytes, _ptr(o2[0]),
-                                                   _stream(), None, 1))
-            g2_done = torch.cuda.Event()
-            g2_done.record(self.s_g2)
-        # witness map (SerialProver.java:36-41): constraint evaluations (R1CStoQAP.java:143-160,195-199) and the
-        # seven transforms on the device; coefficientsH stay in HBM.  Own stream: only the H MSM waits for it, the
-        # three MSMs over the assignment run beside it.
-        self.s_fin.wait_event(ready)
-        with torch.cuda.stream(self.s_fin):
-            d_ev = self.r1cs_dev.evaluate(d_full)
-            _lib.check(L.ozk_qap_witness_dev(_ptr(d_ev[0]), _ptr(d_ev[1]), _ptr(d_ev[2]), m, ctypes.cast(self.omega, ctypes.c_void_p),
-                                             ctypes.cast(self.g, ctypes.c_void_p), _ptr(self.d_h), _ptr(self.q_ws),
-                                             self.q_ws_bytes, _stream()))
-            h_ready = torch.cuda.Event()
-            h_ready.record(self.s_fin)
-        p = self.pipe
-        ev_a = p.submit(self.qa, d_full_r, nv + 2, o1[0])        # :76-79,105  A
-        ev_b = p.submit(self.qb1, d_full_s, nv + 2, o1[1])       # :82-88,108-110  B in G1
-        # A and B1 are complete once their tails are: their share of C — s A + r B1 - r s delta (:114) — is a 3-term
-        # MSM that runs on its own stream while the long MSMs still occupy the pipeline.  (The waits are queued NOW:
-        # the pipeline re-records these per-slot events for the next two submissions.)
-        self.s_fin.wait_event(ev_a)
-        self.s_fin.wait_event(ev_b)
-        ev_l = p.submit(self.dabc, d_aux, nw, o1[2])             # :98-101 deltaABC
-        main.wait_event(h_ready)
-        ev_h = p.submit(self.qh, self.d_h, m + 1, o1[3], last=True)   # :91-93 query H
-        with torch.cuda.stream(self.s_fin):
-            fin_bases = torch.cat((wire_out_to_in(o1[0], 1), wire_out_to_in(o1[1], 1), pk.delta_g1))
-            _lib.check(L.ozk_var_msm_dev(_ptr(fin_bases), _ptr(d_fin_sc), 3, 1, _ptr(o1[4]), _ptr(self.fin_ws),
-                                         self.fin_ws_bytes, _stream()))
-            fin_done = torch.cuda.Event()
-            fin_done.record(self.s_fin)
-        main.wait_event(ev_l)
-        main.wait_event(ev_h)
-        main.wait_event(fin_done)
-        # C = evaluationABC + H(t)Z(t)/delta + (s A + r B1 - r s delta)   (:102,:114)
-        c_out = torch.zeros(192, dtype=torch.uint8, device="cuda")
-        _lib.check(L.ozk_points_sum_dev(_ptr(o1[2:5]), 3, 1, _ptr(c_out), int(main.cuda_stream)))
-        main.wait_event(g2_done)
-        torch.cuda.synchronize()
-        T["gpu_ms"] = (time.perf_counter() - t2) * 1e3
-        proof = Proof(bytes(o1[0].cpu().numpy()), bytes(o2[0].cpu().numpy()), bytes(c_out.cpu().numpy()))
-        self._keep = (d_full, tails, d_full_r, d_full_s, fin_bases, d_ev)
-        if timing is not None:
-            timing.update(T)
-        return proof
-
-    def coefficients_h(self):
-        """coefficientsH of the last prove() (m + 1 ints), for checks."""
-        raw = bytes(self.d_h.cpu().numpy())
-        return [int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(self.m + 1)]
-
-
-# ---------------------------------------------------------------------------- sharded prover
 RECORD_BYTES = 768   # a rank's partial: A_r (G1, 192) | B_r (G2, 384) | C_r (G1, 192), wire-out
 
 
 def shard_plan(nv: int, m: int, nw: int, rank: int, world: int):
-    """The slices [lo, hi) rank `rank` of `world` owns of the five MSMs of a proof, as SerialProver lays them out:
+    """The slices [lo, hi) rank `rank` of `world` owns of the five MSMs of a proof, as the prover lays them out:
     A, B1 and B2 over query A / query B ++ [alpha or beta, delta] (nv + 2 pairs), L over deltaABC (nw), H over
     query H (m + 1)."""
     ab = shard_range(nv + 2, rank, world)
@@ -898,7 +763,7 @@ def c_share_scalars(r: int, s: int, rank: int):
 
 def _rows(parts, lo, hi, row_bytes):
     """rows [lo, hi) of the concatenation of `parts` (uint8 tensors of row_bytes-byte rows), without building the
-    whole concatenation"""
+    whole concatenation (a range inside one part is a view of it)"""
     out, base = [], 0
     for t in parts:
         n = t.numel() // row_bytes
@@ -906,7 +771,7 @@ def _rows(parts, lo, hi, row_bytes):
         if a < b:
             out.append(t[a * row_bytes:b * row_bytes])
         base += n
-    return torch.cat(out)
+    return out[0] if len(out) == 1 else torch.cat(out)
 
 
 def _prepared_bytes(n, type_):
@@ -919,7 +784,8 @@ class ShardedProver:
     share of every proof element over its slices of the key (shard_plan) before any exchange, and sends one
     768-byte record; the proof is the sum of the records (distributed.distributed_prove, device.groth16_combine).
     Only this rank's slices are prepared (key_bytes: this rank's prepared-key bytes against SerialProver's).
-    The witness map runs on every rank (a replica: DESIGN.md section 7)."""
+    The witness map runs on every rank (a replica: DESIGN.md section 7).  This class holds the one schedule of a
+    proof's device work (_enqueue); SerialProver is its rank 0 of a world of one."""
 
     def __init__(self, pk: ProvingKey, rank: int, world: int):
         L = _lib.load()
@@ -936,38 +802,35 @@ class ShardedProver:
             raise ValueError("a world of %d leaves a rank an empty slice (slice lengths nv + 2 = %d, nw = %d, m + 1 = %d)"
                              % (world, nv + 2, nw, m + 1))
         self.plan = plan = shard_plan(nv, m, nw, rank, world)
-        self.n = {k: hi - lo for k, (lo, hi) in plan.items()}
 
         def prep(parts, key, row_bytes, type_):
             lo, hi = plan[key]
-            nb = _prepared_bytes(hi - lo, type_)
-            out = torch.empty(nb, dtype=torch.uint8, device="cuda")
-            _lib.check(L.ozk_var_msm_prepare_dev(_ptr(_rows(parts, lo, hi, row_bytes)), hi - lo, type_, _ptr(out), nb,
-                                                 _stream()))
-            torch.cuda.current_stream().synchronize()   # the concatenated slice dies here
+            out = prepare_bases(_rows(parts, lo, hi, row_bytes), hi - lo, type_)
+            torch.cuda.current_stream().synchronize()   # a concatenated slice dies here
             return out
 
+        # A = alpha + sum z_i A_i(t) + r delta (SerialProver.java:76-79,105): the Java sums a primary-input MSM,
+        # an auxiliary-input MSM, alpha and r delta; here ONE MSM over query A ++ [alphaG1, deltaG1] with scalars
+        # z ++ [1, r] — the same group element, hence the same affine bytes, without the two short MSMs (each of
+        # which costs a whole latency-bound tail) and four additions.  B likewise with beta, delta and s (:82-88,108-110).
         self.qa = prep((pk.query_a, pk.alpha_g1, pk.delta_g1), "A", 96, 1)
         self.qb1 = prep((pk.query_b_g1, pk.beta_g1, pk.delta_g1), "B1", 96, 1)
         self.qb2 = prep((pk.query_b_g2, pk.beta_g2, pk.delta_g2), "B2", 192, 2)
         self.dabc = prep((pk.delta_abc_g1,), "L", 96, 1)
         self.qh = prep((pk.query_h,), "H", 96, 1)
-        self.delta_g1 = pk.delta_g1.clone()
+        self.delta_g1 = pk.delta_g1
         self.key_bytes = {
             "rank": sum(int(t.numel()) for t in (self.qa, self.qb1, self.qb2, self.dabc, self.qh)),
             "serial": (2 * _prepared_bytes(nv + 2, 1) + _prepared_bytes(nv + 2, 2) + _prepared_bytes(nw, 1)
                        + _prepared_bytes(m + 1, 1))}
-        n_ab, n_l, n_h = self.n["A"], self.n["L"], self.n["H"]
-        # the streams and the pipeline of SerialProver, sized to this rank's slices
-        three = os.environ.get("OZK_PROVER_PIPE3", "1") == "1"
-        ts = int(os.environ.get("OZK_PROVER_TAIL_STREAMS", "1"))
-        sizes = [n_ab, n_h, n_l]
-        self.pipe = _G1Pipeline3(sizes, tail_streams=ts) if three else _G1Pipeline(sizes)
+        n_ab, n_l, n_h = (hi - lo for lo, hi in (plan["A"], plan["L"], plan["H"]))
+        self.pipe = _g1_pipeline([n_ab, n_h, n_l])
         self.g2_ws_bytes = int(L.ozk_var_msm_head_workspace_bytes(n_ab, 2))
         self.g2_ws = torch.empty(self.g2_ws_bytes, dtype=torch.uint8, device="cuda")
         self.g2_tail_bytes = int(L.ozk_var_msm_tail_bytes(n_ab, 2))
         self.g2_tail = torch.empty(self.g2_tail_bytes, dtype=torch.uint8, device="cuda")
         self.s_g2 = torch.cuda.Stream()
+        # witness map + C's share: dispatched ahead of the MSMs that do not depend on them (the H MSM waits for the map)
         self.s_fin = torch.cuda.Stream(priority=-1)
         self.fin_ws_bytes = int(L.ozk_var_msm_workspace_bytes(3, 1))
         self.fin_ws = torch.empty(self.fin_ws_bytes, dtype=torch.uint8, device="cuda")
@@ -975,7 +838,7 @@ class ShardedProver:
         self.q_ws = torch.empty(self.q_ws_bytes, dtype=torch.uint8, device="cuda")
         self.d_h = torch.empty((m + 1) * 32, dtype=torch.uint8, device="cuda")
         self.o1 = torch.zeros(4, 192, dtype=torch.uint8, device="cuda")   # B1_r, L_r, H_r, C's 3-term share
-        self.r1cs_dev = R1CSDevice(r1cs)
+        self.r1cs_dev = R1CSDevice(r1cs)   # the constraint matrices, uploaded once per key
         self.omega = ctypes.create_string_buffer(root_of_unity(m).to_bytes(32, "little"), 32)
         self.g = ctypes.create_string_buffer(FR_MULT_GEN.to_bytes(32, "little"), 32)
         torch.cuda.synchronize()
@@ -983,36 +846,42 @@ class ShardedProver:
     def close(self):
         self.pipe.close()
 
-    def prove_partial(self, primary, auxiliary, seed: int = SEED, timing=None, full_bytes=None) -> torch.Tensor:
-        """This rank's 768-byte record A_r | B_r | C_r (uint8 tensor in HBM, complete on return) with
-        C_r = L_r + H_r + s A_r + r B1_r (- rs deltaG1 on rank 0).  `timing` (optional dict) receives the stage
-        times of the device work from its start: witness map done, L and H MSMs done, record done."""
-        L = _lib.load()
-        ni, m, nv = self.ni, self.m, self.nv
-        (lo, hi), (llo, lhi), (hlo, hhi) = self.plan["A"], self.plan["L"], self.plan["H"]
-        n_ab, n_l, n_h = hi - lo, lhi - llo, hhi - hlo
-        t0 = time.perf_counter()
+    def _marshal(self, primary, auxiliary, full_bytes):
+        """`full_bytes` if given: the assignment primary ++ auxiliary already marshalled (assignment_bytes) — what a
+        caller that keeps its witness as bytes hands over; otherwise it is marshalled here."""
         if full_bytes is None:
             full_bytes = assignment_bytes(list(primary) + list(auxiliary))
-        assert full_bytes.size == nv * 32
+        assert full_bytes.size == self.nv * 32
+        return full_bytes
+
+    def _upload_witness(self, full_bytes, seed):
+        """What _enqueue works on, in HBM: the assignment, this rank's slices of z ++ [1, r] and z ++ [1, s], the
+        scalars of C's 3-term share, and the zeroed record."""
         r = fr_random(seed)                                      # SerialProver.java:58-59
         s = fr_random(seed)
+        lo, hi = self.plan["A"]
         d_full = torch.from_numpy(full_bytes).cuda()
         tails = _dev_bytes(_le32([1, r, 1, s] + c_share_scalars(r, s, self.rank)))
-        d_sc_r = torch.cat((d_full, tails[:64]))[32 * lo:32 * hi]        # (z ++ [1, r]) over this rank's slice
-        d_sc_s = torch.cat((d_full, tails[64:128]))[32 * lo:32 * hi]     # (z ++ [1, s])
-        d_aux = d_full[32 * (ni + llo):32 * (ni + lhi)]
-        d_fin_sc = tails[128:]
+        d_sc_r = torch.cat((d_full, tails[:64]))[32 * lo:32 * hi]
+        d_sc_s = torch.cat((d_full, tails[64:128]))[32 * lo:32 * hi]
         rec = torch.zeros(RECORD_BYTES, dtype=torch.uint8, device="cuda")
+        return d_full, d_sc_r, d_sc_s, tails[128:], rec
+
+    def _enqueue(self, d_full, d_sc_r, d_sc_s, d_fin_sc, rec, mark=None):
+        """One proof's device work over the tensors of _upload_witness, asynchronous: on return the current stream is behind
+        all of it, and `rec` will hold A_r | B_r | C_r.  mark(name, stream), if given, is called where the device
+        work starts, where the witness map, the L and H MSMs and the record are done (timing events)."""
+        L = _lib.load()
+        ni, m, o1 = self.ni, self.m, self.o1
+        (lo, hi), (llo, lhi), (hlo, hhi) = self.plan["A"], self.plan["L"], self.plan["H"]
+        n_ab = hi - lo
         main = torch.cuda.current_stream()
-        ev = (lambda: torch.cuda.Event(enable_timing=True)) if timing is not None else None
-        if ev:
-            t_start = ev()
-            t_start.record(main)
+        if mark:
+            mark("start", main)
         ready = torch.cuda.Event()
         ready.record(main)
-        o1 = self.o1
-        # B_r in G2 first, on its own stream (SerialProver.prove)
+        # B_r in G2 (doubleMSM, SerialProver.java:82-88): own stream, nothing to wait for but the uploads.  Issued
+        # first: its tail is the longest latency-bound chain of the proof and hides under the G1 accumulations.
         self.s_g2.wait_event(ready)
         with torch.cuda.stream(self.s_g2):
             _lib.check(L.ozk_var_msm_head_prepared_dev(_ptr(self.qb2), _ptr(d_sc_s), n_ab, 2, _ptr(self.g2_ws),
@@ -1022,7 +891,9 @@ class ShardedProver:
                                                    _stream(), None, 1))
             g2_done = torch.cuda.Event()
             g2_done.record(self.s_g2)
-        # the witness map, whole, on the priority stream: coefficientsH of every rank are the same
+        # witness map (SerialProver.java:36-41): constraint evaluations (R1CStoQAP.java:143-160,195-199) and the
+        # seven transforms on the device; coefficientsH stay in HBM.  Own stream: only the H MSM waits for it, the
+        # three MSMs over the assignment run beside it.  Whole on every rank: coefficientsH are the same on all.
         self.s_fin.wait_event(ready)
         with torch.cuda.stream(self.s_fin):
             d_ev = self.r1cs_dev.evaluate(d_full)
@@ -1031,17 +902,19 @@ class ShardedProver:
                                              self.q_ws_bytes, _stream()))
             h_ready = torch.cuda.Event()
             h_ready.record(self.s_fin)
-            if ev:
-                t_map = ev()
-                t_map.record(self.s_fin)
+            if mark:
+                mark("map", self.s_fin)
         p = self.pipe
-        ev_a = p.submit(self.qa, d_sc_r, n_ab, rec[:192])
-        ev_b = p.submit(self.qb1, d_sc_s, n_ab, o1[0])
+        ev_a = p.submit(self.qa, d_sc_r, n_ab, rec[:192])         # :76-79,105  A
+        ev_b = p.submit(self.qb1, d_sc_s, n_ab, o1[0])            # :82-88,108-110  B in G1
+        # A_r and B1_r are complete once their tails are: their share of C — s A + r B1 - r s delta (:114) — is a
+        # 3-term MSM that runs on its own stream while the long MSMs still occupy the pipeline.  (The waits are queued
+        # NOW: the pipeline re-records these per-slot events for the next two submissions.)
         self.s_fin.wait_event(ev_a)
         self.s_fin.wait_event(ev_b)
-        ev_l = p.submit(self.dabc, d_aux, n_l, o1[1])
+        ev_l = p.submit(self.dabc, d_full[32 * (ni + llo):32 * (ni + lhi)], lhi - llo, o1[1])   # :98-101 deltaABC
         main.wait_event(h_ready)
-        ev_h = p.submit(self.qh, self.d_h[32 * hlo:32 * hhi], n_h, o1[2], last=True)
+        ev_h = p.submit(self.qh, self.d_h[32 * hlo:32 * hhi], hhi - hlo, o1[2], last=True)      # :91-93 query H
         with torch.cuda.stream(self.s_fin):
             fin_bases = torch.cat((wire_out_to_in(rec[:192], 1), wire_out_to_in(o1[0], 1), self.delta_g1))
             _lib.check(L.ozk_var_msm_dev(_ptr(fin_bases), _ptr(d_fin_sc), 3, 1, _ptr(o1[3]), _ptr(self.fin_ws),
@@ -1050,29 +923,69 @@ class ShardedProver:
             fin_done.record(self.s_fin)
         main.wait_event(ev_l)
         main.wait_event(ev_h)
-        if ev:
-            t_msm = ev()
-            t_msm.record(main)
+        if mark:
+            mark("msm", main)
         main.wait_event(fin_done)
-        # C_r = L_r + H_r + (s A_r + r B1_r [- rs delta])
+        # C_r = L_r + H_r + (s A_r + r B1_r [- rs delta]): evaluationABC + H(t)Z(t)/delta + C's share (:102,:114)
         _lib.check(L.ozk_points_sum_dev(_ptr(o1[1:4]), 3, 1, _ptr(rec[576:]), int(main.cuda_stream)))
         main.wait_event(g2_done)
-        if ev:
-            t_end = ev()
-            t_end.record(main)
+        if mark:
+            mark("end", main)
+        self._keep = (d_full, d_sc_r, d_sc_s, d_fin_sc, fin_bases, d_ev)
+
+    def prove_partial(self, primary, auxiliary, seed: int = SEED, timing=None, full_bytes=None) -> torch.Tensor:
+        """This rank's 768-byte record A_r | B_r | C_r (uint8 tensor in HBM, complete on return) with
+        C_r = L_r + H_r + s A_r + r B1_r (- rs deltaG1 on rank 0).  `timing` (optional dict) receives the stage
+        times of the device work from its start: witness map done, L and H MSMs done, record done."""
+        t0 = time.perf_counter()
+        up = self._upload_witness(self._marshal(primary, auxiliary, full_bytes), seed)
+        at = {}
+
+        def mark(name, stream):
+            at[name] = torch.cuda.Event(enable_timing=True)
+            at[name].record(stream)
+
+        self._enqueue(*up, mark=mark if timing is not None else None)
         torch.cuda.synchronize()
-        self._keep = (d_full, tails, d_sc_r, d_sc_s, fin_bases, d_ev)
         if timing is not None:
-            timing.update({"witness_map_done_ms": t_start.elapsed_time(t_map),
-                           "lh_msm_done_ms": t_start.elapsed_time(t_msm),
-                           "record_done_ms": t_start.elapsed_time(t_end),
+            timing.update({"witness_map_done_ms": at["start"].elapsed_time(at["map"]),
+                           "lh_msm_done_ms": at["start"].elapsed_time(at["msm"]),
+                           "record_done_ms": at["start"].elapsed_time(at["end"]),
                            "partial_wall_ms": (time.perf_counter() - t0) * 1e3})
-        return rec
+        return up[-1]
 
     def coefficients_h(self):
-        """coefficientsH of the last prove_partial() (m + 1 ints), for checks."""
-        raw = bytes(self.d_h.cpu().numpy())
-        return [int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(self.m + 1)]
+        """coefficientsH of the last proof (m + 1 ints), for checks."""
+        return _ints_from_dev(self.d_h)
+
+
+class SerialProver(ShardedProver):
+    """SerialProver.prove (SerialProver.java:26-119) over a proving key resident in HBM: rank 0 of a world of one of
+    the sharded schedule, whose record already is the proof (C_0 = L + H + s A + r B1 - rs delta), so nothing is
+    exchanged or combined.  Construct once per key (prepares the bases), call prove() per witness."""
+
+    def __init__(self, pk: ProvingKey):
+        super().__init__(pk, 0, 1)
+
+    def prove(self, primary, auxiliary, seed: int = SEED, timing=None, full_bytes=None) -> Proof:
+        """`full_bytes` (optional): the assignment already marshalled (assignment_bytes).  `timing` (optional dict)
+        receives the host marshalling, the upload and the device work as wall times, a synchronise between each."""
+        T = {}
+        t0 = time.perf_counter()
+        full_bytes = self._marshal(primary, auxiliary, full_bytes)
+        T["marshal_assignment_host_ms"] = (time.perf_counter() - t0) * 1e3
+        t1 = time.perf_counter()
+        up = self._upload_witness(full_bytes, seed)
+        torch.cuda.synchronize()
+        T["upload_ms"] = (time.perf_counter() - t1) * 1e3
+        t2 = time.perf_counter()
+        self._enqueue(*up)
+        torch.cuda.synchronize()
+        T["gpu_ms"] = (time.perf_counter() - t2) * 1e3
+        raw = bytes(up[-1].cpu().numpy())
+        if timing is not None:
+            timing.update(T)
+        return Proof(raw[:192], raw[192:576], raw[576:])
 
 
 # ---------------------------------------------------------------------------- verification (pairing.py)
