@@ -464,6 +464,31 @@ int ozk_fr_poly_eval_dev(const void* d_coeffs, int32_t npolys, int32_t len, int6
                          const uint8_t* r_host32, void* d_out, void* d_workspace, size_t workspace_bytes,
                          void* stream);
 
+/* ---- batched MSM over shared bases (msm_multi.hip; no counterpart in the reference, whose verifier runs one
+ * variable-base MSM per proof): out_i = sum_{j < n} s_ij P_j for k scalar rows over the SAME n bases, G1 only.
+ * A window table of every base is built once (ozk_multi_msm_prepare_dev); a run is table gathers and mixed
+ * additions, no sort, buckets or doublings.  Results are byte-identical to k calls of ozk_var_msm_dev.
+ *   d_bases    n x 96 B wire-in G1 points (X | Y | Z, 32-byte little-endian, as ozk_var_msm_dev; Z = 0 is
+ *              infinity, Z != 1 is accepted)
+ *   d_table    ozk_multi_msm_table_bytes(n, type) bytes, 64-byte affine records; read-only after the build, may
+ *              serve any number of runs and streams ordered after it
+ *   d_scalars  k rows of n x 32 B little-endian, row-major, 16-byte aligned.  The contract is canonical scalars
+ *              in [0, r); a value >= r is REDUCED mod r first (glv_decompose), which is the group element
+ *              ozk_var_msm_dev computes for it too, so both return the same bytes
+ *   d_out      k x 192 B wire-out records (64-byte little-endian coordinates, Z = 1; infinity (0, 1, 0))
+ *   workspace  ozk_multi_msm_workspace_bytes(n, k, type) covers the build and a run of k rows
+ *   plan       window size (signed digits, 2^(bits-1) entries per window) and windows per 128-bit GLV half
+ * Limits: 1 <= n <= 4096, k >= 1, k * n <= 2^28, type == OZK_G1.  Outside them (G2 included) the size functions
+ * return 0 and the entry points OZK_E_INVALID, as they do for a short table or workspace, and nothing is
+ * launched.  Everything is enqueued on `stream`; nothing is allocated or synchronised. */
+size_t ozk_multi_msm_table_bytes(int32_t n, int32_t type);
+int ozk_multi_msm_prepare_dev(const void* d_bases, int32_t n, int32_t type, void* d_table, size_t table_bytes,
+                              void* d_workspace, size_t workspace_bytes, void* stream);
+size_t ozk_multi_msm_workspace_bytes(int32_t n, int32_t k, int32_t type);
+int ozk_multi_msm_dev(const void* d_table, const void* d_scalars, int32_t n, int32_t k, int32_t type, void* d_out,
+                      void* d_workspace, size_t workspace_bytes, void* stream);
+int ozk_multi_msm_plan(int32_t n, int32_t* window_bits, int32_t* windows);
+
 #ifdef __cplusplus
 }
 #endif

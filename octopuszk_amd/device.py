@@ -67,6 +67,59 @@ class VarMsmWorkspace:
         return self.out
 
 
+class SharedBaseMsm:
+    """k MSMs over the SAME n G1 bases, out_i = sum_j s_ij P_j (ozk_multi_msm_*): the window table of the bases is
+    built once, here, asynchronously on the current stream; `run` then only gathers and adds.
+
+    As for VarMsmWorkspace, this object (table, workspace) and the inputs must stay alive until the stream has been
+    synchronised; references to the bases and to the last scalars are kept.  The workspace grows when k grows: the
+    old one is released to torch's stream-ordered allocator, so runs must stay on one stream (or be synchronised)."""
+
+    def __init__(self, d_bases, n):
+        L = _lib.load()
+        self.n = int(n)
+        self.table_bytes = int(L.ozk_multi_msm_table_bytes(self.n, 1))
+        if self.table_bytes == 0:
+            raise _lib.OzkError("shared-base MSM: n = %d rejected (1 <= n <= 4096)" % self.n)
+        if d_bases.numel() * d_bases.element_size() < self.n * 96:
+            raise ValueError("d_bases holds fewer than n wire-format G1 points")
+        wb, oc = ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(L.ozk_multi_msm_plan(self.n, ctypes.byref(wb), ctypes.byref(oc)))
+        self.window_bits, self.windows = wb.value, oc.value
+        self._bases = d_bases
+        self.device = d_bases.device
+        self.table = torch.empty(self.table_bytes, dtype=torch.uint8, device=self.device)
+        self.k_cap, self.ws_bytes, self.ws = 0, 0, None
+        self._grow(1)
+        _lib.check(L.ozk_multi_msm_prepare_dev(_ptr(d_bases), self.n, 1, _ptr(self.table), self.table_bytes,
+                                               _ptr(self.ws), self.ws_bytes, _stream()))
+
+    def _grow(self, k):
+        L = _lib.load()
+        nbytes = int(L.ozk_multi_msm_workspace_bytes(self.n, k, 1))
+        if nbytes == 0:
+            raise _lib.OzkError("shared-base MSM: shape n = %d, k = %d rejected (k >= 1, k * n <= 2^28)" % (self.n, k))
+        if nbytes > self.ws_bytes:
+            self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self.ws_bytes = nbytes
+        self.k_cap = max(self.k_cap, k)
+
+    def run(self, d_scalars, k):
+        """d_scalars: uint8 [k * n * 32], k rows of n little-endian scalars, in HBM.  Asynchronous on the current
+        stream; returns a new uint8 tensor [k * 192] of wire-out points."""
+        L = _lib.load()
+        k = int(k)
+        if k < 1 or d_scalars.numel() * d_scalars.element_size() < k * self.n * 32:
+            raise ValueError("d_scalars holds fewer than k rows of n 32-byte scalars")
+        # (the workspace size is not monotonic in k: the lanes-per-output split changes with it)
+        self._grow(k)
+        out = torch.empty(k * 192, dtype=torch.uint8, device=self.device)
+        self._inputs = d_scalars
+        _lib.check(L.ozk_multi_msm_dev(_ptr(self.table), _ptr(d_scalars), self.n, k, 1, _ptr(out), _ptr(self.ws),
+                                       self.ws_bytes, _stream()))
+        return out
+
+
 class VarMsmPipeline:
     """Several device-resident MSMs in flight: heads (throughput-bound) run back to back on the
     caller's stream and share ONE workspace; each tail (latency-bound: upper window-sum levels,

@@ -186,3 +186,27 @@ class PreparedBases:
             self.close()
         except Exception:
             pass
+
+
+def batched_serial_msm(scalar_rows, bases):
+    """K serialMSM results over the SAME G1 bases, result_i = sum_j scalar_rows[i][j] * bases[j], through the
+    shared-base batched MSM (ozk_multi_msm_*; no counterpart in the reference, which runs serialMSM once per row):
+    the window table of the bases is built once for all rows.  Rows are lists of Python ints (reduced mod r by the
+    library), bases Jacobian integer triples; returns K affine triples (x, y, 1), or (0, 1, 0) for infinity, as
+    unmarshal_g1 gives them."""
+    import numpy as np
+    import torch
+
+    from . import device as _device
+    n = len(bases)
+    rows = list(scalar_rows)
+    if not rows:
+        return []
+    for row in rows:
+        if len(row) != n:
+            raise ValueError("a scalar row of %d entries for %d bases" % (len(row), n))
+    d_bases = torch.from_numpy(np.frombuffer(marshal_g1(bases), dtype=np.uint8).copy()).cuda()
+    d_scalars = torch.from_numpy(np.frombuffer(b"".join(marshal_scalars(row) for row in rows), dtype=np.uint8).copy()).cuda()
+    msm = _device.SharedBaseMsm(d_bases, n)
+    raw = bytes(msm.run(d_scalars, len(rows)).cpu().numpy())
+    return [unmarshal_g1(raw[192 * i:192 * (i + 1)]) for i in range(len(rows))]

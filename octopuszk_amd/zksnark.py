@@ -1002,6 +1002,7 @@ class VerificationKey:
         self.gamma_prep = _pairing.prepare_g2(gamma_g2)
         self.delta_prep = _pairing.prepare_g2(delta_g2)
         self._msm = None
+        self._multi = None
 
     def evaluation_abc(self, primary) -> torch.Tensor:
         """sum primary_i gammaABC_i (Verifier.java:45-47, VariableBaseMSM.serialMSM) through the variable-base MSM;
@@ -1012,6 +1013,18 @@ class VerificationKey:
         if self._msm is None:
             self._msm = _device.VarMsmWorkspace(self.num_inputs, 1)
         return self._msm.run(self.gamma_abc_g1, _dev_bytes(_le32(primary))).clone()
+
+    def evaluation_abc_batch(self, primaries) -> torch.Tensor:
+        """evaluation_abc of every row of `primaries`, concatenated (K x 192 bytes, byte for byte what K calls of
+        evaluation_abc return), through the shared-base batched MSM: the window table of gammaABC is built at the
+        first call and kept with the key.  Asynchronous on the current stream."""
+        from . import device as _device
+        for primary in primaries:
+            if len(primary) != self.num_inputs:
+                raise ValueError("%d primary inputs for a key of %d" % (len(primary), self.num_inputs))
+        if self._multi is None:
+            self._multi = _device.SharedBaseMsm(self.gamma_abc_g1, self.num_inputs)
+        return self._multi.run(_dev_bytes(b"".join(_le32(primary) for primary in primaries)), len(primaries))
 
 
 def verification_key(crs: CRS) -> VerificationKey:
@@ -1058,16 +1071,34 @@ class Verifier:
     def verify(vk: VerificationKey, primary, proof: Proof) -> bool:
         return Verifier.verify_batch(vk, [primary], [proof])[0]
 
+    # verify_batch(abc="auto") takes the batched evaluationABC from this many proofs upwards.  Per proof the
+    # variable-base MSM costs ~0.7 ms; the batched path costs the table build once per key (a serial chain of 128
+    # doublings, ~1 ms, plus 9 small launches per chunk of bases) and then three launches per batch, so it pays from
+    # the second or third proof of the FIRST batch and from the first proof of every later one.  Below the
+    # crossover a key that only ever verifies single proofs keeps the table's memory (128 KiB per input) free.
+    ABC_BATCH_CROSSOVER = 4
+
     @staticmethod
-    def verify_batch(vk: VerificationKey, primaries, proofs) -> list:
+    def verify_batch(vk: VerificationKey, primaries, proofs, abc="auto") -> list:
         """k proofs in one launch pair (the three Miller loops of every proof, then one final exponentiation per
-        proof); evaluationABC is one variable-base MSM per proof."""
+        proof).  evaluationABC: abc="per_proof" runs one variable-base MSM per proof, abc="batched" one shared-base
+        batched MSM for all of them (VerificationKey.evaluation_abc_batch), abc="auto" the batched one from
+        ABC_BATCH_CROSSOVER proofs upwards (or whenever the key already has its table).  The points, and so the
+        verdicts, are the same in all three."""
         from . import pairing as _pairing
+        if abc not in ("auto", "per_proof", "batched"):
+            raise ValueError("abc must be 'auto', 'per_proof' or 'batched'")
         if len(primaries) != len(proofs) or not proofs:
             raise ValueError("one primary input per proof, at least one proof")
         for primary in primaries:
             assert primary[0] % FR == 1   # Verifier.java:31-32
-        abc = torch.cat([vk.evaluation_abc(primary) for primary in primaries])
+        if abc == "auto":
+            batched = len(proofs) >= Verifier.ABC_BATCH_CROSSOVER or vk._multi is not None
+            abc = "batched" if batched and 1 <= vk.num_inputs <= 4096 else "per_proof"
+        if abc == "batched":
+            abc = vk.evaluation_abc_batch(primaries)
+        else:
+            abc = torch.cat([vk.evaluation_abc(primary) for primary in primaries])
         recs = _dev_bytes(b"".join(proof_record(p) for p in proofs))
         ok = _pairing.groth16_verify(vk.alpha_g1_beta_g2, vk.gamma_prep, vk.delta_prep, recs, abc)
         return [bool(v) for v in ok.cpu().tolist()]
