@@ -489,6 +489,33 @@ int ozk_multi_msm_dev(const void* d_table, const void* d_scalars, int32_t n, int
                       void* d_workspace, size_t workspace_bytes, void* stream);
 int ozk_multi_msm_plan(int32_t n, int32_t* window_bits, int32_t* windows);
 
+/* ---- compressed points and compressed Groth16 proofs (point_codec.hip).
+ * A compressed point is its affine x, little-endian, plus two flags in the two top bits of the last byte, which are
+ * free because x < q < 2^254: bit 7 Y_LARGER (the canonical y satisfies y > q - y), bit 6 INFINITY (every other bit
+ * of the encoding is then zero).  G1: 32 bytes.  G2: 64 bytes, x.c0 | x.c1, the flags in byte 63, Y_LARGER decided
+ * on y.c1 unless y.c1 = 0, then on y.c0.  A proof: 128 bytes, A (32) | B (64) | C (32).
+ * Decoding is strict; the code of a point is 0 ok, 1 a coordinate >= q, 2 bad infinity encoding (a stray bit next
+ * to INFINITY, or Y_LARGER on a point with y = 0), 3 no curve point has this x.  There is NO subgroup check: a G2
+ * point that decodes lies on the twist, not necessarily in the order-r subgroup (ozk_groth16_wellformed_dev checks
+ * that).
+ *   ozk_points_decompress_dev   n encodings of `type` (OZK_G1 / OZK_G2) -> n points X | Y | Z with Z = 1 in
+ *                               out_format 0 (wire-in, 32-byte coordinates) or 1 (wire-out, 64-byte coordinates) and
+ *                               n codes.  Infinity, and every point whose code is not 0, is written as O:
+ *                               (0, 1, 0) for G1, ((0, 0), (1, 0), (0, 0)) for G2.
+ *   ozk_points_compress_dev     n points in in_format 0 / 1, any Z (coordinates are taken mod q; of a wire-out
+ *                               coordinate only the low 32 bytes are read) -> n encodings.  Z = 0 gives INFINITY.
+ *   ozk_groth16_proofs_decompress_dev
+ *                               k compressed proofs -> k 768-byte records A | B | C (wire-out), the input of
+ *                               ozk_groth16_verify_dev and ozk_groth16_verify_rlc_dev.  d_codes[i] = 0 when the
+ *                               three points decoded, else the first non-zero code in the order A, B, C.
+ * n or k <= 0, a null pointer, an unknown type or format, a buffer that is not 4-byte aligned: OZK_E_INVALID.
+ * Asynchronous on `stream`. */
+int ozk_points_decompress_dev(const void* d_in, int32_t n, int32_t type, int32_t out_format, void* d_out,
+                              int32_t* d_codes, void* stream);
+int ozk_points_compress_dev(const void* d_in, int32_t n, int32_t type, int32_t in_format, void* d_out, void* stream);
+int ozk_groth16_proofs_decompress_dev(const void* d_in128, int32_t k, void* d_records768, int32_t* d_codes,
+                                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -743,6 +743,49 @@ class Proof:
     def __init__(self, a, b, c):
         self.g_a, self.g_b, self.g_c = a, b, c
 
+    def to_bytes(self) -> bytes:
+        """The 128-byte compressed form A (32) | B (64) | C (32) of DESIGN.md section 13, encoded on the device."""
+        from . import codec as _codec
+        a = _codec.compress_g1(_dev_bytes(bytes(self.g_a)), "wire_out")
+        b = _codec.compress_g2(_dev_bytes(bytes(self.g_b)), "wire_out")
+        c = _codec.compress_g1(_dev_bytes(bytes(self.g_c)), "wire_out")
+        return bytes(torch.cat([a, b, c]).cpu().numpy())
+
+    @staticmethod
+    def from_bytes(b) -> "Proof":
+        """The proof of 128 compressed bytes, decoded on the device.  ValueError names the first point that does not
+        decode and its code (codec.CODE_NAMES)."""
+        if len(b) != 128:
+            raise ValueError("a compressed proof is 128 bytes, not %d" % len(b))
+        return proofs_from_bytes(b)[0]
+
+
+def _decode_failure(what, index, code):
+    from . import codec as _codec
+    return ValueError("%s %s does not decode: code %d (%s)" % (what, index, code, _codec.CODE_NAMES.get(code, "?")))
+
+
+def proofs_from_bytes(buf) -> list:
+    """The proofs of K x 128 compressed bytes, decoded in one launch.  ValueError on the first proof with a point that
+    does not decode."""
+    from . import codec as _codec
+    buf = bytes(buf)
+    if not buf or len(buf) % 128:
+        raise ValueError("%d bytes are not a whole number of 128-byte proofs" % len(buf))
+    k = len(buf) // 128
+    enc = _dev_bytes(buf).view(k, 128)
+    # the three points apart, so that a failure can name its point (the proof entry reports one code per proof)
+    parts = (("A", _codec.decompress_g1(enc[:, :32], "wire_out")), ("B", _codec.decompress_g2(enc[:, 32:96], "wire_out")),
+             ("C", _codec.decompress_g1(enc[:, 96:], "wire_out")))
+    codes = torch.stack([c for _, (_, c) in parts], dim=1).cpu().tolist()
+    for i, row in enumerate(codes):
+        for (name, _), code in zip(parts, row):
+            if code:
+                raise _decode_failure("proof %d: point" % i, name, code)
+    raws = [bytes(pts.cpu().numpy()) for _, (pts, _) in parts]
+    return [Proof(raws[0][192 * i:192 * (i + 1)], raws[1][384 * i:384 * (i + 1)], raws[2][192 * i:192 * (i + 1)])
+            for i in range(k)]
+
 
 RECORD_BYTES = 768   # a rank's partial: A_r (G1, 192) | B_r (G2, 384) | C_r (G1, 192), wire-out
 
@@ -1027,6 +1070,38 @@ class VerificationKey:
         return self._multi.run(_dev_bytes(b"".join(_le32(primary) for primary in primaries)), len(primaries))
 
 
+    MAGIC = b"OZKVK\x00\x00\x01"   # five letters, two zero bytes, format version 1
+
+    def to_bytes(self) -> bytes:
+        """magic and version (8) | num_inputs u32 | 4 bytes of padding | alphaG1betaG2 (384, as the device holds it) |
+        gammaG2 (64) | deltaG2 (64) | gammaABC (32 each), the points compressed"""
+        from . import codec as _codec
+        g2 = _codec.compress_g2(torch.cat([self.gamma_g2.reshape(-1), self.delta_g2.reshape(-1)]))
+        abc = _codec.compress_g1(self.gamma_abc_g1)
+        body = torch.cat([self.alpha_g1_beta_g2.reshape(-1), g2, abc])
+        return self.MAGIC + self.num_inputs.to_bytes(4, "little") + bytes(4) + bytes(body.cpu().numpy())
+
+    @staticmethod
+    def from_bytes(b) -> "VerificationKey":
+        """The key of to_bytes; the points are decoded on the device and the prepared lines of gamma and delta rebuilt
+        by the constructor.  ValueError on a bad header or length and on any point that does not decode."""
+        from . import codec as _codec
+        b = bytes(b)
+        if len(b) < 16 or b[:8] != VerificationKey.MAGIC or b[12:16] != bytes(4):
+            raise ValueError("not a verification key (bad magic, version or padding)")
+        n = int.from_bytes(b[8:12], "little")
+        if n < 1 or len(b) != 16 + 384 + 128 + 32 * n:
+            raise ValueError("a verification key of %d inputs is %d bytes, not %d" % (n, 528 + 32 * n, len(b)))
+        body = _dev_bytes(b[16:])
+        g2, c2 = _codec.decompress_g2(body[384:512])
+        abc, c1 = _codec.decompress_g1(body[512:])
+        for i, code in enumerate(torch.cat([c2, c1]).cpu().tolist()):
+            if code:
+                raise _decode_failure("verification key: point", ("gammaG2", "deltaG2")[i] if i < 2
+                                      else "gammaABC[%d]" % (i - 2), code)
+        return VerificationKey(body[:384].clone(), g2[:192].clone(), g2[192:].clone(), abc)
+
+
 def verification_key(crs: CRS) -> VerificationKey:
     """The verification key of a CRS from serial_setup_generate (SerialSetup.java:159-164): alphaG1betaG2 =
     reducedPairing(alphaG1, betaG2) computed on the device."""
@@ -1085,36 +1160,48 @@ class Verifier:
         batched MSM for all of them (VerificationKey.evaluation_abc_batch), abc="auto" the batched one from
         ABC_BATCH_CROSSOVER proofs upwards (or whenever the key already has its table).  The points, and so the
         verdicts, are the same in all three."""
-        from . import pairing as _pairing
-        if abc not in ("auto", "per_proof", "batched"):
-            raise ValueError("abc must be 'auto', 'per_proof' or 'batched'")
         if len(primaries) != len(proofs) or not proofs:
             raise ValueError("one primary input per proof, at least one proof")
+        abc = Verifier._evaluation_abc(vk, primaries, abc)
+        recs = _dev_bytes(b"".join(proof_record(p) for p in proofs))
+        return Verifier._records_verdicts(vk, recs, abc)
+
+    @staticmethod
+    def _evaluation_abc(vk: VerificationKey, primaries, abc) -> torch.Tensor:
+        """the evaluationABC points of a batch (K x 192 bytes on the device) in the mode `abc` of verify_batch"""
+        if abc not in ("auto", "per_proof", "batched"):
+            raise ValueError("abc must be 'auto', 'per_proof' or 'batched'")
         for primary in primaries:
             assert primary[0] % FR == 1   # Verifier.java:31-32
         if abc == "auto":
-            batched = len(proofs) >= Verifier.ABC_BATCH_CROSSOVER or vk._multi is not None
+            batched = len(primaries) >= Verifier.ABC_BATCH_CROSSOVER or vk._multi is not None
             abc = "batched" if batched and 1 <= vk.num_inputs <= 4096 else "per_proof"
         if abc == "batched":
-            abc = vk.evaluation_abc_batch(primaries)
-        else:
-            abc = torch.cat([vk.evaluation_abc(primary) for primary in primaries])
-        recs = _dev_bytes(b"".join(proof_record(p) for p in proofs))
-        ok = _pairing.groth16_verify(vk.alpha_g1_beta_g2, vk.gamma_prep, vk.delta_prep, recs, abc)
+            return vk.evaluation_abc_batch(primaries)
+        return torch.cat([vk.evaluation_abc(primary) for primary in primaries])
+
+    @staticmethod
+    def _records_verdicts(vk: VerificationKey, recs, abc_points) -> list:
+        """K records on the device (768 bytes each) and their evaluationABC points to K verdicts"""
+        from . import pairing as _pairing
+        ok = _pairing.groth16_verify(vk.alpha_g1_beta_g2, vk.gamma_prep, vk.delta_prep, recs, abc_points)
         return [bool(v) for v in ok.cpu().tolist()]
 
     @staticmethod
-    def _rlc(vk: VerificationKey, primaries, proofs, seed, stage_ms=None):
+    def _rlc(vk: VerificationKey, primaries, proofs, seed, stage_ms=None, recs=None):
         """The randomized check over the well-formed proofs: (verdict, covered flags), verdict 1 / 0 / -1 as
-        ozk_groth16_verify_rlc_dev returns it."""
+        ozk_groth16_verify_rlc_dev returns it.  The proofs are `proofs`, or, with proofs None, the records `recs`
+        already on the device (768 bytes each)."""
         from . import pairing as _pairing
-        if len(primaries) != len(proofs) or not proofs:
+        k = len(proofs) if recs is None else recs.numel() // RECORD_BYTES
+        if len(primaries) != k or not k:
             raise ValueError("one primary input per proof, at least one proof")
         rows = _pack_primaries(primaries, vk.num_inputs)
         rng = random.Random(seed) if seed is not None else secrets.SystemRandom()
-        weights = b"".join((rng.randrange(1, 1 << 128)).to_bytes(32, "little") for _ in proofs)
+        weights = b"".join((rng.randrange(1, 1 << 128)).to_bytes(32, "little") for _ in range(k))
         t0 = time.perf_counter()
-        recs = _dev_bytes(b"".join(proof_record(p) for p in proofs))
+        if recs is None:
+            recs = _dev_bytes(b"".join(proof_record(p) for p in proofs))
         d_inputs = _dev_bytes(b"".join(rows))
         d_r = _dev_bytes(weights)
         if stage_ms is not None:
@@ -1142,12 +1229,28 @@ class Verifier:
         combination.  Use a seed for tests only.  stage_ms: None, or a dict that receives the stage times in ms."""
         primaries, proofs = list(primaries), list(proofs)
         verdict, covered = Verifier._rlc(vk, primaries, proofs, seed, stage_ms)
+        return Verifier._all_after_rlc(verdict, covered, lambda rest: Verifier.verify_batch(
+            vk, [primaries[i] for i in rest], [proofs[i] for i in rest]))
+
+    @staticmethod
+    def _all_after_rlc(verdict, covered, judge) -> bool:
+        """verify_all once the randomized check has spoken; judge(indices) gives the verdicts of verify_batch"""
         if verdict == 0:
             return False
-        rest = [i for i in range(len(proofs)) if verdict < 0 or not covered[i]]
-        if not rest:
-            return True
-        return all(Verifier.verify_batch(vk, [primaries[i] for i in rest], [proofs[i] for i in rest]))
+        rest = [i for i in range(len(covered)) if verdict < 0 or not covered[i]]
+        return not rest or all(judge(rest))
+
+    @staticmethod
+    def _each_after_rlc(verdict, covered, judge) -> list:
+        """verify_batch_rlc once the randomized check has spoken"""
+        if verdict != 1:
+            return judge(list(range(len(covered))))
+        out = [True] * len(covered)
+        rest = [i for i in range(len(covered)) if not covered[i]]
+        if rest:
+            for i, v in zip(rest, judge(rest)):
+                out[i] = v
+        return out
 
     @staticmethod
     def verify_batch_rlc(vk: VerificationKey, primaries, proofs, *, seed=None) -> list:
@@ -1156,12 +1259,87 @@ class Verifier:
         does.  Weights and `seed` as in verify_all (a seeded batch is unsound against anyone who knows the seed)."""
         primaries, proofs = list(primaries), list(proofs)
         verdict, covered = Verifier._rlc(vk, primaries, proofs, seed)
-        if verdict != 1:
-            return Verifier.verify_batch(vk, primaries, proofs)
-        out = [True] * len(proofs)
-        rest = [i for i in range(len(proofs)) if not covered[i]]
-        if rest:
-            for i, v in zip(rest, Verifier.verify_batch(vk, [primaries[i] for i in rest], [proofs[i] for i in rest])):
+        return Verifier._each_after_rlc(verdict, covered, lambda rest: Verifier.verify_batch(
+            vk, [primaries[i] for i in rest], [proofs[i] for i in rest]))
+
+    # ---- the same three checks on compressed proofs: K x 128 bytes (DESIGN.md section 13) as bytes, a bytearray or a
+    # uint8 CUDA tensor.  The buffer is uploaded once and decoded on the device straight into the record buffer of the
+    # checks above; no Proof object is built.  A proof with a point that does not decode is False and stays out of the
+    # pairing work; one that decodes gets the verdict the object path gives Proof.from_bytes of the same bytes (a
+    # proof containing O decodes and is then treated as that path treats it).
+    @staticmethod
+    def _decode_records(buf, k, stage_ms=None):
+        """(K x 768 record bytes on the device as a (K, 768) tensor, the K codes as a list)"""
+        from . import codec as _codec
+        t0 = time.perf_counter()
+        if not isinstance(buf, torch.Tensor):
+            buf = _dev_bytes(bytes(buf)) if len(buf) else torch.empty(0, dtype=torch.uint8)
+        if buf.numel() != 128 * k or not k:
+            raise ValueError("one 128-byte proof per primary input, at least one proof (%d bytes for %d)"
+                             % (buf.numel(), k))
+        if stage_ms is not None:
+            torch.cuda.synchronize()
+            stage_ms["upload_compressed"] = (time.perf_counter() - t0) * 1e3
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+        recs, codes = _codec.decompress_proofs(buf)
+        if stage_ms is not None:
+            ev[1].record()
+            ev[1].synchronize()
+            stage_ms["decompress"] = ev[0].elapsed_time(ev[1])
+        return recs.view(k, RECORD_BYTES), codes.cpu().tolist()
+
+    @staticmethod
+    def _judge_records(vk, primaries, recs, abc="auto"):
+        """judge(indices) for _all_after_rlc / _each_after_rlc over the rows of `recs`"""
+        def judge(rest):
+            rows = recs if len(rest) == recs.shape[0] else recs[torch.tensor(rest, device=recs.device)]
+            prim = [primaries[i] for i in rest]
+            return Verifier._records_verdicts(vk, rows.reshape(-1), Verifier._evaluation_abc(vk, prim, abc))
+        return judge
+
+    @staticmethod
+    def _decodable(primaries, recs, codes):
+        """the decodable proofs of a batch: (their positions, their primary inputs, their records)"""
+        good = [i for i, c in enumerate(codes) if c == 0]
+        if len(good) == len(codes):
+            return good, primaries, recs
+        return good, [primaries[i] for i in good], recs[torch.tensor(good, dtype=torch.long, device=recs.device)]
+
+    @staticmethod
+    def verify_batch_bytes(vk: VerificationKey, primaries, buf, abc="auto") -> list:
+        """verify_batch on K compressed proofs"""
+        primaries = list(primaries)
+        recs, codes = Verifier._decode_records(buf, len(primaries))
+        good, primaries, recs = Verifier._decodable(primaries, recs, codes)
+        out = [False] * len(codes)
+        if good:
+            for i, v in zip(good, Verifier._judge_records(vk, primaries, recs, abc)(list(range(len(good))))):
+                out[i] = v
+        return out
+
+    @staticmethod
+    def verify_all_bytes(vk: VerificationKey, primaries, buf, *, seed=None, stage_ms=None) -> bool:
+        """verify_all on K compressed proofs: False as soon as any proof does not decode.  stage_ms also receives
+        "upload_compressed" and "decompress" (the device time of the decoding launch)."""
+        primaries = list(primaries)
+        recs, codes = Verifier._decode_records(buf, len(primaries), stage_ms)
+        if any(codes):
+            return False
+        verdict, covered = Verifier._rlc(vk, primaries, None, seed, stage_ms, recs=recs.reshape(-1))
+        return Verifier._all_after_rlc(verdict, covered, Verifier._judge_records(vk, primaries, recs))
+
+    @staticmethod
+    def verify_batch_rlc_bytes(vk: VerificationKey, primaries, buf, *, seed=None) -> list:
+        """verify_batch_rlc on K compressed proofs"""
+        primaries = list(primaries)
+        recs, codes = Verifier._decode_records(buf, len(primaries))
+        good, primaries, recs = Verifier._decodable(primaries, recs, codes)
+        out = [False] * len(codes)
+        if good:
+            verdict, covered = Verifier._rlc(vk, primaries, None, seed, recs=recs.reshape(-1))
+            for i, v in zip(good, Verifier._each_after_rlc(verdict, covered,
+                                                            Verifier._judge_records(vk, primaries, recs))):
                 out[i] = v
         return out
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Timing of the device pairing and the Groth16 verifier; prints one JSON line.
 
-    python tools/groth16_verify.py [--quick | --multi-only]
+    python tools/groth16_verify.py [--quick | --multi-only | --compressed-only] [--compressed]
 
   * reduced pairings / s at n = 1, 1024, 65536 (random pairs, G2 steps inline; median of a few runs);
   * one 2^10-constraint proof (15 inputs): Verifier.verify latency, with the evaluationABC MSM shown separately;
@@ -15,6 +15,12 @@
   * Verifier.verify_all and verify_batch_rlc (the randomized batch check) at K = 1, 64, 4096, 65536, with the stage
     split of verify_all (upload, combination, MSMs, Miller loops, product tree, final exponentiation), repeated
     copies of the one proof.  `rlc_floor_ok`: verify_all at K = 4096 within 150 ms and >= 20x verify_batch's per-proof rate.
+  * --compressed: next to every K of the previous item, `compressed`: the device time of
+    ozk_groth16_proofs_decompress_dev on K x 128 bytes already in HBM, Verifier.verify_all_bytes (upload of the
+    compressed buffer included, like verify_all's upload of the records) against verify_all on Proof objects from the
+    same loop, its stage split, and the host time of the Python-integer model (tests/codec_ref.py) decoding a sample of
+    256 proofs, scaled to K: a Python-integer baseline, not a tuned host decoder.  --compressed-only prints just the
+    verify_all item with this addition.
 The floor the issue sets is 1 M reduced pairings / s at n = 65536; `floor_ok` reports it.  The counted figures are
 the Fq multiplications per reduced pairing taken from the code."""
 import json
@@ -91,8 +97,57 @@ def _batched_stages(z, pa, vk, prims, proofs):
     return round(t_abc * 1e3, 3), round(t_pair * 1e3, 3)
 
 
+def _compressed(z, vk, prims, proof, k, t_all):
+    """the compressed-proof path at K = k: decoding alone, verify_all_bytes, and the Python-integer baseline"""
+    from octopuszk_amd import codec
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import codec_ref
+    one = proof.to_bytes()
+    assert z.proof_record(z.Proof.from_bytes(one)) == z.proof_record(proof)
+    buf = one * k
+    d_buf = z._dev_bytes(buf)
+    recs, codes = codec.decompress_proofs(d_buf)
+    assert not codes.any().item()
+    t_dec = _timed(lambda: codec.decompress_proofs(d_buf), 5)
+    assert z.Verifier.verify_all_bytes(vk, prims, buf)
+    t_bytes = _timed(lambda: z.Verifier.verify_all_bytes(vk, prims, buf), 3)
+    stages = {}
+    z.Verifier.verify_all_bytes(vk, prims, buf, stage_ms=stages)
+    sample = 256
+    t0 = time.perf_counter()
+    for _ in range(sample):
+        code, rec = codec_ref.proof_record(one)
+    t_model = (time.perf_counter() - t0) / sample
+    assert code == 0 and rec == z.proof_record(proof)
+    return {"decompress_ms": round(t_dec * 1e3, 3), "decompress_proofs_per_s": round(k / t_dec, 1),
+            "verify_all_bytes_ms": round(t_bytes * 1e3, 2), "verify_all_objects_ms": round(t_all * 1e3, 2),
+            "bytes_minus_objects_ms": round((t_bytes - t_all) * 1e3, 2),
+            "stages_ms": {n: round(v, 3) for n, v in stages.items()},
+            "python_int_model_ms_per_proof": round(t_model * 1e3, 3),
+            "python_int_model_scaled_ms": round(t_model * k * 1e3, 1)}
+
+
+def _verify_all(z, vk, primary, proof, quick, compressed):
+    rlc = {}
+    for k in ([1, 64] if quick else [1, 64, 4096, 65536]):
+        prims, proofs = [primary] * k, [proof] * k
+        assert z.Verifier.verify_all(vk, prims, proofs)
+        t_all = _timed(lambda: z.Verifier.verify_all(vk, prims, proofs), 3)
+        t_rlc = _timed(lambda: z.Verifier.verify_batch_rlc(vk, prims, proofs), 3)
+        stages = {}
+        z.Verifier.verify_all(vk, prims, proofs, stage_ms=stages)
+        rlc[str(k)] = {"verify_all_ms": round(t_all * 1e3, 2), "verify_all_proofs_per_s": round(k / t_all, 1),
+                       "verify_batch_rlc_ms": round(t_rlc * 1e3, 2),
+                       "stages_ms": {n: round(v, 3) for n, v in stages.items()}}
+        if compressed:
+            rlc[str(k)]["compressed"] = _compressed(z, vk, prims, proof, k, t_all)
+    return rlc
+
+
 def main():
     quick = "--quick" in sys.argv
+    compressed_only = "--compressed-only" in sys.argv
+    compressed = compressed_only or "--compressed" in sys.argv
     from octopuszk_amd import pairing as pa
     from octopuszk_amd import zksnark as z
     torch.cuda.set_device(0)
@@ -103,14 +158,14 @@ def main():
     # one G2 point repeated (the G2 generator, wire-in), n G1 points
     g2 = b"".join(int(v).to_bytes(32, "little") for x in z.G2_ONE for v in x)
     res = {}
-    for n in ([1, 1024] if quick else [1, 1024, 65536]):
+    for n in ([] if compressed_only else [1, 1024] if quick else [1, 1024, 65536]):
         P = _points(n, 3)
         Qd = torch.frombuffer(bytearray(g2 * n), dtype=torch.uint8).cuda()
         pa.reduced_pairing(P, Qd)
         t = _timed(lambda: pa.reduced_pairing(P, Qd), 3)
         res[str(n)] = {"ms": round(t * 1e3, 3), "pairings_per_s": round(n / t, 1)}
     out["reduced_pairing"] = res
-    if not quick:
+    if not quick and not compressed_only:
         out["floor_ok"] = res["65536"]["pairings_per_s"] >= 1e6
     # one proof at 2^10
     r1cs, primary, auxiliary = z.serial_construct(1 << 10, 15)
@@ -120,6 +175,10 @@ def main():
     proof = prover.prove(primary, auxiliary)
     prover.close()
     assert z.Verifier.verify(vk, primary, proof)
+    if compressed_only:
+        out = {"metric": "groth16_verify_compressed", "verify_all": _verify_all(z, vk, primary, proof, quick, True)}
+        print(json.dumps(out))
+        return
     out["verify_one_ms"] = round(_timed(lambda: z.Verifier.verify(vk, primary, proof), 5) * 1e3, 3)
     out["abc_msm_one_ms"] = round(_timed(lambda: vk.evaluation_abc(primary), 5) * 1e3, 3)
     batch = {}
@@ -179,17 +238,7 @@ def main():
             z.Verifier.ABC_BATCH_CROSSOVER = keep
         out["rlc_one_tampered_4096"] = {"batched_fallback_ms": round(t_b * 1e3, 2), "per_proof_fallback_ms": round(t_p * 1e3, 2)}
     out["multi_msm"] = _multi_msm(quick)
-    rlc = {}
-    for k in ([1, 64] if quick else [1, 64, 4096, 65536]):
-        prims, proofs = [primary] * k, [proof] * k
-        assert z.Verifier.verify_all(vk, prims, proofs)
-        t_all = _timed(lambda: z.Verifier.verify_all(vk, prims, proofs), 3)
-        t_rlc = _timed(lambda: z.Verifier.verify_batch_rlc(vk, prims, proofs), 3)
-        stages = {}
-        z.Verifier.verify_all(vk, prims, proofs, stage_ms=stages)
-        rlc[str(k)] = {"verify_all_ms": round(t_all * 1e3, 2), "verify_all_proofs_per_s": round(k / t_all, 1),
-                       "verify_batch_rlc_ms": round(t_rlc * 1e3, 2),
-                       "stages_ms": {n: round(v, 3) for n, v in stages.items()}}
+    rlc = _verify_all(z, vk, primary, proof, quick, compressed)
     out["verify_all"] = rlc
     if not quick:
         t = rlc["4096"]["verify_all_ms"]
