@@ -508,8 +508,20 @@ int ozk_multi_msm_plan(int32_t n, int32_t* window_bits, int32_t* windows);
  *                               k compressed proofs -> k 768-byte records A | B | C (wire-out), the input of
  *                               ozk_groth16_verify_dev and ozk_groth16_verify_rlc_dev.  d_codes[i] = 0 when the
  *                               three points decoded, else the first non-zero code in the order A, B, C.
+ *   ozk_points_decompress_prepared_dev
+ *                               n encodings -> the prepared bases of the variable-base MSM over those n points
+ *                               (DESIGN.md section 14), byte for byte what ozk_var_msm_prepare_dev writes from the
+ *                               wire-in output of ozk_points_decompress_dev, and the same n codes, without the
+ *                               wire-in points ever existing: record i = (x, y), record n + i = (beta x, y), canonical
+ *                               Montgomery; infinity, and every point whose code is not 0, is the (0, 0) marker in
+ *                               both.  prepared_bytes >= ozk_var_msm_prepared_bytes(n, type), else OZK_E_INVALID;
+ *                               n > 2^23 (where the MSM leaves the two-record GLV form) is OZK_E_INVALID too.
+ *                               check_subgroup != 0 (G2 only; G1 has cofactor 1 and ignores it): a decoded point P
+ *                               with [r]P != O gets code 4 and the (0, 0) marker.
  * n or k <= 0, a null pointer, an unknown type or format, a buffer that is not 4-byte aligned: OZK_E_INVALID.
  * Asynchronous on `stream`. */
+int ozk_points_decompress_prepared_dev(const void* d_in, int32_t n, int32_t type, void* d_prepared,
+                                       size_t prepared_bytes, int32_t* d_codes, int32_t check_subgroup, void* stream);
 int ozk_points_decompress_dev(const void* d_in, int32_t n, int32_t type, int32_t out_format, void* d_out,
                               int32_t* d_codes, void* stream);
 int ozk_points_compress_dev(const void* d_in, int32_t n, int32_t type, int32_t in_format, void* d_out, void* stream);

@@ -4,7 +4,8 @@ There is no CPU path.
 A compressed point is its affine x, little-endian, with two flags in the top bits of the last byte: bit 7 Y_LARGER
 (the canonical y is the larger of y and q - y), bit 6 INFINITY.  G1 is 32 bytes; G2 is 64, x.c0 | x.c1, Y_LARGER
 decided on y.c1 unless it is 0.  Decoding is strict and returns one int32 code per point: 0 ok, 1 a coordinate >= q,
-2 bad infinity encoding, 3 no curve point has this x.  No subgroup check is made here.
+2 bad infinity encoding, 3 no curve point has this x.  No subgroup check is made, except by decompress_prepared
+(the points of a proving key) where it is asked for: code 4, a G2 point outside the order-r subgroup.
 
 Every function takes and returns uint8 CUDA tensors and is asynchronous on the current stream.  `fmt` names the
 uncompressed side: "wire_in" (X | Y | Z with 32-byte coordinates, what the MSMs and pairings take) or "wire_out"
@@ -16,9 +17,9 @@ from . import lib as _lib
 from .device import _ptr, _stream
 
 G1_COMPRESSED, G2_COMPRESSED, PROOF_COMPRESSED, PROOF_RECORD = 32, 64, 128, 768
-OK, E_RANGE, E_INFINITY, E_NO_POINT = 0, 1, 2, 3
+OK, E_RANGE, E_INFINITY, E_NO_POINT, E_SUBGROUP = 0, 1, 2, 3, 4
 CODE_NAMES = {OK: "ok", E_RANGE: "coordinate >= q", E_INFINITY: "bad infinity encoding",
-              E_NO_POINT: "no curve point has this x"}
+              E_NO_POINT: "no curve point has this x", E_SUBGROUP: "not in the order-r subgroup"}
 _FORMATS = {"wire_in": 0, "wire_out": 1}
 
 
@@ -66,6 +67,24 @@ def decompress_g1(enc, fmt="wire_in"):
 def decompress_g2(enc, fmt="wire_in"):
     """n x 64 bytes -> (n points in `fmt`, n int32 codes); O is ((0, 0), (1, 0), (0, 0))."""
     return _decompress(enc, 2, fmt)
+
+
+def decompress_prepared(enc, type_, check_subgroup=False):
+    """n compressed points of group `type_` (1: G1, 2: G2) -> (the prepared bases device.prepare_bases makes of the
+    decoded points, n int32 codes), without the decoded points in between.  Infinity, and every point whose code is
+    not 0, is the (0, 0) marker in both of its records.  check_subgroup (G2 only): code 4 for a point outside the
+    order-r subgroup."""
+    L = _lib.load()
+    if type_ not in (1, 2):
+        raise ValueError("type_ must be 1 (G1) or 2 (G2)")
+    n = _count(enc, 32 * type_, "compressed points")
+    enc = enc.contiguous()
+    nbytes = int(L.ozk_var_msm_prepared_bytes(n, type_))
+    out = torch.empty(nbytes, dtype=torch.uint8, device=enc.device)
+    codes = torch.empty(n, dtype=torch.int32, device=enc.device)
+    _lib.check(L.ozk_points_decompress_prepared_dev(_ptr(enc), n, type_, _ptr(out), nbytes, _ptr(codes),
+                                                    1 if check_subgroup else 0, _stream()))
+    return out, codes
 
 
 def compress_g1(points, fmt="wire_in"):

@@ -54,17 +54,7 @@ OZK_HD bool bv_g1_wellformed(const u32* p) {
   return is_zero(sub(BvFq(sqr(Y)), rhs));
 }
 
-// [e]q for an affine q, e given as `words` little-endian words: double-and-add from the top bit (jac_madd takes the
-// P == Q and P == -Q cases, so any point and any scalar are exact)
-template <class CV>
-OZK_HD Jac<CV> bv_scalar_mul(const Aff<typename CV::EA>& q, const u32* e, int words) {
-  Jac<CV> acc = jac_infinity<CV>();
-  for (int i = 32 * words - 1; i >= 0; i--) {
-    acc = jac_dbl<CV>(acc);
-    if ((e[i >> 5] >> (i & 31)) & 1) acc = jac_madd<CV>(acc, q);
-  }
-  return acc;
-}
+// (bv_scalar_mul, [e]q for an affine q: ec.cuh, where point_codec.cuh finds it too)
 
 // B: canonical coordinates, Z != 0, Y^2 = X^3 + b' Z^6 with b' = 3 / (9 + u), and [r]B = O (the order-r subgroup;
 // the twist's group has order r h with a large cofactor h, so the curve equation alone is not enough)

@@ -12,7 +12,7 @@
 // The reference has no counterpart (its windows cover all 254 bits, VariableBaseMSM.java:137-143);
 // the group element computed is the same.
 #pragma once
-#include "fp29.cuh"
+#include "curve.cuh"
 
 namespace ozk {
 
@@ -114,6 +114,21 @@ OZK_HD void glv_decompose(const u32 (&k_in)[8], u32 (&k1)[4], bool& neg1, u32 (&
     k1[i] = s1[i];
     k2[i] = s2[i];
   }
+}
+
+// beta of the GLV endomorphism for this curve's base field (G2: beta^2, acting on both Fq2 components)
+template <class CV>
+OZK_HD Fe<FqParams, 16> glv_beta() {
+  if constexpr (CurveIO<CV>::CW == 16) return fe_const<FqParams, 16>(GlvConsts::BETA_G2);
+  else return fe_const<FqParams, 16>(GlvConsts::BETA_G1);
+}
+// phi(q) = (beta x, y) of an affine point with canonical coordinates, canonical again; O = (0, 0) stays O
+template <class CV>
+OZK_HD Aff<typename CV::EA> glv_image(const Aff<typename CV::EA>& q) {
+  Aff<typename CV::EA> q2;
+  q2.x = typename CV::EA(canonical(scale(q.x, glv_beta<CV>())));
+  q2.y = q.y;
+  return q2;
 }
 
 }  // namespace ozk

@@ -105,12 +105,8 @@ constexpr u32 SIDX_NEG = 0x80000000u;
 // are affine) costs 2 Montgomery conversions; Z == 0 -> infinity marker; any other Z is
 // normalised with a per-lane Fermat inversion (correct for reference-produced
 // Jacobian keys, slower).
-// beta of the GLV endomorphism for this curve's base field (G2: beta^2, acting on both Fq2 components)
-template <class CV>
-OZK_HD Fe<FqParams, 16> glv_beta() {
-  if constexpr (CurveIO<CV>::CW == 16) return fe_const<FqParams, 16>(GlvConsts::BETA_G2);
-  else return fe_const<FqParams, 16>(GlvConsts::BETA_G1);
-}
+// (glv_beta, the beta of the GLV endomorphism for this curve: glv.cuh.  point_codec.cuh decodes compressed points
+// into the records this kernel writes.)
 
 // With GLV: record i = (x, y), record n + i = (beta x, y).  Signed-digit plans fold the signs of the
 // two half scalars into the digit signs (k_digits_glv), so the records depend on the bases alone —

@@ -5,14 +5,18 @@
 //   G2  x.c0 | x.c1, each as above; the two flags in byte 63; Y_LARGER decided on y.c1 unless it is 0, then on y.c0
 //
 // Decoding is strict and returns a code per point: 0 ok, 1 a coordinate >= q, 2 bad infinity encoding (or Y_LARGER on
-// a point with y = 0), 3 no curve point has this x.  There is no subgroup check here: [r]B = O stays in
-// bv_g2_wellformed (batch_verify.cuh).
+// a point with y = 0), 3 no curve point has this x.  Proofs get no subgroup check here: [r]B = O stays in
+// bv_g2_wellformed (batch_verify.cuh).  The points of a proving key are decoded straight into the
+// prepared records of the variable-base MSM (codec_g1_decode_prepared / codec_g2_decode_prepared: what
+// k_convert_bases of msm_var.cuh makes of the decoded wire point, without the wire point), and those of G2 can be
+// checked for [r]P = O there: code 4.
 //
 // Bounds: every element that crosses a function boundary is a CdFq / CdF2 (< 2p); whatever is compared or stored is
 // first made canonical, as integer words out of from_mont.  The header compiles for the host too
 // (tests/native/codec_hostcheck.cpp), the kernels at the end only in point_codec.hip.
 #pragma once
 #include "fq2.cuh"
+#include "glv.cuh"
 #include "pairing_consts_gen.h"
 
 namespace ozk {
@@ -21,6 +25,7 @@ using CdFq = Fe<FqParams, 32>;
 using CdF2 = Fe2<32>;
 
 constexpr int CODEC_OK = 0, CODEC_E_RANGE = 1, CODEC_E_INFINITY = 2, CODEC_E_NO_POINT = 3;
+constexpr int CODEC_E_SUBGROUP = 4;   // only from the subgroup check of decoded key points (k_codec_subgroup_g2)
 constexpr u32 CODEC_Y_LARGER = 0x80000000u, CODEC_INFINITY = 0x40000000u;   // in the top word of the encoding
 
 constexpr u32 CODEC_Q_WORDS[8] = {0xd87cfd47u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u,
@@ -143,6 +148,14 @@ struct CodecG2 {
 
 OZK_HD CdFq codec_fq(const u32 (&w)[8]) { return CdFq(to_mont<FqParams>(w)); }
 
+// the code of an encoding from what was found: infinity flag (0 or 2), x >= q (1), no root (3), y = 0 with Y_LARGER (2)
+OZK_HD int codec_code(bool infinity, bool ylarger, bool x_zero, bool x_canonical, bool on, bool y_zero) {
+  if (infinity) return (!x_zero || ylarger) ? CODEC_E_INFINITY : CODEC_OK;
+  if (!x_canonical) return CODEC_E_RANGE;
+  if (!on) return CODEC_E_NO_POINT;
+  return (y_zero && ylarger) ? CODEC_E_INFINITY : CODEC_OK;
+}
+
 // in: 8 words.  The checks in the order of the codes' precedence: infinity flag (0 or 2), x >= q (1), x^3 + 3 not
 // a square (3), y = 0 with Y_LARGER (2).
 OZK_HD int codec_g1_decode(const u32* in, CodecG1& p) {
@@ -158,15 +171,7 @@ OZK_HD int codec_g1_decode(const u32* in, CodecG1& p) {
   from_mont(Y, p.y);
   const bool y0 = codec_words_zero(p.y);
   if (larger(p.y) != ylarger) codec_negate(p.y);
-  int code = CODEC_OK;
-  if (infinity)
-    code = (!codec_words_zero(w) || ylarger) ? CODEC_E_INFINITY : CODEC_OK;
-  else if (!codec_canonical(w))
-    code = CODEC_E_RANGE;
-  else if (!on)
-    code = CODEC_E_NO_POINT;
-  else if (y0 && ylarger)
-    code = CODEC_E_INFINITY;
+  const int code = codec_code(infinity, ylarger, codec_words_zero(w), codec_canonical(w), on, y0);
 #pragma unroll
   for (int i = 0; i < 8; i++) p.x[i] = w[i];
   p.inf = infinity || code != CODEC_OK;
@@ -199,21 +204,71 @@ OZK_HD int codec_g2_decode(const u32* in, CodecG2& p) {
     if (!codec_words_zero(p.y[0])) codec_negate(p.y[0]);
     if (!codec_words_zero(p.y[1])) codec_negate(p.y[1]);
   }
-  int code = CODEC_OK;
-  if (infinity)
-    code = (!codec_words_zero(w0) || !codec_words_zero(w1) || ylarger) ? CODEC_E_INFINITY : CODEC_OK;
-  else if (!codec_canonical(w0) || !codec_canonical(w1))
-    code = CODEC_E_RANGE;
-  else if (!on)
-    code = CODEC_E_NO_POINT;
-  else if (y0 && ylarger)
-    code = CODEC_E_INFINITY;
+  const int code = codec_code(infinity, ylarger, codec_words_zero(w0) && codec_words_zero(w1),
+                              codec_canonical(w0) && codec_canonical(w1), on, y0);
 #pragma unroll
   for (int i = 0; i < 8; i++) {
     p.x[0][i] = w0[i];
     p.x[1][i] = w1[i];
   }
   p.inf = infinity || code != CODEC_OK;
+  return code;
+}
+
+// ---------------------------------------------------------------------------------------------- prepared records
+// A compressed point straight into the two records k_convert_bases (msm_var.cuh) makes of the decoded point: q = (x, y),
+// q2 = (beta x, y), canonical Montgomery; O and every point whose code is not 0 become the (0, 0) marker in both.
+// x enters Montgomery form once and stays; y stays there from the square root on.  The only canonical integer taken
+// is the one Y_LARGER is decided on (G2: inside fq2_sqrt), and the root is negated in the Montgomery domain.
+OZK_HD int codec_g1_decode_prepared(const u32* in, Aff<G1Cfg::EA>& q, Aff<G1Cfg::EA>& q2) {
+  using EA = G1Cfg::EA;
+  u32 w[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) w[i] = in[i];
+  const bool ylarger = (w[7] & CODEC_Y_LARGER) != 0, infinity = (w[7] & CODEC_INFINITY) != 0;
+  w[7] &= ~(CODEC_Y_LARGER | CODEC_INFINITY);
+  const CdFq X = codec_fq(w);
+  const CdFq rhs = CdFq(reduce_to<32>(add(mul(CdFq(sqr(X)), X), fe_const<FqParams, 16>(CODEC_THREE))));
+  CdFq Y;
+  const bool on = fq_sqrt(rhs, Y);
+  u32 yw[8];
+  from_mont(Y, yw);
+  const int code = codec_code(infinity, ylarger, codec_words_zero(w), codec_canonical(w), on, codec_words_zero(yw));
+  const bool inf = infinity || code != CODEC_OK;
+  const Fe<FqParams, 16> zero = fe_zero<FqParams>();
+  const Fe<FqParams, 16> y = select_el(larger(yw) != ylarger, canonical(neg(Y)), canonical(Y));   // -0 = 0
+  q.x = EA(select_el(inf, zero, canonical(X)));
+  q.y = EA(select_el(inf, zero, y));
+  q2 = glv_image<G1Cfg>(q);
+  return code;
+}
+
+OZK_HD int codec_g2_decode_prepared(const u32* in, Aff<G2Cfg::EA>& q, Aff<G2Cfg::EA>& q2) {
+  using EA = G2Cfg::EA;
+  u32 w0[8], w1[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    w0[i] = in[i];
+    w1[i] = in[8 + i];
+  }
+  const bool ylarger = (w1[7] & CODEC_Y_LARGER) != 0, infinity = (w1[7] & CODEC_INFINITY) != 0;
+  w1[7] &= ~(CODEC_Y_LARGER | CODEC_INFINITY);
+  CdF2 X, b;
+  X.c0 = codec_fq(w0);
+  X.c1 = codec_fq(w1);
+  b.c0 = CdFq(fe_const<FqParams, 16>(pc::TWIST_B[0]));
+  b.c1 = CdFq(fe_const<FqParams, 16>(pc::TWIST_B[1]));
+  const CdF2 rhs = reduce_to<32>(add(mul(sqr(X), X), b));
+  CdF2 Y;
+  const bool on = fq2_sqrt(rhs, Y);   // the root that is not larger2
+  const int code = codec_code(infinity, ylarger, codec_words_zero(w0) && codec_words_zero(w1),
+                              codec_canonical(w0) && codec_canonical(w1), on, is_zero(Y));
+  const bool inf = infinity || code != CODEC_OK;
+  const Fe2<16> zero = el_zero(Y);
+  const Fe2<16> y = select_el(ylarger, canonical(neg(Y)), canonical(Y));
+  q.x = EA(select_el(inf, zero, canonical(X)));
+  q.y = EA(select_el(inf, zero, y));
+  q2 = glv_image<G2Cfg>(q);
   return code;
 }
 
@@ -305,6 +360,39 @@ __global__ __launch_bounds__(64) void k_codec_decompress(const u32* __restrict__
     CodecG2 p;
     codes[i] = codec_g2_decode(in + 16L * i, p);
     codec_g2_store(p, S, out + 6L * S * i);
+  }
+}
+
+// n compressed points into the 2 n prepared records of the GLV plan: record i = (x, y), record n + i = (beta x, y)
+template <int TYPE>
+__global__ __launch_bounds__(64) void k_codec_decompress_prepared(const u32* __restrict__ in, int n,
+                                                                  u32* __restrict__ aff, int32_t* __restrict__ codes) {
+  using CV = std::conditional_t<TYPE == 1, G1Cfg, G2Cfg>;
+  using IO = CurveIO<CV>;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Aff<typename CV::EA> q, q2;
+  if constexpr (TYPE == 1)
+    codes[i] = codec_g1_decode_prepared(in + 8L * i, q, q2);
+  else
+    codes[i] = codec_g2_decode_prepared(in + 16L * i, q, q2);
+  IO::store_aff(q, aff + (size_t)i * IO::AFF_WORDS);
+  IO::store_aff(q2, aff + (size_t)(n + i) * IO::AFF_WORDS);
+}
+
+// The order-r check of the G2 records k_codec_decompress_prepared has just written (affine Montgomery already): a
+// finite point with [r]P != O gets code 4 and the (0, 0) marker in both records.  A kernel of its own, so that the
+// decoder keeps its registers.
+__global__ __launch_bounds__(64) void k_codec_subgroup_g2(u32* __restrict__ aff, int n, int32_t* __restrict__ codes) {
+  using IO = CurveIO<G2Cfg>;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Aff<G2Cfg::EA> q = IO::load_aff(aff + (size_t)i * IO::AFF_WORDS);
+  if (is_inf(q) || is_inf(bv_scalar_mul<G2Cfg>(q, GlvConsts::R32, 8))) return;
+  codes[i] = CODEC_E_SUBGROUP;
+  for (int k = 0; k < IO::AFF_WORDS; k++) {
+    aff[(size_t)i * IO::AFF_WORDS + k] = 0;
+    aff[(size_t)(n + i) * IO::AFF_WORDS + k] = 0;
   }
 }
 

@@ -10,6 +10,7 @@ using namespace ozk;
 namespace {
 
 constexpr int CODEC_MAX_N = 1 << 24;
+constexpr int CODEC_PREPARED_MAX_N = 1 << 23;   // the GLV plan of the variable-base MSM (msm_var_driver.cuh GLV_MAX_N)
 
 // words per coordinate of a wire format: 0 wire-in (32-byte coordinates), 1 wire-out (64-byte)
 int coord_words(int32_t format) { return format == 0 ? 8 : format == 1 ? 16 : 0; }
@@ -34,6 +35,31 @@ int ozk_points_decompress_dev(const void* d_in, int32_t n, int32_t type, int32_t
   else
     hipLaunchKernelGGL(k_codec_decompress<2>, grid, block, 0, (hipStream_t)stream, (const u32*)d_in, (int)n, S,
                        (u32*)d_out, d_codes);
+  OZK_HIP(hipGetLastError());
+  return OZK_OK;
+}
+
+int ozk_points_decompress_prepared_dev(const void* d_in, int32_t n, int32_t type, void* d_prepared,
+                                       size_t prepared_bytes, int32_t* d_codes, int32_t check_subgroup, void* stream) {
+  hip_clear_stale();
+  if (!d_in || !d_prepared || !d_codes || n <= 0) return fail(OZK_E_INVALID, "bad argument");
+  if (type != OZK_G1 && type != OZK_G2) return fail(OZK_E_INVALID, "unknown point type %d", (int)type);
+  if (n > CODEC_PREPARED_MAX_N || !ozk_var_msm_glv(n))
+    return fail(OZK_E_INVALID, "%d points: only the two-record GLV form of the prepared bases is written (n <= 2^23)", (int)n);
+  if (prepared_bytes < ozk_var_msm_prepared_bytes(n, type))
+    return fail(OZK_E_INVALID, "prepared buffer too small: %zu < %zu", prepared_bytes, ozk_var_msm_prepared_bytes(n, type));
+  if (misaligned(d_in) || misaligned(d_prepared)) return fail(OZK_E_INVALID, "buffers must be 4-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((n + 63) / 64), block(64);
+  if (type == OZK_G1) {
+    hipLaunchKernelGGL(k_codec_decompress_prepared<1>, grid, block, 0, s, (const u32*)d_in, (int)n, (u32*)d_prepared,
+                       d_codes);
+  } else {
+    hipLaunchKernelGGL(k_codec_decompress_prepared<2>, grid, block, 0, s, (const u32*)d_in, (int)n, (u32*)d_prepared,
+                       d_codes);
+    if (check_subgroup)   // G1 has cofactor 1: nothing to check there
+      hipLaunchKernelGGL(k_codec_subgroup_g2, grid, block, 0, s, (u32*)d_prepared, (int)n, d_codes);
+  }
   OZK_HIP(hipGetLastError());
   return OZK_OK;
 }

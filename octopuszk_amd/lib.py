@@ -115,6 +115,7 @@ _SIGS = {
     "ozk_multi_msm_plan": (ctypes.c_int, [i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
     "ozk_points_decompress_dev": (ctypes.c_int, [vp, i32, i32, i32, vp, vp, vp]),
     "ozk_points_compress_dev": (ctypes.c_int, [vp, i32, i32, i32, vp, vp]),
+    "ozk_points_decompress_prepared_dev": (ctypes.c_int, [vp, i32, i32, vp, sz, vp, i32, vp]),
     "ozk_groth16_proofs_decompress_dev": (ctypes.c_int, [vp, i32, vp, vp, vp]),
 }
 

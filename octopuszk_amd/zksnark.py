@@ -480,9 +480,84 @@ class _LazyScalars(dict):
         return v
 
 
+_PK_G1 = ("alpha_g1", "beta_g1", "delta_g1", "query_a", "query_b_g1", "delta_abc_g1", "query_h")
+_PK_G2 = ("beta_g2", "delta_g2", "query_b_g2")
+
+
+def _r1cs_from_key_file(kf) -> R1CSRelation:
+    h = kf.header
+    return R1CSRelation(*(LinearCombinations(*side) for side in kf.r1cs()), h.num_inputs, h.num_auxiliary)
+
+
+def _key_point_failure(section, index, code):
+    from . import codec as _codec
+    return ValueError("proving key: section %s, point %d does not decode: code %d (%s)"
+                      % (section, index, code, _codec.CODE_NAMES.get(code, "?")))
+
+
+def _first_failure(codes):
+    """(index, code) of the first non-zero code of an int32 device tensor, or None"""
+    bad = torch.nonzero(codes)
+    if bad.numel() == 0:
+        return None
+    j = int(bad[0, 0].item())
+    return j, int(codes[j].item())
+
+
 class ProvingKey:
     """zk_proof_systems/zkSNARK/objects/ProvingKey.java, every group element resident in HBM in the
-    variable-base wire-in format."""
+    variable-base wire-in format.  to_bytes / save and from_bytes / load move it through the key file of DESIGN.md
+    section 14 (keyfile.py); a prover that only proves loads the file without this object
+    (SerialProver.from_key_file)."""
+
+    def to_bytes(self) -> bytes:
+        """The key file: every point compressed on the device (32 bytes per G1 point, 64 per G2), and the R1CS."""
+        from . import codec as _codec
+        from . import keyfile as _keyfile
+        r1cs = self.r1cs
+        sections = {}
+        for name in _PK_G1 + _PK_G2:
+            enc = (_codec.compress_g1 if name in _PK_G1 else _codec.compress_g2)(getattr(self, name), "wire_in")
+            sections[name] = bytes(enc.cpu().numpy())
+        for name, lc in (("r1cs_a", r1cs.A), ("r1cs_b", r1cs.B), ("r1cs_c", r1cs.C)):
+            sections[name] = _keyfile.r1cs_section(lc.ptr, lc.index, lc.value)
+        return _keyfile.build(r1cs.num_inputs, r1cs.num_auxiliary, r1cs.num_constraints, sections)
+
+    def save(self, path):
+        with open(path, "wb") as f:
+            f.write(self.to_bytes())
+
+    @staticmethod
+    def _from_key_file(kf, verify_digest) -> "ProvingKey":
+        from . import codec as _codec
+        if verify_digest:
+            kf.verify_digest()
+        pk = ProvingKey()
+        pk.r1cs = _r1cs_from_key_file(kf)
+        for name in _PK_G1 + _PK_G2:
+            pts, codes = (_codec.decompress_g1 if name in _PK_G1 else _codec.decompress_g2)(_dev_bytes(kf.read(name)), "wire_in")
+            bad = _first_failure(codes)
+            if bad:
+                raise _key_point_failure(name, *bad)
+            setattr(pk, name, pts)
+        return pk
+
+    @staticmethod
+    def from_bytes(b, verify_digest=True) -> "ProvingKey":
+        """The key of a key file, its points decoded on the device into wire-in tensors, with pk.r1cs: what
+        serial_setup_generate returns as crs.proving_key.  ValueError for a malformed file (keyfile.py names what is
+        wrong) and for a point that does not decode (section, index and codec.CODE_NAMES[code])."""
+        from . import keyfile as _keyfile
+        return ProvingKey._from_key_file(_keyfile.KeyFile(b), verify_digest)
+
+    @staticmethod
+    def load(path, verify_digest=True) -> "ProvingKey":
+        from . import keyfile as _keyfile
+        kf = _keyfile.KeyFile(path)
+        try:
+            return ProvingKey._from_key_file(kf, verify_digest)
+        finally:
+            kf.close()
 
 
 class CRS:
@@ -830,38 +905,101 @@ class ShardedProver:
     The witness map runs on every rank (a replica: DESIGN.md section 7).  This class holds the one schedule of a
     proof's device work (_enqueue); SerialProver is its rank 0 of a world of one."""
 
+    # the five MSMs of a proof: plan key -> (the key arrays whose concatenation it runs over, group)
+    # A = alpha + sum z_i A_i(t) + r delta (SerialProver.java:76-79,105): the Java sums a primary-input MSM,
+    # an auxiliary-input MSM, alpha and r delta; here ONE MSM over query A ++ [alphaG1, deltaG1] with scalars
+    # z ++ [1, r] — the same group element, hence the same affine bytes, without the two short MSMs (each of
+    # which costs a whole latency-bound tail) and four additions.  B likewise with beta, delta and s (:82-88,108-110).
+    _MSMS = (("qa", "A", ("query_a", "alpha_g1", "delta_g1"), 1), ("qb1", "B1", ("query_b_g1", "beta_g1", "delta_g1"), 1),
+             ("qb2", "B2", ("query_b_g2", "beta_g2", "delta_g2"), 2), ("dabc", "L", ("delta_abc_g1",), 1),
+             ("qh", "H", ("query_h",), 1))
+
     def __init__(self, pk: ProvingKey, rank: int, world: int):
-        L = _lib.load()
         r1cs = pk.r1cs
+        self._shape(r1cs.num_inputs, r1cs.num_variables, r1cs.num_constraints, rank, world)
+        assert pk.query_h.numel() == (self.m + 1) * 96 and pk.query_a.numel() == self.nv * 96
+        for attr, key, names, type_ in self._MSMS:
+            lo, hi = self.plan[key]
+            setattr(self, attr, prepare_bases(_rows([getattr(pk, n) for n in names], lo, hi, 96 * type_), hi - lo, type_))
+            torch.cuda.current_stream().synchronize()   # a concatenated slice dies here
+        self._finish(r1cs, pk.delta_g1)
+
+    @classmethod
+    def from_key_file(cls, path_or_file, rank: int = 0, world: int = 1, check_subgroup: bool = True, verify_digest=None,
+                      timing=None):
+        """The prover of rank `rank` straight from a key file (a path or a binary file
+        object).  Read are the header, the R1CS sections and, by offset, the rows of shard_plan for this rank — joined
+        compressed, uploaded compressed and decoded on the device into the prepared bases
+        (codec.decompress_prepared): no wire-in copy of the key exists at any time, on the host or in HBM, and a rank
+        never holds more than its 1 / world of it.  check_subgroup: the points of query B in G2, beta and delta are
+        checked for order r.  ValueError for a malformed file and for a point that does not decode (section, index,
+        codec.CODE_NAMES[code]).
+        verify_digest: the SHA-256 of the header covers the whole file, so checking it reads the whole file.  The
+        default (None) checks it when world = 1 and not when world > 1, where the point of a rank is not to read the
+        other ranks' rows; pass True to check it on a rank all the same.
+        `timing` (optional dict) receives read_s, upload_s and decode_s, wall times with a synchronise between."""
+        from . import codec as _codec
+        from . import keyfile as _keyfile
+        kf = _keyfile.KeyFile(path_or_file)
+        T = {"read_s": 0.0, "upload_s": 0.0, "decode_s": 0.0}
+        try:
+            if (world == 1) if verify_digest is None else verify_digest:
+                kf.verify_digest()
+            h = kf.header
+            self = cls.__new__(cls)
+            self._shape(h.num_inputs, h.nv, h.num_constraints, rank, world)
+            t0 = time.perf_counter()
+            r1cs = _r1cs_from_key_file(kf)
+            T["read_s"] += time.perf_counter() - t0
+            for attr, key, names, type_ in self._MSMS:
+                lo, hi = self.plan[key]
+                t0 = time.perf_counter()
+                enc, parts = kf.read_joined(names, lo, hi)
+                t1 = time.perf_counter()
+                d_enc = _dev_bytes(enc)
+                torch.cuda.synchronize()
+                t2 = time.perf_counter()
+                prepared, codes = _codec.decompress_prepared(d_enc, type_, check_subgroup)
+                bad = _first_failure(codes)   # (synchronises)
+                t3 = time.perf_counter()
+                T["read_s"] += t1 - t0
+                T["upload_s"] += t2 - t1
+                T["decode_s"] += t3 - t2
+                if bad:
+                    raise _key_point_failure(*_keyfile.locate(parts, bad[0]), bad[1])
+                setattr(self, attr, prepared)
+            # deltaG1 once more as a wire-in point: a base of the 3-term MSM behind every rank's share of C
+            delta, codes = _codec.decompress_g1(_dev_bytes(kf.read("delta_g1")), "wire_in")
+            bad = _first_failure(codes)
+            if bad:
+                raise _key_point_failure("delta_g1", *bad)
+        finally:
+            kf.close()
+        self._finish(r1cs, delta)
+        if timing is not None:
+            timing.update(T)
+        return self
+
+    def _shape(self, ni, nv, nc, rank, world):
+        """the sizes of the key and this rank's slices of the five MSMs"""
         self.rank, self.world = rank, world
-        self.ni, self.nv = r1cs.num_inputs, r1cs.num_variables
-        self.nw = self.nv - self.ni
-        self.m = lowest_power_of_two(r1cs.num_constraints + self.ni)
-        nv, nw, m = self.nv, self.nw, self.m
-        assert pk.query_h.numel() == (m + 1) * 96 and pk.query_a.numel() == nv * 96
+        self.ni, self.nv = ni, nv
+        self.nw = nv - ni
+        self.m = lowest_power_of_two(nc + ni)
+        nw, m = self.nw, self.m
         if not 0 <= rank < world:
             raise ValueError("rank %d outside a world of %d" % (rank, world))
         if world > min(nv + 2, nw, m + 1):
             raise ValueError("a world of %d leaves a rank an empty slice (slice lengths nv + 2 = %d, nw = %d, m + 1 = %d)"
                              % (world, nv + 2, nw, m + 1))
-        self.plan = plan = shard_plan(nv, m, nw, rank, world)
+        self.plan = shard_plan(nv, m, nw, rank, world)
 
-        def prep(parts, key, row_bytes, type_):
-            lo, hi = plan[key]
-            out = prepare_bases(_rows(parts, lo, hi, row_bytes), hi - lo, type_)
-            torch.cuda.current_stream().synchronize()   # a concatenated slice dies here
-            return out
-
-        # A = alpha + sum z_i A_i(t) + r delta (SerialProver.java:76-79,105): the Java sums a primary-input MSM,
-        # an auxiliary-input MSM, alpha and r delta; here ONE MSM over query A ++ [alphaG1, deltaG1] with scalars
-        # z ++ [1, r] — the same group element, hence the same affine bytes, without the two short MSMs (each of
-        # which costs a whole latency-bound tail) and four additions.  B likewise with beta, delta and s (:82-88,108-110).
-        self.qa = prep((pk.query_a, pk.alpha_g1, pk.delta_g1), "A", 96, 1)
-        self.qb1 = prep((pk.query_b_g1, pk.beta_g1, pk.delta_g1), "B1", 96, 1)
-        self.qb2 = prep((pk.query_b_g2, pk.beta_g2, pk.delta_g2), "B2", 192, 2)
-        self.dabc = prep((pk.delta_abc_g1,), "L", 96, 1)
-        self.qh = prep((pk.query_h,), "H", 96, 1)
-        self.delta_g1 = pk.delta_g1
+    def _finish(self, r1cs, delta_g1):
+        """everything after "the five prepared buffers exist" (qa, qb1, qb2, dabc, qh): the same for a key in HBM and
+        a key file"""
+        L = _lib.load()
+        nv, nw, m, plan = self.nv, self.nw, self.m, self.plan
+        self.delta_g1 = delta_g1
         self.key_bytes = {
             "rank": sum(int(t.numel()) for t in (self.qa, self.qb1, self.qb2, self.dabc, self.qh)),
             "serial": (2 * _prepared_bytes(nv + 2, 1) + _prepared_bytes(nv + 2, 2) + _prepared_bytes(nw, 1)
@@ -1009,6 +1147,12 @@ class SerialProver(ShardedProver):
 
     def __init__(self, pk: ProvingKey):
         super().__init__(pk, 0, 1)
+
+    @classmethod
+    def from_key_file(cls, path_or_file, check_subgroup: bool = True, verify_digest: bool = True, timing=None):
+        """The prover of a key file (ShardedProver.from_key_file for rank 0 of a world of one): the file is read once,
+        its digest checked, its points decoded straight into the prepared bases."""
+        return super().from_key_file(path_or_file, 0, 1, check_subgroup, verify_digest, timing)
 
     def prove(self, primary, auxiliary, seed: int = SEED, timing=None, full_bytes=None) -> Proof:
         """`full_bytes` (optional): the assignment already marshalled (assignment_bytes).  `timing` (optional dict)
