@@ -528,6 +528,26 @@ int ozk_points_compress_dev(const void* d_in, int32_t n, int32_t type, int32_t i
 int ozk_groth16_proofs_decompress_dev(const void* d_in128, int32_t k, void* d_records768, int32_t* d_codes,
                                       void* stream);
 
+/* ---- n points times one scalar (points_scale.hip; no counterpart in the reference): out_i =
+ * [k] P_i, the operation of a phase-2 key contribution (delta_abc_g1 and query_h times 1 / d) and, with k = r - 1 on
+ * one point, of the subgroup test of its new delta_g2.
+ *   d_in      n wire-in points of `type` (OZK_G1 96 B, OZK_G2 192 B: X | Y | Z, 32-byte little-endian; any Z, Z = 0
+ *             is infinity), read as ozk_var_msm_dev reads its bases
+ *   k_host32  the scalar, 32 bytes little-endian in HOST memory (as the t of ozk_fr_powers_dev), read before the call
+ *             returns.  It must be below r: a value >= r is OZK_E_INVALID and nothing is enqueued.  k = 0 is legal
+ *             and gives n points at infinity.
+ *   d_out     n wire-in points, affine-normalised (Z = 1, canonical, non-Montgomery); infinity as
+ *             ozk_points_decompress_dev writes it: (0, 1, 0) for G1, ((0, 0), (1, 0), (0, 0)) for G2.  d_out == d_in
+ *             is allowed (a lane reads its point before it writes); any other overlap is not.
+ * The scalar is recoded once on the host and the digit schedule passed in the kernel arguments, one point per lane:
+ * G1 runs a GLV split in joint sparse form (about 128 doublings and 64 mixed additions per point), G2 the
+ * non-adjacent form of k without the endomorphism, so that the result is exact for EVERY point of the twist, inside
+ * the order-r subgroup or not.  Every addition is complete.
+ * n <= 0 or n > 2^24, a null pointer, an unknown type, a buffer that is not 4-byte aligned: OZK_E_INVALID.
+ * Asynchronous on `stream`; allocates nothing and needs no workspace. */
+int ozk_points_scale_dev(const void* d_in, int32_t n, int32_t type, const uint8_t* k_host32, void* d_out,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,7 @@ _SIGS = {
     "ozk_points_compress_dev": (ctypes.c_int, [vp, i32, i32, i32, vp, vp]),
     "ozk_points_decompress_prepared_dev": (ctypes.c_int, [vp, i32, i32, vp, sz, vp, i32, vp]),
     "ozk_groth16_proofs_decompress_dev": (ctypes.c_int, [vp, i32, vp, vp, vp]),
+    "ozk_points_scale_dev": (ctypes.c_int, [vp, i32, i32, vp, vp, vp]),
 }
 
 

@@ -559,6 +559,16 @@ class ProvingKey:
         finally:
             kf.close()
 
+    def contribute(self, vk=None, d=None, *, nonce=None, previous=b""):
+        """(the key after a phase-2 contribution, its verification key or None, the receipt): ceremony.contribute"""
+        from . import ceremony as _ceremony
+        return _ceremony.contribute(self, vk, d, nonce=nonce, previous=previous)
+
+    def verify_contribution(self, pk_after, receipt, **kw) -> bool:
+        """pk_after is this key after one honest contribution described by `receipt`: ceremony.verify_contribution"""
+        from . import ceremony as _ceremony
+        return _ceremony.verify_contribution(self, pk_after, receipt, **kw)
+
 
 class CRS:
     pass
