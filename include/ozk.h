@@ -548,6 +548,43 @@ int ozk_groth16_proofs_decompress_dev(const void* d_in128, int32_t k, void* d_re
 int ozk_points_scale_dev(const void* d_in, int32_t n, int32_t type, const uint8_t* k_host32, void* d_out,
                          void* stream);
 
+/* ---- point kernels of the setup from a powers-of-tau string (ec_fft.hip; no counterpart in
+ * the reference).  All three read wire-in points of `type` (OZK_G1 96 B, OZK_G2 192 B; any Z, Z = 0 is infinity) as
+ * ozk_points_scale_dev reads them and write affine-normalised wire-in points (Z = 1, canonical), infinity as
+ * ozk_points_decompress_dev writes it.  Every addition is complete, so the result is exact for every input: infinity,
+ * repeated points, P with -P.  Asynchronous on `stream`; they allocate nothing; a bad argument (a null pointer, an
+ * unknown type, a count out of range, a buffer that is not 4-byte aligned, a workspace that is too small) is
+ * OZK_E_INVALID with nothing enqueued.
+ *
+ *   ozk_ec_fft_dev   the radix-2 transform in the exponent: out[j] = sum_i [omega^(i j)] in[i], in natural order, for
+ *                    n a power of two in [1, 2^22].  inverse != 0 uses omega^-1 and multiplies by 1 / n (what
+ *                    SerialFFT.radix2InverseFFT does to scalars).  omega_host32: 32 bytes little-endian in HOST
+ *                    memory, read before the call returns; it must be below r with omega^n = 1 and omega^(n/2) != 1,
+ *                    else OZK_E_INVALID.  d_out must NOT overlap d_in (the first step is a bit-reversing copy).
+ *                    d_workspace: ozk_ec_fft_workspace_bytes(n, type) bytes (0 for a bad n or type): the digit
+ *                    schedules of the 3 n / 4 twiddles, 132 bytes each, recoded on the device at every call.
+ *                    G1 runs the GLV ladder of ozk_points_scale_dev per butterfly, G2 the non-adjacent form without
+ *                    the endomorphism: both are exact on the whole curve / twist, no subgroup assumption.
+ *   ozk_sparse_mat_points_dev
+ *                    out[row] = sum over the row's terms of [coeff] points[index]: the CSR layout, the
+ *                    NULL-coefficients-mean-one rule and the long-row list (rows of more than 64 terms) of
+ *                    ozk_sparse_mat_vec_dev.  An empty row gives infinity.  Coefficients 1 and r - 1 (and NULL) cost
+ *                    one mixed addition, 0 nothing, any other value a per-lane double-and-add over its 254 bits.
+ *                    A long row is cut into 4096 strided partial sums, then 64, then one.  d_workspace:
+ *                    ozk_sparse_mat_points_workspace_bytes(n_long, type) bytes, unused (may be NULL) for n_long = 0.
+ *                    rows in [1, 2^24], n_long in [0, 2^16].  d_out must not overlap an input.
+ *   ozk_points_add_dev
+ *                    out[i] = a[i] + b[i], or a[i] - b[i] for negate_b != 0; n in [1, 2^24].  d_out may be d_a or d_b. */
+size_t ozk_ec_fft_workspace_bytes(int32_t n, int32_t type);
+int ozk_ec_fft_dev(const void* d_in, int32_t n, int32_t type, const uint8_t* omega_host32, int32_t inverse,
+                   void* d_out, void* d_workspace, size_t workspace_bytes, void* stream);
+size_t ozk_sparse_mat_points_workspace_bytes(int32_t n_long, int32_t type);
+int ozk_sparse_mat_points_dev(const void* d_row_ptr, const void* d_index, const void* d_coeff, const void* d_points,
+                              int32_t rows, int32_t type, const void* d_long_rows, int32_t n_long, void* d_out,
+                              void* d_workspace, size_t workspace_bytes, void* stream);
+int ozk_points_add_dev(const void* d_a, const void* d_b, int32_t n, int32_t type, int32_t negate_b, void* d_out,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,12 +32,13 @@ struct ScaleSchedule {
 };
 OZK_HD u32 scale_step(const ScaleSchedule& s, int i) { return (s.w[i >> 3] >> (4 * (i & 7))) & 15u; }
 
-// ---------------------------------------------------------------------------------------------- host recoding
+// ---------------------------------------------------------------------------------------------- recoding
+// (on the host for ozk_points_scale_dev, on the device for the per-twiddle schedules of ec_fft.cuh)
 // Joint sparse form (Solinas 2001) of two non-negative integers below 2^256, least significant column first, each
 // column's signs flipped where its integer is to be subtracted (neg1 / neg2).  u = a mods 4 for an odd a, negated
 // when a = +-3 (mod 8) and b = 2 (mod 4): then (a - u) / 2 is odd exactly when b / 2 is, so that non-zero columns
 // pair up.  sum u_i 2^i = a whatever the choice of sign, which is all the ladder needs.
-inline void scale_jsf(const u32 (&a_in)[8], bool neg1, const u32 (&b_in)[8], bool neg2, ScaleSchedule& s) {
+OZK_HD void scale_jsf(const u32 (&a_in)[8], bool neg1, const u32 (&b_in)[8], bool neg2, ScaleSchedule& s) {
   u32 v[2][9];
   for (int i = 0; i < 8; i++) {
     v[0][i] = a_in[i];
@@ -70,7 +71,7 @@ inline void scale_jsf(const u32 (&a_in)[8], bool neg1, const u32 (&b_in)[8], boo
   s.len = len;
 }
 // k < r (the caller's check).  G1: the GLV halves jointly; G2: k alone.
-inline void scale_recode(const u32 (&k)[8], bool glv, ScaleSchedule& s) {
+OZK_HD void scale_recode(const u32 (&k)[8], bool glv, ScaleSchedule& s) {
   const u32 zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (!glv) return scale_jsf(k, false, zero, false, s);
   u32 h1[4], h2[4], k1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, k2[8] = {0, 0, 0, 0, 0, 0, 0, 0};

@@ -678,6 +678,13 @@ def serial_setup_generate(r1cs: R1CSRelation, seed: int = SEED, log=None) -> CRS
     return crs
 
 
+def setup_from_srs(r1cs: R1CSRelation, srs, log=None) -> CRS:
+    """The key of `r1cs` from a powers-of-tau string (srs.Srs), computed on the GPU without tau, alpha or beta, with
+    gamma = delta = 1: srs.setup_from_srs.  crs.secrets is None: nobody needs to know any."""
+    from . import srs as _srs
+    return _srs.setup_from_srs(r1cs, srs, log)
+
+
 # ---------------------------------------------------------------------------- prover
 class _G1Pipeline:
     """Several G1 MSMs of different lengths in flight over ONE workspace: heads back to back on the caller's
