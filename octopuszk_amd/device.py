@@ -120,7 +120,92 @@ class SharedBaseMsm:
         return out
 
 
-class VarMsmPipeline:
+class _MsmPipeline:
+    """What the two schedules below share: the lengths a pipeline is sized for, its result slots (tail buffer, output
+    and tail-done event per slot), the lone last MSM, and the lifetime of the object.
+
+    `n` is one length or a sequence of lengths: submit(..., n=) then takes any of them, and every buffer holds the
+    largest of its byte query over the lengths (the queries are not monotonic in n, so not the query at the largest).
+    `tail_mode` is the shape of the window sums of the tails (include/ozk.h, ozk_var_msm_tail_mode_dev): 0 latency,
+    1 throughput.  `last_lone` chooses what submit(last=True) means: see the two submit methods."""
+
+    def __init__(self, n, type_, depth, tail_mode, last_lone, device):
+        L = _lib.load()
+        self.sizes = [int(x) for x in n] if isinstance(n, (list, tuple)) else [n]
+        self.n, self.type, self.depth = max(self.sizes), type_, depth
+        self.tail_mode, self.last_lone, self.device = int(tail_mode), bool(last_lone), device
+        self.tail_bytes = self._max_bytes(L.ozk_var_msm_tail_bytes)
+        self.tails = [self._buf(self.tail_bytes) for _ in range(depth)]
+        self.outs = [torch.zeros(192 if type_ == 1 else 384, dtype=torch.uint8, device=device) for _ in range(depth)]
+        self._results = list(self.outs)     # where each slot's result goes: outs[slot], or the caller's `out`
+        self.tail_done = [torch.cuda.Event() for _ in range(depth)]
+        if self.last_lone:                  # a whole MSM's workspace, for submit(last=True)
+            self.full_ws_bytes = self._max_bytes(L.ozk_var_msm_workspace_bytes)
+            self.full_ws = self._buf(self.full_ws_bytes)
+        self.count = 0
+        self._inputs = None
+
+    def _buf(self, nbytes):
+        return torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+
+    def _max_bytes(self, query):
+        return max(int(query(n, self.type)) for n in self.sizes)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    __del__ = _close_on_del
+
+    def prepare(self, d_bases, n=None):
+        return prepare_bases(d_bases, self.n if n is None else n, self.type)
+
+    def _begin(self, d_bases, d_scalars, n, out):
+        """slot, length and output tensor of the submission that starts"""
+        n = self.n if n is None else int(n)
+        if n not in self.sizes:
+            raise ValueError(f"n={n}: the pipeline is sized for the lengths {self.sizes}")
+        slot = self.count % self.depth
+        if out is None:
+            out = self.outs[slot]
+        elif out.numel() * out.element_size() != self.outs[slot].numel() or not out.is_contiguous():
+            raise ValueError(f"out must be {self.outs[slot].numel()} contiguous bytes")
+        self._inputs = (d_bases, d_scalars)
+        self._results[slot] = out
+        return slot, n, out
+
+    def _end(self, stream, slot):
+        self.tail_done[slot].record(stream)
+        self.count += 1
+        return self.count - 1
+
+    def _lone(self, stream, d_bases, d_scalars, prepared, n, out, slot):
+        """submit(last=True) of a last_lone pipeline: nothing follows this MSM, so most of its bucket accumulation and
+        all of its tail run with the chip to themselves — the single-call entry point then does better than the stages:
+        its level-1 launch is a whole number of rounds of the chip and its tail has the latency shape (a
+        2^20-constraint proof's H MSM: 2.49 + 0.22 + 1.1 ms -> see DESIGN.md section 8)."""
+        L = _lib.load()
+        msm = L.ozk_var_msm_prepared_dev if prepared else L.ozk_var_msm_dev
+        _lib.check(msm(_ptr(d_bases), _ptr(d_scalars), n, self.type, _ptr(out), _ptr(self.full_ws), self.full_ws_bytes,
+                       int(stream.cuda_stream)))
+        return self._end(stream, slot)
+
+    def done(self, ticket):
+        """The event that fires when `ticket`'s result is complete (re-recorded by the slot's next submission): for
+        callers that queue the wait on a stream of their own."""
+        assert self.count - ticket <= self.depth, "result buffer already reused"
+        return self.tail_done[ticket % self.depth]
+
+    def result(self, ticket):
+        """Output tensor of `ticket` (outs[slot], valid until `depth` more submissions, or the `out` it was submitted
+        with); the current stream waits for its tail."""
+        torch.cuda.current_stream().wait_event(self.done(ticket))
+        return self._results[ticket % self.depth]
+
+
+class VarMsmPipeline(_MsmPipeline):
     """Several device-resident MSMs in flight: heads (throughput-bound) run back to back on the
     caller's stream and share ONE workspace; each tail (latency-bound: upper window-sum levels,
     Horner, normalisation) runs on a side stream out of its own small tail buffer, overlapping the
@@ -131,17 +216,13 @@ class VarMsmPipeline:
         out = pipe.result(t)                     # makes the current stream wait for that tail
     """
 
-    def __init__(self, n, type_=1, depth=2, device="cuda"):
+    def __init__(self, n, type_=1, depth=2, device="cuda", tail_mode=0, last_lone=False):
+        super().__init__(n, type_, depth, tail_mode, last_lone, device)
         L = _lib.load()
-        self.n, self.type, self.depth = n, type_, depth
-        self.ws_bytes = int(L.ozk_var_msm_head_workspace_bytes(n, type_))
-        self.tail_bytes = int(L.ozk_var_msm_tail_bytes(n, type_))
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=device)
-        self.tails = [torch.empty(self.tail_bytes, dtype=torch.uint8, device=device) for _ in range(depth)]
-        self.outs = [torch.zeros(192 if type_ == 1 else 384, dtype=torch.uint8, device=device) for _ in range(depth)]
+        self.ws_bytes = self._max_bytes(L.ozk_var_msm_head_workspace_bytes)
+        self.ws = self._buf(self.ws_bytes)
         self.side = torch.cuda.Stream(device=device)
         self.head_done = [torch.cuda.Event() for _ in range(depth)]
-        self.tail_done = [torch.cuda.Event() for _ in range(depth)]
         # ordering hint (include/ozk.h): the next head's bucket accumulation is dispatched after the
         # previous tail's multi-wave levels, so that its single-wave Horner kernel is resident first
         self.levels_done = []
@@ -149,7 +230,6 @@ class VarMsmPipeline:
             ev = ctypes.c_void_p()
             _lib.check(L.ozk_order_event_create(ctypes.byref(ev)))
             self.levels_done.append(ev)
-        self.count = 0
 
     def close(self):
         """Destroy the ordering events (after the work that uses them has drained)."""
@@ -160,40 +240,28 @@ class VarMsmPipeline:
                 L.ozk_order_event_destroy(ev)
             self.levels_done = []
 
-    __del__ = _close_on_del
-
-    def prepare(self, d_bases):
-        return prepare_bases(d_bases, self.n, self.type)
-
-    def submit(self, d_bases, d_scalars, prepared=False):
+    def submit(self, d_bases, d_scalars, prepared=False, last=False, n=None, out=None):
+        """last=True: the caller knows that no MSM follows this one.  A last_lone pipeline then runs the whole MSM
+        through the single-call entry point on the caller's stream (_lone); any other treats it like the rest."""
         L = _lib.load()
-        slot = self.count % self.depth
+        slot, n, out = self._begin(d_bases, d_scalars, n, out)
         main = torch.cuda.current_stream()
         if self.count >= self.depth:
             main.wait_event(self.tail_done[slot])      # the tail that last used this slot's buffers
+        if last and self.last_lone:
+            return self._lone(main, d_bases, d_scalars, prepared, n, out, slot)
         prev = self.levels_done[(self.count - 1) % self.depth] if (self.count and self.depth > 1) else None
         head = L.ozk_var_msm_head_prepared_dev if prepared else L.ozk_var_msm_head_ordered_dev
-        _lib.check(head(_ptr(d_bases), _ptr(d_scalars), self.n, self.type, _ptr(self.ws), self.ws_bytes,
+        _lib.check(head(_ptr(d_bases), _ptr(d_scalars), n, self.type, _ptr(self.ws), self.ws_bytes,
                         _ptr(self.tails[slot]), self.tail_bytes, int(main.cuda_stream), prev))
         self.head_done[slot].record(main)
         self.side.wait_event(self.head_done[slot])
-        _lib.check(L.ozk_var_msm_tail_ordered_dev(self.n, self.type, _ptr(self.tails[slot]), self.tail_bytes,
-                                                  _ptr(self.outs[slot]), int(self.side.cuda_stream),
-                                                  self.levels_done[slot]))
-        self.tail_done[slot].record(self.side)
-        self.count += 1
-        return self.count - 1
-
-    def result(self, ticket):
-        """Output tensor of `ticket` (valid until `depth` more submissions); the current stream
-        waits for its tail."""
-        assert self.count - ticket <= self.depth, "result buffer already reused"
-        slot = ticket % self.depth
-        torch.cuda.current_stream().wait_event(self.tail_done[slot])
-        return self.outs[slot]
+        _lib.check(L.ozk_var_msm_tail_mode_dev(n, self.type, _ptr(self.tails[slot]), self.tail_bytes, _ptr(out),
+                                               int(self.side.cuda_stream), self.levels_done[slot], self.tail_mode))
+        return self._end(self.side, slot)
 
 
-class VarMsmPipeline3:
+class VarMsmPipeline3(_MsmPipeline):
     """Three-stage schedule of consecutive device-resident MSMs: SORT of MSM k+1 (base conversion, digits, counting
     sort: HBM / LDS-bound) on the caller's stream | ACCUMULATE of MSM k (bucket accumulation, run merge: vector-ALU
     bound) on a second stream | TAIL of MSM k-1 (window sums, Horner, normalisation: latency-bound) on one or two more.
@@ -202,7 +270,8 @@ class VarMsmPipeline3:
     accumulation blocks per CU (csrc/msm_var.cuh, k_sort2), which is what lets the multiplier run back to back.
     Same interface as VarMsmPipeline (submit -> ticket, result(ticket))."""
 
-    def __init__(self, n, type_=1, depth=3, tail_streams=2, device="cuda", split_accum=None, tail_cus=None):
+    def __init__(self, n, type_=1, depth=3, tail_streams=2, device="cuda", split_accum=None, tail_cus=None,
+                 tail_mode=1, last_lone=False):
         L = _lib.load()
         ts = max(1, tail_streams)
         # tail_cus = N > 0: the tail streams are confined to N compute units and the accumulate stream to the others
@@ -215,18 +284,20 @@ class VarMsmPipeline3:
         self.split = bool(int(os.environ.get("OZK_P3_SPLIT_ACCUM", "0"))) if split_accum is None else bool(split_accum)
         # a result slot is always served by the same tail stream (slot = k mod depth, stream = k mod ts), so whatever a
         # caller enqueues on stream_of(ticket) after result(ticket) is ordered before the slot's next tail
-        self.n, self.type, self.depth = n, type_, (max(2, depth) + ts - 1) // ts * ts
-        sb, swb, awb = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
-        _lib.check(L.ozk_var_msm_stage_bytes(n, type_, ctypes.byref(sb), ctypes.byref(swb), ctypes.byref(awb)))
-        self.sorted_bytes, self.sort_ws_bytes, self.accum_ws_bytes = sb.value, swb.value, awb.value
-        self.tail_bytes = int(L.ozk_var_msm_tail_bytes(n, type_))
-        buf = lambda b: torch.empty(b, dtype=torch.uint8, device=device)
-        self.sorted = [buf(self.sorted_bytes) for _ in range(2)]
-        self.sort_ws, self.accum_ws = buf(self.sort_ws_bytes), buf(self.accum_ws_bytes)
-        self.accum_ws2 = [self.accum_ws, buf(self.accum_ws_bytes)] if self.split else None
+        super().__init__(n, type_, (max(2, depth) + ts - 1) // ts * ts, tail_mode, last_lone, device)
+        self.sorted_bytes = self.sort_ws_bytes = self.accum_ws_bytes = 0
+        for k in self.sizes:
+            sb, swb, awb = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+            _lib.check(L.ozk_var_msm_stage_bytes(k, type_, ctypes.byref(sb), ctypes.byref(swb), ctypes.byref(awb)))
+            self.sorted_bytes = max(self.sorted_bytes, sb.value)
+            self.sort_ws_bytes = max(self.sort_ws_bytes, swb.value)
+            self.accum_ws_bytes = max(self.accum_ws_bytes, awb.value)
+        self.sorted = [self._buf(self.sorted_bytes) for _ in range(2)]
+        self.sort_ws, self.accum_ws = self._buf(self.sort_ws_bytes), self._buf(self.accum_ws_bytes)
+        self.accum_ws2 = [self.accum_ws, self._buf(self.accum_ws_bytes)] if self.split else None
+        # never set in here: tools/sched_probe.py assigns a stream of its own for the second part of a split
+        # accumulate stage (submit: `R`)
         self.rest_st = None
-        self.tails = [buf(self.tail_bytes) for _ in range(self.depth)]
-        self.outs = [torch.zeros(192 if type_ == 1 else 384, dtype=torch.uint8, device=device) for _ in range(self.depth)]
         if self.tail_cus > 0:
             total = int(L.ozk_device_cu_count())
             if not 0 < self.tail_cus < total:
@@ -246,42 +317,45 @@ class VarMsmPipeline3:
         ev = lambda k: [torch.cuda.Event() for _ in range(k)]
         self.sort_done, self.accum_done = ev(2), ev(2)
         self.l1_done = ev(2)
-        self.tail_done = ev(self.depth)
-        self.count = 0
-        self._inputs = None
 
     def close(self):
+        """Destroy the confined streams (after their work has drained); the pipeline cannot be used afterwards."""
         if self._owned:
             torch.cuda.synchronize()
             L = _lib.load()
-            for h in self._owned:
+            owned, self._owned = self._owned, []
+            self.acc = self.tail_st = self.side = None     # no wrapper outlives the stream it wraps
+            for h in owned:
                 L.ozk_stream_destroy(h)
-            self._owned = []
-
-    __del__ = _close_on_del
 
     def _check_stream(self, main):
         if self.tail_cus > 0 and int(main.cuda_stream) == 0:
             raise RuntimeError("VarMsmPipeline3(tail_cus > 0) on the null stream: the confined streams are blocking "
                                "streams and would serialise against it; submit under torch.cuda.stream(<a stream>)")
 
-    def prepare(self, d_bases):
-        return prepare_bases(d_bases, self.n, self.type)
-
-    def submit(self, d_bases, d_scalars, prepared=False, last=False):
-        """last=True: the caller knows that no MSM follows this one (the end of a burst, a prover's final MSM): its
-        tail then runs with the chip to itself and takes the LATENCY shape of the window sums (fused first level +
-        wave levels: ~40 dependent additions shorter) instead of the throughput shape the overlapped tails use."""
+    def submit(self, d_bases, d_scalars, prepared=False, last=False, n=None, out=None):
+        """last=True: the caller knows that no MSM follows this one (the end of a burst, a prover's final MSM).
+        LATENCY TAIL (last_lone=False): it goes through the stages, and its tail, which runs with the chip to itself,
+        takes the latency shape of the window sums (fused first level + wave levels: ~40 dependent additions shorter)
+        whatever tail_mode says.  LONE (last_lone=True): the whole MSM runs through the single-call entry point on
+        the accumulate stream, behind the accumulations already queued (_lone)."""
         L = _lib.load()
         k = self.count
-        s, slot = k % 2, k % self.depth
+        s = k % 2
         main = torch.cuda.current_stream()
         self._check_stream(main)
-        self._inputs = (d_bases, d_scalars)
+        slot, n, out = self._begin(d_bases, d_scalars, n, out)
+        if last and self.last_lone:
+            ready = torch.cuda.Event()
+            ready.record(main)
+            self.acc.wait_event(ready)
+            if k >= self.depth:
+                self.acc.wait_event(self.tail_done[slot])
+            return self._lone(self.acc, d_bases, d_scalars, prepared, n, out, slot)
         if k >= 2:
             main.wait_event(self.accum_done[s])        # sorted set s (and, split, accumulate scratch s) is free again
         sort = L.ozk_var_msm_sort_prepared_dev if prepared else L.ozk_var_msm_sort_dev
-        _lib.check(sort(_ptr(d_bases), _ptr(d_scalars), self.n, self.type, _ptr(self.sorted[s]), self.sorted_bytes,
+        _lib.check(sort(_ptr(d_bases), _ptr(d_scalars), n, self.type, _ptr(self.sorted[s]), self.sorted_bytes,
                         _ptr(self.sort_ws), self.sort_ws_bytes, int(main.cuda_stream)))
         self.sort_done[s].record(main)
         self.acc.wait_event(self.sort_done[s])
@@ -289,48 +363,34 @@ class VarMsmPipeline3:
             self.acc.wait_event(self.tail_done[slot])  # the tail that last used this slot's buffers
         T = self.tail_st[k % len(self.tail_st)]
         accum_ws = self.accum_ws2[s] if self.split else self.accum_ws
-        args = (self.n, self.type, _ptr(self.sorted[s]), self.sorted_bytes, _ptr(accum_ws), self.accum_ws_bytes,
-                _ptr(self.tails[slot]), self.tail_bytes)
+        # (ozk_var_msm_accum_part_dev is the general form of the stage: part 0 all of it, 1 level 1, 2 the rest)
+        accum = lambda stream, part: _lib.check(L.ozk_var_msm_accum_part_dev(
+            _ptr(d_bases) if prepared else None, n, self.type, _ptr(self.sorted[s]), self.sorted_bytes, _ptr(accum_ws),
+            self.accum_ws_bytes, _ptr(self.tails[slot]), self.tail_bytes, int(stream.cuda_stream), part))
         if self.split:
             # the accumulate stage in two parts: sorted set s and accumulate scratch s are free again once the REST of
             # MSM k has run, which is where accum_done[s] is recorded (the next accumulate on scratch s is ordered
             # after it through the sort's wait above)
-            bases = _ptr(d_bases) if prepared else None
-            _lib.check(L.ozk_var_msm_accum_part_dev(bases, *args, int(self.acc.cuda_stream), 1))
+            accum(self.acc, 1)
             self.l1_done[s].record(self.acc)
             R = self.rest_st or T     # (the rest on a stream of its own when the tail streams are confined to a few CUs)
             R.wait_event(self.l1_done[s])
-            _lib.check(L.ozk_var_msm_accum_part_dev(bases, *args, int(R.cuda_stream), 2))
+            accum(R, 2)
             self.accum_done[s].record(R)
             if R is not T:
                 T.wait_event(self.accum_done[s])
         else:
-            if prepared:
-                _lib.check(L.ozk_var_msm_accum_prepared_dev(_ptr(d_bases), *args, int(self.acc.cuda_stream)))
-            else:
-                _lib.check(L.ozk_var_msm_accum_dev(*args, int(self.acc.cuda_stream)))
+            accum(self.acc, 0)
             self.accum_done[s].record(self.acc)
             T.wait_event(self.accum_done[s])
-        if last:
-            _lib.check(L.ozk_var_msm_tail_mode_dev(self.n, self.type, _ptr(self.tails[slot]), self.tail_bytes,
-                                                   _ptr(self.outs[slot]), int(T.cuda_stream), None, 0))
-        else:
-            _lib.check(L.ozk_var_msm_tail_dev(self.n, self.type, _ptr(self.tails[slot]), self.tail_bytes,
-                                              _ptr(self.outs[slot]), int(T.cuda_stream)))
-        self.tail_done[slot].record(T)
-        self.count += 1
-        return k
+        _lib.check(L.ozk_var_msm_tail_mode_dev(n, self.type, _ptr(self.tails[slot]), self.tail_bytes, _ptr(out),
+                                               int(T.cuda_stream), None, 0 if last else self.tail_mode))
+        return self._end(T, slot)
 
     def stream_of(self, ticket):
         """the stream ticket's tail ran on: consumers of result(ticket) that must not stall the caller's (sort)
-        stream enqueue there"""
+        stream enqueue there.  (A lone last MSM ran on the accumulate stream instead: take it through result().)"""
         return self.tail_st[ticket % len(self.tail_st)]
-
-    def result(self, ticket):
-        assert self.count - ticket <= self.depth, "result buffer already reused"
-        slot = ticket % self.depth
-        torch.cuda.current_stream().wait_event(self.tail_done[slot])
-        return self.outs[slot]
 
 
 def gen_g1_bases(n, seed, device="cuda"):

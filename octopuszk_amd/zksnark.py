@@ -37,6 +37,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from . import device as _dev
 from .device import _ptr, _stream, prepare_bases
 from .distributed import shard_range
 from .fft import FR, FR_MULT_GEN, root_of_unity
@@ -686,147 +687,18 @@ def setup_from_srs(r1cs: R1CSRelation, srs, log=None) -> CRS:
 
 
 # ---------------------------------------------------------------------------- prover
-class _G1Pipeline:
-    """Several G1 MSMs of different lengths in flight over ONE workspace: heads back to back on the caller's
-    stream, each tail on a side stream out of its own tail buffer (device.VarMsmPipeline generalised to a
-    length per submission)."""
-
-    def __init__(self, sizes, depth=2, last_lone=True):
-        L = _lib.load()
-        self.depth, self.last_lone = depth, last_lone
-        self.ws_bytes = max(int(L.ozk_var_msm_head_workspace_bytes(n, 1)) for n in sizes)
-        self.tail_bytes = max(int(L.ozk_var_msm_tail_bytes(n, 1)) for n in sizes)
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device="cuda")
-        self.tails = [torch.empty(self.tail_bytes, dtype=torch.uint8, device="cuda") for _ in range(depth)]
-        self.full_ws_bytes = max(int(L.ozk_var_msm_workspace_bytes(n, 1)) for n in sizes)
-        self.full_ws = torch.empty(self.full_ws_bytes, dtype=torch.uint8, device="cuda")   # for submit(last=True)
-        self.side = torch.cuda.Stream()
-        self.head_done = [torch.cuda.Event() for _ in range(depth)]
-        self.tail_done = [torch.cuda.Event() for _ in range(depth)]
-        self.levels_done = []
-        for _ in range(depth):
-            ev = ctypes.c_void_p()
-            _lib.check(L.ozk_order_event_create(ctypes.byref(ev)))
-            self.levels_done.append(ev)
-        self.count = 0
-
-    def submit(self, d_prepared, d_scalars, n, out, last=False):
-        """out: uint8[192] tensor that receives the result (valid once the returned event has fired).
-        last=True: nothing follows this MSM in the pipeline, so most of its bucket accumulation and all of its tail
-        run with the chip to themselves — the single-call entry point then does better than head + tail: its level-1
-        launch is a whole number of rounds of the chip and its tail has the latency shape (a 2^20-constraint proof's H
-        MSM: 2.49 + 0.22 + 1.1 ms -> see DESIGN.md section 8)."""
-        L = _lib.load()
-        slot = self.count % self.depth
-        main = torch.cuda.current_stream()
-        if self.count >= self.depth:
-            main.wait_event(self.tail_done[slot])
-        if last and self.last_lone:
-            _lib.check(L.ozk_var_msm_prepared_dev(_ptr(d_prepared), _ptr(d_scalars), n, 1, _ptr(out), _ptr(self.full_ws),
-                                                  self.full_ws_bytes, int(main.cuda_stream)))
-            self.tail_done[slot].record(main)
-            self.count += 1
-            return self.tail_done[slot]
-        prev = self.levels_done[(self.count - 1) % self.depth] if self.count else None
-        _lib.check(L.ozk_var_msm_head_prepared_dev(_ptr(d_prepared), _ptr(d_scalars), n, 1, _ptr(self.ws), self.ws_bytes,
-                                                   _ptr(self.tails[slot]), self.tail_bytes, int(main.cuda_stream), prev))
-        self.head_done[slot].record(main)
-        self.side.wait_event(self.head_done[slot])
-        # throughput shape of the window sums: the proof keeps the vector ALU busy from start to end, so the additions
-        # the serial levels save are worth more than the dependent additions they add (include/ozk.h)
-        _lib.check(L.ozk_var_msm_tail_mode_dev(n, 1, _ptr(self.tails[slot]), self.tail_bytes, _ptr(out),
-                                               int(self.side.cuda_stream), self.levels_done[slot], 1))
-        self.tail_done[slot].record(self.side)
-        self.count += 1
-        return self.tail_done[slot]
-
-    def close(self):
-        if self.levels_done:
-            L = _lib.load()
-            torch.cuda.synchronize()
-            for ev in self.levels_done:
-                L.ozk_order_event_destroy(ev)
-            self.levels_done = []
-
-
-class _G1Pipeline3:
-    """The three-stage form (device.VarMsmPipeline3 generalised to a length per submission): the SORT of an MSM on the
-    caller's stream, its bucket ACCUMULATION on a second, its TAIL on a third / fourth — so the sort of MSM k + 1 runs
-    beside the accumulation of MSM k instead of after it.  Same interface as _G1Pipeline."""
-
-    def __init__(self, sizes, depth=4, tail_streams=2, last_lone=True):
-        L = _lib.load()
-        self.depth, self.last_lone = depth, last_lone
-        sb = swb = awb = 0
-        for n in sizes:
-            a, b, c = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
-            _lib.check(L.ozk_var_msm_stage_bytes(n, 1, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
-            sb, swb, awb = max(sb, a.value), max(swb, b.value), max(awb, c.value)
-        self.sorted_bytes, self.sort_ws_bytes, self.accum_ws_bytes = sb, swb, awb
-        self.tail_bytes = max(int(L.ozk_var_msm_tail_bytes(n, 1)) for n in sizes)
-        buf = lambda b: torch.empty(b, dtype=torch.uint8, device="cuda")
-        self.sorted = [buf(sb) for _ in range(2)]
-        self.sort_ws, self.accum_ws = buf(swb), buf(awb)
-        self.tails = [buf(self.tail_bytes) for _ in range(depth)]
-        self.full_ws_bytes = max(int(L.ozk_var_msm_workspace_bytes(n, 1)) for n in sizes)
-        self.full_ws = buf(self.full_ws_bytes)
-        self.acc = torch.cuda.Stream()
-        self.tail_st = [torch.cuda.Stream() for _ in range(tail_streams)]
-        ev = lambda k: [torch.cuda.Event() for _ in range(k)]
-        self.sort_done, self.accum_done, self.tail_done = ev(2), ev(2), ev(depth)
-        self.count = 0
-
-    def submit(self, d_prepared, d_scalars, n, out, last=False):
-        L = _lib.load()
-        k = self.count
-        s, slot = k % 2, k % self.depth
-        main = torch.cuda.current_stream()
-        if last and self.last_lone:
-            # the whole MSM on the accumulate stream, behind the accumulations already queued (see _G1Pipeline.submit)
-            ready = torch.cuda.Event()
-            ready.record(main)
-            self.acc.wait_event(ready)
-            if k >= self.depth:
-                self.acc.wait_event(self.tail_done[slot])
-            _lib.check(L.ozk_var_msm_prepared_dev(_ptr(d_prepared), _ptr(d_scalars), n, 1, _ptr(out), _ptr(self.full_ws),
-                                                  self.full_ws_bytes, int(self.acc.cuda_stream)))
-            self.tail_done[slot].record(self.acc)
-            self.count += 1
-            return self.tail_done[slot]
-        if k >= 2:
-            main.wait_event(self.accum_done[s])
-        _lib.check(L.ozk_var_msm_sort_prepared_dev(_ptr(d_prepared), _ptr(d_scalars), n, 1, _ptr(self.sorted[s]),
-                                                   self.sorted_bytes, _ptr(self.sort_ws), self.sort_ws_bytes,
-                                                   int(main.cuda_stream)))
-        self.sort_done[s].record(main)
-        self.acc.wait_event(self.sort_done[s])
-        if k >= self.depth:
-            self.acc.wait_event(self.tail_done[slot])
-        _lib.check(L.ozk_var_msm_accum_prepared_dev(_ptr(d_prepared), n, 1, _ptr(self.sorted[s]), self.sorted_bytes,
-                                                    _ptr(self.accum_ws), self.accum_ws_bytes, _ptr(self.tails[slot]),
-                                                    self.tail_bytes, int(self.acc.cuda_stream)))
-        self.accum_done[s].record(self.acc)
-        T = self.tail_st[k % len(self.tail_st)]
-        T.wait_event(self.accum_done[s])
-        _lib.check(L.ozk_var_msm_tail_mode_dev(n, 1, _ptr(self.tails[slot]), self.tail_bytes, _ptr(out),
-                                               int(T.cuda_stream), None, 1))
-        self.tail_done[slot].record(T)
-        self.count += 1
-        return self.tail_done[slot]
-
-    def close(self):
-        pass
-
-
 def _g1_pipeline(sizes):
-    """The prover's G1 pipeline as the environment selects it: three-stage by default, one tail stream (a
+    """The prover's G1 pipeline (device.VarMsmPipeline3 / VarMsmPipeline over the lengths of its MSMs, throughput-shaped
+    tails: the proof keeps the vector ALU busy from start to end, so the additions the serial levels save are worth more
+    than the dependent additions they add) as the environment selects it: three-stage by default, one tail stream (a
     2^20-constraint proof: 15.6-15.7 ms against 15.9 with the two-stage pipeline of round 2, OZK_PROVER_PIPE3=0; two
     tail streams, OZK_PROVER_TAIL_STREAMS=2, measure the same as one); OZK_PROVER_LAST_LONE=0 sends the last MSM
-    through the stages like the others."""
+    through the stages like the others.  (OZK_P3_SPLIT_ACCUM and OZK_P3_TAIL_CUS are not for the prover.)"""
     lone = os.environ.get("OZK_PROVER_LAST_LONE", "1") != "0"
     if os.environ.get("OZK_PROVER_PIPE3", "1") == "1":
-        return _G1Pipeline3(sizes, tail_streams=int(os.environ.get("OZK_PROVER_TAIL_STREAMS", "1")), last_lone=lone)
-    return _G1Pipeline(sizes, last_lone=lone)
+        return _dev.VarMsmPipeline3(sizes, 1, depth=4, tail_streams=int(os.environ.get("OZK_PROVER_TAIL_STREAMS", "1")),
+                                    tail_mode=1, last_lone=lone, split_accum=False, tail_cus=0)
+    return _dev.VarMsmPipeline(sizes, 1, depth=2, tail_mode=1, last_lone=lone)
 
 
 class Proof:
@@ -1103,16 +975,19 @@ class ShardedProver:
             if mark:
                 mark("map", self.s_fin)
         p = self.pipe
-        ev_a = p.submit(self.qa, d_sc_r, n_ab, rec[:192])         # :76-79,105  A
-        ev_b = p.submit(self.qb1, d_sc_s, n_ab, o1[0])            # :82-88,108-110  B in G1
+        submit = lambda q, d_sc, n, out, last=False: p.done(p.submit(q, d_sc, prepared=True, last=last, n=n, out=out))
+        ev_a = submit(self.qa, d_sc_r, n_ab, rec[:192])           # :76-79,105  A
+        ev_b = submit(self.qb1, d_sc_s, n_ab, o1[0])              # :82-88,108-110  B in G1
         # A_r and B1_r are complete once their tails are: their share of C — s A + r B1 - r s delta (:114) — is a
         # 3-term MSM that runs on its own stream while the long MSMs still occupy the pipeline.  (The waits are queued
         # NOW: the pipeline re-records these per-slot events for the next two submissions.)
         self.s_fin.wait_event(ev_a)
         self.s_fin.wait_event(ev_b)
-        ev_l = p.submit(self.dabc, d_full[32 * (ni + llo):32 * (ni + lhi)], lhi - llo, o1[1])   # :98-101 deltaABC
+        ev_l = submit(self.dabc, d_full[32 * (ni + llo):32 * (ni + lhi)], lhi - llo, o1[1])     # :98-101 deltaABC
         main.wait_event(h_ready)
-        ev_h = p.submit(self.qh, self.d_h[32 * hlo:32 * hhi], hhi - hlo, o1[2], last=True)      # :91-93 query H
+        # query H (:91-93) is the last MSM: alone through the single-call entry point if the pipeline is last_lone,
+        # otherwise through the stages exactly like the others (so not announced: no latency-shaped tail either)
+        ev_h = submit(self.qh, self.d_h[32 * hlo:32 * hhi], hhi - hlo, o1[2], last=p.last_lone)
         with torch.cuda.stream(self.s_fin):
             fin_bases = torch.cat((wire_out_to_in(rec[:192], 1), wire_out_to_in(o1[0], 1), self.delta_g1))
             _lib.check(L.ozk_var_msm_dev(_ptr(fin_bases), _ptr(d_fin_sc), 3, 1, _ptr(o1[3]), _ptr(self.fin_ws),

@@ -57,6 +57,49 @@ def test_three_stage_pipeline_equals_single_calls(n, prepared):
     assert len(set(serial)) == (7 if n > 1 else len(set(serial)))
 
 
+def _narrow_entry_points(d_bases, d_sc, n):
+    """The pipelines issue the accumulate and tail stages through their general entries (ozk_var_msm_accum_part_dev
+    part 0, ozk_var_msm_tail_mode_dev).  The narrow names of the same stages — _accum_dev, _accum_prepared_dev,
+    _tail_dev (throughput, no event), _tail_ordered_dev (latency, with an event) — must give the same bytes.
+    Returns them."""
+    import ctypes
+    import torch
+    from octopuszk_amd import device as dev, lib
+    L = lib.load()
+    p = lambda t: int(t.data_ptr())
+    st = int(torch.cuda.current_stream().cuda_stream)
+    sb, swb, awb = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+    lib.check(L.ozk_var_msm_stage_bytes(n, 1, ctypes.byref(sb), ctypes.byref(swb), ctypes.byref(awb)))
+    tb = int(L.ozk_var_msm_tail_bytes(n, 1))
+    buf = lambda b: torch.empty(b, dtype=torch.uint8, device="cuda")
+    sorted_, sort_ws, accum_ws, tail = buf(sb.value), buf(swb.value), buf(awb.value), buf(tb)
+    prep = dev.prepare_bases(d_bases, n, 1)
+    stage = (n, 1, p(sorted_), sb.value, p(accum_ws), awb.value, p(tail), tb, st)
+    ev = ctypes.c_void_p()
+    lib.check(L.ozk_order_event_create(ctypes.byref(ev)))
+
+    def run(prepared, accum, tail_stage):
+        out = torch.zeros(192, dtype=torch.uint8, device="cuda")
+        sort, b = (L.ozk_var_msm_sort_prepared_dev, prep) if prepared else (L.ozk_var_msm_sort_dev, d_bases)
+        lib.check(sort(p(b), p(d_sc), n, 1, p(sorted_), sb.value, p(sort_ws), swb.value, st))
+        lib.check(accum())
+        lib.check(tail_stage(n, 1, p(tail), tb, p(out), st))
+        torch.cuda.synchronize()
+        return bytes(out.cpu().numpy())
+
+    try:
+        general = run(False, lambda: L.ozk_var_msm_accum_part_dev(None, *stage, 0),
+                      lambda *a: L.ozk_var_msm_tail_mode_dev(*a, None, 1))
+        assert run(False, lambda: L.ozk_var_msm_accum_dev(*stage), L.ozk_var_msm_tail_dev) == general
+        assert run(True, lambda: L.ozk_var_msm_accum_part_dev(p(prep), *stage, 0),
+                   lambda *a: L.ozk_var_msm_tail_mode_dev(*a, ev, 0)) == general
+        assert run(True, lambda: L.ozk_var_msm_accum_prepared_dev(p(prep), *stage),
+                   lambda *a: L.ozk_var_msm_tail_ordered_dev(*a, ev)) == general
+    finally:
+        lib.check(L.ozk_order_event_destroy(ev))
+    return general
+
+
 def test_three_stage_pipeline_vs_oracle_small():
     import numpy as np
     import torch
@@ -81,6 +124,7 @@ def test_three_stage_pipeline_vs_oracle_small():
     torch.cuda.synchronize()
     got = [bytes(pipe.outs[t % pipe.depth].cpu().numpy()) for t, _ in tickets]
     assert got == wants
+    assert _narrow_entry_points(d_bases, torch.from_numpy(sc).cuda(), n) == wants[-1]
 
 
 @pytest.mark.parametrize("n", [7, 300, 1 << 12])
