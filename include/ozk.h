@@ -42,10 +42,12 @@ extern "C" {
 #define OZK_E_NOMEM -3      /* device or host allocation failed */
 #define OZK_E_INTERNAL -4
 
-#define OZK_G1 1 /* `type` / `BNType` value for G1; anything else is G2, as in the reference */
+#define OZK_G1 1 /* `type` / `BNType` value for G1; to the `*_host` entries anything else is G2, as in the reference */
 #define OZK_G2 2
 
 const char* ozk_last_error(void);
+/* 2.  (1 had one entry per variant of the staged MSM — ozk_var_msm_head_dev, _tail_dev, _sort_dev and _accum_dev
+ * took fewer arguments — so a caller bound to those four names must check this before it calls them.) */
 int ozk_version(void);
 /* number of visible HIP devices (0 if none); `taskID % count` selects the device as
  * the reference does (algebra_msm_VariableBaseMSM.cu:1249-1257). */
@@ -110,64 +112,34 @@ int ozk_var_double_msm_auto_host(const uint8_t* bases_g1, const uint8_t* bases_g
 int ozk_shard_last_exchange(void);
 void ozk_shard_comms_release(void);
 
-/* Device-resident variants.  `workspace` must hold ozk_var_msm_workspace_bytes(n, type)
- * bytes; all pointers are device pointers; `stream` is a hipStream_t (NULL = default). */
+/* ---------------- the device-resident MSM --------------------------------
+ * All pointers are device pointers; `stream` is a hipStream_t (NULL = default); everything is asynchronous on it.
+ * n in [1, 2^24].  `type` is OZK_G1 or OZK_G2: any other value is OZK_E_INVALID here (size queries: 0), unlike the
+ * `*_host` entries.  From whole to parts:
+ *     ozk_var_msm_dev  ==  head | tail  ==  sort | accumulate | tail
+ *
+ * The whole MSM on one stream.  `d_workspace` must hold ozk_var_msm_workspace_bytes(n, type) bytes. */
 size_t ozk_var_msm_workspace_bytes(int32_t n, int32_t type);
 int ozk_var_msm_dev(const void* d_bases, const void* d_scalars, int32_t n, int32_t type,
                     void* d_out, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* The same MSM in two phases, for callers that keep several MSMs in flight (a Groth16 prove
  * has six independent ones): the HEAD is the throughput-bound part (sort, bucket accumulation,
  * first window-sum level) and leaves its result in `d_tail` (ozk_var_msm_tail_bytes bytes);
  * the TAIL is the latency-bound remainder (upper window-sum levels, Horner over the windows,
  * normalisation; a few lanes busy for ~2 ms) and reads nothing but `d_tail`.  Running the tail
  * on a second stream lets the next MSM's head (which may reuse the same workspace) overlap
- * it.  ozk_var_msm_dev == head + tail on one stream. */
-/* ---- prepared bases (SURVEY.md §8f N3; no counterpart in the reference, which re-marshals and
- * re-uploads the proving key for every MSM, VariableBaseMSM.java:224-227).  The bases are converted once
- * to the affine Montgomery records the accumulation kernel gathers (with the GLV plan: both halves,
- * 2n x 64 | 128 B) and stay in HBM; an MSM over them skips the conversion and the 96 | 192 B per base of
- * host-to-device traffic.  Results are byte-identical to ozk_var_msm_host on the same inputs.
- *   host form : handle = create(bases) ; msm(handle, scalars) any number of times ; destroy(handle).
- *               A handle serialises its MSMs (internal mutex); use one handle per concurrent caller.
- *   device form: ozk_var_msm_prepare_dev once, then ozk_var_msm_prepared_dev / _head_prepared_dev. */
-int ozk_bases_create_host(const uint8_t* bases, int32_t n, int32_t type, int32_t task_id, void** handle);
-int ozk_var_msm_bases_host(void* handle, const uint8_t* scalars, int32_t n, uint8_t* out);
-int ozk_bases_destroy(void* handle);
-/* OZK_G1 / OZK_G2 for a live handle, 0 for a stale or released one.  A handle is a token into a generation-
- * checked table, not a pointer: a late call with a released (or forged) handle fails with OZK_E_INVALID, and
- * ozk_bases_destroy really frees everything — at once, or when the MSM still running on the handle returns. */
-int ozk_bases_type(void* handle);
-size_t ozk_var_msm_prepared_bytes(int32_t n, int32_t type);
-int ozk_var_msm_prepare_dev(const void* d_bases, int32_t n, int32_t type, void* d_prepared, size_t prepared_size,
-                            void* stream);
-int ozk_var_msm_prepared_dev(const void* d_prepared, const void* d_scalars, int32_t n, int32_t type, void* d_out,
-                             void* d_workspace, size_t workspace_bytes, void* stream);
-int ozk_var_msm_head_prepared_dev(const void* d_prepared, const void* d_scalars, int32_t n, int32_t type,
-                                  void* d_workspace, size_t workspace_bytes, void* d_tail, size_t tail_bytes,
-                                  void* stream, void* previous_levels_done);
-
-/* Ordering hint for several MSMs in flight on two streams.  `tail_ordered` records `levels_done` after its first
- * window-sum level (after the last multi-wave level with OZK_MSM_ORDER_EARLY=0, round 1's form); `head_ordered`
- * waits for it after its sort and before its bucket accumulation, so that the previous MSM's wave-cooperative
- * level is resident before the accumulation takes three of the four wave slots of every SIMD.  Measured at 2^20:
- * 576 Mscalar-mul/s (538 with the late event; 576 with no event at all — the hint no longer buys throughput
- * since the accumulation kernel leaves a slot free, it only keeps the order deterministic).
- * Events come from ozk_order_event_create (a HIP event underneath). */
-int ozk_order_event_create(void** ev);
-int ozk_order_event_destroy(void* ev);
-int ozk_var_msm_head_ordered_dev(const void* d_bases, const void* d_scalars, int32_t n, int32_t type,
-                                 void* d_workspace, size_t workspace_bytes, void* d_tail, size_t tail_bytes,
-                                 void* stream, void* previous_levels_done);
-int ozk_var_msm_tail_ordered_dev(int32_t n, int32_t type, void* d_tail, size_t tail_bytes, void* d_out, void* stream,
-                                 void* levels_done);
-/* The tail's window sums come in two shapes (csrc/msm_var_driver.cuh, tail_shape): LATENCY (mode 0: fused first
- * level + wave-cooperative levels, the fewest dependent additions; what ozk_var_msm_dev, the host entry points and
- * the ordered tail above use) and THROUGHPUT (mode 1: serial levels, 3.0 instead of 5.25 additions per bucket,
- * ~40 dependent additions longer; what ozk_var_msm_tail_dev uses).  A caller that keeps the chip busy with other
- * work — a prover with five MSMs and a witness map in flight — picks throughput: every addition saved is vector-ALU
- * time for something else (a 2^20-constraint proof: 16.6 -> 16.3 ms).  levels_done may be NULL. */
-int ozk_var_msm_tail_mode_dev(int32_t n, int32_t type, void* d_tail, size_t tail_bytes, void* d_out, void* stream,
-                              void* levels_done, int32_t mode);
+ * it.  ozk_var_msm_dev == head + tail on one stream.
+ * d_bases: wire-in points, or, with prepared != 0, the records of ozk_var_msm_prepare_dev.  d_workspace:
+ * ozk_var_msm_head_workspace_bytes bytes.  previous_levels_done and levels_done are ordering events (below) and may
+ * be NULL; mode is the shape of the tail's window sums (below): 0 latency, anything else throughput. */
+size_t ozk_var_msm_head_workspace_bytes(int32_t n, int32_t type);
+size_t ozk_var_msm_tail_bytes(int32_t n, int32_t type);
+int ozk_var_msm_head_dev(const void* d_bases, int32_t prepared, const void* d_scalars, int32_t n, int32_t type,
+                         void* d_workspace, size_t workspace_bytes, void* d_tail, size_t tail_bytes, void* stream,
+                         void* previous_levels_done);
+int ozk_var_msm_tail_dev(int32_t n, int32_t type, void* d_tail, size_t tail_bytes, void* d_out, void* stream,
+                         void* levels_done, int32_t mode);
 
 /* The head itself has two stages that stress different units — SORT (base conversion, digits,
  * counting sort: HBM / LDS) and ACCUMULATE (bucket accumulation ... first window-sum level:
@@ -176,37 +148,61 @@ int ozk_var_msm_tail_mode_dev(int32_t n, int32_t type, void* d_tail, size_t tail
  * accumulate each have private scratch.  ozk_var_msm_head_dev == sort + accumulate.  (On
  * MI355X the three-stage form measures 562-574 Mscalar-mul/s at 2^20 against 576 for head | tail: the
  * sort kernels cannot co-reside with three accumulation blocks per CU and stretch the accumulation
- * when they can — profiles/r02_schedule_experiments.txt.) */
+ * when they can — profiles/r02_schedule_experiments.txt.)
+ * ozk_var_msm_stage_bytes gives the sizes of the three buffers. */
 int ozk_var_msm_stage_bytes(int32_t n, int32_t type, size_t* sorted_bytes, size_t* sort_ws_bytes,
                             size_t* accum_ws_bytes);
-int ozk_var_msm_sort_dev(const void* d_bases, const void* d_scalars, int32_t n, int32_t type,
-                         void* d_sorted, size_t sorted_bytes, void* d_sort_ws, size_t sort_ws_bytes,
-                         void* stream);
-int ozk_var_msm_accum_dev(int32_t n, int32_t type, void* d_sorted, size_t sorted_bytes,
-                          void* d_accum_ws, size_t accum_ws_bytes, void* d_tail, size_t tail_bytes,
-                          void* stream);
-/* the same two stages over prepared bases (ozk_var_msm_prepare_dev): the sort skips the base conversion */
-int ozk_var_msm_sort_prepared_dev(const void* d_prepared, const void* d_scalars, int32_t n, int32_t type,
-                                  void* d_sorted, size_t sorted_bytes, void* d_sort_ws, size_t sort_ws_bytes,
-                                  void* stream);
-int ozk_var_msm_accum_prepared_dev(const void* d_prepared, int32_t n, int32_t type, void* d_sorted,
-                                   size_t sorted_bytes, void* d_accum_ws, size_t accum_ws_bytes, void* d_tail,
-                                   size_t tail_bytes, void* stream);
-/* ACCUMULATE in two parts, for a caller that keeps level 1 (the vector-ALU-bound kernel) back to back on one stream
+/* d_bases and prepared as for the head; over prepared bases the sort skips the base conversion */
+int ozk_var_msm_sort_dev(const void* d_bases, int32_t prepared, const void* d_scalars, int32_t n, int32_t type,
+                         void* d_sorted, size_t sorted_bytes, void* d_sort_ws, size_t sort_ws_bytes, void* stream);
+/* d_prepared: the prepared records the sort read, or NULL (bases converted by the sort).
+ * part splits the stage for a caller that keeps level 1 (the vector-ALU-bound kernel) back to back on one stream
  * and runs the rest (run merge, the short generic levels, the copy of the bucket counts: ~0.1 ms of low-occupancy work)
- * elsewhere: part 1 = level 1 only, part 2 = the rest (same arguments; it reads the sorted set and the accumulate
- * scratch level 1 wrote, so neither may be reused before it has run), part 0 = both (= the two entry points above).
- * d_prepared may be NULL (bases converted by the sort). */
-int ozk_var_msm_accum_part_dev(const void* d_prepared, int32_t n, int32_t type, void* d_sorted, size_t sorted_bytes,
-                               void* d_accum_ws, size_t accum_ws_bytes, void* d_tail, size_t tail_bytes,
-                               void* stream, int32_t part);
-size_t ozk_var_msm_head_workspace_bytes(int32_t n, int32_t type);
-size_t ozk_var_msm_tail_bytes(int32_t n, int32_t type);
-int ozk_var_msm_head_dev(const void* d_bases, const void* d_scalars, int32_t n, int32_t type,
-                         void* d_workspace, size_t workspace_bytes, void* d_tail, size_t tail_bytes,
-                         void* stream);
-int ozk_var_msm_tail_dev(int32_t n, int32_t type, void* d_tail, size_t tail_bytes, void* d_out,
-                         void* stream);
+ * elsewhere: 0 = all of it, 1 = level 1 only, 2 = the rest (same arguments; it reads the sorted set and the accumulate
+ * scratch level 1 wrote, so neither may be reused before it has run).  Any other part: OZK_E_INVALID. */
+int ozk_var_msm_accum_dev(const void* d_prepared, int32_t n, int32_t type, void* d_sorted, size_t sorted_bytes,
+                          void* d_accum_ws, size_t accum_ws_bytes, void* d_tail, size_t tail_bytes, void* stream,
+                          int32_t part);
+
+/* ---- prepared bases (SURVEY.md §8f N3; no counterpart in the reference, which re-marshals and
+ * re-uploads the proving key for every MSM, VariableBaseMSM.java:224-227).  The bases are converted once
+ * to the affine Montgomery records the accumulation kernel gathers (with the GLV plan: both halves,
+ * 2n x 64 | 128 B) and stay in HBM; an MSM over them skips the conversion and the 96 | 192 B per base of
+ * host-to-device traffic.  Results are byte-identical to ozk_var_msm_host on the same inputs.
+ *   device form: ozk_var_msm_prepare_dev once into ozk_var_msm_prepared_bytes bytes, then ozk_var_msm_prepared_dev
+ *               (the whole MSM) or the stages above with prepared != 0. */
+size_t ozk_var_msm_prepared_bytes(int32_t n, int32_t type);
+int ozk_var_msm_prepare_dev(const void* d_bases, int32_t n, int32_t type, void* d_prepared, size_t prepared_size,
+                            void* stream);
+int ozk_var_msm_prepared_dev(const void* d_prepared, const void* d_scalars, int32_t n, int32_t type, void* d_out,
+                             void* d_workspace, size_t workspace_bytes, void* stream);
+/*   host form : handle = create(bases) ; msm(handle, scalars) any number of times ; destroy(handle).
+ *               A handle serialises its MSMs (internal mutex); use one handle per concurrent caller.  As every
+ *               `*_host` entry, create takes any type other than OZK_G1 as G2. */
+int ozk_bases_create_host(const uint8_t* bases, int32_t n, int32_t type, int32_t task_id, void** handle);
+int ozk_var_msm_bases_host(void* handle, const uint8_t* scalars, int32_t n, uint8_t* out);
+int ozk_bases_destroy(void* handle);
+/* OZK_G1 / OZK_G2 for a live handle, 0 for a stale or released one.  A handle is a token into a generation-
+ * checked table, not a pointer: a late call with a released (or forged) handle fails with OZK_E_INVALID, and
+ * ozk_bases_destroy really frees everything — at once, or when the MSM still running on the handle returns. */
+int ozk_bases_type(void* handle);
+
+/* Ordering hint for several MSMs in flight on two streams.  A tail given `levels_done` records it after its first
+ * window-sum level (after the last multi-wave level with OZK_MSM_ORDER_EARLY=0, round 1's form); a head given the
+ * same event as `previous_levels_done` waits for it after its sort and before its bucket accumulation, so that the
+ * previous MSM's wave-cooperative level is resident before the accumulation takes three of the four wave slots of
+ * every SIMD.  Measured at 2^20: 576 Mscalar-mul/s (538 with the late event; 576 with no event at all — the hint no
+ * longer buys throughput since the accumulation kernel leaves a slot free, it only keeps the order deterministic).
+ * Events come from ozk_order_event_create (a HIP event underneath). */
+int ozk_order_event_create(void** ev);
+int ozk_order_event_destroy(void* ev);
+
+/* The tail's window sums come in two shapes (csrc/msm_var_driver.cuh, tail_shape), chosen by the `mode` of
+ * ozk_var_msm_tail_dev: LATENCY (mode 0: fused first level + wave-cooperative levels, the fewest dependent additions;
+ * also what ozk_var_msm_dev and the host entry points use) and THROUGHPUT (mode 1: serial levels, 3.0 instead of 5.25
+ * additions per bucket, ~40 dependent additions longer).  A caller that keeps the chip busy with other
+ * work — a prover with five MSMs and a witness map in flight — picks throughput: every addition saved is vector-ALU
+ * time for something else (a 2^20-constraint proof: 16.6 -> 16.3 ms). */
 
 /* sum of k affine-normalised partial results in wire-out format (k x 192 B / 384 B), as
  * produced by ozk_var_msm_dev on k ranks -> one normalised point.  The multi-GPU

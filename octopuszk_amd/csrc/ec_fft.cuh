@@ -191,17 +191,6 @@ constexpr int EC_LONG = 64;            // rows above this many terms are the lon
 constexpr int EC_LONG_LANES = 4096;    // partial sums of one long row, then 64, then 1
 
 template <int TYPE>
-struct EcType {
-  using CV = G1Cfg;
-  static constexpr bool GLV = true;
-};
-template <>
-struct EcType<2> {
-  using CV = G2Cfg;
-  static constexpr bool GLV = false;
-};
-
-template <int TYPE>
 __global__ __launch_bounds__(64) void k_ecfft_recode(EcFftTwiddle c, int n, ScaleSchedule* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;

@@ -11,7 +11,6 @@ constexpr int ECFFT_MAX_LOGN = 22;
 constexpr int EC_MAX_N = 1 << 24;
 using Fr32 = Fe<FrParams, 32>;
 
-bool misaligned(const void* p) { return ((uintptr_t)p & 3) != 0; }
 size_t pad256(size_t v) { return (v + 255) & ~(size_t)255; }
 int log2_exact(int n) {
   if (n <= 0 || (n & (n - 1))) return -1;
@@ -33,11 +32,11 @@ bool is_one(const Fr32& a) {
 size_t point_bytes(int type) { return type == OZK_G1 ? 96 : 192; }
 
 template <int TYPE>
-int ec_fft_run(const u32* in, int logn, const EcFftTwiddle& last, const EcFftTwiddle& inner, bool inverse, u32* out,
+void ec_fft_run(const u32* in, int logn, const EcFftTwiddle& last, const EcFftTwiddle& inner, bool inverse, u32* out,
                uint8_t* ws, hipStream_t st) {
   const int n = 1 << logn;
   hipLaunchKernelGGL(k_ecfft_permute<TYPE>, dim3((n + 63) / 64), dim3(64), 0, st, in, n, logn, out);
-  if (logn == 0) return OZK_OK;
+  if (logn == 0) return;
   const int n_last = n / 2, n_inner = n / 4;
   ScaleSchedule* t_last = (ScaleSchedule*)ws;
   ScaleSchedule* t_inner = (ScaleSchedule*)(ws + pad256((size_t)n_last * sizeof(ScaleSchedule)));
@@ -53,7 +52,6 @@ int ec_fft_run(const u32* in, int logn, const EcFftTwiddle& last, const EcFftTwi
                        (const ScaleSchedule*)(is_last ? t_last : t_inner), stride, (int)!(is_last && inverse),
                        (const ScaleSchedule*)(is_last && inverse ? t_last : nullptr));
   }
-  return OZK_OK;
 }
 }  // namespace
 
@@ -61,7 +59,7 @@ extern "C" {
 
 size_t ozk_ec_fft_workspace_bytes(int32_t n, int32_t type) {
   const int logn = log2_exact(n);
-  if (logn < 0 || logn > ECFFT_MAX_LOGN || (type != OZK_G1 && type != OZK_G2)) return 0;
+  if (logn < 0 || logn > ECFFT_MAX_LOGN || check_point_type(type)) return 0;
   return pad256((size_t)(n / 2) * sizeof(ScaleSchedule)) + pad256((size_t)(n / 4) * sizeof(ScaleSchedule)) + 256;
 }
 
@@ -69,7 +67,7 @@ int ozk_ec_fft_dev(const void* d_in, int32_t n, int32_t type, const uint8_t* ome
                    void* d_out, void* d_workspace, size_t workspace_bytes, void* stream) {
   hip_clear_stale();
   if (!d_in || !d_out || !omega_host32 || !d_workspace) return fail(OZK_E_INVALID, "null pointer argument");
-  if (type != OZK_G1 && type != OZK_G2) return fail(OZK_E_INVALID, "unknown point type %d", (int)type);
+  if (int rc = check_point_type(type)) return rc;
   const int logn = log2_exact(n);
   if (logn < 0 || logn > ECFFT_MAX_LOGN) return fail(OZK_E_INVALID, "size %d is not a power of two in [1, 2^22]", (int)n);
   if (misaligned(d_in) || misaligned(d_out) || misaligned(d_workspace))
@@ -100,16 +98,16 @@ int ozk_ec_fft_dev(const void* d_in, int32_t n, int32_t type, const uint8_t* ome
   from_mont(k, last.k);
   from_mont(Fr32(sqr(base)), inner.base);
   from_mont(Fr32(fe_one<FrParams>()), inner.k);
-  const int rc = type == OZK_G1
-                     ? ec_fft_run<1>((const u32*)d_in, logn, last, inner, inverse != 0, (u32*)d_out, (uint8_t*)d_workspace, (hipStream_t)stream)
-                     : ec_fft_run<2>((const u32*)d_in, logn, last, inner, inverse != 0, (u32*)d_out, (uint8_t*)d_workspace, (hipStream_t)stream);
-  if (rc != OZK_OK) return rc;
-  OZK_HIP(hipGetLastError());
-  return OZK_OK;
+  return by_point_type(type, [&](auto t) {
+    ec_fft_run<decltype(t)::TYPE>((const u32*)d_in, logn, last, inner, inverse != 0, (u32*)d_out, (uint8_t*)d_workspace,
+                                  (hipStream_t)stream);
+    OZK_HIP(hipGetLastError());
+    return OZK_OK;
+  });
 }
 
 size_t ozk_sparse_mat_points_workspace_bytes(int32_t n_long, int32_t type) {
-  if (n_long <= 0 || (type != OZK_G1 && type != OZK_G2)) return 0;
+  if (n_long <= 0 || check_point_type(type)) return 0;
   return (size_t)n_long * (EC_LONG_LANES + 64) * point_bytes(type) + 256;
 }
 
@@ -119,7 +117,7 @@ int ozk_sparse_mat_points_dev(const void* d_row_ptr, const void* d_index, const 
   hip_clear_stale();
   if (!d_row_ptr || !d_index || !d_points || !d_out || (n_long > 0 && (!d_long_rows || !d_workspace)))
     return fail(OZK_E_INVALID, "null pointer argument");
-  if (type != OZK_G1 && type != OZK_G2) return fail(OZK_E_INVALID, "unknown point type %d", (int)type);
+  if (int rc = check_point_type(type)) return rc;
   if (rows <= 0 || rows > EC_MAX_N || n_long < 0 || n_long > rows || n_long > (1 << 16))
     return fail(OZK_E_INVALID, "row counts out of range");
   if (misaligned(d_row_ptr) || misaligned(d_index) || misaligned(d_coeff) || misaligned(d_points) || misaligned(d_out) ||
@@ -134,40 +132,32 @@ int ozk_sparse_mat_points_dev(const void* d_row_ptr, const void* d_index, const 
   u32* part1 = (u32*)d_workspace;
   u32* part2 = n_long > 0 ? (u32*)((uint8_t*)d_workspace + (size_t)n_long * EC_LONG_LANES * point_bytes(type)) : nullptr;
   const dim3 block(64), grid((rows + 63) / 64);
-  if (type == OZK_G1) {
-    hipLaunchKernelGGL(k_sparse_points<1>, grid, block, 0, st, ptr, idx, co, pts, (int)rows, (u32*)d_out);
+  return by_point_type(type, [&](auto t) {
+    constexpr int T = decltype(t)::TYPE;
+    hipLaunchKernelGGL(k_sparse_points<T>, grid, block, 0, st, ptr, idx, co, pts, (int)rows, (u32*)d_out);
     if (n_long > 0) {
-      hipLaunchKernelGGL(k_sparse_points_long<1>, dim3(n_long * (EC_LONG_LANES / 64)), block, 0, st, ptr, idx, co, pts, lr, part1);
-      hipLaunchKernelGGL(k_points_sum64<1>, dim3(n_long), block, 0, st, (const u32*)part1, n_long * 64, (const u32*)nullptr, part2);
-      hipLaunchKernelGGL(k_points_sum64<1>, dim3((n_long + 63) / 64), block, 0, st, (const u32*)part2, (int)n_long, lr, (u32*)d_out);
+      hipLaunchKernelGGL(k_sparse_points_long<T>, dim3(n_long * (EC_LONG_LANES / 64)), block, 0, st, ptr, idx, co, pts, lr, part1);
+      hipLaunchKernelGGL(k_points_sum64<T>, dim3(n_long), block, 0, st, (const u32*)part1, n_long * 64, (const u32*)nullptr, part2);
+      hipLaunchKernelGGL(k_points_sum64<T>, dim3((n_long + 63) / 64), block, 0, st, (const u32*)part2, (int)n_long, lr, (u32*)d_out);
     }
-  } else {
-    hipLaunchKernelGGL(k_sparse_points<2>, grid, block, 0, st, ptr, idx, co, pts, (int)rows, (u32*)d_out);
-    if (n_long > 0) {
-      hipLaunchKernelGGL(k_sparse_points_long<2>, dim3(n_long * (EC_LONG_LANES / 64)), block, 0, st, ptr, idx, co, pts, lr, part1);
-      hipLaunchKernelGGL(k_points_sum64<2>, dim3(n_long), block, 0, st, (const u32*)part1, n_long * 64, (const u32*)nullptr, part2);
-      hipLaunchKernelGGL(k_points_sum64<2>, dim3((n_long + 63) / 64), block, 0, st, (const u32*)part2, (int)n_long, lr, (u32*)d_out);
-    }
-  }
-  OZK_HIP(hipGetLastError());
-  return OZK_OK;
+    OZK_HIP(hipGetLastError());
+    return OZK_OK;
+  });
 }
 
 int ozk_points_add_dev(const void* d_a, const void* d_b, int32_t n, int32_t type, int32_t negate_b, void* d_out,
                        void* stream) {
   hip_clear_stale();
   if (!d_a || !d_b || !d_out || n <= 0 || n > EC_MAX_N) return fail(OZK_E_INVALID, "bad argument");
-  if (type != OZK_G1 && type != OZK_G2) return fail(OZK_E_INVALID, "unknown point type %d", (int)type);
+  if (int rc = check_point_type(type)) return rc;
   if (misaligned(d_a) || misaligned(d_b) || misaligned(d_out)) return fail(OZK_E_INVALID, "buffers must be 4-byte aligned");
   const dim3 grid((n + 63) / 64), block(64);
-  if (type == OZK_G1)
-    hipLaunchKernelGGL(k_points_add<1>, grid, block, 0, (hipStream_t)stream, (const u32*)d_a, (const u32*)d_b, (int)n,
-                       (int)negate_b, (u32*)d_out);
-  else
-    hipLaunchKernelGGL(k_points_add<2>, grid, block, 0, (hipStream_t)stream, (const u32*)d_a, (const u32*)d_b, (int)n,
-                       (int)negate_b, (u32*)d_out);
-  OZK_HIP(hipGetLastError());
-  return OZK_OK;
+  return by_point_type(type, [&](auto t) {
+    hipLaunchKernelGGL(k_points_add<decltype(t)::TYPE>, grid, block, 0, (hipStream_t)stream, (const u32*)d_a,
+                       (const u32*)d_b, (int)n, (int)negate_b, (u32*)d_out);
+    OZK_HIP(hipGetLastError());
+    return OZK_OK;
+  });
 }
 
 }  // extern "C"

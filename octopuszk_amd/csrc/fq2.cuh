@@ -9,6 +9,9 @@
 // components < 2p, so the generic group law of ec.cuh type-checks unchanged.
 #pragma once
 #include "curve.cuh"
+#if defined(__HIPCC__)
+#include "ozk_common.h"   // fail(), OZK_G1 / OZK_G2: by_point_type below
+#endif
 
 namespace ozk {
 
@@ -296,7 +299,37 @@ struct G2Cfg {
   using XZZZ = Fe2<32>;
 };
 
+// The `type` of the C ABI (OZK_G1 = 1, OZK_G2 = 2) as a compile-time tag.  Kernels that are templates on the integer
+// take T::TYPE, driver templates on the curve take T::CV.  GLV: the scalar ladders use the endomorphism (G2's run
+// the non-adjacent form instead: exact on the whole twist).
+template <int T>
+struct EcType {
+  static constexpr int TYPE = T;
+  using CV = G1Cfg;
+  static constexpr bool GLV = true;
+};
+template <>
+struct EcType<2> {
+  static constexpr int TYPE = 2;
+  using CV = G2Cfg;
+  static constexpr bool GLV = false;
+};
+
 #if defined(__HIPCC__)
+// The one switch on `type`: f(EcType<1>()) or f(EcType<2>()).  Any other value is an error for an entry point
+// (f returns int) and size 0 for a size query (f returns size_t).
+template <class F>
+auto by_point_type(int type, F&& f) -> decltype(f(EcType<1>())) {
+  if (type == OZK_G1) return f(EcType<1>());
+  if (type == OZK_G2) return f(EcType<2>());
+  if constexpr (std::is_same<decltype(f(EcType<1>())), size_t>::value) return 0;
+  else return fail(OZK_E_INVALID, "unknown point type %d", type);
+}
+// for an entry point whose later checks need a valid `type`
+inline int check_point_type(int type) {
+  return by_point_type(type, [](auto) { return OZK_OK; });
+}
+
 // ---- Fq2 on a LANE PAIR, for the serial chains -------------------------------------------------
 // A lone lane runs a G2 doubling (5 Fq2 squarings + 2 Fq2 multiplications = 16 Fq multiplications) in
 // ~20 us, and both the Horner kernel (120 of them) and the fixed-base doubling chain are exactly that.

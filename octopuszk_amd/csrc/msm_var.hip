@@ -20,79 +20,119 @@ using namespace ozk;
 
 extern "C" {
 
+// ---- the device-resident MSM, in the order of include/ozk.h.  Every entry: pointers, n, then by_point_type (fq2.cuh)
+// picks the driver template (msm_var_driver.cuh) for `type` and rejects anything that is not OZK_G1 / OZK_G2.
 size_t ozk_var_msm_workspace_bytes(int32_t n, int32_t type) {
   if (n <= 0) return 0;
-  if (type == OZK_G1) return var_msm_ws_bytes<G1Cfg>(n);
-#if defined(OZK_WITH_G2)
-  return var_msm_ws_bytes<G2Cfg>(n);
-#else
-  return 0;
-#endif
+  return by_point_type(type, [&](auto t) { return var_msm_ws_bytes<typename decltype(t)::CV>(n); });
+}
+size_t ozk_var_msm_head_workspace_bytes(int32_t n, int32_t type) {
+  if (n <= 0) return 0;
+  return by_point_type(type, [&](auto t) { return var_msm_head_ws_bytes<typename decltype(t)::CV>(n); });
+}
+size_t ozk_var_msm_tail_bytes(int32_t n, int32_t type) {
+  if (n <= 0) return 0;
+  return by_point_type(type, [&](auto t) { return var_msm_tail_bytes<typename decltype(t)::CV>(n); });
+}
+size_t ozk_var_msm_prepared_bytes(int32_t n, int32_t type) {
+  if (n <= 0 || n > (1 << 24)) return 0;
+  return by_point_type(type, [&](auto t) { return prepared_bytes<typename decltype(t)::CV>(n); });
+}
+int ozk_var_msm_stage_bytes(int32_t n, int32_t type, size_t* sorted_bytes, size_t* sort_ws_bytes,
+                            size_t* accum_ws_bytes) {
+  if (n <= 0 || n > (1 << 24) || !sorted_bytes || !sort_ws_bytes || !accum_ws_bytes)
+    return fail(OZK_E_INVALID, "bad argument");
+  return by_point_type(type, [&](auto t) {
+    const RegionBytes rb = region_bytes<typename decltype(t)::CV>(n);
+    *sorted_bytes = rb.sorted;
+    *sort_ws_bytes = rb.sort_ws;
+    *accum_ws_bytes = rb.accum_ws;
+    return OZK_OK;
+  });
 }
 
 int ozk_var_msm_dev(const void* d_bases, const void* d_scalars, int32_t n, int32_t type, void* d_out,
                     void* d_workspace, size_t workspace_bytes, void* stream) {
   if (!d_bases || !d_scalars || !d_out || !d_workspace) return fail(OZK_E_INVALID, "null pointer argument");
-  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
-  if (type == OZK_G1)
-    return var_msm_dev<G1Cfg>(d_bases, d_scalars, n, d_out, d_workspace, workspace_bytes, (hipStream_t)stream);
-#if defined(OZK_WITH_G2)
-  return var_msm_dev<G2Cfg>(d_bases, d_scalars, n, d_out, d_workspace, workspace_bytes, (hipStream_t)stream);
-#else
-  return fail(OZK_E_INVALID, "G2 not built");
-#endif
-}
-
-size_t ozk_var_msm_head_workspace_bytes(int32_t n, int32_t type) {
-  if (n <= 0) return 0;
-  return type == OZK_G1 ? var_msm_head_ws_bytes<G1Cfg>(n) : var_msm_head_ws_bytes<G2Cfg>(n);
-}
-size_t ozk_var_msm_tail_bytes(int32_t n, int32_t type) {
-  if (n <= 0) return 0;
-  return type == OZK_G1 ? var_msm_tail_bytes<G1Cfg>(n) : var_msm_tail_bytes<G2Cfg>(n);
-}
-int ozk_var_msm_head_dev(const void* d_bases, const void* d_scalars, int32_t n, int32_t type, void* d_workspace,
-                         size_t workspace_bytes, void* d_tail, size_t tail_bytes, void* stream) {
-  if (!d_bases || !d_scalars || !d_workspace || !d_tail) return fail(OZK_E_INVALID, "null pointer argument");
-  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
-  if (type == OZK_G1)
-    return var_msm_head<G1Cfg>(d_bases, d_scalars, n, d_workspace, workspace_bytes, d_tail, tail_bytes,
-                               (hipStream_t)stream);
-  return var_msm_head<G2Cfg>(d_bases, d_scalars, n, d_workspace, workspace_bytes, d_tail, tail_bytes,
-                             (hipStream_t)stream);
-}
-size_t ozk_var_msm_prepared_bytes(int32_t n, int32_t type) {
-  if (n <= 0 || n > (1 << 24)) return 0;
-  return type == OZK_G1 ? prepared_bytes<G1Cfg>(n) : prepared_bytes<G2Cfg>(n);
-}
-int ozk_var_msm_prepare_dev(const void* d_bases, int32_t n, int32_t type, void* d_prepared, size_t prepared_size,
-                            void* stream) {
-  if (!d_bases || !d_prepared) return fail(OZK_E_INVALID, "null pointer argument");
-  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
-  if (type == OZK_G1) return var_msm_prepare<G1Cfg>(d_bases, n, d_prepared, prepared_size, (hipStream_t)stream);
-  return var_msm_prepare<G2Cfg>(d_bases, n, d_prepared, prepared_size, (hipStream_t)stream);
-}
-int ozk_var_msm_head_prepared_dev(const void* d_prepared, const void* d_scalars, int32_t n, int32_t type,
-                                  void* d_workspace, size_t workspace_bytes, void* d_tail, size_t tail_bytes,
-                                  void* stream, void* previous_levels_done) {
-  if (!d_prepared || !d_scalars || !d_workspace || !d_tail) return fail(OZK_E_INVALID, "null pointer argument");
-  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
-  if (type == OZK_G1)
-    return var_msm_head<G1Cfg>(nullptr, d_scalars, n, d_workspace, workspace_bytes, d_tail, tail_bytes,
-                               (hipStream_t)stream, (hipEvent_t)previous_levels_done, d_prepared);
-  return var_msm_head<G2Cfg>(nullptr, d_scalars, n, d_workspace, workspace_bytes, d_tail, tail_bytes,
-                             (hipStream_t)stream, (hipEvent_t)previous_levels_done, d_prepared);
+  if (int rc = check_batch_size(n)) return rc;
+  return by_point_type(type, [&](auto t) {
+    return var_msm_dev<typename decltype(t)::CV>(d_bases, d_scalars, n, d_out, d_workspace, workspace_bytes,
+                                                 (hipStream_t)stream);
+  });
 }
 int ozk_var_msm_prepared_dev(const void* d_prepared, const void* d_scalars, int32_t n, int32_t type, void* d_out,
                              void* d_workspace, size_t workspace_bytes, void* stream) {
   if (!d_prepared || !d_scalars || !d_out || !d_workspace) return fail(OZK_E_INVALID, "null pointer argument");
-  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
-  if (type == OZK_G1)
-    return var_msm_dev<G1Cfg>(nullptr, d_scalars, n, d_out, d_workspace, workspace_bytes, (hipStream_t)stream,
-                              d_prepared);
-  return var_msm_dev<G2Cfg>(nullptr, d_scalars, n, d_out, d_workspace, workspace_bytes, (hipStream_t)stream,
-                            d_prepared);
+  if (int rc = check_batch_size(n)) return rc;
+  return by_point_type(type, [&](auto t) {
+    return var_msm_dev<typename decltype(t)::CV>(nullptr, d_scalars, n, d_out, d_workspace, workspace_bytes,
+                                                 (hipStream_t)stream, d_prepared);
+  });
 }
+int ozk_var_msm_prepare_dev(const void* d_bases, int32_t n, int32_t type, void* d_prepared, size_t prepared_size,
+                            void* stream) {
+  if (!d_bases || !d_prepared) return fail(OZK_E_INVALID, "null pointer argument");
+  if (int rc = check_batch_size(n)) return rc;
+  return by_point_type(type, [&](auto t) {
+    return var_msm_prepare<typename decltype(t)::CV>(d_bases, n, d_prepared, prepared_size, (hipStream_t)stream);
+  });
+}
+
+// the stages: `prepared` says which of the drivers' two base arguments d_bases is
+int ozk_var_msm_head_dev(const void* d_bases, int32_t prepared, const void* d_scalars, int32_t n, int32_t type,
+                         void* d_workspace, size_t workspace_bytes, void* d_tail, size_t tail_bytes, void* stream,
+                         void* previous_levels_done) {
+  if (!d_bases || !d_scalars || !d_workspace || !d_tail) return fail(OZK_E_INVALID, "null pointer argument");
+  if (int rc = check_batch_size(n)) return rc;
+  return by_point_type(type, [&](auto t) {
+    return var_msm_head<typename decltype(t)::CV>(prepared ? nullptr : d_bases, d_scalars, n, d_workspace,
+                                                  workspace_bytes, d_tail, tail_bytes, (hipStream_t)stream,
+                                                  (hipEvent_t)previous_levels_done, prepared ? d_bases : nullptr);
+  });
+}
+int ozk_var_msm_tail_dev(int32_t n, int32_t type, void* d_tail, size_t tail_bytes, void* d_out, void* stream,
+                         void* levels_done, int32_t mode) {
+  if (!d_tail || !d_out) return fail(OZK_E_INVALID, "null pointer argument");
+  if (int rc = check_batch_size(n)) return rc;
+  return by_point_type(type, [&](auto t) {
+    return var_msm_tail<typename decltype(t)::CV>(n, d_tail, tail_bytes, d_out, (hipStream_t)stream,
+                                                  (hipEvent_t)levels_done, mode ? TAIL_THROUGHPUT : TAIL_LATENCY);
+  });
+}
+int ozk_var_msm_sort_dev(const void* d_bases, int32_t prepared, const void* d_scalars, int32_t n, int32_t type,
+                         void* d_sorted, size_t sorted_bytes, void* d_sort_ws, size_t sort_ws_bytes, void* stream) {
+  if (!d_bases || !d_scalars || !d_sorted || !d_sort_ws) return fail(OZK_E_INVALID, "null pointer argument");
+  if (int rc = check_batch_size(n)) return rc;
+  return by_point_type(type, [&](auto t) {
+    return var_msm_sort<typename decltype(t)::CV>(prepared ? nullptr : d_bases, d_scalars, n, d_sorted, sorted_bytes,
+                                                  d_sort_ws, sort_ws_bytes, (hipStream_t)stream, nullptr,
+                                                  prepared ? d_bases : nullptr);
+  });
+}
+int ozk_var_msm_accum_dev(const void* d_prepared, int32_t n, int32_t type, void* d_sorted, size_t sorted_bytes,
+                          void* d_accum_ws, size_t accum_ws_bytes, void* d_tail, size_t tail_bytes, void* stream,
+                          int32_t part) {
+  if (!d_sorted || !d_accum_ws || !d_tail) return fail(OZK_E_INVALID, "null pointer argument");
+  if (int rc = check_batch_size(n)) return rc;
+  if (part < ACCUM_ALL || part > ACCUM_REST) return fail(OZK_E_INVALID, "part %d is not 0 (all), 1 (level 1) or 2 (rest)", part);
+  return by_point_type(type, [&](auto t) {
+    return var_msm_accum<typename decltype(t)::CV>(n, d_sorted, sorted_bytes, d_accum_ws, accum_ws_bytes, d_tail,
+                                                   tail_bytes, (hipStream_t)stream, d_prepared, part);
+  });
+}
+
+int ozk_order_event_create(void** ev) {
+  if (!ev) return fail(OZK_E_INVALID, "null pointer argument");
+  hipEvent_t e = nullptr;
+  OZK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  *ev = (void*)e;
+  return OZK_OK;
+}
+int ozk_order_event_destroy(void* ev) {
+  if (ev) OZK_HIP(hipEventDestroy((hipEvent_t)ev));
+  return OZK_OK;
+}
+
 // ---- handles of prepared bases: generation-checked table.  The value handed to the caller is a TOKEN
 // (generation << 32 | slot + 1), never a pointer: a stale or forged token resolves to nothing instead of to freed —
 // or recycled — memory, and a released handle's memory really is released (round 2 kept every dead handle's
@@ -158,7 +198,7 @@ void handle_unpin(BasesHandle* h) {
 
 int ozk_bases_create_host(const uint8_t* bases, int32_t n, int32_t type, int32_t task_id, void** handle) {
   if (!bases || !handle) return fail(OZK_E_INVALID, "null pointer argument");
-  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
+  if (int rc = check_batch_size(n)) return rc;
   BasesHandle* h = nullptr;
   const int rc = type == OZK_G1 ? bases_create<G1Cfg>(bases, n, type, task_id, &h)
                                 : bases_create<G2Cfg>(bases, n, type, task_id, &h);
@@ -201,127 +241,12 @@ int ozk_tuning_reload(void) {
   return OZK_OK;
 }
 
-int ozk_order_event_create(void** ev) {
-  if (!ev) return fail(OZK_E_INVALID, "null pointer argument");
-  hipEvent_t e = nullptr;
-  OZK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  *ev = (void*)e;
-  return OZK_OK;
-}
-int ozk_order_event_destroy(void* ev) {
-  if (ev) OZK_HIP(hipEventDestroy((hipEvent_t)ev));
-  return OZK_OK;
-}
-int ozk_var_msm_head_ordered_dev(const void* d_bases, const void* d_scalars, int32_t n, int32_t type,
-                                 void* d_workspace, size_t workspace_bytes, void* d_tail, size_t tail_bytes,
-                                 void* stream, void* previous_levels_done) {
-  if (!d_bases || !d_scalars || !d_workspace || !d_tail) return fail(OZK_E_INVALID, "null pointer argument");
-  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
-  if (type == OZK_G1)
-    return var_msm_head<G1Cfg>(d_bases, d_scalars, n, d_workspace, workspace_bytes, d_tail, tail_bytes,
-                               (hipStream_t)stream, (hipEvent_t)previous_levels_done);
-  return var_msm_head<G2Cfg>(d_bases, d_scalars, n, d_workspace, workspace_bytes, d_tail, tail_bytes,
-                             (hipStream_t)stream, (hipEvent_t)previous_levels_done);
-}
-int ozk_var_msm_tail_ordered_dev(int32_t n, int32_t type, void* d_tail, size_t tail_bytes, void* d_out, void* stream,
-                                 void* levels_done) {
-  if (!d_tail || !d_out) return fail(OZK_E_INVALID, "null pointer argument");
-  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
-  if (type == OZK_G1)
-    return var_msm_tail<G1Cfg>(n, d_tail, tail_bytes, d_out, (hipStream_t)stream, (hipEvent_t)levels_done);
-  return var_msm_tail<G2Cfg>(n, d_tail, tail_bytes, d_out, (hipStream_t)stream, (hipEvent_t)levels_done);
-}
-// the tail with the shape of its window sums chosen by the caller: mode 0 = latency (a lone MSM), 1 = throughput
-// (the caller keeps the chip busy with other work: a prover with five MSMs and a witness map in flight)
-int ozk_var_msm_tail_mode_dev(int32_t n, int32_t type, void* d_tail, size_t tail_bytes, void* d_out, void* stream,
-                              void* levels_done, int32_t mode) {
-  if (!d_tail || !d_out) return fail(OZK_E_INVALID, "null pointer argument");
-  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
-  const int m = mode ? TAIL_THROUGHPUT : TAIL_LATENCY;
-  if (type == OZK_G1)
-    return var_msm_tail<G1Cfg>(n, d_tail, tail_bytes, d_out, (hipStream_t)stream, (hipEvent_t)levels_done, m);
-  return var_msm_tail<G2Cfg>(n, d_tail, tail_bytes, d_out, (hipStream_t)stream, (hipEvent_t)levels_done, m);
-}
-int ozk_var_msm_stage_bytes(int32_t n, int32_t type, size_t* sorted_bytes, size_t* sort_ws_bytes,
-                            size_t* accum_ws_bytes) {
-  if (n <= 0 || n > (1 << 24) || !sorted_bytes || !sort_ws_bytes || !accum_ws_bytes)
-    return fail(OZK_E_INVALID, "bad argument");
-  const RegionBytes rb = type == OZK_G1 ? region_bytes<G1Cfg>(n) : region_bytes<G2Cfg>(n);
-  *sorted_bytes = rb.sorted;
-  *sort_ws_bytes = rb.sort_ws;
-  *accum_ws_bytes = rb.accum_ws;
-  return OZK_OK;
-}
-int ozk_var_msm_sort_dev(const void* d_bases, const void* d_scalars, int32_t n, int32_t type, void* d_sorted,
-                         size_t sorted_bytes, void* d_sort_ws, size_t sort_ws_bytes, void* stream) {
-  if (!d_bases || !d_scalars || !d_sorted || !d_sort_ws) return fail(OZK_E_INVALID, "null pointer argument");
-  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
-  if (type == OZK_G1)
-    return var_msm_sort<G1Cfg>(d_bases, d_scalars, n, d_sorted, sorted_bytes, d_sort_ws, sort_ws_bytes,
-                               (hipStream_t)stream);
-  return var_msm_sort<G2Cfg>(d_bases, d_scalars, n, d_sorted, sorted_bytes, d_sort_ws, sort_ws_bytes,
-                             (hipStream_t)stream);
-}
-int ozk_var_msm_accum_dev(int32_t n, int32_t type, void* d_sorted, size_t sorted_bytes, void* d_accum_ws,
-                          size_t accum_ws_bytes, void* d_tail, size_t tail_bytes, void* stream) {
-  if (!d_sorted || !d_accum_ws || !d_tail) return fail(OZK_E_INVALID, "null pointer argument");
-  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
-  if (type == OZK_G1)
-    return var_msm_accum<G1Cfg>(n, d_sorted, sorted_bytes, d_accum_ws, accum_ws_bytes, d_tail, tail_bytes,
-                                (hipStream_t)stream);
-  return var_msm_accum<G2Cfg>(n, d_sorted, sorted_bytes, d_accum_ws, accum_ws_bytes, d_tail, tail_bytes,
-                              (hipStream_t)stream);
-}
-int ozk_var_msm_accum_part_dev(const void* d_prepared, int32_t n, int32_t type, void* d_sorted, size_t sorted_bytes,
-                               void* d_accum_ws, size_t accum_ws_bytes, void* d_tail, size_t tail_bytes, void* stream,
-                               int32_t part) {
-  if (!d_sorted || !d_accum_ws || !d_tail) return fail(OZK_E_INVALID, "null pointer argument");
-  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
-  if (part < ACCUM_ALL || part > ACCUM_REST) return fail(OZK_E_INVALID, "part %d is not 0 (all), 1 (level 1) or 2 (rest)", part);
-  if (type == OZK_G1)
-    return var_msm_accum<G1Cfg>(n, d_sorted, sorted_bytes, d_accum_ws, accum_ws_bytes, d_tail, tail_bytes,
-                                (hipStream_t)stream, d_prepared, part);
-  return var_msm_accum<G2Cfg>(n, d_sorted, sorted_bytes, d_accum_ws, accum_ws_bytes, d_tail, tail_bytes,
-                              (hipStream_t)stream, d_prepared, part);
-}
-int ozk_var_msm_sort_prepared_dev(const void* d_prepared, const void* d_scalars, int32_t n, int32_t type, void* d_sorted,
-                                  size_t sorted_bytes, void* d_sort_ws, size_t sort_ws_bytes, void* stream) {
-  if (!d_prepared || !d_scalars || !d_sorted || !d_sort_ws) return fail(OZK_E_INVALID, "null pointer argument");
-  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
-  if (type == OZK_G1)
-    return var_msm_sort<G1Cfg>(nullptr, d_scalars, n, d_sorted, sorted_bytes, d_sort_ws, sort_ws_bytes,
-                               (hipStream_t)stream, nullptr, d_prepared);
-  return var_msm_sort<G2Cfg>(nullptr, d_scalars, n, d_sorted, sorted_bytes, d_sort_ws, sort_ws_bytes,
-                             (hipStream_t)stream, nullptr, d_prepared);
-}
-int ozk_var_msm_accum_prepared_dev(const void* d_prepared, int32_t n, int32_t type, void* d_sorted, size_t sorted_bytes,
-                                   void* d_accum_ws, size_t accum_ws_bytes, void* d_tail, size_t tail_bytes,
-                                   void* stream) {
-  if (!d_prepared || !d_sorted || !d_accum_ws || !d_tail) return fail(OZK_E_INVALID, "null pointer argument");
-  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
-  if (type == OZK_G1)
-    return var_msm_accum<G1Cfg>(n, d_sorted, sorted_bytes, d_accum_ws, accum_ws_bytes, d_tail, tail_bytes,
-                                (hipStream_t)stream, d_prepared);
-  return var_msm_accum<G2Cfg>(n, d_sorted, sorted_bytes, d_accum_ws, accum_ws_bytes, d_tail, tail_bytes,
-                              (hipStream_t)stream, d_prepared);
-}
-int ozk_var_msm_tail_dev(int32_t n, int32_t type, void* d_tail, size_t tail_bytes, void* d_out, void* stream) {
-  if (!d_tail || !d_out) return fail(OZK_E_INVALID, "null pointer argument");
-  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
-  if (type == OZK_G1) return var_msm_tail<G1Cfg>(n, d_tail, tail_bytes, d_out, (hipStream_t)stream, nullptr, TAIL_THROUGHPUT);
-  return var_msm_tail<G2Cfg>(n, d_tail, tail_bytes, d_out, (hipStream_t)stream, nullptr, TAIL_THROUGHPUT);
-}
-
 int ozk_var_msm_host(const uint8_t* bases, const uint8_t* scalars, int32_t n, int32_t type, int32_t task_id,
                      uint8_t* out) {
   if (!bases || !scalars || !out) return fail(OZK_E_INVALID, "null pointer argument");
-  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
+  if (int rc = check_batch_size(n)) return rc;
   if (type == OZK_G1) return var_msm_host<G1Cfg>(bases, scalars, n, task_id, out);
-#if defined(OZK_WITH_G2)
-  return var_msm_host<G2Cfg>(bases, scalars, n, task_id, out);
-#else
-  return fail(OZK_E_INVALID, "G2 not built");
-#endif
+  return var_msm_host<G2Cfg>(bases, scalars, n, task_id, out);   // (any other BNType is G2, as in the reference)
 }
 
 // d_result != nullptr (the sharded entry's RCCL form): the 576 bytes stay on the device, G1 (192) || G2 (384)
@@ -332,7 +257,7 @@ static int var_double_msm_host_impl(const uint8_t* bases_g1, const uint8_t* base
   // the 192 n bytes of G2 bases are uploaded (the host thread staging pageable memory) while the G1 MSM
   // already runs on its own stream; the G1 tail then overlaps the G2 head.
   if (!bases_g1 || !bases_g2 || !scalars || (!out && !d_result)) return fail(OZK_E_INVALID, "null pointer argument");
-  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
+  if (int rc = check_batch_size(n)) return rc;
   CtxGuard g;
   int rc = ctx_acquire(task_id, &g.c);
   // both results out: to the host through the pinned result buffer, or device to device
@@ -711,19 +636,12 @@ int ozk_var_double_msm_auto_host(const uint8_t* bases_g1, const uint8_t* bases_g
 static int points_sum_strided(const void* d_points, int k, int type, size_t stride_bytes, void* d_out, hipStream_t st) {
   hip_clear_stale();   // (ozk_common.h: a stale error of the calling thread is not this call's)
   if (!d_points || !d_out || k <= 0 || (stride_bytes & 3)) return fail(OZK_E_INVALID, "bad argument");
-  if (type == OZK_G1) {
-    hipLaunchKernelGGL((k_points_sum<G1Cfg>), dim3(1), dim3(64), 0, st, (const u32*)d_points, k, (int)(stride_bytes / 4),
-                       (u32*)d_out);
-  } else {
-#if defined(OZK_WITH_G2)
-    hipLaunchKernelGGL((k_points_sum<G2Cfg>), dim3(1), dim3(64), 0, st, (const u32*)d_points, k, (int)(stride_bytes / 4),
-                       (u32*)d_out);
-#else
-    return fail(OZK_E_INVALID, "G2 not built");
-#endif
-  }
-  OZK_HIP(hipGetLastError());
-  return OZK_OK;
+  return by_point_type(type, [&](auto t) {
+    hipLaunchKernelGGL((k_points_sum<typename decltype(t)::CV>), dim3(1), dim3(64), 0, st, (const u32*)d_points, k,
+                       (int)(stride_bytes / 4), (u32*)d_out);
+    OZK_HIP(hipGetLastError());
+    return OZK_OK;
+  });
 }
 int ozk_points_sum_dev(const void* d_points, int32_t k, int32_t type, void* d_out, void* stream) {
   return points_sum_strided(d_points, k, type, type == OZK_G1 ? 192 : 384, d_out, (hipStream_t)stream);
@@ -732,14 +650,10 @@ int ozk_points_sum_dev(const void* d_points, int32_t k, int32_t type, void* d_ou
 int ozk_groth16_combine_dev(const void* d_records, int32_t world, void* d_proof, void* stream) {
   hip_clear_stale();   // (ozk_common.h: a stale error of the calling thread is not this call's)
   if (!d_records || !d_proof || world < 1) return fail(OZK_E_INVALID, "bad argument");
-#if defined(OZK_WITH_G2)
   hipLaunchKernelGGL((k_groth16_combine<G1Cfg, G2Cfg>), dim3(3), dim3(64), 0, (hipStream_t)stream,
                      (const u32*)d_records, (int)world, (u32*)d_proof);
   OZK_HIP(hipGetLastError());
   return OZK_OK;
-#else
-  return fail(OZK_E_INVALID, "G2 not built");
-#endif
 }
 
 int ozk_gen_bases_dev(uint64_t seed, int32_t n, int32_t type, void* d_out_wire, void* stream) {
@@ -942,7 +856,7 @@ int ozk_var_msm_plan(int32_t n, int32_t* window_bits, int32_t* windows) {
 int ozk_var_msm_glv(int32_t n) { return n > 0 ? make_plan(n).glv : 0; }
 
 const char* ozk_last_error(void) { return err_buf(); }
-int ozk_version(void) { return 1; }
+int ozk_version(void) { return 2; }
 int ozk_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;

@@ -9,9 +9,6 @@
 #include <atomic>
 #include <vector>
 
-#ifndef OZK_WITH_G2
-#define OZK_WITH_G2 1
-#endif
 #include "msm_var.cuh"
 #include "host_ctx.h"
 #include "fq2.cuh"
@@ -453,7 +450,7 @@ int var_msm_sort(const void* d_bases, const void* d_scalars, int n, void* sorted
                 p.c, p.W, p.n_in, SORTBIG_MAXBINS);
   hipLaunchKernelGGL(k_sort2, dim3(nbins), dim3(SORT2_BLOCK), 0, st, L.coarse, L.P1, L.total, p.cb, L.lo_bits, L.NH,
                      sign_bit, L.nblk, nbins, big_thresh, L.hist, L.sent);
-  // Ordering hint for pipelined MSMs (see ozk_var_msm_tail_ordered_dev): everything up to here may
+  // Ordering hint for pipelined MSMs (see ozk_order_event_create, include/ozk.h): everything up to here may
   // overlap the previous MSM's window-sum levels; the bucket accumulation that follows fills every
   // SIMD's register file, so the previous MSM's single-wave Horner kernel has to be resident first.
   if (order_ev && env_int("OZK_MSM_ORDER", 1)) OZK_HIP(hipStreamWaitEvent(st, order_ev, 0));
@@ -471,7 +468,7 @@ int var_msm_sort(const void* d_bases, const void* d_scalars, int n, void* sorted
 
 // ACCUMULATE stage: bucket accumulation, run merge, generic levels, first window-sum level.
 // Vector-ALU-bound.  Reads the sorted set, leaves W * 2^c / S window-sum elements in the tail buffers.
-// ACCUMULATE in two parts for callers that run them on different streams (ozk_var_msm_accum_part_dev): level 1 is
+// ACCUMULATE in two parts for callers that run them on different streams (ozk_var_msm_accum_dev, `part`): level 1 is
 // the vector-ALU-bound kernel; the REST (run merge, the short generic levels, the copy of the bucket counts) is 0.1 ms
 // of low-occupancy work that reads what level 1 wrote in the accumulate scratch and the sorted set.
 enum { ACCUM_ALL = 0, ACCUM_LEVEL1 = 1, ACCUM_REST = 2 };

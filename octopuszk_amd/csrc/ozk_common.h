@@ -37,6 +37,14 @@ inline int fail(int code, const char* fmt, ...) {
                          __LINE__);                                                         \
   } while (0)
 
+// argument checks shared by the entry points: the pair count of an MSM (a 24-bit index in the packed sort words),
+// and the 4-byte alignment of a buffer the kernels read as words
+inline int check_batch_size(int n) {
+  if (n <= 0 || n > (1 << 24)) return fail(OZK_E_INVALID, "batch_size %d out of range [1, 2^24]", n);
+  return OZK_OK;
+}
+inline bool misaligned(const void* p) { return ((uintptr_t)p & 3) != 0; }
+
 // select the device the reference would: taskID % num_gpus
 // (algebra_msm_VariableBaseMSM.cu:1249-1257)
 inline int select_device(int task_id) {

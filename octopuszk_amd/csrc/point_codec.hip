@@ -14,7 +14,6 @@ constexpr int CODEC_PREPARED_MAX_N = 1 << 23;   // the GLV plan of the variable-
 
 // words per coordinate of a wire format: 0 wire-in (32-byte coordinates), 1 wire-out (64-byte)
 int coord_words(int32_t format) { return format == 0 ? 8 : format == 1 ? 16 : 0; }
-bool misaligned(const void* p) { return ((uintptr_t)p & 3) != 0; }
 
 }  // namespace
 
@@ -25,25 +24,23 @@ int ozk_points_decompress_dev(const void* d_in, int32_t n, int32_t type, int32_t
   hip_clear_stale();
   const int S = coord_words(out_format);
   if (!d_in || !d_out || !d_codes || n <= 0 || n > CODEC_MAX_N) return fail(OZK_E_INVALID, "bad argument");
-  if (type != OZK_G1 && type != OZK_G2) return fail(OZK_E_INVALID, "unknown point type %d", (int)type);
+  if (int rc = check_point_type(type)) return rc;
   if (!S) return fail(OZK_E_INVALID, "unknown point format %d", (int)out_format);
   if (misaligned(d_in) || misaligned(d_out)) return fail(OZK_E_INVALID, "buffers must be 4-byte aligned");
   const dim3 grid((n + 63) / 64), block(64);
-  if (type == OZK_G1)
-    hipLaunchKernelGGL(k_codec_decompress<1>, grid, block, 0, (hipStream_t)stream, (const u32*)d_in, (int)n, S,
-                       (u32*)d_out, d_codes);
-  else
-    hipLaunchKernelGGL(k_codec_decompress<2>, grid, block, 0, (hipStream_t)stream, (const u32*)d_in, (int)n, S,
-                       (u32*)d_out, d_codes);
-  OZK_HIP(hipGetLastError());
-  return OZK_OK;
+  return by_point_type(type, [&](auto t) {
+    hipLaunchKernelGGL(k_codec_decompress<decltype(t)::TYPE>, grid, block, 0, (hipStream_t)stream, (const u32*)d_in,
+                       (int)n, S, (u32*)d_out, d_codes);
+    OZK_HIP(hipGetLastError());
+    return OZK_OK;
+  });
 }
 
 int ozk_points_decompress_prepared_dev(const void* d_in, int32_t n, int32_t type, void* d_prepared,
                                        size_t prepared_bytes, int32_t* d_codes, int32_t check_subgroup, void* stream) {
   hip_clear_stale();
   if (!d_in || !d_prepared || !d_codes || n <= 0) return fail(OZK_E_INVALID, "bad argument");
-  if (type != OZK_G1 && type != OZK_G2) return fail(OZK_E_INVALID, "unknown point type %d", (int)type);
+  if (int rc = check_point_type(type)) return rc;
   if (n > CODEC_PREPARED_MAX_N || !ozk_var_msm_glv(n))
     return fail(OZK_E_INVALID, "%d points: only the two-record GLV form of the prepared bases is written (n <= 2^23)", (int)n);
   if (prepared_bytes < ozk_var_msm_prepared_bytes(n, type))
@@ -51,17 +48,14 @@ int ozk_points_decompress_prepared_dev(const void* d_in, int32_t n, int32_t type
   if (misaligned(d_in) || misaligned(d_prepared)) return fail(OZK_E_INVALID, "buffers must be 4-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((n + 63) / 64), block(64);
-  if (type == OZK_G1) {
-    hipLaunchKernelGGL(k_codec_decompress_prepared<1>, grid, block, 0, s, (const u32*)d_in, (int)n, (u32*)d_prepared,
-                       d_codes);
-  } else {
-    hipLaunchKernelGGL(k_codec_decompress_prepared<2>, grid, block, 0, s, (const u32*)d_in, (int)n, (u32*)d_prepared,
-                       d_codes);
-    if (check_subgroup)   // G1 has cofactor 1: nothing to check there
+  return by_point_type(type, [&](auto t) {
+    hipLaunchKernelGGL(k_codec_decompress_prepared<decltype(t)::TYPE>, grid, block, 0, s, (const u32*)d_in, (int)n,
+                       (u32*)d_prepared, d_codes);
+    if (check_subgroup && decltype(t)::TYPE == OZK_G2)   // G1 has cofactor 1: nothing to check there
       hipLaunchKernelGGL(k_codec_subgroup_g2, grid, block, 0, s, (u32*)d_prepared, (int)n, d_codes);
-  }
-  OZK_HIP(hipGetLastError());
-  return OZK_OK;
+    OZK_HIP(hipGetLastError());
+    return OZK_OK;
+  });
 }
 
 int ozk_points_compress_dev(const void* d_in, int32_t n, int32_t type, int32_t in_format, void* d_out,
@@ -69,18 +63,16 @@ int ozk_points_compress_dev(const void* d_in, int32_t n, int32_t type, int32_t i
   hip_clear_stale();
   const int S = coord_words(in_format);
   if (!d_in || !d_out || n <= 0 || n > CODEC_MAX_N) return fail(OZK_E_INVALID, "bad argument");
-  if (type != OZK_G1 && type != OZK_G2) return fail(OZK_E_INVALID, "unknown point type %d", (int)type);
+  if (int rc = check_point_type(type)) return rc;
   if (!S) return fail(OZK_E_INVALID, "unknown point format %d", (int)in_format);
   if (misaligned(d_in) || misaligned(d_out)) return fail(OZK_E_INVALID, "buffers must be 4-byte aligned");
   const dim3 grid((n + 63) / 64), block(64);
-  if (type == OZK_G1)
-    hipLaunchKernelGGL(k_codec_compress<1>, grid, block, 0, (hipStream_t)stream, (const u32*)d_in, (int)n, S,
-                       (u32*)d_out);
-  else
-    hipLaunchKernelGGL(k_codec_compress<2>, grid, block, 0, (hipStream_t)stream, (const u32*)d_in, (int)n, S,
-                       (u32*)d_out);
-  OZK_HIP(hipGetLastError());
-  return OZK_OK;
+  return by_point_type(type, [&](auto t) {
+    hipLaunchKernelGGL(k_codec_compress<decltype(t)::TYPE>, grid, block, 0, (hipStream_t)stream, (const u32*)d_in, (int)n,
+                       S, (u32*)d_out);
+    OZK_HIP(hipGetLastError());
+    return OZK_OK;
+  });
 }
 
 int ozk_groth16_proofs_decompress_dev(const void* d_in128, int32_t k, void* d_records768, int32_t* d_codes,

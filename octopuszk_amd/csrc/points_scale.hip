@@ -8,7 +8,6 @@ using namespace ozk;
 
 namespace {
 constexpr int SCALE_MAX_N = 1 << 24;
-bool misaligned(const void* p) { return ((uintptr_t)p & 3) != 0; }
 }  // namespace
 
 extern "C" {
@@ -17,7 +16,7 @@ int ozk_points_scale_dev(const void* d_in, int32_t n, int32_t type, const uint8_
                          void* stream) {
   hip_clear_stale();
   if (!d_in || !d_out || !k_host32 || n <= 0 || n > SCALE_MAX_N) return fail(OZK_E_INVALID, "bad argument");
-  if (type != OZK_G1 && type != OZK_G2) return fail(OZK_E_INVALID, "unknown point type %d", (int)type);
+  if (int rc = check_point_type(type)) return rc;
   if (misaligned(d_in) || misaligned(d_out)) return fail(OZK_E_INVALID, "buffers must be 4-byte aligned");
   u32 k[8];
   for (int i = 0; i < 8; i++)
@@ -27,14 +26,12 @@ int ozk_points_scale_dev(const void* d_in, int32_t n, int32_t type, const uint8_
   ScaleSchedule s;
   scale_recode(k, type == OZK_G1, s);
   const dim3 grid((n + 63) / 64), block(64);
-  if (type == OZK_G1)
-    hipLaunchKernelGGL(k_points_scale<1>, grid, block, 0, (hipStream_t)stream, (const u32*)d_in, (int)n, s,
-                       (u32*)d_out);
-  else
-    hipLaunchKernelGGL(k_points_scale<2>, grid, block, 0, (hipStream_t)stream, (const u32*)d_in, (int)n, s,
-                       (u32*)d_out);
-  OZK_HIP(hipGetLastError());
-  return OZK_OK;
+  return by_point_type(type, [&](auto t) {
+    hipLaunchKernelGGL(k_points_scale<decltype(t)::TYPE>, grid, block, 0, (hipStream_t)stream, (const u32*)d_in, (int)n,
+                       s, (u32*)d_out);
+    OZK_HIP(hipGetLastError());
+    return OZK_OK;
+  });
 }
 
 }  // extern "C"

@@ -18,8 +18,8 @@ def _stream():
 
 
 def prepare_bases(d_bases, n, type_):
-    """Affine Montgomery records of the `n` bases `d_bases` (wire format) for the *_prepared_dev entry points
-    (submit(..., prepared=True)): done once per proving key, skips the conversion kernel in every MSM.
+    """Affine Montgomery records of the `n` bases `d_bases` (wire format) for ozk_var_msm_prepared_dev and the
+    staged entry points' prepared form (submit(..., prepared=True)): done once per proving key, skips the conversion kernel in every MSM.
     Asynchronous on the current stream."""
     L = _lib.load()
     nbytes = int(L.ozk_var_msm_prepared_bytes(n, type_))
@@ -126,7 +126,7 @@ class _MsmPipeline:
 
     `n` is one length or a sequence of lengths: submit(..., n=) then takes any of them, and every buffer holds the
     largest of its byte query over the lengths (the queries are not monotonic in n, so not the query at the largest).
-    `tail_mode` is the shape of the window sums of the tails (include/ozk.h, ozk_var_msm_tail_mode_dev): 0 latency,
+    `tail_mode` is the shape of the window sums of the tails (include/ozk.h, ozk_var_msm_tail_dev): 0 latency,
     1 throughput.  `last_lone` chooses what submit(last=True) means: see the two submit methods."""
 
     def __init__(self, n, type_, depth, tail_mode, last_lone, device):
@@ -251,13 +251,13 @@ class VarMsmPipeline(_MsmPipeline):
         if last and self.last_lone:
             return self._lone(main, d_bases, d_scalars, prepared, n, out, slot)
         prev = self.levels_done[(self.count - 1) % self.depth] if (self.count and self.depth > 1) else None
-        head = L.ozk_var_msm_head_prepared_dev if prepared else L.ozk_var_msm_head_ordered_dev
-        _lib.check(head(_ptr(d_bases), _ptr(d_scalars), n, self.type, _ptr(self.ws), self.ws_bytes,
-                        _ptr(self.tails[slot]), self.tail_bytes, int(main.cuda_stream), prev))
+        _lib.check(L.ozk_var_msm_head_dev(_ptr(d_bases), int(prepared), _ptr(d_scalars), n, self.type, _ptr(self.ws),
+                                          self.ws_bytes, _ptr(self.tails[slot]), self.tail_bytes,
+                                          int(main.cuda_stream), prev))
         self.head_done[slot].record(main)
         self.side.wait_event(self.head_done[slot])
-        _lib.check(L.ozk_var_msm_tail_mode_dev(n, self.type, _ptr(self.tails[slot]), self.tail_bytes, _ptr(out),
-                                               int(self.side.cuda_stream), self.levels_done[slot], self.tail_mode))
+        _lib.check(L.ozk_var_msm_tail_dev(n, self.type, _ptr(self.tails[slot]), self.tail_bytes, _ptr(out),
+                                          int(self.side.cuda_stream), self.levels_done[slot], self.tail_mode))
         return self._end(self.side, slot)
 
 
@@ -280,7 +280,7 @@ class VarMsmPipeline3(_MsmPipeline):
         self.tail_cus = int(os.environ.get("OZK_P3_TAIL_CUS", "0")) if tail_cus is None else int(tail_cus)
         self._owned = []
         # split_accum: level 1 alone on the accumulate stream, the rest of the stage (run merge, generic levels) at the
-        # head of the tail stream (ozk_var_msm_accum_part_dev); the accumulate scratch is then double-buffered too
+        # head of the tail stream (ozk_var_msm_accum_dev, part 1 | 2); the accumulate scratch is then double-buffered too
         self.split = bool(int(os.environ.get("OZK_P3_SPLIT_ACCUM", "0"))) if split_accum is None else bool(split_accum)
         # a result slot is always served by the same tail stream (slot = k mod depth, stream = k mod ts), so whatever a
         # caller enqueues on stream_of(ticket) after result(ticket) is ordered before the slot's next tail
@@ -354,17 +354,17 @@ class VarMsmPipeline3(_MsmPipeline):
             return self._lone(self.acc, d_bases, d_scalars, prepared, n, out, slot)
         if k >= 2:
             main.wait_event(self.accum_done[s])        # sorted set s (and, split, accumulate scratch s) is free again
-        sort = L.ozk_var_msm_sort_prepared_dev if prepared else L.ozk_var_msm_sort_dev
-        _lib.check(sort(_ptr(d_bases), _ptr(d_scalars), n, self.type, _ptr(self.sorted[s]), self.sorted_bytes,
-                        _ptr(self.sort_ws), self.sort_ws_bytes, int(main.cuda_stream)))
+        _lib.check(L.ozk_var_msm_sort_dev(_ptr(d_bases), int(prepared), _ptr(d_scalars), n, self.type,
+                                          _ptr(self.sorted[s]), self.sorted_bytes, _ptr(self.sort_ws),
+                                          self.sort_ws_bytes, int(main.cuda_stream)))
         self.sort_done[s].record(main)
         self.acc.wait_event(self.sort_done[s])
         if k >= self.depth:
             self.acc.wait_event(self.tail_done[slot])  # the tail that last used this slot's buffers
         T = self.tail_st[k % len(self.tail_st)]
         accum_ws = self.accum_ws2[s] if self.split else self.accum_ws
-        # (ozk_var_msm_accum_part_dev is the general form of the stage: part 0 all of it, 1 level 1, 2 the rest)
-        accum = lambda stream, part: _lib.check(L.ozk_var_msm_accum_part_dev(
+        # part 0: all of the stage, 1: level 1, 2: the rest
+        accum = lambda stream, part: _lib.check(L.ozk_var_msm_accum_dev(
             _ptr(d_bases) if prepared else None, n, self.type, _ptr(self.sorted[s]), self.sorted_bytes, _ptr(accum_ws),
             self.accum_ws_bytes, _ptr(self.tails[slot]), self.tail_bytes, int(stream.cuda_stream), part))
         if self.split:
@@ -383,8 +383,8 @@ class VarMsmPipeline3(_MsmPipeline):
             accum(self.acc, 0)
             self.accum_done[s].record(self.acc)
             T.wait_event(self.accum_done[s])
-        _lib.check(L.ozk_var_msm_tail_mode_dev(n, self.type, _ptr(self.tails[slot]), self.tail_bytes, _ptr(out),
-                                               int(T.cuda_stream), None, 0 if last else self.tail_mode))
+        _lib.check(L.ozk_var_msm_tail_dev(n, self.type, _ptr(self.tails[slot]), self.tail_bytes, _ptr(out),
+                                          int(T.cuda_stream), None, 0 if last else self.tail_mode))
         return self._end(T, slot)
 
     def stream_of(self, ticket):

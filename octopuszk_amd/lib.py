@@ -37,30 +37,23 @@ _SIGS = {
     "ozk_var_msm_glv": (ctypes.c_int, [i32]),
     "ozk_gen_bases_dev": (ctypes.c_int, [ctypes.c_uint64, i32, i32, vp, vp]),
     "ozk_var_msm_stage_bytes": (ctypes.c_int, [i32, i32, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(sz)]),
-    "ozk_var_msm_sort_dev": (ctypes.c_int, [vp, vp, i32, i32, vp, sz, vp, sz, vp]),
-    "ozk_var_msm_accum_dev": (ctypes.c_int, [i32, i32, vp, sz, vp, sz, vp, sz, vp]),
-    "ozk_var_msm_sort_prepared_dev": (ctypes.c_int, [vp, vp, i32, i32, vp, sz, vp, sz, vp]),
-    "ozk_var_msm_accum_prepared_dev": (ctypes.c_int, [vp, i32, i32, vp, sz, vp, sz, vp, sz, vp]),
+    "ozk_var_msm_sort_dev": (ctypes.c_int, [vp, i32, vp, i32, i32, vp, sz, vp, sz, vp]),
+    "ozk_var_msm_accum_dev": (ctypes.c_int, [vp, i32, i32, vp, sz, vp, sz, vp, sz, vp, i32]),
     "ozk_device_cu_count": (ctypes.c_int, []),
     "ozk_stream_create_cu_range": (ctypes.c_int, [i32, i32, ctypes.POINTER(ctypes.c_void_p)]),
     "ozk_stream_destroy": (ctypes.c_int, [vp]),
-    "ozk_var_msm_accum_part_dev": (ctypes.c_int, [vp, i32, i32, vp, sz, vp, sz, vp, sz, vp, i32]),
     "ozk_var_msm_head_workspace_bytes": (sz, [i32, i32]),
     "ozk_var_msm_tail_bytes": (sz, [i32, i32]),
-    "ozk_var_msm_head_dev": (ctypes.c_int, [vp, vp, i32, i32, vp, sz, vp, sz, vp]),
-    "ozk_var_msm_tail_dev": (ctypes.c_int, [i32, i32, vp, sz, vp, vp]),
+    "ozk_var_msm_head_dev": (ctypes.c_int, [vp, i32, vp, i32, i32, vp, sz, vp, sz, vp, vp]),
+    "ozk_var_msm_tail_dev": (ctypes.c_int, [i32, i32, vp, sz, vp, vp, vp, i32]),
     "ozk_bases_create_host": (ctypes.c_int, [vp, i32, i32, i32, ctypes.POINTER(vp)]),
     "ozk_var_msm_bases_host": (ctypes.c_int, [vp, vp, i32, vp]),
     "ozk_bases_destroy": (ctypes.c_int, [vp]),
     "ozk_var_msm_prepared_bytes": (sz, [i32, i32]),
     "ozk_var_msm_prepare_dev": (ctypes.c_int, [vp, i32, i32, vp, sz, vp]),
     "ozk_var_msm_prepared_dev": (ctypes.c_int, [vp, vp, i32, i32, vp, vp, sz, vp]),
-    "ozk_var_msm_head_prepared_dev": (ctypes.c_int, [vp, vp, i32, i32, vp, sz, vp, sz, vp, vp]),
     "ozk_order_event_create": (ctypes.c_int, [ctypes.POINTER(vp)]),
     "ozk_order_event_destroy": (ctypes.c_int, [vp]),
-    "ozk_var_msm_head_ordered_dev": (ctypes.c_int, [vp, vp, i32, i32, vp, sz, vp, sz, vp, vp]),
-    "ozk_var_msm_tail_ordered_dev": (ctypes.c_int, [i32, i32, vp, sz, vp, vp, vp]),
-    "ozk_var_msm_tail_mode_dev": (ctypes.c_int, [i32, i32, vp, sz, vp, vp, vp, i32]),
     "ozk_points_sum_dev": (ctypes.c_int, [vp, i32, i32, vp, vp]),
     "ozk_groth16_combine_dev": (ctypes.c_int, [vp, i32, vp, vp]),
     "ozk_fixed_batch_msm_host": (ctypes.c_int, [i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp]),

@@ -954,11 +954,10 @@ class ShardedProver:
         # first: its tail is the longest latency-bound chain of the proof and hides under the G1 accumulations.
         self.s_g2.wait_event(ready)
         with torch.cuda.stream(self.s_g2):
-            _lib.check(L.ozk_var_msm_head_prepared_dev(_ptr(self.qb2), _ptr(d_sc_s), n_ab, 2, _ptr(self.g2_ws),
-                                                       self.g2_ws_bytes, _ptr(self.g2_tail), self.g2_tail_bytes, _stream(),
-                                                       None))
-            _lib.check(L.ozk_var_msm_tail_mode_dev(n_ab, 2, _ptr(self.g2_tail), self.g2_tail_bytes, _ptr(rec[192:576]),
-                                                   _stream(), None, 1))
+            _lib.check(L.ozk_var_msm_head_dev(_ptr(self.qb2), 1, _ptr(d_sc_s), n_ab, 2, _ptr(self.g2_ws),
+                                              self.g2_ws_bytes, _ptr(self.g2_tail), self.g2_tail_bytes, _stream(), None))
+            _lib.check(L.ozk_var_msm_tail_dev(n_ab, 2, _ptr(self.g2_tail), self.g2_tail_bytes, _ptr(rec[192:576]),
+                                              _stream(), None, 1))
             g2_done = torch.cuda.Event()
             g2_done.record(self.s_g2)
         # witness map (SerialProver.java:36-41): constraint evaluations (R1CStoQAP.java:143-160,195-199) and the

@@ -57,11 +57,11 @@ def test_three_stage_pipeline_equals_single_calls(n, prepared):
     assert len(set(serial)) == (7 if n > 1 else len(set(serial)))
 
 
-def _narrow_entry_points(d_bases, d_sc, n):
-    """The pipelines issue the accumulate and tail stages through their general entries (ozk_var_msm_accum_part_dev
-    part 0, ozk_var_msm_tail_mode_dev).  The narrow names of the same stages — _accum_dev, _accum_prepared_dev,
-    _tail_dev (throughput, no event), _tail_ordered_dev (latency, with an event) — must give the same bytes.
-    Returns them."""
+def _stage_entry_points(d_bases, d_sc, n):
+    """sort -> accumulate -> tail through the C entries themselves (ozk_var_msm_sort_dev, _accum_dev, _tail_dev), on one
+    stream: wire or prepared bases, each with the latency tail (mode 0) recording an ordering event and with the
+    throughput tail (mode 1) without one, and the accumulate stage in its two parts (1 then 2) once.  All must give
+    the same bytes.  Returns them."""
     import ctypes
     import torch
     from octopuszk_amd import device as dev, lib
@@ -74,30 +74,29 @@ def _narrow_entry_points(d_bases, d_sc, n):
     buf = lambda b: torch.empty(b, dtype=torch.uint8, device="cuda")
     sorted_, sort_ws, accum_ws, tail = buf(sb.value), buf(swb.value), buf(awb.value), buf(tb)
     prep = dev.prepare_bases(d_bases, n, 1)
-    stage = (n, 1, p(sorted_), sb.value, p(accum_ws), awb.value, p(tail), tb, st)
     ev = ctypes.c_void_p()
     lib.check(L.ozk_order_event_create(ctypes.byref(ev)))
 
-    def run(prepared, accum, tail_stage):
+    def run(prepared, levels_done, mode, parts=(0,)):
         out = torch.zeros(192, dtype=torch.uint8, device="cuda")
-        sort, b = (L.ozk_var_msm_sort_prepared_dev, prep) if prepared else (L.ozk_var_msm_sort_dev, d_bases)
-        lib.check(sort(p(b), p(d_sc), n, 1, p(sorted_), sb.value, p(sort_ws), swb.value, st))
-        lib.check(accum())
-        lib.check(tail_stage(n, 1, p(tail), tb, p(out), st))
+        lib.check(L.ozk_var_msm_sort_dev(p(prep if prepared else d_bases), int(prepared), p(d_sc), n, 1, p(sorted_),
+                                         sb.value, p(sort_ws), swb.value, st))
+        for part in parts:
+            lib.check(L.ozk_var_msm_accum_dev(p(prep) if prepared else None, n, 1, p(sorted_), sb.value, p(accum_ws),
+                                              awb.value, p(tail), tb, st, part))
+        lib.check(L.ozk_var_msm_tail_dev(n, 1, p(tail), tb, p(out), st, levels_done, mode))
         torch.cuda.synchronize()
         return bytes(out.cpu().numpy())
 
     try:
-        general = run(False, lambda: L.ozk_var_msm_accum_part_dev(None, *stage, 0),
-                      lambda *a: L.ozk_var_msm_tail_mode_dev(*a, None, 1))
-        assert run(False, lambda: L.ozk_var_msm_accum_dev(*stage), L.ozk_var_msm_tail_dev) == general
-        assert run(True, lambda: L.ozk_var_msm_accum_part_dev(p(prep), *stage, 0),
-                   lambda *a: L.ozk_var_msm_tail_mode_dev(*a, ev, 0)) == general
-        assert run(True, lambda: L.ozk_var_msm_accum_prepared_dev(p(prep), *stage),
-                   lambda *a: L.ozk_var_msm_tail_ordered_dev(*a, ev)) == general
+        first = run(False, None, 1)
+        assert run(False, ev, 0) == first
+        assert run(True, None, 1) == first
+        assert run(True, ev, 0) == first
+        assert run(True, ev, 0, parts=(1, 2)) == first
     finally:
         lib.check(L.ozk_order_event_destroy(ev))
-    return general
+    return first
 
 
 def test_three_stage_pipeline_vs_oracle_small():
@@ -124,7 +123,7 @@ def test_three_stage_pipeline_vs_oracle_small():
     torch.cuda.synchronize()
     got = [bytes(pipe.outs[t % pipe.depth].cpu().numpy()) for t, _ in tickets]
     assert got == wants
-    assert _narrow_entry_points(d_bases, torch.from_numpy(sc).cuda(), n) == wants[-1]
+    assert _stage_entry_points(d_bases, torch.from_numpy(sc).cuda(), n) == wants[-1]
 
 
 @pytest.mark.parametrize("n", [7, 300, 1 << 12])
@@ -152,6 +151,36 @@ def test_three_stage_pipeline_g2_equals_single_calls(n):
     want = o.g2_out_le(G.to_affine(o.naive_msm(G, [int.from_bytes(bytes(inputs[0].cpu().numpy()[32 * i:32 * i + 32]), "little")
                                                    for i in range(n)], bases)))
     assert serial[0] == want
+
+
+@pytest.mark.parametrize("n", [1, 33])
+def test_head_and_tail_entries_g2_equal_the_single_call(n):
+    """ozk_var_msm_head_dev (wire bases, then prepared) + ozk_var_msm_tail_dev (mode 0, then 1) over G2 against
+    ozk_var_msm_dev on the same inputs, byte for byte."""
+    import numpy as np
+    import torch
+    from octopuszk_amd import device as dev, lib
+    L = lib.load()
+    rng = random.Random(500 + n)
+    G = o.G2
+    bases = [G.to_affine(G.mul(G.one, rng.randrange(1, 1 << 64))) for _ in range(n)]
+    d_bases = torch.from_numpy(np.frombuffer(b"".join(o.g2_to_wire(b) for b in bases), dtype=np.uint8).copy()).cuda()
+    d_sc = torch.from_numpy(_scalars(n, 80 + n)).cuda()
+    want = bytes(dev.VarMsmWorkspace(n, 2).run(d_bases, d_sc).cpu().numpy())
+    assert want != bytes(384)
+    p = lambda t: int(t.data_ptr())
+    st = int(torch.cuda.current_stream().cuda_stream)
+    wb, tb = int(L.ozk_var_msm_head_workspace_bytes(n, 2)), int(L.ozk_var_msm_tail_bytes(n, 2))
+    ws, tail = (torch.empty(b, dtype=torch.uint8, device="cuda") for b in (wb, tb))
+    prep = dev.prepare_bases(d_bases, n, 2)
+    for prepared in (0, 1):
+        for mode in (0, 1):
+            out = torch.zeros(384, dtype=torch.uint8, device="cuda")
+            lib.check(L.ozk_var_msm_head_dev(p(prep if prepared else d_bases), prepared, p(d_sc), n, 2, p(ws), wb,
+                                             p(tail), tb, st, None))
+            lib.check(L.ozk_var_msm_tail_dev(n, 2, p(tail), tb, p(out), st, None, mode))
+            torch.cuda.synchronize()
+            assert bytes(out.cpu().numpy()) == want, (prepared, mode)
 
 
 @pytest.mark.parametrize("logn", [20, 21])
@@ -264,7 +293,7 @@ def test_device_clock_timing_agrees_with_hip_events():
 def test_cu_partitioned_and_split_schedules_give_the_same_bytes(split):
     """VarMsmPipeline3(tail_cus=32): tail streams on 32 compute units, the accumulate stream on the others
     (ozk_stream_create_cu_range); split_accum: level 1 and the rest of the accumulate stage on different streams
-    (ozk_var_msm_accum_part_dev).  Same bytes as the single-call path; the partitioned form refuses the null stream."""
+    (ozk_var_msm_accum_dev, part 1 | 2).  Same bytes as the single-call path; the partitioned form refuses the null stream."""
     import torch
     from octopuszk_amd import device as dev, lib
     L = lib.load()

@@ -63,19 +63,19 @@ off_hist = a256(ne * 64); off_total = a256(off_hist + NB * 4); off_sent = a256(o
 REC = 40
 for attempt in range(12):
     d_sorted.zero_(); d_sortws.zero_(); d_acc.fill_(fillv); d_tail.fill_(fillv)
-    ozk.check(L.ozk_var_msm_sort_dev(ptr(d_bases), ptr(d_scalars), n, 1, ptr(d_sorted), sb.value, ptr(d_sortws), swb.value, st))
+    ozk.check(L.ozk_var_msm_sort_dev(ptr(d_bases), 0, ptr(d_scalars), n, 1, ptr(d_sorted), sb.value, ptr(d_sortws), swb.value, st))
     torch.cuda.synchronize()
     total = int(d_sorted[off_total:off_total + 4].view(torch.int32)[0])
     hist_sort = d_sorted[off_hist:off_hist + NB * 4].view(torch.int32).cpu().numpy().copy()
     sbid0 = d_sorted[off_sent:off_sent + total * 8].view(torch.int32).cpu().numpy().astype(np.int64).reshape(-1, 2)[:, 1] & 0xffffffff
     sidx0 = d_sorted[off_sent:off_sent + total * 8].view(torch.int32).cpu().numpy().astype(np.int64).reshape(-1, 2)[:, 0] & 0xffffffff
-    ozk.check(L.ozk_var_msm_accum_dev(n, 1, ptr(d_sorted), sb.value, ptr(d_acc), ab.value, ptr(d_tail), tb, st))
+    ozk.check(L.ozk_var_msm_accum_dev(None, n, 1, ptr(d_sorted), sb.value, ptr(d_acc), ab.value, ptr(d_tail), tb, st, 0))
     torch.cuda.synchronize()
     recs = d_tail[:NB * REC * 4].view(torch.int32).cpu().numpy().astype(np.int64).reshape(NB, REC) & 0xffffffff
     hist_t = d_tail[NB * REC * 4:NB * REC * 4 + NB * 4].view(torch.int32).cpu().numpy().copy()
     hist_after = d_sorted[off_hist:off_hist + NB * 4].view(torch.int32).cpu().numpy().copy()
     sbid1 = d_sorted[off_sent:off_sent + total * 8].view(torch.int32).cpu().numpy().astype(np.int64).reshape(-1, 2)[:, 1] & 0xffffffff
-    ozk.check(L.ozk_var_msm_tail_dev(n, 1, ptr(d_tail), tb, ptr(d_out), st))
+    ozk.check(L.ozk_var_msm_tail_dev(n, 1, ptr(d_tail), tb, ptr(d_out), st, None, 1))
     torch.cuda.synchronize()
     ok = bytes(d_out.cpu().numpy()) == want
     print("attempt", attempt, "result ok:", ok, "| total", total, "| hist(sort)==model", bool((hist_sort == cntb).all()),

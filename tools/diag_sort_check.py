@@ -56,7 +56,7 @@ off_hist = a256(ne * 64); off_total = a256(off_hist + NB * 4); off_sent = a256(o
 want_total = int((exp_b >= 0).sum())
 for rep in range(int(os.environ.get("DIAG_REPS", "12"))):
     d_sorted.zero_(); d_sortws.zero_()
-    ozk.check(L.ozk_var_msm_sort_dev(ptr(d_bases), ptr(d_scalars), n, 1, ptr(d_sorted), sb.value, ptr(d_sortws), swb.value, st))
+    ozk.check(L.ozk_var_msm_sort_dev(ptr(d_bases), 0, ptr(d_scalars), n, 1, ptr(d_sorted), sb.value, ptr(d_sortws), swb.value, st))
     torch.cuda.synchronize()
     total = int(d_sorted[off_total:off_total + 4].view(torch.int32)[0])
     msgs = []

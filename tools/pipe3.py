@@ -28,15 +28,15 @@ def submit():
     k = cnt[0]; s = k % 2
     if k >= 2:
         S.wait_event(accum_done[s])          # sorted set s free again
-    ozk.check(L.ozk_var_msm_sort_dev(p(bases), p(d_sc), n, 1, p(sorted_[s]), sb.value, p(sort_ws), swb.value, ctypes.c_void_p(S.cuda_stream)))
+    ozk.check(L.ozk_var_msm_sort_dev(p(bases), 0, p(d_sc), n, 1, p(sorted_[s]), sb.value, p(sort_ws), swb.value, ctypes.c_void_p(S.cuda_stream)))
     sort_done[s].record(S)
     A.wait_event(sort_done[s])
     if k >= 2:
         A.wait_event(tail_done[s])           # tail buffer s free again
-    ozk.check(L.ozk_var_msm_accum_dev(n, 1, p(sorted_[s]), sb.value, p(accum_ws), awb.value, p(tails[s]), tb, ctypes.c_void_p(A.cuda_stream)))
+    ozk.check(L.ozk_var_msm_accum_dev(None, n, 1, p(sorted_[s]), sb.value, p(accum_ws), awb.value, p(tails[s]), tb, ctypes.c_void_p(A.cuda_stream), 0))
     accum_done[s].record(A)
     T.wait_event(accum_done[s])
-    ozk.check(L.ozk_var_msm_tail_dev(n, 1, p(tails[s]), tb, p(outs[s]), ctypes.c_void_p(T.cuda_stream)))
+    ozk.check(L.ozk_var_msm_tail_dev(n, 1, p(tails[s]), tb, p(outs[s]), ctypes.c_void_p(T.cuda_stream), None, 1))
     tail_done[s].record(T)
     cnt[0] += 1
 for _ in range(6): submit()
