@@ -54,7 +54,7 @@ OZK_HD bool bv_g1_wellformed(const u32* p) {
   return is_zero(sub(BvFq(sqr(Y)), rhs));
 }
 
-// (bv_scalar_mul, [e]q for an affine q: ec.cuh, where point_codec.cuh finds it too)
+// (scalar_mul, [e]q for an affine q: ec.cuh, where point_codec.cuh finds it too)
 
 // B: canonical coordinates, Z != 0, Y^2 = X^3 + b' Z^6 with b' = 3 / (9 + u), and [r]B = O (the order-r subgroup;
 // the twist's group has order r h with a large cofactor h, so the curve equation alone is not enough)
@@ -74,7 +74,7 @@ OZK_BIG bool bv_g2_wellformed(const u32* p) {
   q.x.c1 = canonical(x.c1);
   q.y.c0 = canonical(y.c0);
   q.y.c1 = canonical(y.c1);
-  return is_inf(bv_scalar_mul<G2Cfg>(q, BV_R_WORDS, 8));
+  return is_inf(scalar_mul<G2Cfg>(q, BV_R_WORDS, 8));
 }
 
 OZK_HD int bv_proof_wellformed(const u32* rec) {
@@ -89,7 +89,7 @@ OZK_HD void bv_g1_mul_affine(const u32* p, const u32* r, int words, BvFq& x, BvF
   Aff<G1Cfg::EA> q;
   q.x = canonical(BvFq(mul(X, zi2)));
   q.y = canonical(BvFq(mul(Y, BvFq(mul(zi2, zi)))));
-  const Jac<G1Cfg> t = bv_scalar_mul<G1Cfg>(q, r, words);
+  const Jac<G1Cfg> t = scalar_mul<G1Cfg>(q, r, words);
   if (is_inf(t)) {
     x = fe_zero<FqParams>();
     y = fe_one<FqParams>();

@@ -15,6 +15,7 @@
 // wire out (reference JNI output, VariableBaseMSM.cu:1655-1659): per Fq value 64 B LE,
 //          upper 32 B zero.
 #pragma once
+#include <stddef.h>
 #include "ec.cuh"
 #include "quad.cuh"
 
@@ -81,6 +82,36 @@ struct ElemTraits<Fe<P, B>> {
 #pragma unroll
     for (int i = 1; i < 8; i++) o |= p[i];
     return o == 0;
+  }
+};
+
+// ---- coordinate formats of a written point: the store of one coordinate (Fq, or Fq2 as c0 | c1) and FQ_WORDS,
+// the words one Fq value takes; the coordinates of a point lie CW / 8 * FQ_WORDS words apart
+struct WireIn {   // 8 words little-endian: the JNI input, and what the point kernels write for each other
+  static constexpr int FQ_WORDS = 8;
+  template <class E>
+  static OZK_HD void store(const E& e, u32* p) { ElemTraits<E>::to_wire(e, p); }
+};
+struct WireOut {  // 16 words little-endian, upper half zero: the variable-base return layout
+  static constexpr int FQ_WORDS = 16;
+  template <class E>
+  static OZK_HD void store(const E& e, u32* p) { ElemTraits<E>::to_wire_out(e, p); }
+};
+struct FixedBE {  // 8 zero words, then the value's words reversed and byte-swapped: the fixed-base return layout
+  static constexpr int FQ_WORDS = 16;   // (FixedBaseMSM.cu:740-748 swap_helper)
+  template <class P, int B>
+  static OZK_HD void store(const Fe<P, B>& e, u32* p) {
+    u32 w[8];
+    from_mont(e, w);
+#pragma unroll
+    for (int i = 0; i < 8; i++) p[i] = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) p[8 + i] = __builtin_bswap32(w[7 - i]);
+  }
+  template <class E2>
+  static OZK_HD void store(const E2& e, u32* p) {
+    store(e.c0, p);
+    store(e.c1, p + 16);
   }
 };
 
@@ -162,7 +193,122 @@ struct CurveIO {
     r.Z = ElemTraits<EZ>::from_wire(p + 2 * CW);
     return r;
   }
+  static OZK_HD Aff<EA> aff_infinity() {
+    Aff<EA> q;
+    q.x = EA(el_zero(q.x));
+    q.y = EA(el_zero(q.x));
+    return q;
+  }
+  // A wire-in point (X | Y | Z, any Z) as a canonical affine Montgomery point (equal points give equal words), read as
+  // k_convert_bases (msm_var.cuh) reads it: Z = 0, or a Z that reduces to zero such as Z = q, is O = (0, 0); Z = 1
+  // costs the two conversions; any other Z one inversion more.
+  static OZK_HD Aff<EA> aff_from_wire(const u32* p) {
+    using ET = ElemTraits<EA>;
+    Aff<EA> q = aff_infinity();
+    if (ET::wire_is_zero(p + 2 * CW)) return q;
+    const EA X = ET::from_wire(p), Y = ET::from_wire(p + CW);
+    if (ET::wire_is_one(p + 2 * CW)) {
+      q.x = EA(canonical(X));
+      q.y = EA(canonical(Y));
+      return q;
+    }
+    const EA Z = ET::from_wire(p + 2 * CW);
+    if (is_zero(Z)) return q;
+    const auto zi = inv(Z);
+    const auto zi2 = sqr(zi);
+    q.x = EA(canonical(mul(X, zi2)));
+    q.y = EA(canonical(mul(Y, mul(zi2, zi))));
+    return q;
+  }
+
+  // ---- writing a normalised point X | Y | Z in the format FMT: (x, y, 1), infinity as (0, 1, 0) (BNG1.java:163-172)
+  template <class FMT>
+  static OZK_HD void write_xyz(const EA& x, const EA& y, const EA& z, u32* out) {
+    constexpr int S = CW / 8 * FMT::FQ_WORDS;
+    FMT::store(x, out);
+    FMT::store(y, out + S);
+    FMT::store(z, out + 2 * S);
+  }
+  template <class FMT>
+  static OZK_HD void write_inf(u32* out) {
+    EA t;
+    write_xyz<FMT>(EA(el_zero(t)), EA(el_one(t)), EA(el_zero(t)), out);
+  }
+  template <class FMT>
+  static OZK_HD void write_aff(bool inf, const Aff<EA>& q, u32* out) {   // (the caller knows whether q is O)
+    if (inf) return write_inf<FMT>(out);
+    write_xyz<FMT>(q.x, q.y, EA(el_one(q.x)), out);
+  }
+  template <class FMT>
+  static OZK_HD void write_aff(const Aff<EA>& q, u32* out) { write_aff<FMT>(is_inf(q), q, out); }
+  // r (not O) as an affine point below 17/16 p, the inverse of its Z given
+  template <class ZI>
+  static OZK_HD Aff<EA> jac_to_aff(const Jac<CV>& r, const ZI& zi) {
+    const auto zi2 = sqr(zi);
+    Aff<EA> q;
+    q.x = EA(reduce_to<17>(mul(r.X, zi2)));
+    q.y = EA(reduce_to<17>(mul(r.Y, mul(zi2, zi))));
+    return q;
+  }
+  // (each coordinate is stored as soon as it is known: the order of the variable-base tail, k_finalize)
+  template <class FMT, class ZI>
+  static OZK_HD void write_jac(const Jac<CV>& r, const ZI& zi, bool negate, u32* out) {
+    constexpr int S = CW / 8 * FMT::FQ_WORDS;
+    const auto zi2 = sqr(zi);
+    FMT::store(EA(reduce_to<17>(mul(r.X, zi2))), out);
+    EA y = EA(reduce_to<17>(mul(r.Y, mul(zi2, zi))));
+    if (negate) y = EA(canonical(neg(y)));
+    FMT::store(y, out + S);
+    FMT::store(EA(el_one(r.X)), out + 2 * S);
+  }
+  template <class FMT>
+  static OZK_HD void write(const Jac<CV>& r, u32* out) {
+    if (is_inf(r)) return write_inf<FMT>(out);
+    write_jac<FMT>(r, inv(r.Z), false, out);
+  }
 };
+
+// Montgomery's trick over stored Jacobian records: lane t of `lanes` = ceil(n / BATCH) normalises up to BATCH of the
+// n records with one inversion and hands each to sink(index, is_infinity, affine point); infinity comes as (0, 0).
+// The lane's batch is INTERLEAVED — elements t, t + lanes, t + 2 lanes, ... — so that consecutive lanes touch
+// consecutive records (any grouping serves the trick; consecutive elements per lane made every access a 100-B record
+// at a 864-B stride).  k_fb_norm 216 -> 203 us at 2^20: the kernel is bound by its 2^17 safegcd inversions (45 % of
+// its instructions), not by these accesses.
+template <class CV, int BATCH, class Sink>
+OZK_HD void batch_normalise(const u32* jac, size_t n, size_t t, size_t lanes, Sink sink) {
+  using IO = CurveIO<CV>;
+  using EZ32 = decltype(reduce_to<32>(typename CV::EZ()));
+  auto at = [&](int k) { return (size_t)k * lanes + t; };
+  // prefix[k] = product of the non-zero Z_0..Z_k
+  EZ32 prefix[BATCH];
+  EZ32 run = EZ32(el_one(prefix[0]));
+#pragma unroll
+  for (int k = 0; k < BATCH; k++) {
+    if (at(k) < n) {
+      const auto Z = reduce_to<32>(ElemTraits<typename CV::EZ>::load_raw(jac + at(k) * IO::JAC_WORDS + 2 * IO::RW));
+      if (!is_zero(Z)) run = EZ32(mul(run, Z));
+    }
+    prefix[k] = run;
+  }
+  EZ32 invrun = EZ32(inv(run));
+#pragma unroll
+  for (int k = BATCH - 1; k >= 0; k--) {
+    if (at(k) < n) {
+      const Jac<CV> p = IO::load_jac(jac + at(k) * IO::JAC_WORDS);
+      const auto Z = reduce_to<32>(p.Z);
+      const bool inf = is_zero(Z);
+      Aff<typename CV::EA> q = IO::aff_infinity();
+      if (!inf) {
+        // 1/Z_k = invrun * prefix[k-1];  invrun <- invrun * Z_k
+        EZ32 zi = invrun;
+        if (k > 0) zi = EZ32(mul(invrun, prefix[k - 1]));
+        invrun = EZ32(mul(invrun, Z));
+        q = IO::jac_to_aff(p, zi);
+      }
+      sink(at(k), inf, q);
+    }
+  }
+}
 
 #if defined(__HIPCC__)
 // Workgroup barrier with an EXPLICIT wait for this wave's outstanding LDS and global operations.

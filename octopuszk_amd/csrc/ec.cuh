@@ -385,7 +385,7 @@ OZK_HD Jac<CV> jac_neg(const Jac<CV>& p) {
 // [e]q for an affine q, e given as `words` little-endian words: double-and-add from the top bit (jac_madd takes the
 // P == Q and P == -Q cases, so any point and any scalar are exact)
 template <class CV>
-OZK_HD Jac<CV> bv_scalar_mul(const Aff<typename CV::EA>& q, const u32* e, int words) {
+OZK_HD Jac<CV> scalar_mul(const Aff<typename CV::EA>& q, const u32* e, int words) {
   Jac<CV> acc = jac_infinity<CV>();
   for (int i = 32 * words - 1; i >= 0; i--) {
     acc = jac_dbl<CV>(acc);

@@ -23,75 +23,31 @@
 
 namespace ozk {
 
-template <class CV>
-constexpr int point_words() { return 3 * CurveIO<CV>::CW; }
-
 // ---------------------------------------------------------------------------------------------- points
-template <class CV>
-OZK_HD void ec_write_inf(u32* out) {
-  using EA = typename CV::EA;
-  using ET = ElemTraits<EA>;
-  constexpr int CW = CurveIO<CV>::CW;
-  EA tag;
-  tag = EA(el_zero(tag));
-  ET::to_wire(EA(el_zero(tag)), out);
-  ET::to_wire(EA(el_one(tag)), out + CW);
-  ET::to_wire(EA(el_zero(tag)), out + 2 * CW);
-}
-template <class CV>
-OZK_HD void ec_write_aff(const Aff<typename CV::EA>& q, u32* out) {
-  using EA = typename CV::EA;
-  using ET = ElemTraits<EA>;
-  constexpr int CW = CurveIO<CV>::CW;
-  if (is_inf(q)) return ec_write_inf<CV>(out);
-  ET::to_wire(q.x, out);
-  ET::to_wire(q.y, out + CW);
-  ET::to_wire(EA(el_one(q.x)), out + 2 * CW);
-}
-// r (not O) with the inverse of its Z given, optionally negated
-template <class CV, class ZI>
-OZK_HD void ec_write_jac(const Jac<CV>& r, const ZI& zi, bool negate, u32* out) {
-  using EA = typename CV::EA;
-  using ET = ElemTraits<EA>;
-  constexpr int CW = CurveIO<CV>::CW;
-  const auto zi2 = sqr(zi);
-  const EA x = EA(reduce_to<17>(mul(r.X, zi2)));
-  EA y = EA(reduce_to<17>(mul(r.Y, mul(zi2, zi))));
-  if (negate) y = EA(canonical(neg(y)));
-  ET::to_wire(x, out);
-  ET::to_wire(y, out + CW);
-  ET::to_wire(EA(el_one(x)), out + 2 * CW);
-}
-template <class CV>
-OZK_HD void ec_write(const Jac<CV>& r, u32* out) {
-  if (is_inf(r)) return ec_write_inf<CV>(out);
-  ec_write_jac<CV>(r, inv(r.Z), false, out);
-}
 // a and -b (negate_b) or b, normalised with one inversion between them
 template <class CV>
 OZK_HD void ec_write2(const Jac<CV>& a, const Jac<CV>& b, bool negate_b, u32* oa, u32* ob) {
+  using IO = CurveIO<CV>;
   const bool ia = is_inf(a), ib = is_inf(b);
   if (ia || ib) {
-    ec_write<CV>(a, oa);
-    if (ib) return ec_write_inf<CV>(ob);
-    return ec_write_jac<CV>(b, inv(b.Z), negate_b, ob);
+    IO::template write<WireIn>(a, oa);
+    if (ib) return IO::template write_inf<WireIn>(ob);
+    return IO::template write_jac<WireIn>(b, inv(b.Z), negate_b, ob);
   }
   const auto za = reduce_to<32>(a.Z), zb = reduce_to<32>(b.Z);
   const auto ti = inv(mul(za, zb));
-  ec_write_jac<CV>(a, mul(ti, zb), false, oa);
-  ec_write_jac<CV>(b, mul(ti, za), negate_b, ob);
+  IO::template write_jac<WireIn>(a, mul(ti, zb), false, oa);
+  IO::template write_jac<WireIn>(b, mul(ti, za), negate_b, ob);
 }
 template <class CV>
-OZK_HD Aff<typename CV::EA> ec_to_affine(const Jac<CV>& r) {
+OZK_HD Aff<typename CV::EA> ec_to_affine(const Jac<CV>& r) {   // canonical; O as (0, 0)
+  using IO = CurveIO<CV>;
   using EA = typename CV::EA;
-  Aff<EA> q;
-  q.x = EA(el_zero(q.x));
-  q.y = EA(el_zero(q.x));
+  Aff<EA> q = IO::aff_infinity();
   if (is_inf(r)) return q;
-  const auto zi = inv(r.Z);
-  const auto zi2 = sqr(zi);
-  q.x = EA(canonical(mul(r.X, zi2)));
-  q.y = EA(canonical(mul(r.Y, mul(zi2, zi))));
+  q = IO::jac_to_aff(r, inv(r.Z));
+  q.x = EA(canonical(q.x));
+  q.y = EA(canonical(q.y));
   return q;
 }
 template <class EA>
@@ -105,10 +61,11 @@ OZK_HD Aff<EA> ec_neg(const Aff<EA>& q) {   // -O = O: canonical(-0) = 0
 // out = a + b or a - b
 template <class CV>
 OZK_HD void points_add_one(const u32* pa, const u32* pb, bool negate_b, u32* out) {
-  const auto a = scale_load<CV>(pa);
-  auto b = scale_load<CV>(pb);
+  using IO = CurveIO<CV>;
+  const auto a = IO::aff_from_wire(pa);
+  auto b = IO::aff_from_wire(pb);
   if (negate_b) b = ec_neg(b);
-  ec_write<CV>(jac_madd<CV>(from_affine<CV>(a), b), out);
+  IO::template write<WireIn>(jac_madd<CV>(from_affine<CV>(a), b), out);
 }
 
 // ---------------------------------------------------------------------------------------------- twiddles
@@ -138,8 +95,8 @@ OZK_HD void ecfft_schedule(const EcFftTwiddle& c, u32 i, bool glv, ScaleSchedule
 template <class CV, bool GLV>
 OZK_HD void ecfft_butterfly(const u32* pa, const u32* pb, const ScaleSchedule* sa, const ScaleSchedule* sb, u32* oa,
                             u32* ob) {
-  auto a = scale_load<CV>(pa);
-  const auto b = scale_load<CV>(pb);
+  auto a = CurveIO<CV>::aff_from_wire(pa);
+  const auto b = CurveIO<CV>::aff_from_wire(pb);
   if (sa) a = ec_to_affine<CV>(scale_ladder<CV, GLV>(a, *sa));
   const Jac<CV> v = sb ? scale_ladder<CV, GLV>(b, *sb) : from_affine<CV>(b);
   const Jac<CV> sum = jac_madd<CV>(v, a);
@@ -154,10 +111,10 @@ OZK_HD bool words_are(const u32* w, const u32 (&v)[8]) {
   return d == 0;
 }
 // acc + [c] P: c null or 1 adds P, c = r - 1 subtracts it, c = 0 (and every multiple of r below 2^256) adds nothing;
-// any other c runs a per-lane double-and-add over its bits, exact on the whole curve
+// any other c runs a per-lane double-and-add over its bits (scalar_mul), exact on the whole curve
 template <class CV>
 OZK_HD Jac<CV> sparse_term(const Jac<CV>& acc, const u32* p, const u32* c) {
-  auto q = scale_load<CV>(p);
+  auto q = CurveIO<CV>::aff_from_wire(p);
   if (c) {
     u32 k[8];
     for (int i = 0; i < 8; i++) k[i] = c[i];
@@ -169,17 +126,7 @@ OZK_HD Jac<CV> sparse_term(const Jac<CV>& acc, const u32* p, const u32* c) {
     if (words_are(k, m1)) {
       q = ec_neg(q);
     } else if (!words_are(k, one)) {
-      Jac<CV> v = jac_infinity<CV>();
-      if (!is_inf(q)) {
-        for (int wi = 7; wi >= 0; wi--) {
-          const u32 word = k[wi];
-#pragma unroll 1
-          for (int bit = 31; bit >= 0; bit--) {
-            v = jac_dbl<CV>(v);
-            if ((word >> bit) & 1) v = jac_madd<CV>(v, q);
-          }
-        }
-      }
+      const Jac<CV> v = is_inf(q) ? jac_infinity<CV>() : scalar_mul<CV>(q, k, 8);
       q = ec_to_affine<CV>(v);
     }
   }
@@ -203,11 +150,12 @@ __global__ __launch_bounds__(64) void k_ecfft_recode(EcFftTwiddle c, int n, Scal
 template <int TYPE>
 __global__ __launch_bounds__(64) void k_ecfft_permute(const u32* __restrict__ in, int n, int logn, u32* __restrict__ out) {
   using CV = typename EcType<TYPE>::CV;
-  constexpr int PW = point_words<CV>();
+  using IO = CurveIO<CV>;
+  constexpr int PW = IO::WIRE_JAC_WORDS;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const u32 j = logn ? __brev((u32)i) >> (32 - logn) : 0u;
-  ec_write_aff<CV>(scale_load<CV>(in + (size_t)PW * i), out + (size_t)PW * j);
+  IO::template write_aff<WireIn>(IO::aff_from_wire(in + (size_t)PW * i), out + (size_t)PW * j);
 }
 
 // one pass of half-size h = 1 << logh over n = 1 << logn points, in place.  tab[j * stride]: the schedule of offset
@@ -216,7 +164,7 @@ template <int TYPE>
 __global__ __launch_bounds__(64) void k_ecfft_pass(u32* data, int logn, int logh, const ScaleSchedule* tab, int stride,
                                                    int skip0, const ScaleSchedule* sa) {
   using CV = typename EcType<TYPE>::CV;
-  constexpr int PW = point_words<CV>();
+  constexpr int PW = CurveIO<CV>::WIRE_JAC_WORDS;
   const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (1u << (logn - 1))) return;
   const int logb = logn - 1 - logh;
@@ -230,7 +178,7 @@ __global__ __launch_bounds__(64) void k_ecfft_pass(u32* data, int logn, int logh
 template <int TYPE>
 __global__ __launch_bounds__(64) void k_points_add(const u32* a, const u32* b, int n, int negate_b, u32* out) {
   using CV = typename EcType<TYPE>::CV;
-  constexpr int PW = point_words<CV>();
+  constexpr int PW = CurveIO<CV>::WIRE_JAC_WORDS;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   points_add_one<CV>(a + (size_t)PW * i, b + (size_t)PW * i, negate_b != 0, out + (size_t)PW * i);
@@ -242,7 +190,8 @@ __global__ __launch_bounds__(64) void k_sparse_points(const u32* __restrict__ pt
                                                       const u32* __restrict__ coeff, const u32* __restrict__ points,
                                                       int rows, u32* __restrict__ out) {
   using CV = typename EcType<TYPE>::CV;
-  constexpr int PW = point_words<CV>();
+  using IO = CurveIO<CV>;
+  constexpr int PW = IO::WIRE_JAC_WORDS;
   const int row = blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= rows) return;
   const u32 b = ptr[row], e = ptr[row + 1];
@@ -250,7 +199,7 @@ __global__ __launch_bounds__(64) void k_sparse_points(const u32* __restrict__ pt
   Jac<CV> acc = jac_infinity<CV>();
   for (u32 t = b; t < e; t++)
     acc = sparse_term<CV>(acc, points + (size_t)PW * idx[t], coeff ? coeff + (size_t)8 * t : nullptr);
-  ec_write<CV>(acc, out + (size_t)PW * row);
+  IO::template write<WireIn>(acc, out + (size_t)PW * row);
 }
 // lane l of long row lr sums the terms b + l, b + l + 4096, ... into part[lr * 4096 + l]
 template <int TYPE>
@@ -258,7 +207,8 @@ __global__ __launch_bounds__(64) void k_sparse_points_long(const u32* __restrict
                                                            const u32* __restrict__ coeff, const u32* __restrict__ points,
                                                            const u32* __restrict__ long_rows, u32* __restrict__ part) {
   using CV = typename EcType<TYPE>::CV;
-  constexpr int PW = point_words<CV>();
+  using IO = CurveIO<CV>;
+  constexpr int PW = IO::WIRE_JAC_WORDS;
   const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
   const u32 lr = g / EC_LONG_LANES, l = g % EC_LONG_LANES;
   const u32 row = long_rows[lr];
@@ -266,19 +216,20 @@ __global__ __launch_bounds__(64) void k_sparse_points_long(const u32* __restrict
   Jac<CV> acc = jac_infinity<CV>();
   for (u32 t = b + l; t < e; t += EC_LONG_LANES)
     acc = sparse_term<CV>(acc, points + (size_t)PW * idx[t], coeff ? coeff + (size_t)8 * t : nullptr);
-  ec_write<CV>(acc, part + (size_t)PW * g);
+  IO::template write<WireIn>(acc, part + (size_t)PW * g);
 }
 // out[dest ? dest[g] : g] = the sum of in[64 g .. 64 g + 64), g < groups
 template <int TYPE>
 __global__ __launch_bounds__(64) void k_points_sum64(const u32* __restrict__ in, int groups, const u32* __restrict__ dest,
                                                      u32* __restrict__ out) {
   using CV = typename EcType<TYPE>::CV;
-  constexpr int PW = point_words<CV>();
+  using IO = CurveIO<CV>;
+  constexpr int PW = IO::WIRE_JAC_WORDS;
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= groups) return;
   Jac<CV> acc = jac_infinity<CV>();
-  for (int i = 0; i < 64; i++) acc = jac_madd<CV>(acc, scale_load<CV>(in + (size_t)PW * (64 * (size_t)g + i)));
-  ec_write<CV>(acc, out + (size_t)PW * (dest ? dest[g] : (u32)g));
+  for (int i = 0; i < 64; i++) acc = jac_madd<CV>(acc, IO::aff_from_wire(in + (size_t)PW * (64 * (size_t)g + i)));
+  IO::template write<WireIn>(acc, out + (size_t)PW * (dest ? dest[g] : (u32)g));
 }
 #endif
 

@@ -142,98 +142,29 @@ __global__ void __launch_bounds__(256) k_fb_main_glv(const u32* __restrict__ sca
   IO::store_jac(jac_add(part[0], part[1]), jac_out + (size_t)i * IO::JAC_WORDS);
 }
 
-// 64-byte big-endian store of one Fq value: 8 zero words, then the value's words reversed
-// and byte-swapped (FixedBaseMSM.cu:740-748 swap_helper layout)
-template <class P, int B>
-__device__ __forceinline__ void store_be64(const Fe<P, B>& e, u32* p) {
-  u32 w[8];
-  from_mont(e, w);
-#pragma unroll
-  for (int i = 0; i < 8; i++) p[i] = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) p[8 + i] = __builtin_bswap32(w[7 - i]);
-}
-template <int B>
-__device__ __forceinline__ void store_be_coord(const Fe<FqParams, B>& e, u32* p) { store_be64(e, p); }
-template <int B>
-__device__ __forceinline__ void store_be_coord(const Fe2<B>& e, u32* p) {
-  store_be64(e.c0, p);
-  store_be64(e.c1, p + 16);
-}
-
 constexpr int FB_BATCH = 8;
-// lane t normalises FB_BATCH results: prefix products of Z, one inversion, back-substitution.
+// lane t normalises FB_BATCH results with one inversion (batch_normalise, curve.cuh).
 // out element i is at out + i*out_stride_words (+ coordinate offsets).
 // compact = 1: X|Y|Z as 32-byte little-endian values (the wire-IN format of the variable-base natives,
 // VariableBaseMSM.java:221-228), so that keys go from the setup to the prover without being reformatted
 // (SURVEY.md §8f N4); compact = 0: the reference's 64-byte big-endian coordinates.
+// Infinity is (0, 1, 0), BNG1.java:163-166.  (G1: eight waves per SIMD asked for, which holds the kernel at 64 VGPRs.)
 template <class CV>
-__global__ void __launch_bounds__(256) k_fb_norm(const u32* __restrict__ jac, int n, u32* __restrict__ out,
+__global__ void __launch_bounds__(256, CV::WIDE_INPUTS ? 8 : 1) k_fb_norm(const u32* __restrict__ jac, int n, u32* __restrict__ out,
                                                  int out_stride_words, int compact) {
   using IO = CurveIO<CV>;
-  using EA = typename CV::EA;
-  using ET = ElemTraits<EA>;
-  using EZ32 = decltype(reduce_to<32>(typename CV::EZ()));
-  constexpr int OW = 2 * ET::WORDS;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int lanes = (n + FB_BATCH - 1) / FB_BATCH;
   if (t >= lanes) return;
-  // the lane's batch is INTERLEAVED — elements t, t + lanes, t + 2 lanes, ... — so that consecutive lanes touch
-  // consecutive records (any grouping serves Montgomery's trick; consecutive elements per lane made every access
-  // a 100-B record at a 864-B stride).  k_fb_norm 216 -> 203 us at 2^20: the kernel is bound by its 2^17 safegcd
-  // inversions (45 % of its instructions), not by these accesses.
-  auto at = [&](int k) { return (size_t)k * (size_t)lanes + (size_t)t; };
-  // prefix[k] = product of the non-zero Z_0..Z_k
-  EZ32 prefix[FB_BATCH];
-  EZ32 run = EZ32(el_one(prefix[0]));
-#pragma unroll
-  for (int k = 0; k < FB_BATCH; k++) {
-    if (at(k) < (size_t)n) {
-      const auto Z = reduce_to<32>(ElemTraits<typename CV::EZ>::load_raw(jac + at(k) * IO::JAC_WORDS + 2 * IO::RW));
-      if (!is_zero(Z)) run = EZ32(mul(run, Z));
-    }
-    prefix[k] = run;
-  }
-  EZ32 invrun = EZ32(inv(run));
-#pragma unroll
-  for (int k = FB_BATCH - 1; k >= 0; k--) {
-    if (at(k) < (size_t)n) {
-      const Jac<CV> p = IO::load_jac(jac + at(k) * IO::JAC_WORDS);
-      u32* o = out + at(k) * out_stride_words;
-      const auto Z = reduce_to<32>(p.Z);
-      if (is_zero(Z)) {  // (0, 1, 0), BNG1.java:163-166
-        if (compact) {
-          ET::to_wire(EA(el_zero(p.X)), o);
-          ET::to_wire(EA(el_one(p.X)), o + ET::WORDS);
-          ET::to_wire(EA(el_zero(p.X)), o + 2 * ET::WORDS);
-        } else {
-          store_be_coord(EA(el_zero(p.X)), o);
-          store_be_coord(EA(el_one(p.X)), o + OW);
-          store_be_coord(EA(el_zero(p.X)), o + 2 * OW);
-        }
-      } else {
-        // 1/Z_k = invrun * prefix[k-1];  invrun <- invrun * Z_k
-        EZ32 zi = invrun;
-        if (k > 0) zi = EZ32(mul(invrun, prefix[k - 1]));
-        invrun = EZ32(mul(invrun, Z));
-        const auto zi2 = sqr(zi);
-        const EA ax = EA(reduce_to<17>(mul(p.X, zi2))), ay = EA(reduce_to<17>(mul(p.Y, mul(zi2, zi))));
-        if (compact) {
-          ET::to_wire(ax, o);
-          ET::to_wire(ay, o + ET::WORDS);
-          ET::to_wire(EA(el_one(p.X)), o + 2 * ET::WORDS);
-        } else {
-          store_be_coord(ax, o);
-          store_be_coord(ay, o + OW);
-          store_be_coord(EA(el_one(p.X)), o + 2 * OW);
-        }
-      }
-    }
-  }
+  batch_normalise<CV, FB_BATCH>(jac, n, t, lanes, [&](size_t i, bool inf, const Aff<typename CV::EA>& q) {
+    u32* o = out + i * out_stride_words;
+    if (compact) IO::template write_aff<WireIn>(inf, q, o);
+    else IO::template write_aff<FixedBE>(inf, q, o);
+  });
 }
 
-// The GLV gather-add over an AFFINE table: lane t normalises FB_BATCH consecutive table entries with one
-// shared inversion (k_fb_table_affine), after which every gather is a mixed XYZZ addition (madd-2008-s,
+// The GLV gather-add over an AFFINE table: lane t normalises FB_BATCH table entries with one shared inversion
+// (k_fb_table_affine), after which every gather is a mixed XYZZ addition (madd-2008-s,
 // 8M + 2S) instead of a full Jacobian one (11M + 5S); 16 gathers per scalar against ~16 multiplications
 // per table entry for the normalisation.  Infinity entries (entry 0 of every window; every entry when the
 // base is infinity) become the (0, 0) marker.
@@ -242,50 +173,16 @@ __global__ void __launch_bounds__(256) k_fb_table_affine(const u32* __restrict__
                                                          u32* __restrict__ aff_phi) {
   using IO = CurveIO<CV>;
   using EA = typename CV::EA;
-  using EZ32 = decltype(reduce_to<32>(typename CV::EZ()));
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int lanes = (n + FB_BATCH - 1) / FB_BATCH;
   if (t >= lanes) return;
-  // the lane's batch is INTERLEAVED — elements t, t + lanes, t + 2 lanes, ... — so that consecutive lanes touch
-  // consecutive records (any grouping serves Montgomery's trick; consecutive elements per lane made every access
-  // a 100-B record at a 864-B stride).  k_fb_norm 216 -> 203 us at 2^20: the kernel is bound by its 2^17 safegcd
-  // inversions (45 % of its instructions), not by these accesses.
-  auto at = [&](int k) { return (size_t)k * (size_t)lanes + (size_t)t; };
-  EZ32 prefix[FB_BATCH];
-  EZ32 run = EZ32(el_one(prefix[0]));
-#pragma unroll
-  for (int k = 0; k < FB_BATCH; k++) {
-    if (at(k) < (size_t)n) {
-      const auto Z = reduce_to<32>(ElemTraits<typename CV::EZ>::load_raw(jac + at(k) * IO::JAC_WORDS + 2 * IO::RW));
-      if (!is_zero(Z)) run = EZ32(mul(run, Z));
-    }
-    prefix[k] = run;
-  }
-  EZ32 invrun = EZ32(inv(run));
-#pragma unroll
-  for (int k = FB_BATCH - 1; k >= 0; k--) {
-    if (at(k) < (size_t)n) {
-      const Jac<CV> p = IO::load_jac(jac + at(k) * IO::JAC_WORDS);
-      const auto Z = reduce_to<32>(p.Z);
-      Aff<EA> q;
-      if (is_zero(Z)) {
-        q.x = EA(el_zero(p.X));
-        q.y = EA(el_zero(p.X));
-      } else {
-        EZ32 zi = invrun;
-        if (k > 0) zi = EZ32(mul(invrun, prefix[k - 1]));
-        invrun = EZ32(mul(invrun, Z));
-        const auto zi2 = sqr(zi);
-        q.x = EA(reduce_to<17>(mul(p.X, zi2)));
-        q.y = EA(reduce_to<17>(mul(p.Y, mul(zi2, zi))));
-      }
-      IO::store_aff(q, aff + at(k) * IO::AFF_WORDS);
-      // the same entry under the endomorphism, phi(x, y) = (beta x, y): the second half scalar gathers from this
-      // copy, so both halves add into ONE accumulator (k_fb_main_glv_affine); (0, 0) stays (0, 0)
-      q.x = EA(reduce_to<17>(scale(q.x, glv_beta_fixed<CV>())));
-      IO::store_aff(q, aff_phi + at(k) * IO::AFF_WORDS);
-    }
-  }
+  batch_normalise<CV, FB_BATCH>(jac, n, t, lanes, [&](size_t i, bool, Aff<EA> q) {
+    IO::store_aff(q, aff + i * IO::AFF_WORDS);
+    // the same entry under the endomorphism, phi(x, y) = (beta x, y): the second half scalar gathers from this
+    // copy, so both halves add into ONE accumulator (k_fb_main_glv_affine); (0, 0) stays (0, 0)
+    q.x = EA(reduce_to<17>(scale(q.x, glv_beta_fixed<CV>())));
+    IO::store_aff(q, aff_phi + i * IO::AFF_WORDS);
+  });
 }
 
 // s B = s2 (s1 s2 (sum_w T[w][d1_w]) + sum_w T_phi[w][d2_w]) with s1, s2 = +-1 the signs of the two half scalars: ONE
@@ -351,7 +248,7 @@ __global__ void __launch_bounds__(256) k_field_mul(const u32* __restrict__ in, i
   if (i >= n) return;
   const auto b = ET::from_wire(in + (size_t)n * 8);
   const auto x = ET::from_wire(in + (size_t)i * 8);
-  store_be64(mul(x, b), out + (size_t)i * 16);
+  FixedBE::store(mul(x, b), out + (size_t)i * 16);
 }
 
 struct FbLayout {

@@ -12,12 +12,12 @@
 // Jacobian scratch stays small:
 //   k_mm_chain    D[b][j] = 2^b P_j, one lane per base                        (the serial item: ~128 doublings)
 //   k_mm_level k  entry 2^k + i = entry i + D[w*ws + k], all bases, windows and i in parallel
-//   k_mm_affine   Jacobian -> affine, FB_BATCH entries per shared inversion
+//   k_mm_affine   Jacobian -> affine, MM_BATCH entries per shared inversion
 // Evaluation:
 //   k_mm_eval     T = 2^t lanes per output, lane = (half, slice of the bases): recode in registers, gather,
 //                 xyzz_madd_lazy; phi on the half-1 lanes' sums; shuffle tree over the lanes of one output
 //   k_mm_parts    only when an output spans several waves (T > 64): one wave sums its partial records
-//   k_mm_norm     affine normalisation, FB_BATCH outputs per shared inversion, 192-byte wire-out records
+//   k_mm_norm     affine normalisation, MM_BATCH outputs per shared inversion, 192-byte wire-out records
 #include "msm_var.cuh"   // RunAcc (XYZZ accumulator), shfl_down_jac, glv_beta
 #include "msm_multi.cuh"
 #include "ozk_common.h"
@@ -59,43 +59,12 @@ __global__ void __launch_bounds__(256) k_mm_level(u32* __restrict__ jt, const u3
 
 // lane t normalises entries t, t + lanes, ... (interleaved, as k_fb_table_affine); infinity -> (0, 0)
 __global__ void __launch_bounds__(256) k_mm_affine(const u32* __restrict__ jac, size_t n, u32* __restrict__ aff) {
-  using EA = MmCV::EA;
-  using EZ32 = decltype(reduce_to<32>(MmCV::EZ()));
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t lanes = (n + MM_BATCH - 1) / MM_BATCH;
   if (t >= lanes) return;
-  auto at = [&](int k) { return (size_t)k * lanes + t; };
-  EZ32 prefix[MM_BATCH];
-  EZ32 run = EZ32(el_one(prefix[0]));
-#pragma unroll
-  for (int k = 0; k < MM_BATCH; k++) {
-    if (at(k) < n) {
-      const auto Z = reduce_to<32>(ElemTraits<MmCV::EZ>::load_raw(jac + at(k) * MmIO::JAC_WORDS + 2 * MmIO::RW));
-      if (!is_zero(Z)) run = EZ32(mul(run, Z));
-    }
-    prefix[k] = run;
-  }
-  EZ32 invrun = EZ32(inv(run));
-#pragma unroll
-  for (int k = MM_BATCH - 1; k >= 0; k--) {
-    if (at(k) < n) {
-      const Jac<MmCV> p = MmIO::load_jac(jac + at(k) * MmIO::JAC_WORDS);
-      const auto Z = reduce_to<32>(p.Z);
-      Aff<EA> q;
-      if (is_zero(Z)) {
-        q.x = EA(el_zero(p.X));
-        q.y = EA(el_zero(p.X));
-      } else {
-        EZ32 zi = invrun;
-        if (k > 0) zi = EZ32(mul(invrun, prefix[k - 1]));
-        invrun = EZ32(mul(invrun, Z));
-        const auto zi2 = sqr(zi);
-        q.x = EA(reduce_to<17>(mul(p.X, zi2)));
-        q.y = EA(reduce_to<17>(mul(p.Y, mul(zi2, zi))));
-      }
-      MmIO::store_aff(q, aff + at(k) * MmIO::AFF_WORDS);
-    }
-  }
+  batch_normalise<MmCV, MM_BATCH>(jac, n, t, lanes, [&](size_t i, bool, const Aff<MmCV::EA>& q) {
+    MmIO::store_aff(q, aff + i * MmIO::AFF_WORDS);
+  });
 }
 
 __device__ __forceinline__ Aff<MmCV::EA> mm_load_record(const u32* p) {
@@ -190,46 +159,12 @@ __global__ void __launch_bounds__(64) k_mm_parts(const u32* __restrict__ parts, 
 // k Jacobian sums -> wire-out records (64-byte little-endian coordinates, Z = 1; infinity (0, 1, 0)), as
 // write_normalised (msm_var.cuh) with the inversion shared by MM_BATCH outputs
 __global__ void __launch_bounds__(256) k_mm_norm(const u32* __restrict__ jac, int n, u32* __restrict__ out) {
-  using EA = MmCV::EA;
-  using ET = ElemTraits<EA>;
-  using EZ32 = decltype(reduce_to<32>(MmCV::EZ()));
-  constexpr int OW = 2 * ET::WORDS;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int lanes = (n + MM_BATCH - 1) / MM_BATCH;
   if (t >= lanes) return;
-  auto at = [&](int k) { return (size_t)k * (size_t)lanes + (size_t)t; };
-  EZ32 prefix[MM_BATCH];
-  EZ32 run = EZ32(el_one(prefix[0]));
-#pragma unroll
-  for (int k = 0; k < MM_BATCH; k++) {
-    if (at(k) < (size_t)n) {
-      const auto Z = reduce_to<32>(ElemTraits<MmCV::EZ>::load_raw(jac + at(k) * MmIO::JAC_WORDS + 2 * MmIO::RW));
-      if (!is_zero(Z)) run = EZ32(mul(run, Z));
-    }
-    prefix[k] = run;
-  }
-  EZ32 invrun = EZ32(inv(run));
-#pragma unroll
-  for (int k = MM_BATCH - 1; k >= 0; k--) {
-    if (at(k) < (size_t)n) {
-      const Jac<MmCV> p = MmIO::load_jac(jac + at(k) * MmIO::JAC_WORDS);
-      u32* o = out + at(k) * (3 * OW);
-      const auto Z = reduce_to<32>(p.Z);
-      if (is_zero(Z)) {
-        ET::to_wire_out(EA(el_zero(p.X)), o);
-        ET::to_wire_out(EA(el_one(p.X)), o + OW);
-        ET::to_wire_out(EA(el_zero(p.X)), o + 2 * OW);
-      } else {
-        EZ32 zi = invrun;
-        if (k > 0) zi = EZ32(mul(invrun, prefix[k - 1]));
-        invrun = EZ32(mul(invrun, Z));
-        const auto zi2 = sqr(zi);
-        ET::to_wire_out(EA(reduce_to<17>(mul(p.X, zi2))), o);
-        ET::to_wire_out(EA(reduce_to<17>(mul(p.Y, mul(zi2, zi)))), o + OW);
-        ET::to_wire_out(EA(el_one(p.X)), o + 2 * OW);
-      }
-    }
-  }
+  batch_normalise<MmCV, MM_BATCH>(jac, n, t, lanes, [&](size_t i, bool inf, const Aff<MmCV::EA>& q) {
+    MmIO::write_aff<WireOut>(inf, q, out + i * (3 * WireOut::FQ_WORDS));
+  });
 }
 
 // ---- host side ---------------------------------------------------------------------------------

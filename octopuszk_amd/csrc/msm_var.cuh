@@ -101,7 +101,9 @@ constexpr u32 SIDX_NEG = 0x80000000u;
 #if defined(__HIPCC__)
 
 // ------------------------------------------------------------------ convert
-// One lane per base.  Z == 1 (the prover's normal case: keys produced by this library
+// One lane per base, reading as CurveIO::aff_from_wire (curve.cuh) reads: the body stays written out here because
+// the shared function, inlined, compiles to other instructions and this kernel runs inside every timed MSM.
+// Z == 1 (the prover's normal case: keys produced by this library
 // are affine) costs 2 Montgomery conversions; Z == 0 -> infinity marker; any other Z is
 // normalised with a per-lane Fermat inversion (correct for reference-produced
 // Jacobian keys, slower).
@@ -1428,20 +1430,7 @@ __global__ void __launch_bounds__(256) k_bucket_combine(SliceBuckets t, int K, u
 // 32 B zero (VariableBaseMSM.cu:1655-1659); infinity -> (0, 1, 0) (BNG1.java:163-172).
 template <class CV>
 __device__ __forceinline__ void write_normalised_inline(const Jac<CV>& r, u32* out) {
-  using EA = typename CV::EA;
-  using ET = ElemTraits<EA>;
-  constexpr int OW = 2 * ET::WORDS;  // wire-out words per coordinate
-  if (is_inf(r)) {
-    ET::to_wire_out(EA(el_zero(r.X)), out);
-    ET::to_wire_out(EA(el_one(r.X)), out + OW);
-    ET::to_wire_out(EA(el_zero(r.X)), out + 2 * OW);
-  } else {
-    const auto zi = inv(r.Z);
-    const auto zi2 = sqr(zi);
-    ET::to_wire_out(EA(reduce_to<17>(mul(r.X, zi2))), out);
-    ET::to_wire_out(EA(reduce_to<17>(mul(r.Y, mul(zi2, zi)))), out + OW);
-    ET::to_wire_out(EA(el_one(r.X)), out + 2 * OW);
-  }
+  CurveIO<CV>::template write<WireOut>(r, out);
 }
 // (the out-of-line form the existing kernels call; k_groth16_combine inlines the body so that it needs no call stack)
 template <class CV>
@@ -1605,12 +1594,7 @@ __global__ void __launch_bounds__(256) k_gen_bases(u64 seed, int n, const u32* _
     r = jac_dbl(r);
     if ((k >> b) & 1) r = jac_madd(r, g);
   }
-  const auto zi = inv(r.Z);
-  const auto zi2 = sqr(zi);
-  u32* o = out_wire + (size_t)i * IO::WIRE_JAC_WORDS;
-  ET::to_wire(EA(reduce_to<17>(mul(r.X, zi2))), o);
-  ET::to_wire(EA(reduce_to<17>(mul(r.Y, mul(zi2, zi)))), o + IO::CW);
-  ET::to_wire(EA(el_one(r.X)), o + 2 * IO::CW);
+  IO::template write_jac<WireIn>(r, inv(r.Z), false, out_wire + (size_t)i * IO::WIRE_JAC_WORDS);
 }
 
 #endif  // __HIPCC__

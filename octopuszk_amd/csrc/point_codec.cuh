@@ -388,7 +388,7 @@ __global__ __launch_bounds__(64) void k_codec_subgroup_g2(u32* __restrict__ aff,
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const Aff<G2Cfg::EA> q = IO::load_aff(aff + (size_t)i * IO::AFF_WORDS);
-  if (is_inf(q) || is_inf(bv_scalar_mul<G2Cfg>(q, GlvConsts::R32, 8))) return;
+  if (is_inf(q) || is_inf(scalar_mul<G2Cfg>(q, GlvConsts::R32, 8))) return;
   codes[i] = CODEC_E_SUBGROUP;
   for (int k = 0; k < IO::AFF_WORDS; k++) {
     aff[(size_t)i * IO::AFF_WORDS + k] = 0;

@@ -86,32 +86,6 @@ OZK_HD void scale_recode(const u32 (&k)[8], bool glv, ScaleSchedule& s) {
 inline bool scale_scalar_ok(const u32 (&k)[8]) { return !mp_geq<8>(k, GlvConsts::R32); }
 
 // ---------------------------------------------------------------------------------------------- one point
-// A wire-in point (X | Y | Z, any Z) as an affine Montgomery point, read as k_convert_bases (msm_var.cuh) reads it:
-// Z = 0 (also Z = q ...) is O = (0, 0), Z = 1 costs the two conversions, any other Z one inversion more.
-template <class CV>
-OZK_HD Aff<typename CV::EA> scale_load(const u32* p) {
-  using EA = typename CV::EA;
-  using ET = ElemTraits<EA>;
-  constexpr int CW = CurveIO<CV>::CW;
-  Aff<EA> q;
-  q.x = EA(el_zero(q.x));
-  q.y = EA(el_zero(q.x));
-  if (ET::wire_is_zero(p + 2 * CW)) return q;
-  const EA X = ET::from_wire(p), Y = ET::from_wire(p + CW);
-  if (ET::wire_is_one(p + 2 * CW)) {
-    q.x = EA(canonical(X));
-    q.y = EA(canonical(Y));
-    return q;
-  }
-  const EA Z = ET::from_wire(p + 2 * CW);
-  if (is_zero(Z)) return q;
-  const auto zi = inv(Z);
-  const auto zi2 = sqr(zi);
-  q.x = EA(canonical(mul(X, zi2)));
-  q.y = EA(canonical(mul(Y, mul(zi2, zi))));
-  return q;
-}
-
 // [k] q for the schedule of k.  GLV (G1 only) reads both digits of a step, otherwise the second is never set.
 template <class CV, bool GLV>
 OZK_HD Jac<CV> scale_ladder(const Aff<typename CV::EA>& q, const ScaleSchedule& s) {
@@ -155,22 +129,8 @@ OZK_HD Jac<CV> scale_ladder(const Aff<typename CV::EA>& q, const ScaleSchedule& 
 // is read whole before anything is written, so out may be in.
 template <class CV, bool GLV>
 OZK_HD void scale_point(const u32* in, const ScaleSchedule& s, u32* out) {
-  using EA = typename CV::EA;
-  using ET = ElemTraits<EA>;
-  constexpr int CW = CurveIO<CV>::CW;
-  const Aff<EA> q = scale_load<CV>(in);
-  const Jac<CV> r = scale_ladder<CV, GLV>(q, s);
-  if (is_inf(r)) {
-    ET::to_wire(EA(el_zero(q.x)), out);
-    ET::to_wire(EA(el_one(q.x)), out + CW);
-    ET::to_wire(EA(el_zero(q.x)), out + 2 * CW);
-    return;
-  }
-  const auto zi = inv(r.Z);
-  const auto zi2 = sqr(zi);
-  ET::to_wire(EA(reduce_to<17>(mul(r.X, zi2))), out);
-  ET::to_wire(EA(reduce_to<17>(mul(r.Y, mul(zi2, zi)))), out + CW);
-  ET::to_wire(EA(el_one(q.x)), out + 2 * CW);
+  using IO = CurveIO<CV>;
+  IO::template write<WireIn>(scale_ladder<CV, GLV>(IO::aff_from_wire(in), s), out);
 }
 
 #if defined(__HIPCC__)

@@ -44,10 +44,22 @@ extern "C" void efhc_add(const u32* a, const u32* b, int type, int negate_b, u32
   else
     points_add_one<G2Cfg>(a, b, negate_b != 0, out);
 }
+template <class CV>
+static void efhc_term_of(const u32* acc, const u32* p, const u32* c, u32* out) {
+  using IO = CurveIO<CV>;
+  IO::template write<WireIn>(sparse_term<CV>(from_affine<CV>(IO::aff_from_wire(acc)), p, c), out);
+}
 // out = acc + [c] p; c null: the coefficient one
 extern "C" void efhc_term(const u32* acc, const u32* p, const u32* c, int type, u32* out) {
   if (type == 1)
-    ec_write<G1Cfg>(sparse_term<G1Cfg>(from_affine<G1Cfg>(scale_load<G1Cfg>(acc)), p, c), out);
+    efhc_term_of<G1Cfg>(acc, p, c, out);
   else
-    ec_write<G2Cfg>(sparse_term<G2Cfg>(from_affine<G2Cfg>(scale_load<G2Cfg>(acc)), p, c), out);
+    efhc_term_of<G2Cfg>(acc, p, c, out);
+}
+// out = the wire-in point `in` (any Z) read with aff_from_wire and written back with write<WireIn>
+extern "C" void efhc_roundtrip(const u32* in, int type, u32* out) {
+  if (type == 1)
+    CurveIO<G1Cfg>::write<WireIn>(from_affine<G1Cfg>(CurveIO<G1Cfg>::aff_from_wire(in)), out);
+  else
+    CurveIO<G2Cfg>::write<WireIn>(from_affine<G2Cfg>(CurveIO<G2Cfg>::aff_from_wire(in)), out);
 }

@@ -54,5 +54,5 @@ extern "C" void kfhc_g2_convert(const u32* wire, u32* out) {
 // [r]q == O for one stored G2 record (32 words): the test k_codec_subgroup_g2 makes
 extern "C" int kfhc_g2_in_subgroup(const u32* rec) {
   const Aff<G2Cfg::EA> q = CurveIO<G2Cfg>::load_aff(rec);
-  return is_inf(q) || is_inf(bv_scalar_mul<G2Cfg>(q, GlvConsts::R32, 8)) ? 1 : 0;
+  return is_inf(q) || is_inf(scalar_mul<G2Cfg>(q, GlvConsts::R32, 8)) ? 1 : 0;
 }

@@ -65,6 +65,33 @@ def test_fixed_base_infinity_base_and_small_orders():
             assert P == C.to_affine(C.mul(base, s_)), hex(s_)
 
 
+@pytest.mark.parametrize("is_g1", [True, False])
+@pytest.mark.parametrize("all_zero", [False, True])
+def test_fixed_base_short_batches_with_infinities(is_g1, all_zero):
+    """n = 19 results are three lanes of the shared inversion (8 per lane, interleaved: lane 0 holds 0, 3, .., 18) with a
+    short last batch; zero scalars put O first, in the middle and last in lane 0's batch and first in lane 1's.  With
+    every scalar zero each lane inverts the empty product.  Both output layouts, every point against the oracle."""
+    import ctypes
+    from octopuszk_amd import fixed_base_msm as fb, lib
+    from octopuszk_amd.variable_base_msm import marshal_scalars
+    C = o.G1 if is_g1 else o.G2
+    n, window = 19, 5
+    rng = random.Random(190 + is_g1)
+    base = C.mul(C.one, rng.randrange(1, o.R))                # Jacobian, Z != 1
+    scalars = [rng.randrange(1, o.R) for _ in range(n)]
+    for i in range(n) if all_zero else (0, 1, 3, 9, 18):
+        scalars[i] = 0
+    want = [C.to_affine(o.fixed_base_mul(C, base, 254, window, s)) for s in scalars]
+    assert [i for i, P in enumerate(want) if C.is_zero(P)] == [i for i, s in enumerate(scalars) if s == 0]
+    assert fb.batch_msm(254, window, base, scalars, is_g1=is_g1) == want
+    to_wire = o.g1_to_wire if is_g1 else o.g2_to_wire
+    out = ctypes.create_string_buffer(n * (96 if is_g1 else 192))
+    lib.check(lib.load().ozk_fixed_batch_msm_compact_host((254 + window - 1) // window, window, n, fb._vp(to_wire(base)),
+                                                          fb._vp(marshal_scalars(scalars)), 1 if is_g1 else 2, 0,
+                                                          ctypes.cast(out, ctypes.c_void_p)))
+    assert out.raw == b"".join(to_wire(P) for P in want)
+
+
 def test_fixed_base_truncates_to_outerc_windows():
     # only the first outerc windows of the scalar are used (FixedBaseMSM.java:146-164)
     from octopuszk_amd import fixed_base_msm as fb

@@ -243,7 +243,7 @@ def test_decode_to_prepared_matches_model(kfhc, type_):
 
 
 def test_subgroup_function_on_the_host(kfhc):
-    """[r]P = O through bv_scalar_mul on stored records, as the subgroup kernel runs it: multiples of the generator
+    """[r]P = O through scalar_mul on stored records, as the subgroup kernel runs it: multiples of the generator
     pass, twist points from random x do not (the model multiplies by r in oracle integers)"""
     rng = random.Random(5)
     inside = [o.G2.to_affine(o.G2.mul(o.G2.one, rng.randrange(1, o.R))) for _ in range(3)]

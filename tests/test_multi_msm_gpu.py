@@ -182,6 +182,20 @@ def test_special_bases(name):
     _assert_rows(got, _oracle_reference([tuple(c % o.Q for c in P) for P in bases], small), name + " vs oracle")
 
 
+def test_infinity_outputs_at_the_ends_of_the_normalising_batches():
+    """k = 11 outputs are two lanes of the shared inversion of k_mm_norm (lane 0 holds 0, 2, .., 10, lane 1 holds 1, ..,
+    9: a short batch); all-zero rows 0, 5 and 10 put O first and last in lane 0's batch and in the middle of lane 1's"""
+    from octopuszk_amd.device import SharedBaseMsm
+    n, k = 5, 11
+    d_bases = _dev(_wire(_random_bases(n, 55)))
+    rows = _random_rows(k, n, 56)
+    for i in (0, 5, 10):
+        rows[i] = 0
+    got = _run(SharedBaseMsm(d_bases, n), rows)
+    assert [i for i in range(k) if got[i] == INF_RECORD] == [0, 5, 10]
+    _assert_rows(got, _var_reference(d_bases, n, rows), "n=5 k=11 vs ozk_var_msm_dev")
+
+
 def test_edge_scalars_against_oracle():
     """every edge scalar alone and in company, n = 3, against the oracle's naive MSM"""
     from octopuszk_amd.device import SharedBaseMsm

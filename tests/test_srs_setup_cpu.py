@@ -152,6 +152,24 @@ def test_sum_and_sparse_term_match_the_model(efhc, type_):
             assert bytes(out) == cref.wire(type_, want), (A, B, c)
 
 
+@pytest.mark.parametrize("type_", [1, 2])
+def test_wire_point_reader_and_writer_round_trip(efhc, type_):
+    """CurveIO::aff_from_wire then write<WireIn> (curve.cuh), the reader and writer every point kernel shares: Z = 0
+    (in both spellings), Z = 1, a random Z, and Z = q given as raw words, which reads as O; byte for byte against
+    the oracle's affine point"""
+    C, P, S, J, O = _points(type_)
+    n = 24 * type_
+    flat = (lambda A: list(A)) if type_ == 1 else (lambda A: [c for xy in A for c in xy])
+    raw = lambda A: b"".join(_le(c) for c in flat(A))
+    zq = Q if type_ == 1 else (Q, 0)
+    z0 = 0 if type_ == 1 else (0, 0)
+    zqq = Q if type_ == 1 else (Q, Q)
+    for A, want in ((O, O), ((P[0], P[1], z0), O), (P, P), (S, S), (J, S), ((J[0], J[1], zq), O), ((P[0], P[1], zqq), O)):
+        out = (ctypes.c_uint32 * n)()
+        efhc.efhc_roundtrip(_words(raw(A)), type_, out)
+        assert bytes(out) == cref.wire(type_, C.to_affine(want)), A
+
+
 def test_sparse_term_is_exact_outside_the_subgroup(efhc):
     """the per-lane ladder of a general coefficient assumes no subgroup: [r] P of such a twist point is not O"""
     P = cref.twist_point_outside_the_subgroup()
