@@ -118,7 +118,7 @@ OZK_HD Jac<CV> sparse_term(const Jac<CV>& acc, const u32* p, const u32* c) {
   if (c) {
     u32 k[8];
     for (int i = 0; i < 8; i++) k[i] = c[i];
-    for (int it = 0; it < 6 && mp_geq<8>(k, GlvConsts::R32); it++) mp_sub<8>(k, GlvConsts::R32);
+    reduce_mod_r(k);
     const u32 one[8] = {1, 0, 0, 0, 0, 0, 0, 0};
     u32 m1[8];
     for (int i = 0; i < 8; i++) m1[i] = GlvConsts::R32[i];

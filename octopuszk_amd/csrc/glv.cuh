@@ -29,30 +29,28 @@ struct GlvConsts {
   static constexpr u32 BETA_G2[9] = {0x18ccb791u, 0x175b1c3au, 0xb83d6e2u, 0xe8ed071u, 0x1282bee2u, 0x4220e84u, 0x1fe4017fu, 0x15084d4au, 0x169119u};
 };
 
-// r[0..NR) = low NR words of a[0..NA) * b[0..NB)
+// r[0..NR) = low NR words of a[0..NA) * b[0..NB), row by row (one row per word of b) on a 64-bit multiply-add:
+//     t = a[i] * b[j] + r[i + j] + carry  <=  (2^32 - 1)^2 + 2 (2^32 - 1) = 2^64 - 1
+// never overflows, so a row needs no third carry word; the low word of t is the new r[i + j], the high word the
+// carry into the next position.  Terms at positions >= NR are not computed.
 template <int NA, int NB, int NR>
 OZK_HD void mp_mul_lo(const u32* a, const u32* b, u32* r) {
-  u64 carry = 0;
 #pragma unroll
-  for (int k = 0; k < NR; k++) {
-    u64 lo = carry & 0xffffffffull;
-    u64 hi = carry >> 32;
+  for (int k = 0; k < NR; k++) r[k] = 0;
+#pragma unroll
+  for (int j = 0; j < NB; j++) {
+    u32 carry = 0;
 #pragma unroll
     for (int i = 0; i < NA; i++) {
-      const int j = k - i;
-      if (j >= 0 && j < NB) {
-        const u64 p = (u64)a[i] * b[j];
-        lo += p & 0xffffffffull;
-        hi += p >> 32;
+      if (i + j < NR) {
+        const u64 t = mad64(a[i], b[j], (u64)r[i + j] + carry);
+        r[i + j] = (u32)t;
+        carry = (u32)(t >> 32);
       }
     }
-    r[k] = (u32)lo;
-    carry = hi + (lo >> 32);
+    if (NA + j < NR) r[NA + j] = carry;   // (no earlier row reaches this word)
   }
 }
-// full product, NA + NB words
-template <int NA, int NB>
-OZK_HD void mp_mul(const u32* a, const u32* b, u32* r) { mp_mul_lo<NA, NB, NA + NB>(a, b, r); }
 
 template <int N>
 OZK_HD void mp_sub(u32* a, const u32* b) {  // a -= b (mod 2^(32N))
@@ -73,42 +71,73 @@ OZK_HD bool mp_geq(const u32* a, const u32* b) {
   return true;
 }
 template <int N>
-OZK_HD void mp_neg(u32* a) {  // two's complement negate
-  u64 c = 1;
+OZK_HD void mp_cneg(u32* a, bool neg) {  // two's complement negate when neg, by selects: a = (a ^ m) + (m & 1), m = -neg
+  const u32 m = 0u - (u32)neg;
+  u64 c = m & 1u;
 #pragma unroll
   for (int i = 0; i < N; i++) {
-    c += (u64)(~a[i]);
+    c += (u64)(a[i] ^ m);
     a[i] = (u32)c;
     c >>= 32;
   }
 }
 
+// k <- k mod r for ANY 256-bit k, without a branch.  With k7, r7 the top words, q' = floor(k7 / (r7 + 1)) is
+// floor(k / r) or one less: k >= k7 2^224 and r < (r7 + 1) 2^224 give q' <= k / r, and k / r < (k7 + 1) / r7 <=
+// (q' + 1)(1 + 1 / r7) < q' + 2 because q' + 1 <= 6 < r7.  So k - q' r is in [0, 2r): one conditional subtraction.
+OZK_HD void reduce_mod_r(u32 (&k)[8]) {
+  const u32 q = k[7] / (GlvConsts::R32[7] + 1u);   // 0 .. 5 (a division by a constant: multiply-high and shift)
+  u64 m = 0;
+  u32 br = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {   // k -= q r
+    m = mad64(q, GlvConsts::R32[i], m);
+    const u64 t = (u64)k[i] - (u32)m - br;
+    k[i] = (u32)t;
+    br = (u32)(t >> 32) & 1u;
+    m >>= 32;
+  }
+  u32 d[8];
+  br = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {   // d = k - r
+    const u64 t = (u64)k[i] - GlvConsts::R32[i] - br;
+    d[i] = (u32)t;
+    br = (u32)(t >> 32) & 1u;
+  }
+#pragma unroll
+  for (int i = 0; i < 8; i++) k[i] = br ? k[i] : d[i];
+}
+
 // k: any 256-bit value (reduced mod r first).  Outputs |k1|, |k2| as 4 words each (< 2^128) + signs.
+// Sizes: c1 <= k G1C / 2^256 < r G1C / 2^256 <= B2 < 2^64 and c2 < |B1| < 2^127, so c1 has 2 words and c2 has 4
+// (words 8-9 and 8-11 of the two products, carries out of the low words included; the words above are zero).
+// k1 and k2 are below 2^127 in magnitude (tests/test_glv.py), so they are computed modulo 2^128 in two's complement:
+// bit 127 is the sign, and no product word at or above 2^128 is formed.
 OZK_HD void glv_decompose(const u32 (&k_in)[8], u32 (&k1)[4], bool& neg1, u32 (&k2)[4], bool& neg2) {
   u32 k[8];
 #pragma unroll
   for (int i = 0; i < 8; i++) k[i] = k_in[i];
-  for (int it = 0; it < 6 && mp_geq<8>(k, GlvConsts::R32); it++) mp_sub<8>(k, GlvConsts::R32);
-  u32 p1[11], p2[13];
-  mp_mul<8, 3>(k, GlvConsts::G1C, p1);
-  mp_mul<8, 5>(k, GlvConsts::G2C, p2);
-  const u32* c1 = p1 + 8;  // 3 words
-  const u32* c2 = p2 + 8;  // 5 words
-  // everything modulo 2^160, two's complement: the true values are below 2^128 in magnitude
-  u32 t1[5], t2[5], s1[5], s2[5];
-  mp_mul_lo<3, 2, 5>(c1, GlvConsts::A1, t1);
-  mp_mul_lo<5, 4, 5>(c2, GlvConsts::A2, t2);
+  reduce_mod_r(k);
+  u32 p1[10], p2[12];
+  mp_mul_lo<8, 3, 10>(k, GlvConsts::G1C, p1);
+  mp_mul_lo<8, 5, 12>(k, GlvConsts::G2C, p2);
+  const u32* c1 = p1 + 8;  // 2 words
+  const u32* c2 = p2 + 8;  // 4 words
+  u32 t1[4], t2[4], s1[4], s2[4];
+  mp_mul_lo<2, 2, 4>(c1, GlvConsts::A1, t1);
+  mp_mul_lo<4, 4, 4>(c2, GlvConsts::A2, t2);
 #pragma unroll
-  for (int i = 0; i < 5; i++) s1[i] = k[i];
-  mp_sub<5>(s1, t1);
-  mp_sub<5>(s1, t2);                                  // k1 = k - c1 a1 - c2 a2
-  mp_mul_lo<3, 4, 5>(c1, GlvConsts::B1ABS, s2);
-  mp_mul_lo<5, 2, 5>(c2, GlvConsts::B2, t2);
-  mp_sub<5>(s2, t2);                                  // k2 = c1 |b1| - c2 b2
-  neg1 = (s1[4] >> 31) != 0;
-  neg2 = (s2[4] >> 31) != 0;
-  if (neg1) mp_neg<5>(s1);
-  if (neg2) mp_neg<5>(s2);
+  for (int i = 0; i < 4; i++) s1[i] = k[i];
+  mp_sub<4>(s1, t1);
+  mp_sub<4>(s1, t2);                                  // k1 = k - c1 a1 - c2 a2
+  mp_mul_lo<2, 4, 4>(c1, GlvConsts::B1ABS, s2);
+  mp_mul_lo<4, 2, 4>(c2, GlvConsts::B2, t2);
+  mp_sub<4>(s2, t2);                                  // k2 = c1 |b1| - c2 b2
+  neg1 = (s1[3] >> 31) != 0;
+  neg2 = (s2[3] >> 31) != 0;
+  mp_cneg<4>(s1, neg1);
+  mp_cneg<4>(s2, neg2);
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     k1[i] = s1[i];

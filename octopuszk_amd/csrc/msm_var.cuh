@@ -1208,16 +1208,49 @@ k_segreduce_small(const u32* __restrict__ d_count, int n_in, int L, u32* __restr
 // Run merge between level 1 and the generic levels.  After level 1 a bucket cut by lane
 // boundaries is a run of adjacent slots with the same id (two for almost every bucket; a few
 // more for the top window, whose digits have fewer significant bits).  Every run of at most
-// RUN_MAX slots is summed by the lane that owns its first slot and written to its bucket; all
-// its slots die.  Longer runs (skewed digit distributions) are left to the generic levels and
-// counted in *remaining.  Each lane decides from bid_in alone, so there are no races.
+// RUN_MAX slots is summed into its bucket; all its slots die.  Longer runs (skewed digit
+// distributions) are left to the generic levels and counted in *remaining.  Each lane classifies
+// its slots from bid_in alone; the run belongs to its first slot, so there are no races.
+//
+// A run is [tail piece of lane t | head piece of lane t + 1 | (placeholder of t + 1 | head piece of t + 2)* ]:
+// it starts at an odd slot (a tail piece), every other odd slot inside it is the infinity placeholder of a
+// chunk cut on both sides, every even slot a head piece — so only the slots s + 1, s + 3, ... are added.
+// level-1 pieces are all XYZZ records (the placeholder included): 12M + 2S general additions, no conversion.
+//
+// The additions are not done by the classifying lane: at the workload's geometry (2^20 pairs: 260 772 cut buckets,
+// 203 976 in two pieces, 56 796 in three, none longer) nearly every wave holds a run that needs a second addition,
+// so a loop per lane runs the ~2500-instruction addition twice in every wave for the ~45 lanes of a block that
+// need it.  Instead the block keeps a work list in LDS and adds in ROUNDS: round k does addition k of every run
+// that has one, on the first `length` threads of the block, so the left-over additions fill whole waves and the
+// other waves skip the body.  The partial sum of a run waits in its bucket record between rounds; block_sync()
+// orders those records as it orders the levels of k_segreduce_small (a run is only ever touched by its own block).
+// At most RUN_MAX / 2 rounds (a run of RUN_MAX slots has RUN_MAX / 2 odd offsets); the list length is block-uniform.
+//
+// hist_src / hist_dst: the n_hist bucket counts are copied for the tail on the way (the sorted set that holds
+// them is reused by the next MSM's sort) — one launch fewer on the queue that sets the pipeline's period.
 constexpr int RUN_MAX = 16;
+constexpr int RUNMERGE_BLOCK = 256;
 template <class CV>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(RUNMERGE_BLOCK)
 k_runmerge(const u32* __restrict__ bid_in, const u32* __restrict__ pts, int n_slots,
-           u32* __restrict__ buckets, u32* __restrict__ bid_out, u32* __restrict__ remaining) {
+           u32* __restrict__ buckets, u32* __restrict__ bid_out, u32* __restrict__ remaining,
+           const u32* __restrict__ hist_src, u32* __restrict__ hist_dst, size_t n_hist) {
   using IO = CurveIO<CV>;
+  // G2 keeps the loop per lane: its addition needs 271 registers, one wave per SIMD, so a wave that skips a round
+  // frees nothing for another, and the rounds would only add their barriers and the trip of the partial sums
+  // through memory
+  constexpr bool LIST = !CV::LDS_ACC;
+  constexpr int ROUNDS = RUN_MAX / 2;
+  constexpr int CAP = 2 * RUNMERGE_BLOCK;   // a thread classifies two slots
+  // work items (first slot of the run, last slot - first slot), ping-pong between rounds; one counter per round,
+  // so none is ever reset: 5 KiB
+  __shared__ u32 item_s[2][CAP];
+  __shared__ uint8_t item_span[2][CAP];
+  __shared__ u32 item_cnt[ROUNDS + 1];
+  if (threadIdx.x <= ROUNDS) item_cnt[threadIdx.x] = 0;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  for (size_t i = (size_t)t; i < n_hist; i += (size_t)gridDim.x * blockDim.x) hist_dst[i] = hist_src[i];
+  block_sync();
   u32 alive = 0;
 #pragma unroll 1
   for (int k = 0; k < 2; k++) {
@@ -1233,16 +1266,18 @@ k_runmerge(const u32* __restrict__ bid_in, const u32* __restrict__ pts, int n_sl
       const bool is_short = (x - s < RUN_MAX) && (e - x < RUN_MAX) && (e - s + 1 <= RUN_MAX);
       if (!is_short) {
         out = bx;
-      } else if (s == x) {  // owner of the run: sum it
-        // level-1 pieces are all XYZZ records (the neutral placeholder of a chunk cut on both sides
-        // included): 12M + 2S general additions, no conversion
-        // A run is [tail piece of lane t | head piece of lane t + 1 | (placeholder of t + 1 | head piece of t + 2)* ]:
-        // it starts at an odd slot (a tail piece), every other odd slot inside it is the infinity placeholder of a
-        // chunk cut on both sides, every even slot a head piece — so only the even slots are added (round 4: a run of
-        // four slots costs two additions instead of three, one of them with infinity; almost every wave holds one)
-        Xyzz<CV> acc = IO::load_xyzz(pts + (size_t)s * IO::REC_WORDS);
-        for (int q = s + 1; q <= e; q += 2) acc = xyzz_add(acc, IO::load_xyzz(pts + (size_t)q * IO::REC_WORDS));
-        IO::store_rec_xyzz(acc, buckets + (size_t)bx * IO::REC_WORDS);
+      } else if (s == x) {  // first slot of the run
+        if constexpr (!LIST) {
+          Xyzz<CV> acc = IO::load_xyzz(pts + (size_t)s * IO::REC_WORDS);
+          for (int q = s + 1; q <= e; q += 2) acc = xyzz_add(acc, IO::load_xyzz(pts + (size_t)q * IO::REC_WORDS));
+          IO::store_rec_xyzz(acc, buckets + (size_t)bx * IO::REC_WORDS);
+        } else if (e > s) {
+          const u32 j = atomicAdd(&item_cnt[0], 1u);
+          item_s[0][j] = (u32)s;
+          item_span[0][j] = (uint8_t)(e - s);
+        } else {  // a run of one piece: nothing to add
+          IO::store_rec_xyzz(IO::load_xyzz(pts + (size_t)s * IO::REC_WORDS), buckets + (size_t)bx * IO::REC_WORDS);
+        }
       }
     }
     bid_out[x] = out;
@@ -1254,6 +1289,28 @@ k_runmerge(const u32* __restrict__ bid_in, const u32* __restrict__ pts, int n_sl
   }
   for (int o = 32; o > 0; o >>= 1) alive += __shfl_xor(alive, o);
   if ((threadIdx.x & 63) == 0 && alive) atomicAdd(remaining, alive);
+#pragma unroll 1
+  for (int r = 0; LIST && r < ROUNDS; r++) {
+    block_sync();   // the items of this round, and the bucket records the round before wrote
+    const u32 len = (u32)__builtin_amdgcn_readfirstlane((int)item_cnt[r]);
+    if (len == 0) break;
+    const int cur = r & 1;
+#pragma unroll 1
+    for (u32 i = threadIdx.x; i < len; i += RUNMERGE_BLOCK) {
+      const u32 s = item_s[cur][i];
+      const u32 span = item_span[cur][i];
+      u32* bucket = buckets + (size_t)bid_in[s] * IO::REC_WORDS;
+      const u32 off = 2u * (u32)r + 1u;   // this round adds slot s + off to (round 0) slot s / the sum so far
+      const u32* sum = r == 0 ? pts + (size_t)s * IO::REC_WORDS : bucket;
+      const Xyzz<CV> acc = xyzz_add(IO::load_xyzz(sum), IO::load_xyzz(pts + ((size_t)s + off) * IO::REC_WORDS));
+      IO::store_rec_xyzz(acc, bucket);
+      if (off + 2u <= span) {
+        const u32 j = atomicAdd(&item_cnt[r + 1], 1u);
+        item_s[cur ^ 1][j] = s;
+        item_span[cur ^ 1][j] = (uint8_t)span;
+      }
+    }
+  }
 }
 
 // ------------------------------------------------------------------ window sums

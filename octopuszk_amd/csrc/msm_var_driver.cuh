@@ -532,8 +532,10 @@ int var_msm_accum(int n, void* sorted, size_t sorted_bytes, void* accum_ws, size
   }
   // run merge: completes every bucket cut into at most RUN_MAX pieces; counts the surviving slots
   size_t n_in = 2 * lanes;
+  // (it also copies the bucket counts for the tail, which needs them after the next head has reused the sorted set)
+  static_assert(RUNMERGE_BLOCK == 256, "k_runmerge's work list is sized for this launch");
   hipLaunchKernelGGL((k_runmerge<CT>), dim3((unsigned)((lanes + TB - 1) / TB)), dim3(TB), 0, st, L.slot_bid[0],
-                     L.slot_pts[0], (int)n_in, L.buckets, L.slot_bid2, L.total + 1);
+                     L.slot_pts[0], (int)n_in, L.buckets, L.slot_bid2, L.total + 1, (const u32*)L.hist, L.hist_t, L.NB);
   // levels >= 2 over the surviving partial slots, ping-pong, until a single lane has seen everything
   // (they return at once when nothing survived)
   int cur = 0;
@@ -555,8 +557,6 @@ int var_msm_accum(int n, void* sorted, size_t sorted_bytes, void* accum_ws, size
     n_in = 2 * lanes;
     cur ^= 1;
   }
-  // the tail needs the bucket counts after the next head has reused the sorted set
-  OZK_HIP(hipMemcpyAsync(L.hist_t, L.hist, L.NB * sizeof(u32), hipMemcpyDeviceToDevice, st));
   OZK_HIP(hipGetLastError());
   return OZK_OK;
 }
