@@ -188,7 +188,7 @@ int ozk_bases_destroy(void* handle);
 int ozk_bases_type(void* handle);
 
 /* Ordering hint for several MSMs in flight on two streams.  A tail given `levels_done` records it after its first
- * window-sum level (after the last multi-wave level with OZK_MSM_ORDER_EARLY=0, round 1's form); a head given the
+ * window-sum level; a head given the
  * same event as `previous_levels_done` waits for it after its sort and before its bucket accumulation, so that the
  * previous MSM's wave-cooperative level is resident before the accumulation takes three of the four wave slots of
  * every SIMD.  Measured at 2^20: 576 Mscalar-mul/s (538 with the late event; 576 with no event at all — the hint no

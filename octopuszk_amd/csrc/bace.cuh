@@ -16,7 +16,7 @@ constexpr int BACE_LDS_FFT_MAX = 2048;      // transforms up to this size: one w
 constexpr int BACE_WG = 64;                 // circuit interpreter: one wave per workgroup, one lane per point
 constexpr int BACE_MAX_LANES = 65536;       // lanes of one interpreter launch (each loops over points beyond that)
 constexpr int BACE_LDS_SLOTS_MAX = 28;      // 28 x 9 words x 64 lanes x 4 B = 63 KiB of LDS per workgroup
-constexpr int BACE_LDS_SLOTS_DEFAULT = 16;  // 36 KiB: four workgroups per CU
+// (OZK_BACE_LDS_SLOTS defaults to 16 slots in LDS, 36 KiB: four workgroups per CU)
 constexpr int BACE_MAX_N = 65535;           // columns: gridDim.y of the batched kernels
 constexpr int BACE_OP_WORDS = 4;            // {op, dst, a, b}
 
@@ -243,7 +243,7 @@ __global__ void __launch_bounds__(256) k_bace_fold(const u32* __restrict__ proof
 
 // ---- host side ----
 static int bace_lds_slot_cap() {
-  int cap = env_int("OZK_BACE_LDS_SLOTS", BACE_LDS_SLOTS_DEFAULT);
+  int cap = knob(K_BACE_LDS_SLOTS);
   if (cap < 0) cap = 0;
   if (cap > BACE_LDS_SLOTS_MAX) cap = BACE_LDS_SLOTS_MAX;
   return cap;
@@ -302,7 +302,7 @@ static int bace_twiddles(int size, bool inverse, const BaceLayout& L, u32* slot,
   bace_root_host(ilog2((uint32_t)size), inverse, om);
   *tw = slot;
   if (size < 2) return OZK_OK;   // (a transform of one element reads no twiddle)
-  if (env_int("OZK_FFT_PLAN_CACHE", 1)) {
+  if (knob(K_FFT_PLAN_CACHE)) {
     int rc = plan_get(size, (const uint8_t*)om, nullptr, st, &pin.p);
     if (rc) return rc;
     if (pin.p) {

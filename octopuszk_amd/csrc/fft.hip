@@ -527,12 +527,12 @@ static int fft_core(const u32* d_in, int n, const u32* tw, u32* d_out, int out_s
   // first (a later pass with K stages touches HBM in runs of TILE / 2^K elements).  2^22: 8 + 8 + 6; 2^21: 7 + 8 + 6.
   // OZK_FFT_PLAN=0: the even split of rounds 1-2 (2^22: 8 + 7 + 7).
   constexpr int tile = FFT_TILE_SMALL;
-  int maxk = env_int("OZK_FFT_MAXK", 8);
+  int maxk = knob(K_FFT_MAXK);
   if (maxk < 3) maxk = 3;
   if (maxk > 10) maxk = 10;
   int npass = (logn + maxk - 1) / maxk;
   int plan[16], planned = 0;
-  if (env_int("OZK_FFT_PLAN", 1) && npass > 1) {
+  if (knob(K_FFT_PLAN) && npass > 1) {
     const int evenmax = maxk & ~1;
     for (int np = npass; np <= npass + 1 && !planned; np++)
       for (int k0 = (logn < maxk ? logn : maxk); k0 >= 3 && !planned; k0--) {
@@ -545,7 +545,7 @@ static int fft_core(const u32* d_in, int n, const u32* tw, u32* d_out, int out_s
       }
     if (planned) npass = planned;
   }
-  if (const char* ks = getenv("OZK_FFT_KS")) {   // experiment: explicit stage counts, e.g. "8,6,8" (must sum to log2 n)
+  if (const char* ks = knob_str(K_FFT_KS)) {   // experiment: explicit stage counts, e.g. "8,6,8" (must sum to log2 n)
     int k[16], c = 0, sum = 0;
     for (const char* q = ks; *q && c < 16;) {
       k[c] = atoi(q);
@@ -577,7 +577,7 @@ static int fft_core(const u32* d_in, int n, const u32* tw, u32* d_out, int out_s
     a.logn = logn;
     a.sbits = sbits;
     a.K = K;
-    a.pyr = env_int("OZK_FFT_TW_PYRAMID", 1) != 0;
+    a.pyr = knob(K_FFT_TW_PYRAMID) != 0;
     a.scale = last ? scale : nullptr;
     a.in_cs = pass == 0 ? in_cs : (size_t)n * 8;
     a.out_cs = last ? out_cs : (size_t)n * 8;
@@ -642,7 +642,7 @@ struct FftPlan : PinCacheItem {
 constexpr int FFT_PLANS = 4;  // per device
 static PinCache<FftPlan> g_plans;
 static PinCacheLimits plan_limits() {
-  long mb = env_int("OZK_FFT_PLAN_CACHE_MB", 4096);   // (a 2^26 witness-map plan is 4 GiB; larger domains build per call)
+  long mb = knob(K_FFT_PLAN_CACHE_MB);   // (a 2^26 witness-map plan is 4 GiB; larger domains build per call)
   if (mb < 0) mb = 0;
   return PinCacheLimits{FFT_PLANS, (size_t)mb << 20};
 }
@@ -684,7 +684,7 @@ static int fft_dev(const void* d_in, int n, const uint8_t* omega_host, void* d_o
                    hipStream_t st, int out_stride = 16) {
   const FftLayout L = fft_layout(n, wsp, wsb);
   if (L.bytes > wsb) return fail(OZK_E_INVALID, "workspace too small: need %zu bytes, got %zu", L.bytes, wsb);
-  if (n >= 2 && env_int("OZK_FFT_PLAN_CACHE", 1)) {
+  if (n >= 2 && knob(K_FFT_PLAN_CACHE)) {
     PlanPin pin;
     int rc = plan_get(n, omega_host, nullptr, st, &pin.p);
     if (rc) return rc;
@@ -951,7 +951,7 @@ static int qap_witness_dev(const void* d_A, const void* d_B, const void* d_C, in
   QapLayout L = qap_layout(m, wsp, wsb);
   if (L.bytes > wsb) return fail(OZK_E_INVALID, "workspace too small: need %zu bytes, got %zu", L.bytes, wsb);
   PlanPin pin;  // held until the last launch below is enqueued
-  if (env_int("OZK_FFT_PLAN_CACHE", 1)) {
+  if (knob(K_FFT_PLAN_CACHE)) {
     int prc = plan_get(m, omega_host, g_host, st, &pin.p);
     if (prc) return prc;
   }
@@ -976,7 +976,7 @@ static int qap_witness_dev(const void* d_A, const void* d_B, const void* d_C, in
   // (resp. g^-i / m) from a full table of the plan instead of four extra passes over the data (44 k_coset_scale
   // launches = 0.22 of the 2.07 ms of round 2's map at 2^21).  Transforms too small for the tiled kernel keep the
   // separate kernel.
-  const bool fold = m >= FFT_TILE_SMALL && env_int("OZK_QAP_FOLD_SCALE", 1) != 0;
+  const bool fold = m >= FFT_TILE_SMALL && knob(K_QAP_FOLD_SCALE) != 0;
   for (int k = 0; k < 3; k++) {
     // coefficients (times m), then a_i g^i / m, then the evaluations on the coset
     if ((rc = fft_core(in[k], m, L.tw_i, v[k], 8, L.buf[0], L.buf[1], st, fold ? L.sc_g : nullptr))) return rc;

@@ -9,10 +9,10 @@ namespace ozk {
 // A handful of helper threads that do nothing but memcpy between caller memory and the pinned ring: one
 // core moves ~12 GB/s, the PCIe link 57 GB/s.  Started on first use; they sleep on a condition variable.
 namespace {
-constexpr int COPY_HELPERS = 3;  // + the calling thread (default; OZK_COPY_HELPERS up to COPY_HELPERS_MAX)
+// OZK_COPY_HELPERS threads (default 3, up to COPY_HELPERS_MAX) + the calling thread
 constexpr int COPY_HELPERS_MAX = 11;
 static int copy_helpers() {
-  static const int h = env_int("OZK_COPY_HELPERS", COPY_HELPERS);   // 0: the calling thread copies alone
+  static const int h = knob(K_COPY_HELPERS);   // 0: the calling thread copies alone
   return h < 0 ? 0 : (h > COPY_HELPERS_MAX ? COPY_HELPERS_MAX : h);
 }
 constexpr int COPY_QUEUE = 64;
@@ -258,7 +258,7 @@ static int stage_wait(HostCtx* c, int b) {
     host_call_stats().stage_waits++;
     const auto t0 = std::chrono::steady_clock::now();
     OZK_HIP(hipEventSynchronize(c->stage_free[b]));
-    if (env_int("OZK_HOST_TRACE", 0)) {
+    if (knob(K_HOST_TRACE)) {
       const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
       if (ms > 1.0) fprintf(stderr, "[ozk] stage_wait #%d buffer %d: %.2f ms\n", host_call_stats().stage_waits, b, ms);
     }
@@ -292,7 +292,7 @@ int staged_h2d(HostCtx* c, void* d_dst, const void* h_src, size_t bytes, hipStre
     const auto te0 = std::chrono::steady_clock::now();
     OZK_HIP(hipMemcpyAsync((uint8_t*)d_dst + off, c->stage[b], len, hipMemcpyHostToDevice, st));
     OZK_HIP(hipEventRecord(c->stage_free[b], st));
-    if (env_int("OZK_HOST_TRACE", 0) >= 2)   // absolute CLOCK_MONOTONIC ns: comparable with rocprofv3's timestamps
+    if (knob(K_HOST_TRACE) >= 2)   // absolute CLOCK_MONOTONIC ns: comparable with rocprofv3's timestamps
       fprintf(stderr, "[ozk] h2d chunk %zu B buffer %d stream %p: enqueue began %lld ns, returned %lld ns\n", len, b, (void*)st,
               (long long)std::chrono::duration_cast<std::chrono::nanoseconds>(te0.time_since_epoch()).count(),
               (long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count());

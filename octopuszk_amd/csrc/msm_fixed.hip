@@ -290,7 +290,7 @@ struct FbPlan {
 static FbPlan fb_choose(int outerc, int ws, int n) {
   // GLV form when the caller's windows cover a whole Fr scalar (they always do in the reference:
   // outerc = ceil(scalarSize / windowSize), FixedBaseMSM.java:71-99); the plain form otherwise
-  const bool glv = env_int("OZK_MSM_GLV", 1) != 0 && (long long)outerc * ws >= 254;
+  const bool glv = knob(K_MSM_GLV) != 0 && (long long)outerc * ws >= 254;
   // In the GLV form the table's window size is the library's choice (s B does not depend on it): the
   // caller's (17 bits at 2^20) balances ONE 254-bit digit string against the table; with two 127-bit
   // strings over one table a narrower window is cheaper.  Cost in multiplications: 2 ceil(128/w) mixed
@@ -304,12 +304,12 @@ static FbPlan fb_choose(int outerc, int ws, int n) {
       const double cost = 2.0 * o * 10.0 * (double)n + o * 32.0 * (double)(1u << w);  // (the doubling chain is o w ~ 128 long either way)
       if (w == 1 || cost < best) { best = cost; wt = w; }
     }
-    wt = env_int("OZK_FB_WS", wt);
+    wt = knob_or(K_FB_WS, wt);
     if (wt < 1 || wt > ws) wt = ws;
   }
   FbPlan fp;
   fp.glv = glv;
-  fp.affine = glv && env_int("OZK_FB_AFFINE", 1) != 0;
+  fp.affine = glv && knob(K_FB_AFFINE) != 0;
   fp.wt = wt;
   fp.oc = glv ? (128 + wt - 1) / wt : outerc;
   return fp;
@@ -413,7 +413,7 @@ struct FbTab : PinCacheItem {
 constexpr int FB_TABS = 4;  // per device
 static PinCache<FbTab> g_tabs;
 static PinCacheLimits tab_limits() {
-  long mb = env_int("OZK_FB_TABLE_CACHE_MB", 1024);
+  long mb = knob(K_FB_TABLE_CACHE_MB);
   if (mb < 0) mb = 0;
   return PinCacheLimits{FB_TABS, (size_t)mb << 20};
 }
@@ -474,7 +474,7 @@ static int tab_get(FbPlan* fp, int outerc, int ws, int n, const uint8_t* base_ho
   std::vector<FbTab*> dead;
   FbTab* t = nullptr;
   const auto res = g_tabs.acquire(
-      key, bytes, tab_limits(), env_int("OZK_FB_TABLE_CACHE_SECOND_USE", 1) != 0,
+      key, bytes, tab_limits(), knob(K_FB_TABLE_CACHE_SECOND_USE) != 0,
       [&]() -> FbTab* {
         FbTab* nt = new (std::nothrow) FbTab();
         if (nt) {
@@ -529,7 +529,7 @@ static int fb_table_host_base(int outerc, int ws, int n, const uint8_t* base_hos
                               hipStream_t st, FbPlan* fp, TabPin* pin) {
   constexpr size_t base_bytes = std::is_same<CV, G1Cfg>::value ? 96 : 192;
   *fp = fb_choose(outerc, ws, n);
-  if (fp->affine && env_int("OZK_FB_TABLE_CACHE", 1)) {
+  if (fp->affine && knob(K_FB_TABLE_CACHE)) {
     const int rc = tab_get<CV>(fp, outerc, ws, n, base_host, wsp, wsb, st, &pin->t);
     if (rc || pin->t) return rc;   // (no cached table for this call: build one in the workspace, below)
   }
@@ -629,7 +629,7 @@ static int fixed_batch_host(int32_t outerc, int32_t ws, int32_t n, const uint8_t
   OZK_HIP(hipEventRecord(c->ev[0], cp));
   OZK_HIP(hipStreamWaitEvent(st, c->ev[0], 0));
   // (4 ranges: 8 measured 0.2 ms faster at 2^20, but with occasional 10-30 ms calls that 4 never showed)
-  int K = env_int("OZK_FB_HOST_RANGES", 4);
+  int K = knob(K_FB_HOST_RANGES);
   if (K > MAX_SLICES) K = MAX_SLICES;
   if (K > n / 4096) K = n / 4096;
   if (K < 1) K = 1;

@@ -181,7 +181,7 @@ static MmPlan mm_plan(int n) {
   MmPlan p;
   p.ws = mm_window_bits(n);
   // OZK_MM_WS: the window size for measurements (read once, like every tuning switch: table and calls agree)
-  const int forced = env_int("OZK_MM_WS", 0);
+  const int forced = knob_or(K_MM_WS, p.ws);
   if (forced >= MM_WS_MIN && forced <= MM_WS_MAX) p.ws = forced;
   p.oc = mm_windows(p.ws);
   p.per_base = mm_records_per_base(p.ws);

@@ -49,6 +49,12 @@ struct MsmPlan {
   int L1;       // sorted entries per lane at level 1
   int LK;       // slots per lane at levels >= 2
   int S;        // buckets per lane per wsum level (power of two)
+  // what the stages would otherwise decide for themselves (msm_var_driver.cuh, make_plan / plan_for)
+  int lone;        // 1: a single-call MSM, nothing runs beside its level-1 kernel (G1: the chunk is rounded as G2's)
+  int small_sort;  // 1: the whole sort in one launch (k_sort_small)
+  int S_lat;       // buckets per lane in the fused first window-sum level of a latency-mode tail
+  int fin_max;     // window-sum elements per window left to k_finalize
+  int tail_mode;   // -1: as the caller asks; 0 / 1: latency / throughput shape forced
 };
 
 OZK_HD u32 scalar_digit(const u32 (&s)[8], int w, int c) {

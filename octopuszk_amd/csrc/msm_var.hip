@@ -18,32 +18,39 @@ OZK_G2_DRIVER_INSTANCES(extern)
 
 using namespace ozk;
 
+// The size queries and the stages of the C ABI build the staged plan of their MSM, ONCE, and hand it down: f(curve tag, plan).
+template <class F>
+static auto with_plan(int n, int type, F f) {
+  return by_point_type(type, [&](auto t) { return f(t, plan_for<typename decltype(t)::CV>(n, false)); });
+}
+#define CV_OF(t) typename decltype(t)::CV
+
 extern "C" {
 
 // ---- the device-resident MSM, in the order of include/ozk.h.  Every entry: pointers, n, then by_point_type (fq2.cuh)
 // picks the driver template (msm_var_driver.cuh) for `type` and rejects anything that is not OZK_G1 / OZK_G2.
 size_t ozk_var_msm_workspace_bytes(int32_t n, int32_t type) {
   if (n <= 0) return 0;
-  return by_point_type(type, [&](auto t) { return var_msm_ws_bytes<typename decltype(t)::CV>(n); });
+  return with_plan(n, type, [](auto t, const MsmPlan& p) { return var_msm_ws_bytes<CV_OF(t)>(p); });
 }
 size_t ozk_var_msm_head_workspace_bytes(int32_t n, int32_t type) {
   if (n <= 0) return 0;
-  return by_point_type(type, [&](auto t) { return var_msm_head_ws_bytes<typename decltype(t)::CV>(n); });
+  return with_plan(n, type, [](auto t, const MsmPlan& p) { return var_msm_head_ws_bytes<CV_OF(t)>(p); });
 }
 size_t ozk_var_msm_tail_bytes(int32_t n, int32_t type) {
   if (n <= 0) return 0;
-  return by_point_type(type, [&](auto t) { return var_msm_tail_bytes<typename decltype(t)::CV>(n); });
+  return with_plan(n, type, [](auto t, const MsmPlan& p) { return var_msm_tail_bytes<CV_OF(t)>(p); });
 }
 size_t ozk_var_msm_prepared_bytes(int32_t n, int32_t type) {
   if (n <= 0 || n > (1 << 24)) return 0;
-  return by_point_type(type, [&](auto t) { return prepared_bytes<typename decltype(t)::CV>(n); });
+  return by_point_type(type, [&](auto t) { return prepared_bytes<CV_OF(t)>(make_plan(n)); });
 }
 int ozk_var_msm_stage_bytes(int32_t n, int32_t type, size_t* sorted_bytes, size_t* sort_ws_bytes,
                             size_t* accum_ws_bytes) {
   if (n <= 0 || n > (1 << 24) || !sorted_bytes || !sort_ws_bytes || !accum_ws_bytes)
     return fail(OZK_E_INVALID, "bad argument");
-  return by_point_type(type, [&](auto t) {
-    const RegionBytes rb = region_bytes<typename decltype(t)::CV>(n);
+  return with_plan(n, type, [&](auto t, const MsmPlan& p) {
+    const RegionBytes rb = region_bytes<CV_OF(t)>(p);
     *sorted_bytes = rb.sorted;
     *sort_ws_bytes = rb.sort_ws;
     *accum_ws_bytes = rb.accum_ws;
@@ -56,7 +63,7 @@ int ozk_var_msm_dev(const void* d_bases, const void* d_scalars, int32_t n, int32
   if (!d_bases || !d_scalars || !d_out || !d_workspace) return fail(OZK_E_INVALID, "null pointer argument");
   if (int rc = check_batch_size(n)) return rc;
   return by_point_type(type, [&](auto t) {
-    return var_msm_dev<typename decltype(t)::CV>(d_bases, d_scalars, n, d_out, d_workspace, workspace_bytes,
+    return var_msm_dev<CV_OF(t)>(d_bases, d_scalars, n, d_out, d_workspace, workspace_bytes,
                                                  (hipStream_t)stream);
   });
 }
@@ -65,7 +72,7 @@ int ozk_var_msm_prepared_dev(const void* d_prepared, const void* d_scalars, int3
   if (!d_prepared || !d_scalars || !d_out || !d_workspace) return fail(OZK_E_INVALID, "null pointer argument");
   if (int rc = check_batch_size(n)) return rc;
   return by_point_type(type, [&](auto t) {
-    return var_msm_dev<typename decltype(t)::CV>(nullptr, d_scalars, n, d_out, d_workspace, workspace_bytes,
+    return var_msm_dev<CV_OF(t)>(nullptr, d_scalars, n, d_out, d_workspace, workspace_bytes,
                                                  (hipStream_t)stream, d_prepared);
   });
 }
@@ -74,7 +81,7 @@ int ozk_var_msm_prepare_dev(const void* d_bases, int32_t n, int32_t type, void* 
   if (!d_bases || !d_prepared) return fail(OZK_E_INVALID, "null pointer argument");
   if (int rc = check_batch_size(n)) return rc;
   return by_point_type(type, [&](auto t) {
-    return var_msm_prepare<typename decltype(t)::CV>(d_bases, n, d_prepared, prepared_size, (hipStream_t)stream);
+    return var_msm_prepare<CV_OF(t)>(d_bases, n, d_prepared, prepared_size, (hipStream_t)stream);
   });
 }
 
@@ -84,29 +91,28 @@ int ozk_var_msm_head_dev(const void* d_bases, int32_t prepared, const void* d_sc
                          void* previous_levels_done) {
   if (!d_bases || !d_scalars || !d_workspace || !d_tail) return fail(OZK_E_INVALID, "null pointer argument");
   if (int rc = check_batch_size(n)) return rc;
-  return by_point_type(type, [&](auto t) {
-    return var_msm_head<typename decltype(t)::CV>(prepared ? nullptr : d_bases, d_scalars, n, d_workspace,
-                                                  workspace_bytes, d_tail, tail_bytes, (hipStream_t)stream,
-                                                  (hipEvent_t)previous_levels_done, prepared ? d_bases : nullptr);
+  return with_plan(n, type, [&](auto t, const MsmPlan& p) {
+    return var_msm_head<CV_OF(t)>(p, prepared ? nullptr : d_bases, d_scalars, d_workspace, workspace_bytes, d_tail,
+                                  tail_bytes, (hipStream_t)stream, (hipEvent_t)previous_levels_done,
+                                  prepared ? d_bases : nullptr);
   });
 }
 int ozk_var_msm_tail_dev(int32_t n, int32_t type, void* d_tail, size_t tail_bytes, void* d_out, void* stream,
                          void* levels_done, int32_t mode) {
   if (!d_tail || !d_out) return fail(OZK_E_INVALID, "null pointer argument");
   if (int rc = check_batch_size(n)) return rc;
-  return by_point_type(type, [&](auto t) {
-    return var_msm_tail<typename decltype(t)::CV>(n, d_tail, tail_bytes, d_out, (hipStream_t)stream,
-                                                  (hipEvent_t)levels_done, mode ? TAIL_THROUGHPUT : TAIL_LATENCY);
+  return with_plan(n, type, [&](auto t, const MsmPlan& p) {
+    return var_msm_tail<CV_OF(t)>(p, d_tail, tail_bytes, d_out, (hipStream_t)stream, (hipEvent_t)levels_done,
+                                  mode ? TAIL_THROUGHPUT : TAIL_LATENCY);
   });
 }
 int ozk_var_msm_sort_dev(const void* d_bases, int32_t prepared, const void* d_scalars, int32_t n, int32_t type,
                          void* d_sorted, size_t sorted_bytes, void* d_sort_ws, size_t sort_ws_bytes, void* stream) {
   if (!d_bases || !d_scalars || !d_sorted || !d_sort_ws) return fail(OZK_E_INVALID, "null pointer argument");
   if (int rc = check_batch_size(n)) return rc;
-  return by_point_type(type, [&](auto t) {
-    return var_msm_sort<typename decltype(t)::CV>(prepared ? nullptr : d_bases, d_scalars, n, d_sorted, sorted_bytes,
-                                                  d_sort_ws, sort_ws_bytes, (hipStream_t)stream, nullptr,
-                                                  prepared ? d_bases : nullptr);
+  return with_plan(n, type, [&](auto t, const MsmPlan& p) {
+    return var_msm_sort<CV_OF(t)>(p, prepared ? nullptr : d_bases, d_scalars, d_sorted, sorted_bytes, d_sort_ws,
+                                  sort_ws_bytes, (hipStream_t)stream, nullptr, prepared ? d_bases : nullptr);
   });
 }
 int ozk_var_msm_accum_dev(const void* d_prepared, int32_t n, int32_t type, void* d_sorted, size_t sorted_bytes,
@@ -115,9 +121,9 @@ int ozk_var_msm_accum_dev(const void* d_prepared, int32_t n, int32_t type, void*
   if (!d_sorted || !d_accum_ws || !d_tail) return fail(OZK_E_INVALID, "null pointer argument");
   if (int rc = check_batch_size(n)) return rc;
   if (part < ACCUM_ALL || part > ACCUM_REST) return fail(OZK_E_INVALID, "part %d is not 0 (all), 1 (level 1) or 2 (rest)", part);
-  return by_point_type(type, [&](auto t) {
-    return var_msm_accum<typename decltype(t)::CV>(n, d_sorted, sorted_bytes, d_accum_ws, accum_ws_bytes, d_tail,
-                                                   tail_bytes, (hipStream_t)stream, d_prepared, part);
+  return with_plan(n, type, [&](auto t, const MsmPlan& p) {
+    return var_msm_accum<CV_OF(t)>(p, d_sorted, sorted_bytes, d_accum_ws, accum_ws_bytes, d_tail, tail_bytes,
+                                   (hipStream_t)stream, d_prepared, part);
   });
 }
 
@@ -287,7 +293,8 @@ static int var_double_msm_host_impl(const uint8_t* bases_g1, const uint8_t* base
     // curve (var_msm_host's form) — the 288 n bytes of bases hide most of both accumulations.
     const int per = host_slice_per(n, K);
     const size_t padded = (size_t)K * per;
-    const size_t w1 = host_sliced_ws_bytes<G1Cfg>(K, per), w2 = host_sliced_ws_bytes<G2Cfg>(K, per);
+    const MsmPlan p1 = plan_for<G1Cfg>(per, false), p2 = plan_for<G2Cfg>(per, false);
+    const size_t w1 = host_sliced_ws_bytes<G1Cfg>(p1, K), w2 = host_sliced_ws_bytes<G2Cfg>(p2, K);
     if ((rc = ctx_reserve(c, pad256(padded * 32) + pad256(padded * 96) + pad256(padded * 192) + 1024 + w1 + w2 + 1024)))
       return rc;
     uint8_t* d_sc = c->arena;
@@ -299,15 +306,16 @@ static int var_double_msm_host_impl(const uint8_t* bases_g1, const uint8_t* base
     hipStream_t up = c->st[2];
     if (padded > (size_t)n) OZK_HIP(hipMemsetAsync(d_sc + (size_t)n * 32, 0, (padded - n) * 32, up));
     if ((rc = staged_h2d(c, d_sc, scalars, (size_t)n * 32, up))) return rc;
-    if ((rc = host_sliced_msm<G1Cfg>(c, bases_g1, nullptr, n, K, per, d_b1, d_sc, d_w1, d_out, c->slice_ev, c->st[0], up)))
+    if ((rc = host_sliced_msm<G1Cfg>(c, p1, bases_g1, nullptr, n, K, d_b1, d_sc, d_w1, d_out, c->slice_ev, c->st[0], up)))
       return rc;
-    if ((rc = host_sliced_msm<G2Cfg>(c, bases_g2, nullptr, n, K, per, d_b2, d_sc, d_w2, d_out + 256, c->slice_ev + K,
+    if ((rc = host_sliced_msm<G2Cfg>(c, p2, bases_g2, nullptr, n, K, d_b2, d_sc, d_w2, d_out + 256, c->slice_ev + K,
                                      c->st[1], up)))
       return rc;
     return finish(c, d_out, c->st[0], c->st[1]);
   }
   const size_t b1 = (size_t)n * 96, b2 = (size_t)n * 192, sc = (size_t)n * 32;
-  const size_t w1 = var_msm_ws_bytes<G1Cfg>(n), w2 = var_msm_ws_bytes<G2Cfg>(n);
+  // (sized as ozk_var_msm_workspace_bytes sizes them: var_msm_dev's lone plan never needs more)
+  const size_t w1 = var_msm_ws_bytes<G1Cfg>(plan_for<G1Cfg>(n, false)), w2 = var_msm_ws_bytes<G2Cfg>(plan_for<G2Cfg>(n, false));
   if ((rc = ctx_reserve(c, pad256(b1) + pad256(b2) + pad256(sc) + 1024 + pad256(w1) + pad256(w2) + 1024))) return rc;
   uint8_t* d_b1 = c->arena;
   uint8_t* d_b2 = d_b1 + pad256(b1);
@@ -433,7 +441,7 @@ ShardComm* shard_comm_get(int D) {
     if (ok) {
       const ncclResult_t r = g_rccl.CommInitAll(sc->comm.data(), D, devs.data());
       if (r != ncclSuccess) {
-        if (env_int("OZK_HOST_TRACE", 0)) fprintf(stderr, "[ozk] ncclCommInitAll(%d) failed: %s\n", D, g_rccl.GetErrorString(r));
+        if (knob(K_HOST_TRACE)) fprintf(stderr, "[ozk] ncclCommInitAll(%d) failed: %s\n", D, g_rccl.GetErrorString(r));
         ok = false;
       }
     }
@@ -486,7 +494,7 @@ static int var_msm_sharded(const uint8_t* b1, const uint8_t* b2, const uint8_t* 
   // takes the host form rather than wait (trylock)
   ShardComm* sc = nullptr;
   bool have_mu = false;
-  if (env_int("OZK_SHARD_RCCL", 1) && pthread_mutex_trylock(&g_shard_mu) == 0) {
+  if (knob(K_SHARD_RCCL) && pthread_mutex_trylock(&g_shard_mu) == 0) {
     have_mu = true;
     sc = shard_comm_get(D);
   }
@@ -622,14 +630,14 @@ void ozk_shard_comms_release(void) {
 // box (all slices on device 0): unverified on multi-GPU hardware.
 int ozk_var_msm_auto_host(const uint8_t* bases, const uint8_t* scalars, int32_t n, int32_t type, int32_t task_id,
                           uint8_t* out) {
-  if (env_int("OZK_SHARD", 0) && n >= env_int("OZK_SHARD_MIN_N", 1 << 21) && ozk_device_count() > 1)
-    return ozk_var_msm_sharded_host(bases, scalars, n, type, env_int("OZK_SHARD_COUNT", 0), out);
+  if (knob(K_SHARD) && n >= knob(K_SHARD_MIN_N) && ozk_device_count() > 1)
+    return ozk_var_msm_sharded_host(bases, scalars, n, type, knob(K_SHARD_COUNT), out);
   return ozk_var_msm_host(bases, scalars, n, type, task_id, out);
 }
 int ozk_var_double_msm_auto_host(const uint8_t* bases_g1, const uint8_t* bases_g2, const uint8_t* scalars, int32_t n,
                                  int32_t task_id, uint8_t* out) {
-  if (env_int("OZK_SHARD", 0) && n >= env_int("OZK_SHARD_MIN_N", 1 << 21) && ozk_device_count() > 1)
-    return ozk_var_double_msm_sharded_host(bases_g1, bases_g2, scalars, n, env_int("OZK_SHARD_COUNT", 0), out);
+  if (knob(K_SHARD) && n >= knob(K_SHARD_MIN_N) && ozk_device_count() > 1)
+    return ozk_var_double_msm_sharded_host(bases_g1, bases_g2, scalars, n, knob(K_SHARD_COUNT), out);
   return ozk_var_double_msm_host(bases_g1, bases_g2, scalars, n, task_id, out);
 }
 
@@ -637,7 +645,7 @@ static int points_sum_strided(const void* d_points, int k, int type, size_t stri
   hip_clear_stale();   // (ozk_common.h: a stale error of the calling thread is not this call's)
   if (!d_points || !d_out || k <= 0 || (stride_bytes & 3)) return fail(OZK_E_INVALID, "bad argument");
   return by_point_type(type, [&](auto t) {
-    hipLaunchKernelGGL((k_points_sum<typename decltype(t)::CV>), dim3(1), dim3(64), 0, st, (const u32*)d_points, k,
+    hipLaunchKernelGGL((k_points_sum<CV_OF(t)>), dim3(1), dim3(64), 0, st, (const u32*)d_points, k,
                        (int)(stride_bytes / 4), (u32*)d_out);
     OZK_HIP(hipGetLastError());
     return OZK_OK;

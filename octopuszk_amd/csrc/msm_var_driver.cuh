@@ -85,11 +85,17 @@ inline ProfState g_prof;
 
 // GLV needs 2n <= 2^24 sortable points (24-bit index in the packed coarse words).
 constexpr int GLV_MAX_N = 1 << 23;
+// Numbers that were tuning switches until their sweeps settled them (profiles/r02_schedule_experiments.txt,
+// r03_schedule_experiments.txt): slots per lane at the generic levels and buckets per lane per window-sum level (plan
+// fields LK and S), the LDS a G1 level-1 workgroup asks for (var_msm_accum), and the lane count below which the
+// remaining generic levels run in one single-block launch.
+constexpr int PLAN_LK = 16, PLAN_S = 4, L1_LDS_G1 = 41216, SMALL_LEVEL_LANES = 1024;
 
+// The curve-independent part of the plan.  The stages take plan_for's.
 static MsmPlan make_plan(int n) {
   MsmPlan p;
   p.n_in = n;
-  p.glv = env_int("OZK_MSM_GLV", 1) != 0 && n <= GLV_MAX_N;
+  p.glv = knob(K_MSM_GLV) != 0 && n <= GLV_MAX_N;
   p.n = p.glv ? 2 * n : n;
   // Window size by cost model: bucket additions (points x windows) plus ~3.4 addition-equivalents
   // per bucket for the window sums (two Jacobian additions of 16-18 multiplications against 10 for a
@@ -97,7 +103,7 @@ static MsmPlan make_plan(int n) {
   // bits: 9 windows, the ninth 7 bits wide) also piles thousands of entries into a few buckets and
   // wakes the generic reduction levels — measured on G2 at 2^18: 8.1 ms with c = 15, the model's
   // c = 16 avoids it.
-  const int sd_ok = p.glv && env_int("OZK_MSM_SIGNED", 1) != 0;
+  const int sd_ok = p.glv && knob(K_MSM_SIGNED) != 0;
   const int bits = p.glv ? 128 : 256;
   int c = 4;
   double best = 1e300;
@@ -121,11 +127,11 @@ static MsmPlan make_plan(int n) {
       c = k;
     }
   }
-  c = env_int("OZK_MSM_C", c);
+  c = knob_or(K_MSM_C, c);
   if (c < 1) c = 1;
   if (c > 16) c = 16;
   p.c = c;
-  p.sd = p.glv && c >= 2 && env_int("OZK_MSM_SIGNED", 1) != 0;
+  p.sd = sd_ok && c >= 2;
   p.cb = c - p.sd;
   p.W = ((p.glv ? 128 : 256) + c - 1) / c;
   // entries per level-1 lane: 56 at 2^20 (64 entries per bucket: a bucket is cut into ~2 pieces, which
@@ -139,7 +145,7 @@ static MsmPlan make_plan(int n) {
     // G2 2^20 -0.15 ms, a 2^20-constraint proof -0.3 ms; smaller MSMs lose 30-100 us with it)
     // (round 4, with the 8-byte entry stream: 52 measures 0.8 % above 56 and 48 on the 100-step bench, twice on one box —
     // 48 / 52 / 56 / 60 / 64 / 72 -> 702 / 709 / 703 / 694 / 670 / 637 Mscalar-mul/s, profiles/r04_l1_chunk_sweep.txt)
-    long long l1_min = env_int("OZK_MSM_L1_MIN", p.n >= (1 << 20) ? 52 : 40);
+    long long l1_min = p.n >= (1 << 20) ? 52 : 40;
     // SMALL MSMs (round 4): below ~2^17 pairs the launch does not fill the chip — 818 lanes at 2^10 — and the level is
     // a chain of L1 dependent additions on lone waves (~5 us each): 200 us of a 0.94 ms MSM at n = 2^10
     // (profiles/r04_small_n_probe.txt).  Shorter chunks, down to 8 entries, as long as (a) the lanes still fit one
@@ -160,14 +166,19 @@ static MsmPlan make_plan(int n) {
     }
     if (l1 < l1_min) l1 = l1_min;
     if (l1 > 1024) l1 = 1024;
-    p.L1 = env_int("OZK_MSM_L1", (int)l1);
+    p.L1 = knob_or(K_MSM_L1, (int)l1);
   }
-  p.LK = env_int("OZK_MSM_LK", 16);
   if (p.L1 < 2) p.L1 = 2;
-  if (p.LK < 4) p.LK = 4;
-  int S = env_int("OZK_MSM_S", 4);
-  int sg = ilog2((uint32_t)(S < 2 ? 2 : S));
-  p.S = 1 << sg;
+  p.LK = PLAN_LK;
+  p.S = PLAN_S;
+  p.lone = 0;
+  p.small_sort = p.n <= SORTS_MAX_N && p.cb <= SORTS_MAX_CB && knob(K_MSM_SMALL_SORT) != 0;
+  p.S_lat = p.S;
+  p.fin_max = knob(K_MSM_FIN_MAX);
+  if (p.fin_max < 1) p.fin_max = 1;
+  if (p.fin_max > 16) p.fin_max = 16;
+  p.tail_mode = knob(K_MSM_TAIL_MODE);
+  if (p.tail_mode != 0 && p.tail_mode != 1) p.tail_mode = -1;
   return p;
 }
 
@@ -182,18 +193,17 @@ static MsmPlan make_plan(int n) {
 // its three workgroups per CU: 2^20 = 1171 workgroups of 56 entries = 1.52 rounds of 768; 86 entries make it 763 (one
 // round): single MSM 2.52 -> 2.44 ms — and 85 entries (771 workgroups, three too many) 2.75 ms.  In the three-stage
 // schedule a one-round launch leaves the tails and the next sort no workgroup slot until it ends (86: 628 against
-// 690-709 Mscalar-mul/s), so the staged entry points keep the default chunk.  The single-call entry points mark their
-// thread (LonePlan) for the duration of the call.
-static thread_local int g_lone_plan = 0;
-struct LonePlan {
-  int prev;
-  LonePlan() : prev(g_lone_plan) { g_lone_plan = 1; }
-  ~LonePlan() { g_lone_plan = prev; }
-};
+// 690-709 Mscalar-mul/s), so the staged entry points keep the default chunk.  The single-call entry points
+// (var_msm_dev) ask for the `lone` plan.
+// The plan of ONE MSM: built once per call, after argument validation, and handed to every stage and size function.
 template <class CV>
-static MsmPlan plan_for(int n) {
+static MsmPlan plan_for(int n, bool lone) {
   MsmPlan p = make_plan(n);
-  if ((CV::LDS_ACC || g_lone_plan) && env_int("OZK_MSM_L1", 0) == 0 && env_int("OZK_MSM_L1_ROUNDS", 1) != 0) {
+  p.lone = lone;
+  // at most two rounds (2^21: 128 entries per lane, 11.30 -> 11.13 ms against the four rounds of 64; one round of
+  // 256 measures the same); OZK_MSM_L1_ROUNDS=0 switches the rule off, 1 asks for a single round
+  const long long max_rounds = knob(K_MSM_L1_ROUNDS);
+  if ((CV::LDS_ACC || lone) && knob_or(K_MSM_L1, 0) == 0 && max_rounds != 0) {
     static int cu_count = 0;   // (benign race: every thread computes the same value)
     if (cu_count == 0) {
       int dev = 0, cus = 0;
@@ -207,13 +217,17 @@ static MsmPlan plan_for(int n) {
     const long long cap = (long long)p.n * p.W;           // sorted entries (upper bound: zero digits are skipped)
     const long long blocks = ((cap + p.L1 - 1) / p.L1 + 255) / 256;
     long long rounds = blocks / slots > 0 ? blocks / slots : 1;
-    // at most two rounds (2^21: 128 entries per lane, 11.30 -> 11.13 ms against the four rounds of 64; one round of
-    // 256 measures the same); OZK_MSM_L1_ROUNDS=0 switches the rule off, 1 asks for a single round
-    const long long max_rounds = env_int("OZK_MSM_L1_ROUNDS", 2);
     if (rounds > max_rounds) rounds = max_rounds;
     long long l1 = (cap + 256LL * slots * rounds - 1) / (256LL * slots * rounds);
     if (l1 > p.L1 && l1 <= 1024) p.L1 = (int)l1;
   }
+  // The fused first level of a LATENCY tail: 8 buckets per lane for G1 (2^20: single MSM 2.63-2.71 -> 2.51-2.53 ms on
+  // one box; 16: 2.60), the plan's 4 for G2 (8: 7.43 against 7.38 ms).  Small MSMs — fewer than 2^13 buckets per
+  // window — keep 4: the serial part of the level is what they wait for (2^10: 0.84 -> 0.80 ms,
+  // profiles/r04_small_n_ab.txt).  The fused level's output is 64 S times smaller than its input, so it fits the tail
+  // buffers — sized for the plan's S — for ANY S.
+  const int s_lat = knob_or(K_MSM_S_LAT, std::is_same<CV, G1Cfg>::value && p.cb >= 13 ? 8 : p.S);
+  if (s_lat >= 2 && s_lat <= 64) p.S_lat = 1 << ilog2((uint32_t)s_lat);
   return p;
 }
 
@@ -300,9 +314,9 @@ MsmLayout make_layout3(const MsmPlan& p, void* sorted, void* sort_ws, void* accu
   return L;
 }
 template <class CV>
-RegionBytes region_bytes(int n) {
+RegionBytes region_bytes(const MsmPlan& p) {
   RegionBytes rb;
-  make_layout3<CV>(plan_for<CV>(n), nullptr, nullptr, nullptr, &rb);
+  make_layout3<CV>(p, nullptr, nullptr, nullptr, &rb);
   return rb;
 }
 
@@ -345,23 +359,13 @@ size_t tail_layout(const MsmPlan& p, MsmLayout& L, void* tail, size_t tail_bytes
 //     whatever runs beside it), so the cheaper form wins although it is 4 launches and ~40 dependent additions
 //     longer: 607 -> 664 Mscalar-mul/s at 2^20 (profiles/r03_schedule_experiments.txt).
 enum { TAIL_LATENCY = 0, TAIL_THROUGHPUT = 1 };
-struct TailShape {
-  bool fused;
-  int serial_above;
-};
-static TailShape tail_shape(int mode) {
-  const int forced = env_int("OZK_MSM_TAIL_MODE", -1);
-  if (forced == 0 || forced == 1) mode = forced;
-  TailShape t;
-  t.fused = env_int("OZK_MSM_WSUM_FUSED", mode == TAIL_THROUGHPUT ? 0 : 1) != 0;
-  t.serial_above = env_int("OZK_MSM_TAIL_SERIAL_ABOVE", mode == TAIL_THROUGHPUT ? 64 : (1 << 30));
-  return t;
-}
-// elements per window the first level leaves, and the g (log2 of buckets per element) they carry
-static void first_level_shape(const MsmPlan& p, bool fused, int* m_out, int* g_out) {
+constexpr int TAIL_SERIAL_ABOVE = 64;   // THROUGHPUT: serial levels down to this many elements per window
+// elements per window the first level leaves when a lane takes S buckets, and the g (log2 of buckets per element)
+// they carry
+static void first_level_shape(const MsmPlan& p, int S, bool fused, int* m_out, int* g_out) {
   const int m_in = 1 << p.cb;
-  const int nseg = (m_in + p.S - 1) / p.S;
-  const int sg = ilog2((uint32_t)p.S);
+  const int nseg = (m_in + S - 1) / S;
+  const int sg = ilog2((uint32_t)S);
   if (fused) {
     *m_out = (nseg + 63) / 64;
     *g_out = sg + 6;
@@ -370,32 +374,30 @@ static void first_level_shape(const MsmPlan& p, bool fused, int* m_out, int* g_o
     *g_out = sg;
   }
 }
-// First window-sum level, always the first kernel of the TAIL (it reads the bucket records of the tail region).
-// Fused form: a lane sums S = 4 buckets, its wave combines the 64 lane results in registers -> W * 2^cb / 256
-// elements.
+// First window-sum level with S buckets per lane, always the first kernel of the TAIL (it reads the bucket records of
+// the tail region).  No issue priority (above).
 template <class CV>
-void launch_wsum0(const MsmPlan& p, const MsmLayout& L, hipStream_t st, int prio, bool fused) {
+void launch_wsum0(const MsmPlan& p, const MsmLayout& L, hipStream_t st, int S, bool fused) {
   const int TB = 256;
   const int m_in = 1 << p.cb;
   int m_out, g;
-  first_level_shape(p, fused, &m_out, &g);
+  first_level_shape(p, S, fused, &m_out, &g);
   const int tot = m_out * p.W;
   if (fused)
-    hipLaunchKernelGGL((k_wsum_fused<CV>), dim3(tot), dim3(64), 0, st, L.buckets, L.hist_t, m_in, p.S,
-                       ilog2((uint32_t)p.S), L.wA[0], L.wR[0], m_out, p.W, prio);
+    hipLaunchKernelGGL((k_wsum_fused<CV>), dim3(tot), dim3(64), 0, st, L.buckets, L.hist_t, m_in, S,
+                       ilog2((uint32_t)S), L.wA[0], L.wR[0], m_out, p.W, 0);
   else
     hipLaunchKernelGGL((k_wsum<CV, true>), dim3((tot + TB - 1) / TB), dim3(TB), 0, st, (const u32*)nullptr,
-                       L.buckets, L.hist_t, m_in, p.S, 0, L.wA[0], L.wR[0], m_out, p.W, prio);
+                       L.buckets, L.hist_t, m_in, S, 0, L.wA[0], L.wR[0], m_out, p.W, 0);
 }
 
 // SORT stage: bases -> affine Montgomery, digits, two-level counting sort.  Memory / LDS-bound;
 // leaves the "sorted set".
 template <class CV>
-int var_msm_sort(const void* d_bases, const void* d_scalars, int n, void* sorted, size_t sorted_bytes,
+int var_msm_sort(const MsmPlan& p, const void* d_bases, const void* d_scalars, void* sorted, size_t sorted_bytes,
                         void* sort_ws, size_t sort_ws_bytes, hipStream_t st, hipEvent_t order_ev = nullptr,
                         const void* prepared = nullptr) {
   hip_clear_stale();   // (ozk_common.h: a stale error of the calling thread is not this call's)
-  const MsmPlan p = plan_for<CV>(n);
   if (prepared && p.glv && !p.sd) return fail(OZK_E_INVALID, "prepared bases need the signed-digit plan");
   RegionBytes rb;
   const MsmLayout L = make_layout3<CV>(p, sorted, sort_ws, nullptr, &rb, prepared);
@@ -406,7 +408,7 @@ int var_msm_sort(const void* d_bases, const void* d_scalars, int n, void* sorted
   const u32* bases = (const u32*)d_bases;
   const u32* scalars = (const u32*)d_scalars;
   const int n_in = p.n_in;
-  n = p.n;  // from here on: the points the pipeline sorts (2 * n_in with GLV)
+  const int n = p.n;  // the points the pipeline sorts (2 * n_in with GLV)
   OZK_HIP(hipMemsetAsync(L.total, 0, 4 * sizeof(u32), st));
   if (p.glv) {
     hipLaunchKernelGGL(k_digits_glv, dim3((n_in + TB - 1) / TB), dim3(TB), 0, st, scalars, n_in, p.c, p.W, p.sd,
@@ -420,10 +422,10 @@ int var_msm_sort(const void* d_bases, const void* d_scalars, int n, void* sorted
                          (const uint8_t*)nullptr);
     hipLaunchKernelGGL(k_digits, dim3((n_in + TB - 1) / TB), dim3(TB), 0, st, scalars, n_in, p.c, p.W, L.digits);
   }
-  if (n <= SORTS_MAX_N && p.cb <= SORTS_MAX_CB && env_int("OZK_MSM_SMALL_SORT", 1)) {
+  if (p.small_sort) {
     // a small MSM: the whole sort in one launch (msm_var.cuh k_sort_small); L.total[0] was zeroed above
     hipLaunchKernelGGL(k_sort_small, dim3(p.W), dim3(SORTS_BLOCK), 0, st, L.digits, n, p.cb, p.sd, L.total, L.hist, L.sent);
-    if (order_ev && env_int("OZK_MSM_ORDER", 1)) OZK_HIP(hipStreamWaitEvent(st, order_ev, 0));
+    if (order_ev) OZK_HIP(hipStreamWaitEvent(st, order_ev, 0));
     OZK_HIP(hipGetLastError());
     return OZK_OK;
   }
@@ -453,7 +455,7 @@ int var_msm_sort(const void* d_bases, const void* d_scalars, int n, void* sorted
   // Ordering hint for pipelined MSMs (see ozk_order_event_create, include/ozk.h): everything up to here may
   // overlap the previous MSM's window-sum levels; the bucket accumulation that follows fills every
   // SIMD's register file, so the previous MSM's single-wave Horner kernel has to be resident first.
-  if (order_ev && env_int("OZK_MSM_ORDER", 1)) OZK_HIP(hipStreamWaitEvent(st, order_ev, 0));
+  if (order_ev) OZK_HIP(hipStreamWaitEvent(st, order_ev, 0));
   // bins above the threshold (skewed digits), split over a fixed grid; no-ops otherwise
   hipLaunchKernelGGL(k_sortbig_list, dim3(1), dim3(256), 0, st, L.P1, L.total, L.nblk, nbins, big_thresh, L.bigbins);
   hipLaunchKernelGGL(k_sortbig_count, dim3(1024), dim3(SORT_BLOCK), 0, st, L.coarse, L.bigbins,
@@ -473,11 +475,11 @@ int var_msm_sort(const void* d_bases, const void* d_scalars, int n, void* sorted
 // of low-occupancy work that reads what level 1 wrote in the accumulate scratch and the sorted set.
 enum { ACCUM_ALL = 0, ACCUM_LEVEL1 = 1, ACCUM_REST = 2 };
 template <class CV>
-int var_msm_accum(int n, void* sorted, size_t sorted_bytes, void* accum_ws, size_t accum_ws_bytes, void* tail,
-                         size_t tail_bytes, hipStream_t st, const void* prepared = nullptr, int part = ACCUM_ALL) {
+int var_msm_accum(const MsmPlan& p, void* sorted, size_t sorted_bytes, void* accum_ws, size_t accum_ws_bytes,
+                         void* tail, size_t tail_bytes, hipStream_t st, const void* prepared = nullptr,
+                         int part = ACCUM_ALL) {
   hip_clear_stale();   // (ozk_common.h: a stale error of the calling thread is not this call's)
   using CT = CV;  // (an out-of-line-multiplication variant for the tails measured 40 % slower)
-  const MsmPlan p = plan_for<CV>(n);
   RegionBytes rb;
   MsmLayout L = make_layout3<CV>(p, sorted, nullptr, accum_ws, &rb, prepared);
   if (rb.sorted > sorted_bytes || rb.accum_ws > accum_ws_bytes)
@@ -506,7 +508,7 @@ int var_msm_accum(int n, void* sorted, size_t sorted_bytes, void* accum_ws, size
   // bench without the launch-order hint 417 -> 476 (with it: unchanged, 480).
   // 40.25 KiB, not the 48 KiB of rounds 1-2: three blocks then leave 39.25 KiB to whatever runs beside them, which
   // is what the next MSM's sort kernels (k_sort1_scatter 34 KiB, k_sort2 38 KiB) need to be resident at all.
-  if (!CV::LDS_ACC) acc_lds = (size_t)env_int("OZK_L1_LDS", 41216);
+  if (!CV::LDS_ACC) acc_lds = L1_LDS_G1;
   auto launch_l1 = [&](auto kern) {
     if (acc_lds > 65536)
       OZK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)acc_lds));
@@ -516,15 +518,8 @@ int var_msm_accum(int n, void* sorted, size_t sorted_bytes, void* accum_ws, size
                           L.buckets, L.slot_bid[0], L.slot_pts[0], (int)lanes, clk);
     return OZK_OK;
   };
-  // the lazily carried mixed addition (ec.cuh xyzz_madd_lazy) where the curve has it; OZK_L1_LAZY=0: the carried form
-  int rc_l1;
-  if constexpr (CV::LAZY_MADD) {
-    if (env_int("OZK_L1_LAZY", 1)) rc_l1 = launch_l1(k_segreduce<CV, true, true>);
-    else rc_l1 = launch_l1(k_segreduce<CV, true, false>);
-  } else {
-    rc_l1 = launch_l1(k_segreduce<CV, true, false>);
-  }
-  if (rc_l1) return rc_l1;
+  // the lazily carried mixed addition (ec.cuh xyzz_madd_lazy) where the curve has it
+  if (int rc_l1 = launch_l1(k_segreduce<CV, true, CV::LAZY_MADD>)) return rc_l1;
   }
   if (part == ACCUM_LEVEL1) {
     OZK_HIP(hipGetLastError());
@@ -540,10 +535,9 @@ int var_msm_accum(int n, void* sorted, size_t sorted_bytes, void* accum_ws, size
   // (they return at once when nothing survived)
   int cur = 0;
   bool first_generic = true;
-  const int small_lanes = env_int("OZK_MSM_SMALL_LEVEL_LANES", 1024);
   while (true) {
     lanes = (n_in + p.LK - 1) / p.LK;
-    if (!first_generic && (int)lanes <= small_lanes) {  // the remaining levels in one single-block launch
+    if (!first_generic && (int)lanes <= SMALL_LEVEL_LANES) {  // the remaining levels in one single-block launch
       hipLaunchKernelGGL((k_segreduce_small<CT>), dim3(1), dim3(TB), 0, st, L.total + 1, (int)n_in, p.LK, L.buckets,
                          L.slot_bid[cur], L.slot_pts[cur], L.slot_bid[cur ^ 1], L.slot_pts[cur ^ 1]);
       break;
@@ -563,55 +557,42 @@ int var_msm_accum(int n, void* sorted, size_t sorted_bytes, void* accum_ws, size
 
 // Head = SORT + ACCUMULATE on one stream, the three regions carved from one workspace.
 template <class CV>
-int var_msm_head(const void* d_bases, const void* d_scalars, int n, void* ws, size_t ws_bytes, void* tail,
+int var_msm_head(const MsmPlan& p, const void* d_bases, const void* d_scalars, void* ws, size_t ws_bytes, void* tail,
                         size_t tail_bytes, hipStream_t st, hipEvent_t order_ev = nullptr,
                         const void* prepared = nullptr) {
-  const RegionBytes rb = region_bytes<CV>(n);
+  const RegionBytes rb = region_bytes<CV>(p);
   if (rb.sorted + rb.sort_ws + rb.accum_ws > ws_bytes)
     return fail(OZK_E_INVALID, "workspace too small: need %zu bytes, got %zu", rb.sorted + rb.sort_ws + rb.accum_ws,
                 ws_bytes);
   uint8_t* w = (uint8_t*)ws;
-  int rc = var_msm_sort<CV>(d_bases, d_scalars, n, w, rb.sorted, w + rb.sorted, rb.sort_ws, st, order_ev, prepared);
+  int rc = var_msm_sort<CV>(p, d_bases, d_scalars, w, rb.sorted, w + rb.sorted, rb.sort_ws, st, order_ev, prepared);
   if (rc) return rc;
-  return var_msm_accum<CV>(n, w, rb.sorted, w + rb.sorted + rb.sort_ws, rb.accum_ws, tail, tail_bytes, st, prepared);
+  return var_msm_accum<CV>(p, w, rb.sorted, w + rb.sorted + rb.sort_ws, rb.accum_ws, tail, tail_bytes, st, prepared);
 }
 
 // Tail phase: the latency-bound remainder (wave-cooperative window-sum levels, Horner over the
 // windows, affine normalisation).  Reads only the tail buffers; writes the wire-out result.
 template <class CV>
-int var_msm_tail(int n, void* tail, size_t tail_bytes, void* d_out, hipStream_t st,
+int var_msm_tail(const MsmPlan& p, void* tail, size_t tail_bytes, void* d_out, hipStream_t st,
                         hipEvent_t order_ev = nullptr, int mode = TAIL_LATENCY) {
   hip_clear_stale();   // (ozk_common.h: a stale error of the calling thread is not this call's)
   using CT = CV;
-  MsmPlan p = plan_for<CV>(n);
   MsmLayout L;
-  L.m1 = (((size_t)1 << p.cb) + p.S - 1) / p.S;
   const size_t tneed = tail_layout<CV>(p, L, tail, tail_bytes);
   if (tneed > tail_bytes) return fail(OZK_E_INVALID, "tail buffer too small: need %zu bytes, got %zu", tneed, tail_bytes);
-  const TailShape shape = tail_shape(mode);
-  if (shape.fused && mode == TAIL_LATENCY) {
-    // the fused first level of a LONE tail: 8 buckets per lane for G1 (2^20: single MSM 2.63-2.71 -> 2.51-2.53 ms on
-    // one box; 16: 2.60), the plan's 4 for G2 (8: 7.43 against 7.38 ms).  The buffers are sized for the plan's S,
-    // which is never larger, so the fewer elements of a wider first level always fit.
-    // (small MSMs — fewer than 2^13 buckets per window — keep 4: the serial part of the level is what they wait for,
-    // 2^10: 0.84 -> 0.80 ms)
-    // (The fused level's output is 64 S times smaller than its input, so it fits the buffers — sized for the plan's
-    // S — for ANY S; the plain form needs S >= the plan's.)
-    int s_dflt = p.S;
-    if (std::is_same<CV, G1Cfg>::value && p.cb >= 13) s_dflt = 8;   // (below 2^13 buckets per window the plan's 4 measures
-                                                                      // as well or better: profiles/r04_small_n_ab.txt)
-    const int s_lat = env_int("OZK_MSM_S_LAT", s_dflt);
-    if (s_lat >= 2 && s_lat <= 64) p.S = 1 << ilog2((uint32_t)s_lat);
-  }
-  launch_wsum0<CV>(p, L, st, env_int("OZK_MSM_WSUM0_PRIO", 0), shape.fused);
+  // the shape the caller asks for unless the plan forces one; LATENCY: fused first level (as wide as the plan says
+  // when the caller asked for that shape itself), no serial levels
+  const int shape = p.tail_mode >= 0 ? p.tail_mode : mode;
+  const bool fused = shape == TAIL_LATENCY;
+  const int S0 = fused && mode == TAIL_LATENCY ? p.S_lat : p.S;
+  launch_wsum0<CV>(p, L, st, S0, fused);
   int m_in, g, k = 0;
-  first_level_shape(p, shape.fused, &m_in, &g);
+  first_level_shape(p, S0, fused, &m_in, &g);
   const int TB = 256;
   const int sg = ilog2((uint32_t)p.S);
   // Serial S-per-lane levels first in THROUGHPUT mode (3 additions per element instead of the wave form's 13, but
-  // 12 dependent additions deep per level); none in LATENCY mode (tail_shape above).
-  const int serial_above = shape.serial_above < 1 ? 1 : shape.serial_above;
-  while (m_in > serial_above) {
+  // 12 dependent additions deep per level); none in LATENCY mode.
+  while (shape == TAIL_THROUGHPUT && m_in > TAIL_SERIAL_ABOVE) {
     const int m_out = (m_in + p.S - 1) / p.S;
     const int tot = m_out * p.W;
     hipLaunchKernelGGL((k_wsum<CT, false>), dim3((tot + TB - 1) / TB), dim3(TB), 0, st, L.wA[k], L.wR[k],
@@ -620,20 +601,16 @@ int var_msm_tail(int n, void* tail, size_t tail_bytes, void* d_out, hipStream_t 
     g += sg;
     k ^= 1;
   }
-  // wave-cooperative levels until a handful of elements per window is left; k_finalize finishes those
-  int fin_max = env_int("OZK_MSM_FIN_MAX", 4);
-  if (fin_max < 1) fin_max = 1;
-  if (fin_max > 16) fin_max = 16;
   // Launch-order hint for pipelined MSMs: the event fires here, after the FIRST window-sum level, so that the next
   // accumulation starts as soon as its sort is done and the wave level behind this point is already resident.
-  // Round 1 recorded it after the wave level (OZK_MSM_ORDER_EARLY=0), when the accumulation kernel filled every
-  // register file; since that kernel is capped at 3 blocks per CU the late event only delays the next
-  // accumulation by ~0.18 ms per MSM: measured 538 (late) against 576 Mscalar-mul/s (early, or no hint at all).
+  // Round 1 recorded it after the wave level, when the accumulation kernel filled every register file; since that
+  // kernel is capped at 3 blocks per CU the late event only delayed the next accumulation by ~0.18 ms per MSM:
+  // measured 538 (late) against 576 Mscalar-mul/s (early, or no hint at all), and the late form is gone.
   // Also measured and not shipped (profiles/r02_schedule_experiments.txt): the merge of the level-1 pieces moved
   // from the head to the tail stream (524-550), a three-stage schedule sort | accumulate | tail (562-599).
-  const bool order_early = env_int("OZK_MSM_ORDER_EARLY", 1) != 0;
-  if (order_ev && order_early) OZK_HIP(hipEventRecord(order_ev, st));
-  while (m_in > fin_max) {
+  if (order_ev) OZK_HIP(hipEventRecord(order_ev, st));
+  // wave-cooperative levels until a handful of elements per window is left; k_finalize finishes those
+  while (m_in > p.fin_max) {
     const int m_out = (m_in + 63) / 64;
     const int tot = m_out * p.W;
     hipLaunchKernelGGL((k_wsum_wave<CT>), dim3(tot), dim3(64), 0, st, L.wA[k], L.wR[k], m_in, g, L.wA[k ^ 1],
@@ -642,7 +619,6 @@ int var_msm_tail(int n, void* tail, size_t tail_bytes, void* d_out, hipStream_t 
     g += 6;
     k ^= 1;
   }
-  if (order_ev && !order_early) OZK_HIP(hipEventRecord(order_ev, st));  // the multi-wave levels are done
   // one wave: Horner over the windows is serial
   hipLaunchKernelGGL((k_finalize<CT>), dim3(1), dim3(64), 0, st, L.wA[k], L.wR[k], m_in, g, p.W, p.c, p.sd,
                      (u32*)d_out);
@@ -651,37 +627,35 @@ int var_msm_tail(int n, void* tail, size_t tail_bytes, void* d_out, hipStream_t 
 }
 
 template <class CV>
-size_t var_msm_tail_bytes(int n) {
-  const MsmPlan p = plan_for<CV>(n);
+size_t var_msm_tail_bytes(const MsmPlan& p) {
   MsmLayout L;
-  L.m1 = (((size_t)1 << p.cb) + p.S - 1) / p.S;
   return tail_layout<CV>(p, L, nullptr, 0);
+}
+
+template <class CV>
+size_t var_msm_head_ws_bytes(const MsmPlan& p) {
+  const RegionBytes rb = region_bytes<CV>(p);
+  return rb.sorted + rb.sort_ws + rb.accum_ws;
+}
+template <class CV>
+size_t var_msm_ws_bytes(const MsmPlan& p) {
+  return var_msm_head_ws_bytes<CV>(p) + var_msm_tail_bytes<CV>(p);
 }
 
 // head + tail on one stream, the tail buffers carved from the end of the workspace
 template <class CV>
 int var_msm_dev(const void* d_bases, const void* d_scalars, int n, void* d_out, void* ws,
                        size_t ws_bytes, hipStream_t st, const void* prepared = nullptr) {
-  LonePlan lone;   // (before any size is computed: the lone plan's regions are never larger than the staged plan's)
-  const RegionBytes rb0 = region_bytes<CV>(n);
-  const size_t main_bytes = rb0.sorted + rb0.sort_ws + rb0.accum_ws;
-  const size_t tb = var_msm_tail_bytes<CV>(n);
+  // the LONE plan: its regions are never larger than those of the staged plan the size queries report
+  const MsmPlan p = plan_for<CV>(n, true);
+  const size_t main_bytes = var_msm_head_ws_bytes<CV>(p);
+  const size_t tb = var_msm_tail_bytes<CV>(p);
   if (main_bytes + tb > ws_bytes)
     return fail(OZK_E_INVALID, "workspace too small: need %zu bytes, got %zu", main_bytes + tb, ws_bytes);
   uint8_t* tail = (uint8_t*)ws + main_bytes;
-  int rc = var_msm_head<CV>(d_bases, d_scalars, n, ws, main_bytes, tail, tb, st, nullptr, prepared);
+  int rc = var_msm_head<CV>(p, d_bases, d_scalars, ws, main_bytes, tail, tb, st, nullptr, prepared);
   if (rc) return rc;
-  return var_msm_tail<CV>(n, tail, tb, d_out, st);
-}
-
-template <class CV>
-size_t var_msm_head_ws_bytes(int n) {
-  const RegionBytes rb = region_bytes<CV>(n);
-  return rb.sorted + rb.sort_ws + rb.accum_ws;
-}
-template <class CV>
-size_t var_msm_ws_bytes(int n) {
-  return var_msm_head_ws_bytes<CV>(n) + var_msm_tail_bytes<CV>(n);
+  return var_msm_tail<CV>(p, tail, tb, d_out, st);
 }
 
 // host-buffer variant (what the JNI native calls): staged upload, run, download, all on a cached context
@@ -700,9 +674,9 @@ size_t var_msm_ws_bytes(int n) {
 // 2^17 MSM takes as long as a 2^18 one, tools/host_slices_probe.py), at most OZK_HOST_SLICES (8).  Measured
 // ozk_var_msm_host at 2^20 G1: 6.0 ms unsliced, 4.8 ms in 4 slices; 2^22: 19.7 -> 12.8 ms in 8; G2 2^20: 13.6 -> 11.5.
 inline int host_slices(int n) {
-  int kmax = env_int("OZK_HOST_SLICES", 8);
+  int kmax = knob(K_HOST_SLICES);
   if (kmax > MAX_SLICES) kmax = MAX_SLICES;
-  int min_log = env_int("OZK_HOST_SLICE_MIN_LOG", 18);  // (tests lower it to slice small inputs)
+  int min_log = knob(K_HOST_SLICE_MIN_LOG);  // (tests lower it to slice small inputs)
   if (min_log < 4) min_log = 4;
   if (min_log > 30) min_log = 30;
   int k = n >> min_log;
@@ -713,46 +687,47 @@ inline int host_slices(int n) {
 // Size of the first K - 1 slices.  The LAST slice is the one whose sort + accumulation cannot hide under an upload,
 // so it gets half an average slice (n / 2K pairs) and the others share the rest (2^20: G1 unchanged at 4.8 ms, G2
 // 11.2 -> 11.0 ms, the double MSM 13.95 -> 13.5 ms).
-// (OZK_HOST_SLICE_TAPER=0: K equal slices.)
+// (Against K equal slices: profiles/r02_host_path.txt.)
 inline int host_slice_per(int n, int K) {
   if (K < 2) return n;
-  if (env_int("OZK_HOST_SLICE_TAPER", 1) == 0) return (n + K - 1) / K;
   const long long rest = (long long)n - (long long)n / (2 * K);
   return (int)((rest + K - 2) / (K - 1));
 }
-static bool plans_agree(int n1, int n2) {
-  const MsmPlan a = make_plan(n1), b = make_plan(n2);
+static bool plans_agree(const MsmPlan& a, const MsmPlan& b) {
   return a.c == b.c && a.cb == b.cb && a.W == b.W && a.sd == b.sd && a.glv == b.glv && a.S == b.S;
 }
 
-// The sliced part of a host MSM, on a context the caller holds: K - 1 slices of `per` pairs and a last one with the
+// The sliced part of a host MSM, on a context the caller holds: K - 1 slices of `per` pairs (p, the staged plan of
+// `per` pairs: per = p.n_in) and a last one with the
 // rest (run with its own size when its plan has the same windows as the others', else padded to `per`).
 // d_bases / d_sc hold K * per records; `scalars` == nullptr: the caller has already queued the upload of ALL scalars
 // (and the zero padding) on `up`, so only the bases go up here.  Slice events ev[0 .. K).  Leaves the result
 // (wire-out) in d_out on `st`.
 template <class CV>
-size_t host_sliced_ws_bytes(int K, int per) {
-  return pad256(var_msm_head_ws_bytes<CV>(per)) + (size_t)K * pad256(var_msm_tail_bytes<CV>(per));
+size_t host_sliced_ws_bytes(const MsmPlan& p, int K) {
+  return pad256(var_msm_head_ws_bytes<CV>(p)) + (size_t)K * pad256(var_msm_tail_bytes<CV>(p));
 }
 template <class CV>
-int host_sliced_msm(HostCtx* c, const uint8_t* bases, const uint8_t* scalars, int n, int K, int per, uint8_t* d_bases,
-                    uint8_t* d_sc, uint8_t* d_ws, uint8_t* d_out, hipEvent_t* ev, hipStream_t st, hipStream_t up) {
+int host_sliced_msm(HostCtx* c, const MsmPlan& p, const uint8_t* bases, const uint8_t* scalars, int n, int K,
+                    uint8_t* d_bases, uint8_t* d_sc, uint8_t* d_ws, uint8_t* d_out, hipEvent_t* ev, hipStream_t st,
+                    hipStream_t up) {
   hip_clear_stale();   // (ozk_common.h: a stale error of the calling thread is not this call's)
   using IO = CurveIO<CV>;
   const size_t base_rec = (size_t)IO::WIRE_JAC_WORDS * 4;
+  const int per = p.n_in;
   const size_t padded = (size_t)K * per;
-  const size_t main_bytes = pad256(var_msm_head_ws_bytes<CV>(per));
-  const size_t tb = pad256(var_msm_tail_bytes<CV>(per));
+  const size_t main_bytes = pad256(var_msm_head_ws_bytes<CV>(p));
+  const size_t tb = pad256(var_msm_tail_bytes<CV>(p));
   uint8_t* d_tails = d_ws + main_bytes;
   int rc;
   const long long last_ns = (long long)n - (long long)(K - 1) * per;
   if (last_ns < 1) return fail(OZK_E_INTERNAL, "slice plan: %d slices of %d pairs exceed n = %d", K, per, n);
-  const bool exact_last = last_ns < per && plans_agree(per, (int)last_ns);
+  const MsmPlan p_last = plan_for<CV>((int)last_ns, false);   // the last slice's own plan, used if its windows agree
+  const bool exact_last = last_ns < per && plans_agree(p, p_last);
   if (padded > (size_t)n && !exact_last) {
     if (scalars) OZK_HIP(hipMemsetAsync(d_sc + (size_t)n * 32, 0, (padded - n) * 32, up));
     OZK_HIP(hipMemsetAsync(d_bases + (size_t)n * base_rec, 0, (padded - n) * base_rec, up));  // Z = 0: infinity
   }
-  const MsmPlan p = plan_for<CV>(per);
   SliceBuckets sb = {};
   for (int s = 0; s < K; s++) {
     const size_t lo = (size_t)s * per;
@@ -762,8 +737,8 @@ int host_sliced_msm(HostCtx* c, const uint8_t* bases, const uint8_t* scalars, in
     OZK_HIP(hipEventRecord(ev[s], up));
     OZK_HIP(hipStreamWaitEvent(st, ev[s], 0));
     uint8_t* tail = d_tails + (size_t)s * tb;
-    const int n_head = (s == K - 1 && exact_last) ? (int)last_ns : per;
-    if ((rc = var_msm_head<CV>(d_bases + lo * base_rec, d_sc + lo * 32, n_head, d_ws, main_bytes, tail, tb, st))) return rc;
+    const MsmPlan& p_head = (s == K - 1 && exact_last) ? p_last : p;
+    if ((rc = var_msm_head<CV>(p_head, d_bases + lo * base_rec, d_sc + lo * 32, d_ws, main_bytes, tail, tb, st))) return rc;
     MsmLayout L;
     tail_layout<CV>(p, L, tail, tb);
     sb.buckets[s] = L.buckets;
@@ -773,7 +748,7 @@ int host_sliced_msm(HostCtx* c, const uint8_t* bases, const uint8_t* scalars, in
   hipLaunchKernelGGL((k_bucket_combine<CV>), dim3((unsigned)((NB + 255) / 256)), dim3(256), 0, st, sb, K,
                      (u32*)sb.buckets[0], (u32*)sb.hist[0], NB);
   OZK_HIP(hipGetLastError());
-  return var_msm_tail<CV>(per, d_tails, tb, d_out, st);
+  return var_msm_tail<CV>(p, d_tails, tb, d_out, st);
 }
 
 // where a host entry point's result goes: the caller's host memory (through the context's pinned result buffer), or —
@@ -800,7 +775,7 @@ int var_msm_host(const uint8_t* bases, const uint8_t* scalars, int n, int task_i
   const int K = host_slices(n);
   if (K == 1) {
     const size_t base_bytes = (size_t)n * base_rec, sc_bytes = (size_t)n * 32;
-    const size_t ws_bytes = var_msm_ws_bytes<CV>(n);
+    const size_t ws_bytes = var_msm_ws_bytes<CV>(plan_for<CV>(n, false));   // as ozk_var_msm_workspace_bytes sizes it
     if ((rc = ctx_reserve(c, pad256(base_bytes) + pad256(sc_bytes) + 1024 + ws_bytes + 1024))) return rc;
     uint8_t* d_bases = c->arena;
     uint8_t* d_sc = d_bases + pad256(base_bytes);
@@ -813,15 +788,16 @@ int var_msm_host(const uint8_t* bases, const uint8_t* scalars, int n, int task_i
     return host_result(c, out, d_result, d_out, out_bytes, st);
   }
   const int per = host_slice_per(n, K);          // workspace and tails are laid out for `per` pairs
+  const MsmPlan p = plan_for<CV>(per, false);
   const size_t padded = (size_t)K * per;
-  if ((rc = ctx_reserve(c, pad256(padded * base_rec) + pad256(padded * 32) + 1024 + host_sliced_ws_bytes<CV>(K, per) + 1024)))
+  if ((rc = ctx_reserve(c, pad256(padded * base_rec) + pad256(padded * 32) + 1024 + host_sliced_ws_bytes<CV>(p, K) + 1024)))
     return rc;
   uint8_t* d_bases = c->arena;
   uint8_t* d_sc = d_bases + pad256(padded * base_rec);
   uint8_t* d_out = d_sc + pad256(padded * 32);
   uint8_t* d_ws = d_out + 1024;
   // uploads on the context's copy stream: they must not wait behind kernels
-  if ((rc = host_sliced_msm<CV>(c, bases, scalars, n, K, per, d_bases, d_sc, d_ws, d_out, c->slice_ev, c->st[0], c->st[2])))
+  if ((rc = host_sliced_msm<CV>(c, p, bases, scalars, n, K, d_bases, d_sc, d_ws, d_out, c->slice_ev, c->st[0], c->st[2])))
     return rc;
   return host_result(c, out, d_result, d_out, out_bytes, c->st[0]);
 }
@@ -830,8 +806,7 @@ int var_msm_host(const uint8_t* bases, const uint8_t* scalars, int n, int task_i
 // array, kept in HBM across MSMs.  A Groth16 proving key is fixed; the reference re-marshals and
 // re-uploads it for every proof (VariableBaseMSM.java:224-227).
 template <class CV>
-size_t prepared_bytes(int n) {
-  const MsmPlan p = plan_for<CV>(n);
+size_t prepared_bytes(const MsmPlan& p) {
   return (((size_t)p.n * CurveIO<CV>::AFF_WORDS * sizeof(u32)) + 255) & ~(size_t)255;
 }
 template <class CV>
@@ -839,7 +814,7 @@ int var_msm_prepare(const void* d_bases, int n, void* d_prepared, size_t bytes, 
   hip_clear_stale();   // (ozk_common.h: a stale error of the calling thread is not this call's)
   const MsmPlan p = make_plan(n);
   if (p.glv && !p.sd) return fail(OZK_E_INVALID, "prepared bases need the signed-digit plan");
-  if (bytes < prepared_bytes<CV>(n)) return fail(OZK_E_INVALID, "prepared buffer too small");
+  if (bytes < prepared_bytes<CV>(p)) return fail(OZK_E_INVALID, "prepared buffer too small");
   hipLaunchKernelGGL((k_convert_bases<CV>), dim3((n + 255) / 256), dim3(256), 0, st, (const u32*)d_bases,
                      (u32*)d_prepared, n, p.glv, (const uint8_t*)nullptr);
   OZK_HIP(hipGetLastError());
@@ -870,8 +845,9 @@ int bases_create(const uint8_t* bases, int n, int type, int task_id, BasesHandle
   h->n = n;
   h->type = type == OZK_G1 ? OZK_G1 : OZK_G2;
   pthread_mutex_init(&h->mu, nullptr);
-  const size_t wire = (size_t)n * IO::WIRE_JAC_WORDS * 4, pb = prepared_bytes<CV>(n);
-  h->ws_bytes = var_msm_ws_bytes<CV>(n);
+  const MsmPlan p = plan_for<CV>(n, false);   // sizes as the public queries report them
+  const size_t wire = (size_t)n * IO::WIRE_JAC_WORDS * 4, pb = prepared_bytes<CV>(p);
+  h->ws_bytes = var_msm_ws_bytes<CV>(p);
   hipError_t e = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking);
   uint8_t* d_wire = nullptr;
   if (e == hipSuccess) e = hipMalloc((void**)&h->d_prepared, pb);
@@ -941,20 +917,21 @@ int bases_msm(BasesHandle* h, const uint8_t* scalars, uint8_t* out) {
 
 // the G2 instantiations live in msm_var_g2.hip
 #define OZK_G2_DRIVER_INSTANCES(PREFIX)                                                                              \
-  PREFIX template int ozk::var_msm_sort<ozk::G2Cfg>(const void*, const void*, int, void*, size_t, void*, size_t,    \
-                                                    hipStream_t, hipEvent_t, const void*);                          \
-  PREFIX template int ozk::var_msm_accum<ozk::G2Cfg>(int, void*, size_t, void*, size_t, void*, size_t, hipStream_t,  \
-                                                     const void*, int);                                              \
-  PREFIX template int ozk::var_msm_head<ozk::G2Cfg>(const void*, const void*, int, void*, size_t, void*, size_t,     \
-                                                    hipStream_t, hipEvent_t, const void*);                          \
-  PREFIX template int ozk::var_msm_tail<ozk::G2Cfg>(int, void*, size_t, void*, hipStream_t, hipEvent_t, int);        \
+  PREFIX template int ozk::var_msm_sort<ozk::G2Cfg>(const ozk::MsmPlan&, const void*, const void*, void*, size_t, void*, \
+                                                    size_t, hipStream_t, hipEvent_t, const void*);                  \
+  PREFIX template int ozk::var_msm_accum<ozk::G2Cfg>(const ozk::MsmPlan&, void*, size_t, void*, size_t, void*, size_t, \
+                                                     hipStream_t, const void*, int);                                 \
+  PREFIX template int ozk::var_msm_head<ozk::G2Cfg>(const ozk::MsmPlan&, const void*, const void*, void*, size_t, void*, \
+                                                    size_t, hipStream_t, hipEvent_t, const void*);                  \
+  PREFIX template int ozk::var_msm_tail<ozk::G2Cfg>(const ozk::MsmPlan&, void*, size_t, void*, hipStream_t, hipEvent_t, \
+                                                    int);                                                            \
   PREFIX template int ozk::var_msm_dev<ozk::G2Cfg>(const void*, const void*, int, void*, void*, size_t, hipStream_t,  \
                                                    const void*);                                                     \
   PREFIX template int ozk::var_msm_host<ozk::G2Cfg>(const uint8_t*, const uint8_t*, int, int, uint8_t*, uint8_t*);             \
-  PREFIX template size_t ozk::host_sliced_ws_bytes<ozk::G2Cfg>(int, int);                                            \
-  PREFIX template int ozk::host_sliced_msm<ozk::G2Cfg>(ozk::HostCtx*, const uint8_t*, const uint8_t*, int, int, int, \
-                                                       uint8_t*, uint8_t*, uint8_t*, uint8_t*, hipEvent_t*,         \
-                                                       hipStream_t, hipStream_t);                                   \
+  PREFIX template size_t ozk::host_sliced_ws_bytes<ozk::G2Cfg>(const ozk::MsmPlan&, int);                            \
+  PREFIX template int ozk::host_sliced_msm<ozk::G2Cfg>(ozk::HostCtx*, const ozk::MsmPlan&, const uint8_t*,           \
+                                                       const uint8_t*, int, int, uint8_t*, uint8_t*, uint8_t*,      \
+                                                       uint8_t*, hipEvent_t*, hipStream_t, hipStream_t);            \
   PREFIX template int ozk::var_msm_prepare<ozk::G2Cfg>(const void*, int, void*, size_t, hipStream_t);                \
   PREFIX template int ozk::bases_create<ozk::G2Cfg>(const uint8_t*, int, int, int, ozk::BasesHandle**);              \
   PREFIX template int ozk::bases_msm<ozk::G2Cfg>(ozk::BasesHandle*, const uint8_t*, uint8_t*);

@@ -4,7 +4,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <pthread.h>
 #include <stdlib.h>
 #include <stdarg.h>
@@ -13,6 +12,7 @@
 #include <string.h>
 
 #include "../../include/ozk.h"
+#include "knobs.h"   // the tuning switches: knob(), knob_or(), env_reload()
 
 namespace ozk {
 
@@ -77,52 +77,6 @@ inline int ilog2(uint32_t v) {
   while (v >>= 1) r++;
   return r;
 }
-// Tuning switches (OZK_* environment variables) are read ONCE and cached: an MSM asks for its plan several
-// times (workspace-size query, head, tail), and a variable changing in between would desynchronise the
-// layouts.  ozk_tuning_reload() (tests, tuning scripts) drops the cache.
-// The cache is PER THREAD (round 4): a host entry point reads dozens of knobs, and through round 3 every read
-// took one process-wide mutex — eight Spark task threads on eight devices serialised on it.  A thread's table
-// is valid for one generation of the process-wide counter that env_reload() bumps; a read costs a pointer
-// compare (the names are string literals) or a short strcmp, no lock and no shared write.
-inline std::atomic<unsigned>& env_generation() {
-  static std::atomic<unsigned> g(1);
-  return g;
-}
-struct EnvCache {
-  unsigned gen = 0;
-  int n = 0;
-  const char* ptr[96];
-  char names[96][40];
-  int vals[96];
-  bool has[96];
-};
-inline int env_int(const char* name, int dflt) {
-  static thread_local EnvCache c;
-  const unsigned g = env_generation().load(std::memory_order_acquire);
-  if (c.gen != g) {
-    c.gen = g;
-    c.n = 0;
-  }
-  int k = 0;
-  for (; k < c.n; k++)
-    if (c.ptr[k] == name || strcmp(c.names[k], name) == 0) break;
-  if (k == c.n) {
-    const char* s = getenv(name);
-    const bool has = s && *s;
-    const int val = has ? atoi(s) : 0;
-    if (c.n < 96 && strlen(name) < 40) {
-      c.ptr[k] = name;
-      strcpy(c.names[k], name);
-      c.has[k] = has;
-      c.vals[k] = val;
-      c.n++;
-    }
-    return has ? val : dflt;
-  }
-  return c.has[k] ? c.vals[k] : dflt;
-}
-inline void env_reload() { env_generation().fetch_add(1, std::memory_order_acq_rel); }
-
 // The calling thread's HIP error state may hold an error left by somebody else's call (another native library in
 // the same process, torch's probes; the runtime keeps the last NON-success code until it is read —
 // hip_runtime_api.h, hipGetLastError).  Every function here that checks its kernel launches with
