@@ -1,6 +1,6 @@
 // BACE on the GPU: Williams' Merlin-Arthur proof for batch arithmetic-circuit evaluation (the reference's bace/
 // package: Prover.computeProof, Verifier.verifyProof / getResult, NaiveEvaluator.getResult, Common.getInputPolynomials).
-// Included at the end of fft.hip: it reuses that unit's twiddle plans (plan_get), its tiled pass kernel (fft_core,
+// Included at the end of fft.hip: it reuses that unit's twiddle plans (domain_tables), its tiled pass kernel (fft_core,
 // batched through PassArgs::in_cs / out_cs) and its block sum (r1cs_block_sum).  DESIGN.md section 11.
 //
 //   n inputs per instance, N instances (a power of two), circuit degree deg, D = lowestPowerOfTwo(deg N).
@@ -49,29 +49,6 @@ static void bace_inv_pow2_host(int k, bool mont, u32 (&out)[8]) {
   else from_mont(a, out);
 }
 
-// small host values reach the device as kernel arguments (captured at launch: no host buffer has to outlive the call)
-struct BaceWords {
-  u32 w[32];
-};
-__global__ void k_bace_put(BaceWords c, int nw, u32* __restrict__ dst) {
-  for (int i = threadIdx.x; i < nw; i += blockDim.x) dst[i] = c.w[i];
-}
-
-__device__ __forceinline__ void bace_store(u32* dst, const Fe<FrP, 16>& v) {
-  u32 o[8];
-  pack(v, o);
-  uint4* d = reinterpret_cast<uint4*>(dst);
-  d[0] = make_uint4(o[0], o[1], o[2], o[3]);
-  d[1] = make_uint4(o[4], o[5], o[6], o[7]);
-}
-template <int B = 85>
-__device__ __forceinline__ Fe<FrP, B> bace_load(const u32* src) {
-  const uint4* s = reinterpret_cast<const uint4*>(src);
-  const uint4 a = s[0], b = s[1];
-  const u32 w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  return unpack<FrP, B>(w);
-}
-
 // ---- the columns ----
 // out[j N + k] = in[k n + j] / N (row-major instances -> column-major, with the 1/N of the inverse transforms that
 // follow: the transform is linear, so scaling its input is the same as scaling its output).  k_mont = (1/N) R.
@@ -80,8 +57,8 @@ __global__ void __launch_bounds__(256) k_bace_to_cols(const u32* __restrict__ in
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (long long)n * N) return;
   const long long j = t / N, k = t % N;
-  const auto x = bace_load<85>(in + ((size_t)k * n + (size_t)j) * 8);
-  bace_store(out + (size_t)t * 8, canonical(mul(x, ElemTraits<Fe<FrP, 16>>::load(k_mont))));
+  const auto x = fr_load<85>(in + ((size_t)k * n + (size_t)j) * 8);
+  fr_store(canonical(mul(x, ElemTraits<Fe<FrP, 16>>::load(k_mont))), out + (size_t)t * 8);
 }
 
 // ---- transforms up to BACE_LDS_FFT_MAX: one workgroup per column, the whole column in LDS ----
@@ -96,7 +73,7 @@ __global__ void __launch_bounds__(256) k_bace_fft_lds(const u32* in, size_t in_c
   for (int i = threadIdx.x; i < n; i += 256) {
     const int s = logn ? (int)(__brev((unsigned)i) >> (32 - logn)) : 0;
     u32 o[8];
-    pack(canonical(bace_load<85>(src + (size_t)s * 8)), o);
+    pack(canonical(fr_load<85>(src + (size_t)s * 8)), o);
 #pragma unroll
     for (int k = 0; k < 8; k++) lds[i * 8 + k] = o[k];
   }
@@ -121,7 +98,7 @@ __global__ void __launch_bounds__(256) k_bace_fft_lds(const u32* in, size_t in_c
     block_sync();
   }
   u32* dst = out + (size_t)blockIdx.x * out_cs;
-  for (int i = threadIdx.x; i < n; i += 256) bace_store(dst + (size_t)i * 8, canonical(ET::load(lds + i * 8)));
+  for (int i = threadIdx.x; i < n; i += 256) fr_store(canonical(ET::load(lds + i * 8)), dst + (size_t)i * 8);
 }
 
 // ---- the circuit interpreter ----
@@ -153,7 +130,7 @@ __device__ __forceinline__ BaceV bace_slot_get(const BaceEval& e, const u32* lds
     for (int i = 0; i < 9; i++) v.l[i] = lds[(s * 9 + i) * BACE_WG + threadIdx.x];
     return v;
   }
-  return bace_load<32>(e.hbm + ((size_t)(s - e.lds_slots) * e.lanes + g) * 8);
+  return fr_load<32>(e.hbm + ((size_t)(s - e.lds_slots) * e.lanes + g) * 8);
 }
 __device__ __forceinline__ void bace_slot_put(const BaceEval& e, u32* lds, int s, int g, const BaceV& v) {
   if (s < e.lds_slots) {
@@ -161,11 +138,7 @@ __device__ __forceinline__ void bace_slot_put(const BaceEval& e, u32* lds, int s
     for (int i = 0; i < 9; i++) lds[(s * 9 + i) * BACE_WG + threadIdx.x] = v.l[i];
     return;
   }
-  u32 o[8];
-  pack(v, o);
-  uint4* d = reinterpret_cast<uint4*>(e.hbm + ((size_t)(s - e.lds_slots) * e.lanes + g) * 8);
-  d[0] = make_uint4(o[0], o[1], o[2], o[3]);
-  d[1] = make_uint4(o[4], o[5], o[6], o[7]);
+  fr_store(v, e.hbm + ((size_t)(s - e.lds_slots) * e.lanes + g) * 8);
 }
 
 __global__ void __launch_bounds__(BACE_WG) k_bace_circuit(BaceEval e) {
@@ -179,7 +152,7 @@ __global__ void __launch_bounds__(BACE_WG) k_bace_circuit(BaceEval e) {
       const int4 op = e.prog[t];
       BaceV v;
       if (op.x == 0) {
-        v = BaceV(mul(bace_load<85>(e.in + (size_t)p * e.pstride + (size_t)op.z * e.jstride), r2));
+        v = BaceV(mul(fr_load<85>(e.in + (size_t)p * e.pstride + (size_t)op.z * e.jstride), r2));
       } else if (op.x == 1) {
         v = BaceV(ElemTraits<Fe<FrP, 16>>::load(e.consts + (size_t)op.z * 8));
       } else if (op.x == 2) {
@@ -190,7 +163,7 @@ __global__ void __launch_bounds__(BACE_WG) k_bace_circuit(BaceEval e) {
       bace_slot_put(e, lds, op.y, g, v);
       last = v;
     }
-    bace_store(e.out + (size_t)p * 8, canonical(mul(last, ko)));   // Montgomery x plain = plain
+    fr_store(canonical(mul(last, ko)), e.out + (size_t)p * 8);   // Montgomery x plain = plain
   }
 }
 
@@ -198,14 +171,6 @@ __global__ void __launch_bounds__(BACE_WG) k_bace_circuit(BaceEval e) {
 // Lane g of polynomial y (S = gridDim.x x 256 lanes per polynomial) runs Horner in r^S over the coefficients
 // c[g], c[g + S], ... (consecutive lanes read consecutive coefficients), multiplies by r^g, and the workgroup's sum
 // goes to partial[y gridDim.x + blockIdx.x]; k_bace_sum_partials adds each polynomial's partials.
-__device__ __forceinline__ BaceV bace_pow(const Fe<FrP, 16>& b, u32 e) {
-  BaceV r = BaceV(fe_one<FrP>());
-  for (int i = 31; i >= 0; i--) {
-    r = BaceV(sqr(r));
-    if ((e >> i) & 1) r = BaceV(mul(r, b));
-  }
-  return r;
-}
 __global__ void __launch_bounds__(256) k_fr_poly_eval(const u32* __restrict__ c, size_t poly_cs, int len,
                                                       const u32* __restrict__ r_mont, u32* __restrict__ partial) {
   __shared__ u32 part[9 * 256];
@@ -215,21 +180,21 @@ __global__ void __launch_bounds__(256) k_fr_poly_eval(const u32* __restrict__ c,
   const auto r = ElemTraits<Fe<FrP, 16>>::load(r_mont);
   FrAcc acc = FrAcc(fe_zero<FrP>());
   if (g < (u32)len) {
-    const BaceV rS = bace_pow(r, S);
+    const BaceV rS = fe_pow_u32(r, S);
     for (long long k = ((u32)len - 1 - g) / S; k >= 0; k--)   // plain: (acc rS R) / R
-      acc = FrAcc(reduce_to<32>(add(mul(acc, rS), bace_load<16>(cp + ((size_t)g + (size_t)k * S) * 8))));
-    acc = FrAcc(mul(acc, bace_pow(r, g)));
+      acc = FrAcc(reduce_to<32>(add(mul(acc, rS), fr_load<16>(cp + ((size_t)g + (size_t)k * S) * 8))));
+    acc = FrAcc(mul(acc, fe_pow_u32(r, g)));
   }
   const FrAcc sum = r1cs_block_sum(acc, part);
-  if (threadIdx.x == 0) bace_store(partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8, canonical(sum));
+  if (threadIdx.x == 0) fr_store(canonical(sum), partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8);
 }
 __global__ void __launch_bounds__(256) k_bace_sum_partials(const u32* __restrict__ partial, int per, u32* __restrict__ out) {
   __shared__ u32 part[9 * 256];
   FrAcc acc = FrAcc(fe_zero<FrP>());
   for (int i = threadIdx.x; i < per; i += 256)
-    acc = FrAcc(reduce_to<32>(add(acc, bace_load<16>(partial + ((size_t)blockIdx.x * per + i) * 8))));
+    acc = FrAcc(reduce_to<32>(add(acc, fr_load<16>(partial + ((size_t)blockIdx.x * per + i) * 8))));
   const FrAcc sum = r1cs_block_sum(acc, part);
-  if (threadIdx.x == 0) bace_store(out + (size_t)blockIdx.x * 8, canonical(sum));
+  if (threadIdx.x == 0) fr_store(canonical(sum), out + (size_t)blockIdx.x * 8);
 }
 
 // ---- result extraction: f[i] = sum_k proof[i + k N], k < D / N (the proof folded mod z^N - 1) ----
@@ -237,8 +202,8 @@ __global__ void __launch_bounds__(256) k_bace_fold(const u32* __restrict__ proof
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   FrAcc acc = FrAcc(fe_zero<FrP>());
-  for (int k = i; k < D; k += N) acc = FrAcc(reduce_to<32>(add(acc, bace_load<85>(proof + (size_t)k * 8))));
-  bace_store(f + (size_t)i * 8, canonical(acc));
+  for (int k = i; k < D; k += N) acc = FrAcc(reduce_to<32>(add(acc, fr_load<85>(proof + (size_t)k * 8))));
+  fr_store(canonical(acc), f + (size_t)i * 8);
 }
 
 // ---- host side ----
@@ -255,7 +220,7 @@ static int bace_lanes(int npoints) {
 
 struct BaceLayout {
   u32 *cst;                      // [0] 1/N (Montgomery)  [8] 1/D (plain)  [16] 1 (plain)  [24] r (Montgomery)
-  u32 *omega, *small;            // per-call twiddles (without the plan cache)
+  DomainTables dom;              // consts->omega and small of the per-call twiddle builds (without the plan cache)
   u32 *tw[4];                    // omega_N^-1, omega_N, omega_D, omega_D^-1: n/2 ... pyramids of N or D entries
   u32 *cols, *lde, *vals, *buf0, *buf1, *partial;
   int4* prog;
@@ -271,12 +236,9 @@ static size_t bace_hbm_words(int n_slots, int npoints) {
 static BaceLayout bace_layout(int n, int N, int D, int n_ops, int n_slots, int n_consts, int npoints, void* wsp) {
   BaceLayout L;
   Bump b(wsp, ~(size_t)0);
-  const int half = D / 2 > 0 ? D / 2 : 1;
-  const int lo = half < TW_LO ? half : TW_LO;
-  const int hi = (half + lo - 1) / lo;
   L.cst = b.take<u32>(64);
-  L.omega = b.take<u32>(8);
-  L.small = b.take<u32>((size_t)(lo + hi) * 8);
+  L.dom = DomainTables{};
+  carve_head(b, PowTable::twiddles(fft_half(D)), L.dom);
   L.tw[0] = b.take<u32>((size_t)N * 8);
   L.tw[1] = b.take<u32>((size_t)N * 8);
   L.tw[2] = b.take<u32>((size_t)D * 8);
@@ -300,22 +262,13 @@ static int bace_twiddles(int size, bool inverse, const BaceLayout& L, u32* slot,
                          const u32** tw) {
   u32 om[8];
   bace_root_host(ilog2((uint32_t)size), inverse, om);
-  *tw = slot;
+  DomainTables t = L.dom;
+  *tw = t.tw_f = slot;
   if (size < 2) return OZK_OK;   // (a transform of one element reads no twiddle)
-  if (knob(K_FFT_PLAN_CACHE)) {
-    int rc = plan_get(size, (const uint8_t*)om, nullptr, st, &pin.p);
-    if (rc) return rc;
-    if (pin.p) {
-      *tw = pin.p->tw_f;
-      return OZK_OK;
-    }
-  }
-  BaceWords c;
-  memcpy(c.w, om, 32);
-  hipLaunchKernelGGL(k_bace_put, dim3(1), dim3(64), 0, st, c, 8, L.omega);
-  fft_build_twiddles(L.omega, size, L.small, slot, st);
-  OZK_HIP(hipGetLastError());
-  return OZK_OK;
+  // (om is a temporary: by value)
+  const int rc = domain_tables(size, (const uint8_t*)om, nullptr, true, &t, pin, st);
+  *tw = t.tw_f;
+  return rc;
 }
 
 // `batch` columns of `size` elements: column c from in + c in_cs to out + c out_cs (words), one pipeline of launches
@@ -412,7 +365,7 @@ static int bace_columns(const BaceLayout& L, const void* d_inputs, int n, int N,
 
 static int bace_check_shape(int n, int N, int D) {
   if (n <= 0 || n > BACE_MAX_N) return fail(OZK_E_INVALID, "input count %d out of range [1, %d]", n, BACE_MAX_N);
-  if (N <= 0 || (N & (N - 1)) || N > (1 << 28)) return fail(OZK_E_INVALID, "instance count %d is not a power of two in [1, 2^28]", N);
+  if (int rc = check_pow2(N, 1, "instance count")) return rc;
   if (D < N || (D & (D - 1)) || D > (1 << 28))
     return fail(OZK_E_INVALID, "D = %d is not a power of two in [N, 2^28] (N = %d)", D, N);
   return OZK_OK;

@@ -7,7 +7,9 @@ second level of its power table).  Every result is compared byte for byte with t
 Which path ran is observable: both layouts take omega first, so on the per-call path the first 32 bytes of the
 workspace hold omega after the call, and on the plan path they keep the zeros the test put there.  The rest of the
 workspace starts poisoned.  ozk_host_cache_release() goes before every call: a plan cached by an earlier test would be
-a hit (the cache looks a key up before it looks at the byte budget), and the per-call path would not run."""
+a hit (the cache looks a key up before it looks at the byte budget), and the per-call path would not run.  The one
+exception is test_transform_and_witness_map_share_a_domain, which releases once and then keeps the cache across its
+three calls (release=False): what it checks is two kinds of plan living side by side."""
 import ctypes
 import functools
 import random
@@ -58,7 +60,7 @@ def _fft_case(n):
     return a.tobytes(), w, want64, want32
 
 
-def _fft_compact(L, n):
+def _fft_compact(L, n, release=True):
     """ozk_fft_compact_dev on _fft_case(n): (output tensor with its guard, workspace) after the call"""
     from octopuszk_amd import lib
     data, w, _, _ = _fft_case(n)
@@ -66,15 +68,16 @@ def _fft_compact(L, n):
     assert wsb > 0
     ws, d_in, out = _workspace(wsb), _upload(data), u.poisoned(n * 32 + u.GUARD)
     hw = ctypes.create_string_buffer(w, 32)
-    L.ozk_host_cache_release()
+    if release:
+        L.ozk_host_cache_release()
     lib.check(L.ozk_fft_compact_dev(d_in.data_ptr(), n, u.vp(hw), out.data_ptr(), ws.data_ptr(), wsb, _stream()))
     torch.cuda.synchronize()
     return out, ws
 
 
-def _check_fft_compact(L, n, per_call):
+def _check_fft_compact(L, n, per_call, release=True):
     _, w, _, want32 = _fft_case(n)
-    out, ws = _fft_compact(L, n)
+    out, ws = _fft_compact(L, n, release)
     assert bytes(out[:n * 32].cpu().numpy()) == want32
     assert u.tail_untouched(out, n * 32)
     # (a transform of one element has no plan: its omega always lands in the workspace)
@@ -125,7 +128,7 @@ def _qap_case(m):
     return raw, o.to_le32(o.fr_root_of_unity(m)), want
 
 
-def _check_qap_witness(L, m, per_call):
+def _check_qap_witness(L, m, per_call, release=True):
     from octopuszk_amd import lib
     raw, w, want = _qap_case(m)
     wsb = int(L.ozk_qap_witness_workspace_bytes(m))
@@ -133,7 +136,8 @@ def _check_qap_witness(L, m, per_call):
     ws, d_h = _workspace(wsb), u.poisoned((m + 1) * 32 + u.GUARD)
     d_abc = [_upload(v) for v in raw]
     hw, hg = ctypes.create_string_buffer(w, 32), u.host32(o.FR_MULT_GEN)
-    L.ozk_host_cache_release()
+    if release:
+        L.ozk_host_cache_release()
     lib.check(L.ozk_qap_witness_dev(d_abc[0].data_ptr(), d_abc[1].data_ptr(), d_abc[2].data_ptr(), m, u.vp(hw), u.vp(hg),
                                     d_h.data_ptr(), ws.data_ptr(), wsb, _stream()))
     torch.cuda.synchronize()
@@ -169,6 +173,25 @@ def test_workspace_shows_which_path_built_the_tables(knob, monkeypatch):
         _check_qap_witness(L, 1024, True)
     _check_fft_compact(L, 4096, False)
     _check_qap_witness(L, 1024, False)
+
+
+@pytest.mark.parametrize("n", [2, 1024])
+@pytest.mark.parametrize("knobs", [{}, {"OZK_FFT_PLAN_CACHE_MB": "0"}], ids=u.knob_id)
+def test_transform_and_witness_map_share_a_domain(knobs, n, monkeypatch):
+    """The plan cache's two kinds of key on ONE domain, interleaved with nothing released in between: a transform, the
+    witness map, the transform again, all with the same omega (_fft_case and _qap_case both take fr_root_of_unity(n)).
+    Both kinds of plan are carved by one function and looked up in one cache: same_key must keep (n, omega) apart from
+    (n, omega, g), or the witness map would find a plan without its coset tables and the second transform one that
+    is not its own.  n = 2 is the smallest plan, n = 1024 the smallest tiled transform (the witness map's last passes
+    fold the scalings in).  With the byte budget at 0 the same three calls build their tables in their workspaces."""
+    from octopuszk_amd import lib
+    L = lib.load()
+    assert _fft_case(n)[1] == _qap_case(n)[1]
+    with u.knobs_set(L, monkeypatch, knobs):
+        L.ozk_host_cache_release()
+        _check_fft_compact(L, n, _per_call(knobs), release=False)
+        _check_qap_witness(L, n, _per_call(knobs), release=False)
+        _check_fft_compact(L, n, _per_call(knobs), release=False)
 
 
 # ---------------------------------------------------------------------------------------------- BACE

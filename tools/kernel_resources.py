@@ -5,7 +5,7 @@
 
 Reads the gfx950 code object out of every octopuszk_amd/_obj/*.o (llvm-objcopy the .hip_fatbin section,
 clang-offload-bundler --unbundle, llvm-readelf --notes) and prints one line per kernel:
-VGPRs, AGPRs, spilled VGPRs, scratch bytes per lane, static LDS bytes, max workgroup size.
+VGPRs, AGPRs, SGPRs, spilled VGPRs, scratch bytes per lane, static LDS bytes, max workgroup size.
 `--spills` lists only kernels with a non-zero spill count or scratch (exit code 1 if any has more than one wave
 per workgroup: the throughput kernels must not spill)."""
 import os
@@ -38,7 +38,7 @@ def kernels_of(obj):
             cur = {}
             ks.append(cur)
         m = re.match(r"\s+-?\s*\.(\w+):\s+(\S+)\s*$", line)
-        if m and cur is not None and m.group(1) in ("agpr_count", "vgpr_count", "vgpr_spill_count", "sgpr_spill_count",
+        if m and cur is not None and m.group(1) in ("agpr_count", "vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count",
                                                     "group_segment_fixed_size", "private_segment_fixed_size",
                                                     "max_flat_workgroup_size", "name"):
             cur[m.group(1)] = m.group(2)
@@ -56,7 +56,7 @@ def main():
                 rows.append((f[:-len(".hip.o")], k))
     names = demangle([k["name"] for _, k in rows])
     bad = 0
-    print("%-14s %5s %5s %6s %8s %7s %5s  %s" % ("TU", "VGPR", "AGPR", "spill", "scratch", "LDS", "wg", "kernel"))
+    print("%-14s %5s %5s %5s %6s %8s %7s %5s  %s" % ("TU", "VGPR", "AGPR", "SGPR", "spill", "scratch", "LDS", "wg", "kernel"))
     for (tu, k), nm in zip(rows, names):
         nm = re.sub(r"\(.*$", "", nm).replace("ozk::", "")
         if args and not any(a in nm for a in args):
@@ -67,7 +67,7 @@ def main():
         wg = int(k.get("max_flat_workgroup_size", 0))
         if (spill or scratch) and wg > 64:
             bad += 1
-        print("%-14s %5s %5s %6d %8d %7s %5d  %s" % (tu, k.get("vgpr_count"), k.get("agpr_count"), spill, scratch,
+        print("%-14s %5s %5s %5s %6d %8d %7s %5d  %s" % (tu, k.get("vgpr_count"), k.get("agpr_count"), k.get("sgpr_count"), spill, scratch,
                                                       k.get("group_segment_fixed_size"), wg, nm))
     return 1 if (only_spills and bad) else 0
 
