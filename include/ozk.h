@@ -216,7 +216,7 @@ int ozk_points_sum_dev(const void* d_points, int32_t k, int32_t type, void* d_ou
 int ozk_groth16_combine_dev(const void* d_records, int32_t world, void* d_proof, void* stream);
 
 /* Measurement hooks (bench.py): timing of the dominant kernel (the level-1 bucket accumulation,
- * k_segreduce<.., true>) per launch.  ozk_prof_enable(2): the kernel's own waves stamp the device's constant-rate
+ * k_segreduce<.., true> or k_l1_whole) per launch.  ozk_prof_enable(2): the kernel's own waves stamp the device's constant-rate
  * clock (first wave start -> last wave end), which leaves the schedule untouched; ozk_prof_enable(1): HIP start /
  * stop events on the dispatch (16 + k: on every (k+1)-th launch only) — exact too, but an event-carrying dispatch
  * costs the three-stage schedule 4-13 % of its throughput, so bench.py uses it as a cross-check in a second pass;
@@ -240,6 +240,12 @@ int ozk_var_msm_plan(int32_t n, int32_t* window_bits, int32_t* windows);
 /* 1 when the MSM of n pairs runs as 2n half-length pairs through the GLV endomorphism (the windows
  * reported above then cover 128 bits); 0 otherwise (n > 2^23 or OZK_MSM_GLV=0). */
 int ozk_var_msm_glv(int32_t n);
+/* Which level-1 path the calling thread's most recent variable-base MSM (or accumulate stage) took, for tests and
+ * profiles: 1 = whole buckets on lane groups, 0 = fixed chunks and the run merge, -1 = no MSM on this thread yet.
+ * A whole-bucket plan is decided on the device (a bucket too long for its lane group, or a skewed sort bin, sends
+ * the MSM down the chunked path): the call waits for the device and reads the flag from the MSM's sorted set, so ask
+ * before the next MSM sorts into the same buffers. */
+int ozk_var_msm_last_l1_path(void);
 
 /* Synthetic inputs for benchmarks / full-size tests (BASELINE.md config 2 generator):
  * writes n G1 bases P_i = k_i * G, k_i = splitmix64(seed + i) (k_i = 1 if that is 0), in the

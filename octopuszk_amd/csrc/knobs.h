@@ -27,6 +27,7 @@ constexpr int KNOB_STRING = KNOB_COMPUTED + 1;  // a string, read with knob_str(
   X(MSM_SIGNED, "OZK_MSM_SIGNED", 1, "0: unsigned window digits in the GLV form")                                        \
   X(MSM_C, "OZK_MSM_C", KNOB_COMPUTED, "window bits, 1..16 (default: the cost model's choice)")                          \
   X(MSM_L1, "OZK_MSM_L1", KNOB_COMPUTED, "sorted entries per level-1 lane (default: from the bucket size; 0 as unset)")   \
+  X(MSM_L1_WHOLE, "OZK_MSM_L1_WHOLE", 1, "G1 level 1 by whole buckets on lane groups: 0 never, 1 on every plan that can take it (unset: where it pays)") \
   X(MSM_L1_ROUNDS, "OZK_MSM_L1_ROUNDS", 2, "most rounds of resident workgroups level 1 is rounded up to; 0: no rounding") \
   X(MSM_TAIL_MODE, "OZK_MSM_TAIL_MODE", -1, "0 / 1: force the latency / throughput shape of the window sums")            \
   X(MSM_SMALL_SORT, "OZK_MSM_SMALL_SORT", 1, "0: small MSMs take the two-level sort too")                                \

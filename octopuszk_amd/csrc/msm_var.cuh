@@ -33,6 +33,7 @@
 #pragma once
 #include "curve.cuh"
 #include "glv.cuh"
+#include "l1_whole.h"
 
 namespace ozk {
 
@@ -55,6 +56,8 @@ struct MsmPlan {
   int S_lat;       // buckets per lane in the fused first window-sum level of a latency-mode tail
   int fin_max;     // window-sum elements per window left to k_finalize
   int tail_mode;   // -1: as the caller asks; 0 / 1: latency / throughput shape forced
+  int l1_whole;    // 1: level 1 by whole buckets on lane groups where the data allow it (G1; k_bucket_items, k_l1_whole)
+  int l1_gtop;     // lanes per bucket of the top window on that path (l1_whole.h WholeGeom::g_top)
 };
 
 OZK_HD u32 scalar_digit(const u32 (&s)[8], int w, int c) {
@@ -1163,7 +1166,11 @@ __global__ void __launch_bounds__(256, (FIRST && CV::LDS_ACC) ? 2 : 1)
 k_segreduce(const u32* __restrict__ bid_in, const u32* __restrict__ idx_in, const u32* __restrict__ pts_in,
             const u32* __restrict__ d_count, int n_in_static, int L,
             u32* __restrict__ buckets, u32* __restrict__ bid_out, u32* __restrict__ pts_out,
-            int n_lanes, unsigned long long* __restrict__ clk) {
+            int n_lanes, unsigned long long* __restrict__ clk, const u32* __restrict__ whole_bad = nullptr) {
+  // level 1 of a whole-bucket plan: k_l1_whole has done the work unless the item kernel found the data unfit
+  if constexpr (FIRST) {
+    if (whole_bad != nullptr && *whole_bad == 0) return;
+  }
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   unsigned long long w0 = 0, c0 = 0;
   if constexpr (FIRST) {
@@ -1240,7 +1247,8 @@ template <class CV>
 __global__ void __launch_bounds__(RUNMERGE_BLOCK)
 k_runmerge(const u32* __restrict__ bid_in, const u32* __restrict__ pts, int n_slots,
            u32* __restrict__ buckets, u32* __restrict__ bid_out, u32* __restrict__ remaining,
-           const u32* __restrict__ hist_src, u32* __restrict__ hist_dst, size_t n_hist) {
+           const u32* __restrict__ hist_src, u32* __restrict__ hist_dst, size_t n_hist,
+           const u32* __restrict__ whole_bad = nullptr) {
   using IO = CurveIO<CV>;
   // G2 keeps the loop per lane: its addition needs 271 registers, one wave per SIMD, so a wave that skips a round
   // frees nothing for another, and the rounds would only add their barriers and the trip of the partial sums
@@ -1256,6 +1264,8 @@ k_runmerge(const u32* __restrict__ bid_in, const u32* __restrict__ pts, int n_sl
   if (threadIdx.x <= ROUNDS) item_cnt[threadIdx.x] = 0;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   for (size_t i = (size_t)t; i < n_hist; i += (size_t)gridDim.x * blockDim.x) hist_dst[i] = hist_src[i];
+  // whole-bucket level 1 (k_l1_whole) left no slots: only the counts were to copy, *remaining stays 0
+  if (whole_bad != nullptr && *whole_bad == 0) return;
   block_sync();
   u32 alive = 0;
 #pragma unroll 1
@@ -1315,6 +1325,149 @@ k_runmerge(const u32* __restrict__ bid_in, const u32* __restrict__ pts, int n_sl
         item_s[cur ^ 1][j] = s;
         item_span[cur ^ 1][j] = (uint8_t)span;
       }
+    }
+  }
+}
+
+// ------------------------------------------------------------------ level 1 by whole buckets (G1, signed GLV plans)
+// The chunked level 1 above cuts 260 772 of the workload's 262 144 buckets into two or three pieces, which travel
+// through the slot arrays to k_runmerge: ~100 us of latency-bound work on the stream that sets the pipeline's period.
+// Here a bucket is accumulated by a small GROUP of adjacent lanes (l1_whole.h: 2, or 4 in the top window), their
+// partial sums meet in registers (DPP quad permutes) and the finished bucket is stored once: no slots, no
+// classification, no run logic in the loop.
+//
+// k_bin_sums, k_bucket_items: one block per coarse sort bin.  The sorted entries ascend by bucket id over the whole
+// array, so a bin's first entry is the sum of the counts (hist) of all bins before it; the sort's own bin offsets live
+// in the sort scratch, which the next MSM's sort is already overwriting.  k_bin_sums leaves every bin's entry count,
+// k_bucket_items adds up the ones before its bin, ranks the bin's buckets by count and writes one item (entry offset,
+// count, bucket id, 0) per bucket at rank * nbins + bin.  (A search of the sorted entries for the bin's first one, in
+// the same launch, took 30-150 us in the schedule: every block's first probes hit the same few cache lines.)
+// *bad (zeroed by the sort stage's memset of `total`) is raised when a bucket is too long for its lane group or a bin
+// went to the k_sortbig_* kernels: such an MSM takes the chunked path, and nothing here is read again.
+constexpr int ITEMS_BLOCK = WHOLE_NB_MAX;
+__device__ __forceinline__ u32 items_block_sum(u32 v, u32* wsum) {   // sum over the block's two waves
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+  block_sync();
+  return wsum[0] + wsum[1];
+}
+static __global__ void __launch_bounds__(ITEMS_BLOCK)
+k_bin_sums(const u32* __restrict__ hist, WholeGeom geo, int cb, int lo_bits, u32* __restrict__ binsum) {
+  static_assert(ITEMS_BLOCK == 128, "two waves");
+  __shared__ u32 wsum[2];
+  const int t = threadIdx.x, bin = blockIdx.x;
+  const int w = bin / geo.NH, h = bin - w * geo.NH;
+  const u32 bucket0 = ((u32)w << cb) | ((u32)h << lo_bits);
+  const u32 sum = items_block_sum(t < geo.nb ? hist[bucket0 + t] : 0u, wsum);
+  if (t == 0) binsum[bin] = sum;
+}
+static __global__ void __launch_bounds__(ITEMS_BLOCK)
+k_bucket_items(const u32* __restrict__ hist, const u32* __restrict__ binsum, WholeGeom geo, int cb, int lo_bits,
+               u32 big_thresh, uint4* __restrict__ items, u32* __restrict__ bad) {
+  __shared__ u32 cnt[WHOLE_NB_MAX];
+  __shared__ u32 wsum[2];
+  const int t = threadIdx.x, bin = blockIdx.x;
+  const int w = bin / geo.NH, h = bin - w * geo.NH;
+  const u32 bucket0 = ((u32)w << cb) | ((u32)h << lo_bits);
+  const u32 c = t < geo.nb ? hist[bucket0 + t] : 0u;
+  cnt[t] = c;
+  u32 before = 0;
+  for (int j = t; j < bin; j += ITEMS_BLOCK) before += binsum[j];
+  const u32 base = items_block_sum(before, wsum);   // (its barrier also publishes cnt[])
+  if (t >= geo.nb) return;
+  u32 excl = 0, sum = 0;
+  for (int j = 0; j < geo.nb; j++) {
+    const u32 cj = cnt[j];
+    sum += cj;
+    excl += j < t ? cj : 0u;
+  }
+  const u32 rank = whole_rank(cnt, geo.nb, t);
+  items[whole_item_index(rank, (u32)bin, (u32)whole_nbins(geo))] = make_uint4(base + excl, c, bucket0 + (u32)t, 0u);
+  if (c > whole_limit(whole_group(geo, bin)) || sum > big_thresh) *bad = 1u;
+}
+
+// partner lane's value across a quad permute (lane ^ 1: 0xB1 = [1,0,3,2]; lane ^ 2: 0x4E = [2,3,0,1])
+template <int CTRL, class CV>
+__device__ __forceinline__ Xyzz<CV> xyzz_quad_swap(const Xyzz<CV>& a) {
+  using IO = CurveIO<CV>;
+  constexpr int RW = IO::RW;
+  u32 w[4 * RW];
+  ElemTraits<typename CV::XX>::store_raw(a.X, w);
+  ElemTraits<typename CV::XY>::store_raw(a.Y, w + RW);
+  ElemTraits<typename CV::XZZ>::store_raw(a.ZZ, w + 2 * RW);
+  ElemTraits<typename CV::XZZZ>::store_raw(a.ZZZ, w + 3 * RW);
+#pragma unroll
+  for (int k = 0; k < 4 * RW; k++) w[k] = (u32)__builtin_amdgcn_update_dpp(0, (int)w[k], CTRL, 0xf, 0xf, true);
+  Xyzz<CV> b;
+  b.X = ElemTraits<typename CV::XX>::load_raw(w);
+  b.Y = ElemTraits<typename CV::XY>::load_raw(w + RW);
+  b.ZZ = ElemTraits<typename CV::XZZ>::load_raw(w + 2 * RW);
+  b.ZZZ = ElemTraits<typename CV::XZZZ>::load_raw(w + 3 * RW);
+  return b;
+}
+
+// k_l1_whole: lane t serves part g of G of one item (l1_whole.h whole_lane_map / whole_part) with the software-
+// pipelined gather of the chunked loop (segreduce_lane: record one entry ahead through the buffer resource, index
+// word two ahead, look-ahead unconditional and clamped) and xyzz_madd_lazy from the point at infinity: no bucket id
+// is read, nothing is compared.  Then log2 G steps of the complete xyzz_add over the group (an empty part, a
+// doubling and P + (-P) included), and lane 0 of the group stores the bucket.  Count 0 writes nothing: the window
+// sums skip such buckets by their count.  Lanes past the grid's end stay in the kernel as empty parts, so that every
+// lane of a wave is active at the exchange.  `clk`: as k_segreduce.
+template <class CV>
+__global__ void __launch_bounds__(256)
+k_l1_whole(const uint4* __restrict__ items, const uint2* __restrict__ sent, const u32* __restrict__ pts_in,
+           const u32* __restrict__ bad, WholeGeom geo, u32 n_lanes, u32* __restrict__ buckets,
+           unsigned long long* __restrict__ clk) {
+  using IO = CurveIO<CV>;
+  using Acc = RunAcc<CV, true>;
+  if (*bad != 0u) return;   // the chunked kernels run instead
+  unsigned long long w0 = 0, c0 = 0;
+  if (clk != nullptr && threadIdx.x == 0) {
+    w0 = (unsigned long long)wall_clock64();
+    c0 = (unsigned long long)clock64();
+    atomicMax(&clk[0], ~w0);
+  }
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  u32 item, g, G;
+  whole_lane_map(geo, t < n_lanes ? t : 0u, &item, &g, &G);
+  const bool valid = t < n_lanes && item != WHOLE_NO_ITEM;   // (a padding lane: an empty part of no bucket)
+  uint4 it = items[valid ? item : 0u];
+  if (!valid) it.y = 0u;
+  u32 first, n_e;
+  whole_part(it.y, g, G, &first, &n_e);
+  Xyzz<CV> a = xyzz_from_affine<CV>(IO::aff_infinity());
+  if (n_e != 0u) {
+    const u32* idx_c = reinterpret_cast<const u32*>(sent + (size_t)it.x + first);   // entry k's index word at [2 k]
+    u32 v_cur = idx_c[0];
+    u32 v_next = idx_c[n_e > 1u ? 2 : 0];
+    const __amdgpu_buffer_rsrc_t table = Acc::table_rsrc(pts_in);
+    typename Acc::Raw r = Acc::load_raw_buf(table, v_cur);
+    for (u32 k = 0; k < n_e; k++) {
+      const bool negate = (v_cur & SIDX_NEG) != 0;
+      const auto q = Acc::decode_unsigned(r);
+      const u32 k2 = (k + 2 < n_e) ? k + 2 : n_e - 1;
+      r = Acc::load_raw_buf(table, v_next);
+      v_cur = v_next;
+      v_next = idx_c[2 * (size_t)k2];
+      a = xyzz_madd_lazy(a, q, negate);
+    }
+  }
+  if (__ballot(G > 1u) != 0ull) {
+    const Xyzz<CV> b = xyzz_quad_swap<0xB1, CV>(a);
+    if (G > 1u) a = xyzz_add(a, b);
+  }
+  if (__ballot(G > 2u) != 0ull) {
+    const Xyzz<CV> b = xyzz_quad_swap<0x4E, CV>(a);
+    if (G > 2u) a = xyzz_add(a, b);
+  }
+  if (g == 0u && it.y != 0u) IO::store_rec_xyzz(a, buckets + (size_t)it.z * IO::REC_WORDS);
+  if (clk != nullptr && (threadIdx.x & 63) == 0) {
+    const unsigned long long w1 = (unsigned long long)wall_clock64();
+    atomicMax(&clk[1], w1);
+    if (threadIdx.x == 0) {
+      atomicAdd(&clk[2], (unsigned long long)clock64() - c0);
+      atomicAdd(&clk[3], w1 - w0);
     }
   }
 }

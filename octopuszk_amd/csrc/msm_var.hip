@@ -863,6 +863,17 @@ int ozk_var_msm_plan(int32_t n, int32_t* window_bits, int32_t* windows) {
 
 int ozk_var_msm_glv(int32_t n) { return n > 0 ? make_plan(n).glv : 0; }
 
+int ozk_var_msm_last_l1_path(void) {
+  const L1PathLast& last = g_l1_path_last;
+  if (last.planned <= 0) return last.planned;
+  u32 bad = 0;
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&bad, last.d_bad, sizeof(bad), hipMemcpyDeviceToHost) != hipSuccess) {
+    (void)hipGetLastError();
+    return -1;
+  }
+  return bad ? 0 : 1;
+}
+
 const char* ozk_last_error(void) { return err_buf(); }
 int ozk_version(void) { return 2; }
 int ozk_device_count(void) {

@@ -179,6 +179,8 @@ static MsmPlan make_plan(int n) {
   if (p.fin_max > 16) p.fin_max = 16;
   p.tail_mode = knob(K_MSM_TAIL_MODE);
   if (p.tail_mode != 0 && p.tail_mode != 1) p.tail_mode = -1;
+  p.l1_whole = 0;   // (plan_for: G1 only)
+  p.l1_gtop = WHOLE_G;
   return p;
 }
 
@@ -203,6 +205,7 @@ static MsmPlan plan_for(int n, bool lone) {
   // at most two rounds (2^21: 128 entries per lane, 11.30 -> 11.13 ms against the four rounds of 64; one round of
   // 256 measures the same); OZK_MSM_L1_ROUNDS=0 switches the rule off, 1 asks for a single round
   const long long max_rounds = knob(K_MSM_L1_ROUNDS);
+  bool rounded = false;   // the chunk was raised to a whole number of rounds of the chip
   if ((CV::LDS_ACC || lone) && knob_or(K_MSM_L1, 0) == 0 && max_rounds != 0) {
     static int cu_count = 0;   // (benign race: every thread computes the same value)
     if (cu_count == 0) {
@@ -219,7 +222,10 @@ static MsmPlan plan_for(int n, bool lone) {
     long long rounds = blocks / slots > 0 ? blocks / slots : 1;
     if (rounds > max_rounds) rounds = max_rounds;
     long long l1 = (cap + 256LL * slots * rounds - 1) / (256LL * slots * rounds);
-    if (l1 > p.L1 && l1 <= 1024) p.L1 = (int)l1;
+    if (l1 > p.L1 && l1 <= 1024) {
+      p.L1 = (int)l1;
+      rounded = true;
+    }
   }
   // The fused first level of a LATENCY tail: 8 buckets per lane for G1 (2^20: single MSM 2.63-2.71 -> 2.51-2.53 ms on
   // one box; 16: 2.60), the plan's 4 for G2 (8: 7.43 against 7.38 ms).  Small MSMs — fewer than 2^13 buckets per
@@ -228,8 +234,39 @@ static MsmPlan plan_for(int n, bool lone) {
   // buffers — sized for the plan's S — for ANY S.
   const int s_lat = knob_or(K_MSM_S_LAT, std::is_same<CV, G1Cfg>::value && p.cb >= 13 ? 8 : p.S);
   if (s_lat >= 2 && s_lat <= 64) p.S_lat = 1 << ilog2((uint32_t)s_lat);
+  // Level 1 by whole buckets (msm_var.cuh k_l1_whole): G1's signed-digit GLV plans that take the two-level sort, whose
+  // coarse bins hold at most WHOLE_NB_MAX buckets.  The top window's digits have top_bits significant bits: where that
+  // is fewer than c its buckets are 2^(c - top_bits) times as long, and four lanes share one.
+  // OZK_MSM_L1_WHOLE unset: where it pays.  Alone on the chip a lane's serial chain of additions is what a small MSM
+  // waits for, and the whole-bucket loop is the slower loop: a lone MSM keeps the chunked path when its launch was
+  // shaped into whole rounds of the chip (2^20: 2.36 ms chunked, 2.45 by whole buckets) or when a lane's share of a
+  // bucket — of an ordinary one, or of the top window's longer ones — would exceed the chunk (2^16, c = 13: the top
+  // window's 256-entry buckets make chains of 64 where the chunk is shorter: 1.02 -> 1.22 ms; 2^18: 1.35 -> 1.32,
+  // profiles/r08_ab_whole_buckets.txt).  The staged plans gain where the run merge's latency was.  1 forces the path
+  // on every plan that can take it (tests), 0 forbids it.
+  const int whole_knob = knob_or(K_MSM_L1_WHOLE, -1);
+  bool whole_pays = true;
+  if (lone) {
+    const int tb = 127 - (p.W - 1) * p.c;
+    const long long per_bucket = (long long)p.n >> p.cb;
+    const long long per_top = (tb >= 1 && tb < p.c) ? ((long long)p.n >> (tb - p.sd > 0 ? tb - p.sd : 0)) : per_bucket;
+    whole_pays = !rounded && per_bucket / WHOLE_G <= p.L1 && per_top / 4 <= p.L1;
+  }
+  if (std::is_same<CV, G1Cfg>::value && p.glv && p.sd && !p.small_sort && (whole_knob == -1 ? whole_pays : whole_knob != 0)) {
+    const int top_bits = 127 - (p.W - 1) * p.c;
+    p.l1_whole = 1;
+    p.l1_gtop = (top_bits >= 1 && top_bits < p.c) ? 4 : WHOLE_G;
+  }
   return p;
 }
+
+// Which level-1 path the calling thread's last var_msm_accum took (ozk_var_msm_last_l1_path): the plan's choice on the
+// host and, for a whole-bucket plan, the device flag the item kernel leaves in the sorted set.
+struct L1PathLast {
+  int planned = -1;             // -1: no call yet; 0: chunked plan; 1: whole-bucket plan, the device flag decides
+  const u32* d_bad = nullptr;   // sorted set: total[2]
+};
+inline thread_local L1PathLast g_l1_path_last;
 
 struct MsmLayout {
   // all device pointers into the workspace
@@ -488,6 +525,12 @@ int var_msm_accum(const MsmPlan& p, void* sorted, size_t sorted_bytes, void* acc
   const size_t tneed = tail_layout<CV>(p, L, tail, tail_bytes);
   if (tneed > tail_bytes) return fail(OZK_E_INVALID, "tail buffer too small: need %zu bytes, got %zu", tneed, tail_bytes);
   const int TB = 256;
+  // whole-bucket level 1 where the plan asks for it and the items (16 bytes per bucket, 4 per sort bin) fit the accumulate scratch
+  const bool whole = !CV::LDS_ACC && p.l1_whole && (1 << L.lo_bits) <= WHOLE_NB_MAX &&
+                     L.NB * sizeof(uint4) + (size_t)p.W * L.NH * sizeof(u32) <= rb.accum_ws;
+  u32* whole_bad = L.total + 2;
+  g_l1_path_last.planned = whole ? 1 : 0;
+  g_l1_path_last.d_bad = whole_bad;
   // level 1 over the sorted entries
   size_t lanes = (L.cap + p.L1 - 1) / p.L1;
   if (part != ACCUM_REST) {
@@ -513,11 +556,33 @@ int var_msm_accum(const MsmPlan& p, void* sorted, size_t sorted_bytes, void* acc
     if (acc_lds > 65536)
       OZK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)acc_lds));
     hipExtLaunchKernelGGL(kern, dim3((unsigned)((lanes + TB - 1) / TB)), dim3(TB), (uint32_t)acc_lds, st,
-                          prof ? prof_e0 : (hipEvent_t) nullptr, prof ? prof_e1 : (hipEvent_t) nullptr, 0u,
+                          prof && !whole ? prof_e0 : (hipEvent_t) nullptr, prof && !whole ? prof_e1 : (hipEvent_t) nullptr, 0u,
                           (const u32*)nullptr, (const u32*)L.sent, (const u32*)L.aff, (const u32*)L.total, 0, p.L1,
-                          L.buckets, L.slot_bid[0], L.slot_pts[0], (int)lanes, clk);
+                          L.buckets, L.slot_bid[0], L.slot_pts[0], (int)lanes, clk, whole ? (const u32*)whole_bad : (const u32*)nullptr);
     return OZK_OK;
   };
+  // Whole-bucket plan: the items (at the head of THIS stage: they live in the accumulate scratch, where the slot
+  // arrays are — dead until the chunked kernel runs, and private to the stage, unlike the sort scratch) and the
+  // whole-bucket kernel; the chunked kernel below, the run merge and the generic levels stay queued and return at
+  // once unless the item kernel raised the flag.  The kernel's timing (events, clock words) goes with the whole-bucket
+  // launch; the clock words also take the chunked launch's stamps, so a fallback is timed too.
+  if constexpr (!CV::LDS_ACC) {
+    if (whole) {
+      const WholeGeom geo{p.W, L.NH, 1 << L.lo_bits, p.l1_gtop};
+      const u32 big_thresh = (u32)(p.n / 64) > SORT_BIG ? (u32)(p.n / 64) : SORT_BIG;   // as var_msm_sort
+      uint4* items = (uint4*)accum_ws;
+      u32* binsum = (u32*)(items + L.NB);
+      hipLaunchKernelGGL(k_bin_sums, dim3((unsigned)whole_nbins(geo)), dim3(ITEMS_BLOCK), 0, st, (const u32*)L.hist, geo,
+                         p.cb, L.lo_bits, binsum);
+      hipLaunchKernelGGL(k_bucket_items, dim3((unsigned)whole_nbins(geo)), dim3(ITEMS_BLOCK), 0, st, (const u32*)L.hist,
+                         (const u32*)binsum, geo, p.cb, L.lo_bits, big_thresh, items, whole_bad);
+      const long long wl = whole_lanes(geo);
+      hipExtLaunchKernelGGL((k_l1_whole<CV>), dim3((unsigned)((wl + TB - 1) / TB)), dim3(TB), (uint32_t)acc_lds, st,
+                            prof ? prof_e0 : (hipEvent_t) nullptr, prof ? prof_e1 : (hipEvent_t) nullptr, 0u,
+                            (const uint4*)items, (const uint2*)L.sent, (const u32*)L.aff, (const u32*)whole_bad, geo,
+                            (u32)wl, L.buckets, clk);
+    }
+  }
   // the lazily carried mixed addition (ec.cuh xyzz_madd_lazy) where the curve has it
   if (int rc_l1 = launch_l1(k_segreduce<CV, true, CV::LAZY_MADD>)) return rc_l1;
   }
@@ -530,7 +595,8 @@ int var_msm_accum(const MsmPlan& p, void* sorted, size_t sorted_bytes, void* acc
   // (it also copies the bucket counts for the tail, which needs them after the next head has reused the sorted set)
   static_assert(RUNMERGE_BLOCK == 256, "k_runmerge's work list is sized for this launch");
   hipLaunchKernelGGL((k_runmerge<CT>), dim3((unsigned)((lanes + TB - 1) / TB)), dim3(TB), 0, st, L.slot_bid[0],
-                     L.slot_pts[0], (int)n_in, L.buckets, L.slot_bid2, L.total + 1, (const u32*)L.hist, L.hist_t, L.NB);
+                     L.slot_pts[0], (int)n_in, L.buckets, L.slot_bid2, L.total + 1, (const u32*)L.hist, L.hist_t, L.NB,
+                     whole ? (const u32*)whole_bad : (const u32*)nullptr);
   // levels >= 2 over the surviving partial slots, ping-pong, until a single lane has seen everything
   // (they return at once when nothing survived)
   int cur = 0;

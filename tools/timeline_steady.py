@@ -9,7 +9,10 @@ K = int(sys.argv[2]) if len(sys.argv) > 2 else 2
 min_us = float(sys.argv[3]) if len(sys.argv) > 3 else 3.0
 t = glob.glob(d + '/*/*_kernel_trace.csv')[0]
 rows = sorted(csv.DictReader(open(t)), key=lambda r: int(r['Start_Timestamp']))
-l1 = [i for i, r in enumerate(rows) if 'k_segreduce<ozk::G1Cfg, true' in r['Kernel_Name']]
+# level 1: the whole-bucket kernel where the trace has it (the chunked kernel is then queued behind it as a no-op)
+l1 = [i for i, r in enumerate(rows) if 'k_l1_whole<ozk::G1Cfg' in r['Kernel_Name']]
+if not l1:
+    l1 = [i for i, r in enumerate(rows) if 'k_segreduce<ozk::G1Cfg, true' in r['Kernel_Name']]
 m = len(l1) // 2
 lo, hi = l1[m], l1[m + K]
 t0 = int(rows[lo]['Start_Timestamp'])
@@ -39,3 +42,10 @@ for r in rows:
 print("per-kernel averages (us) over the middle half, and per MSM:")
 for nm in sorted(tot, key=lambda k: -tot[k]):
     print("  %-42s n=%4d avg=%8.1f" % (nm, cnt[nm], tot[nm] / cnt[nm]))
+# the accumulate stream's epilogue: end of one level-1 launch -> start of the next, over the middle half
+mid = l1[len(l1) // 4:3 * len(l1) // 4 + 1]
+gaps = sorted((int(rows[b]['Start_Timestamp']) - int(rows[a]['End_Timestamp'])) / 1e3 for a, b in zip(mid, mid[1:]))
+durs = sorted((int(rows[a]['End_Timestamp']) - int(rows[a]['Start_Timestamp'])) / 1e3 for a in mid)
+if gaps:
+    print("level 1: median %.1f us; gap to the next level-1 start: median %.1f us (min %.1f, max %.1f) over %d launches" %
+          (durs[len(durs) // 2], gaps[len(gaps) // 2], gaps[0], gaps[-1], len(gaps)))

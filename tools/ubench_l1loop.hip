@@ -7,9 +7,13 @@
 //   C  B with sequential indices (cache-friendly)
 //   G  B with the prefetched record in LDS instead of registers (gfx950 LDS-direct 16-byte loads)
 //   D  B + the run logic (bucket id per entry, run boundaries every ~64 entries, finished runs stored as 160-byte records)
+//   K' K over runs of Poisson-distributed length, mean 64 (the workload's buckets)
+//   W  the library's k_l1_whole over the same Poisson runs: whole buckets on lane pairs, items in rank-major order
+//      (128 consecutive runs = one coarse bin), in-register merge, one store per bucket; no run logic
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DOZK_WITH_G2 tools/ubench_l1loop.hip -o tools/ubench_l1loop
 #include <hip/hip_runtime.h>
 #include <stdio.h>
+#include <random>
 #include <vector>
 #include "../octopuszk_amd/csrc/msm_var.cuh"
 using namespace ozk;
@@ -244,6 +248,61 @@ int main() {
                             : timeit([&] { hipLaunchKernelGGL(k_loop<3>, dim3(blocks), dim3(256), lds, 0, d_idx, d_bid, d_pts, d_buckets, d_out, L); });
     const double adds = (double)NE;
     printf("%-52s %.3f ms for %.2f M additions -> %.3f ms per 16.78 M\n", names[mode], ms, adds * 1e-6, ms * 16.777216e6 / adds);
+  }
+  {
+    // Poisson runs (mean 64) over the same number of entries; K' walks them in chunks of L as K does, W by items
+    std::mt19937 gen(12345);
+    std::poisson_distribution<int> pois(64.0);
+    std::vector<uint2> h(NE + 1);
+    std::vector<u32> run_off, run_cnt;
+    size_t filled = 0;
+    while (filled < NE) {
+      size_t len = (size_t)pois(gen);
+      if (len > NE - filled) len = NE - filled;
+      run_off.push_back((u32)filled);
+      run_cnt.push_back((u32)len);
+      for (size_t i = 0; i < len; i++) h[filled + i] = make_uint2(h_idx[filled + i], (u32)(run_cnt.size() - 1) & 0x3ffff);
+      filled += len;
+    }
+    while (run_cnt.size() % 256) {   // whole bins of 128 runs, an even number of bins
+      run_off.push_back((u32)NE);
+      run_cnt.push_back(0);
+    }
+    h[NE] = h[NE - 1];
+    uint2* d_ent_p;
+    (void)hipMalloc(&d_ent_p, (NE + 1) * 8);
+    (void)hipMemcpy(d_ent_p, h.data(), (NE + 1) * 8, hipMemcpyHostToDevice);
+    const int nruns = (int)run_cnt.size(), nbins = nruns / 128;
+    const WholeGeom geo{2, nbins / 2, 128, 2};
+    std::vector<uint4> h_items((size_t)nruns);
+    for (int bin = 0; bin < nbins; bin++)
+      for (int i = 0; i < 128; i++) {
+        const int run = bin * 128 + i;
+        h_items[whole_item_index(whole_rank(&run_cnt[(size_t)bin * 128], 128, i), (u32)bin, (u32)nbins)] =
+            make_uint4(run_off[run], run_cnt[run], (u32)run & 0x3ffff, 0u);
+      }
+    uint4* d_items;
+    u32* d_bad;
+    (void)hipMalloc(&d_items, (size_t)nruns * 16);
+    (void)hipMalloc(&d_bad, 4);
+    (void)hipMemcpy(d_items, h_items.data(), (size_t)nruns * 16, hipMemcpyHostToDevice);
+    (void)hipMemset(d_bad, 0, 4);
+    const long long wl = whole_lanes(geo);
+    // (the host work above let the chip idle: bring the clock back up before anything is timed, then K again as the
+    // reference of this part of the run)
+    for (int r = 0; r < 40; r++) hipLaunchKernelGGL(k_loop<10>, dim3(blocks), dim3(256), lds, 0, d_idx, d_bid, d_pts, d_buckets, d_out, L, d_ent);
+    const double ms_k0 = timeit([&] { hipLaunchKernelGGL(k_loop<10>, dim3(blocks), dim3(256), lds, 0, d_idx, d_bid, d_pts, d_buckets, d_out, L, d_ent); });
+    printf("%-52s %.3f ms for %.2f M additions -> %.3f ms per 16.78 M\n", "K again (after 40 warm launches)", ms_k0, (double)NE * 1e-6, ms_k0 * 16.777216e6 / (double)NE);
+    const double ms_k = timeit([&] { hipLaunchKernelGGL(k_loop<10>, dim3(blocks), dim3(256), lds, 0, d_idx, d_bid, d_pts, d_buckets, d_out, L, d_ent_p); });
+    printf("%-52s %.3f ms for %.2f M additions -> %.3f ms per 16.78 M\n", "K' = K over Poisson(64) runs", ms_k, (double)NE * 1e-6, ms_k * 16.777216e6 / (double)NE);
+    const double ms_w = timeit([&] {
+      hipLaunchKernelGGL((k_l1_whole<G1Cfg>), dim3((unsigned)((wl + 255) / 256)), dim3(256), lds, 0, (const uint4*)d_items,
+                         (const uint2*)d_ent_p, (const u32*)d_pts, (const u32*)d_bad, geo, (u32)wl, d_buckets,
+                         (unsigned long long*)nullptr);
+    });
+    printf("%-52s %.3f ms for %.2f M additions + %d merges -> %.3f ms per 16.78 M  (%lld lanes, %u blocks)\n",
+           "W whole buckets on lane pairs (k_l1_whole)", ms_w, (double)NE * 1e-6, nruns, ms_w * 16.777216e6 / (double)NE, wl,
+           (unsigned)((wl + 255) / 256));
   }
   return 0;
 }
