@@ -550,6 +550,24 @@ int ozk_groth16_proofs_decompress_dev(const void* d_in128, int32_t k, void* d_re
 int ozk_points_scale_dev(const void* d_in, int32_t n, int32_t type, const uint8_t* k_host32, void* d_out,
                          void* stream);
 
+/* ---- n points times n scalars (points_mul.hip; no counterpart in the reference): out_i =
+ * [k_i] P_i, the operation of a phase-1 contribution to a powers-of-tau string (tau_g1[i] times s^i and so on).
+ *   d_in       n wire-in points of `type`, read exactly as ozk_points_scale_dev reads them
+ *   d_scalars  n x 32 bytes little-endian in DEVICE memory: what ozk_fr_powers_dev writes
+ *   d_out      n wire-in points exactly as ozk_points_scale_dev writes them (Z = 1, canonical; its infinity).
+ *              d_out == d_in is allowed (a lane reads its point and its scalar before it writes); any other overlap
+ *              is not.
+ *   d_codes    NULL, or n x int32: 0 for a point that was multiplied, 1 where k_i >= r; that point is written as
+ *              infinity and its neighbours are not affected.  k_i = 0 and P_i at infinity give infinity with code 0.
+ * One point per lane, 64-lane workgroups.  The lane recodes its own scalar in the kernel (G1: the GLV halves in joint
+ * sparse form; G2: the non-adjacent form of k without the endomorphism, exact on the whole twist) into 32 words of
+ * LDS at a stride of 33 words per lane (8448 bytes per workgroup), and runs the ladder of ozk_points_scale_dev over
+ * them.  Every addition is complete: the result is [k_i] P_i for every point of the curve and every k_i in [0, r).
+ * n <= 0 or n > 2^24, a null d_in, d_scalars or d_out, an unknown type, a buffer that is not 4-byte aligned:
+ * OZK_E_INVALID with nothing enqueued.  Asynchronous on `stream`; allocates nothing and needs no workspace. */
+int ozk_points_mul_dev(const void* d_in, const void* d_scalars, int32_t n, int32_t type, void* d_out,
+                       int32_t* d_codes, void* stream);
+
 /* ---- point kernels of the setup from a powers-of-tau string (ec_fft.hip; no counterpart in
  * the reference).  All three read wire-in points of `type` (OZK_G1 96 B, OZK_G2 192 B; any Z, Z = 0 is infinity) as
  * ozk_points_scale_dev reads them and write affine-normalised wire-in points (Z = 1, canonical), infinity as

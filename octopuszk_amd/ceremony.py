@@ -68,8 +68,9 @@ def _enc(points, type_) -> bytes:
     return _bytes((_codec.compress_g1 if type_ == G1 else _codec.compress_g2)(points))
 
 
-def _challenge(body: bytes, r_enc: bytes) -> int:
-    return int.from_bytes(hashlib.sha256(b"OZK-phase2-pok" + body + r_enc).digest()[:16], "little") or 1
+def _challenge(body: bytes, r_enc: bytes, tag=b"OZK-phase2-pok") -> int:
+    """the 128-bit Schnorr challenge of a receipt, never zero (srs.py: the same under the phase-1 tag)"""
+    return int.from_bytes(hashlib.sha256(tag + body + r_enc).digest()[:16], "little") or 1
 
 
 def _weights(seed: bytes, n: int) -> bytes:
@@ -130,6 +131,40 @@ def _decode_code(enc: bytes, type_) -> int:
     return _codec.E_INFINITY if y_zero and ylarger else _codec.OK
 
 
+def _require_points(fields):
+    """fields: (name, compressed encoding, type_) of a receipt's points; ValueError naming the first that does not
+    decode"""
+    for name, enc, type_ in fields:
+        code = _decode_code(enc, type_)
+        if code:
+            raise ValueError("receipt: %s does not decode: code %d (%s)" % (name, code, _codec.CODE_NAMES.get(code, "?")))
+
+
+def _receipt_head(b, magic, size):
+    """bytes of a receipt with the right length and magic, or ValueError"""
+    b = bytes(b)
+    if len(b) != size:
+        raise ValueError("receipt: length %d, not %d" % (len(b), size))
+    if b[:8] != magic:
+        raise ValueError("receipt: wrong magic or version")
+    return b
+
+
+def _pok_holds(base, moved, r_enc: bytes, z: int, c: int):
+    """z base - c moved - R = O as one 3-point MSM (base, moved: one wire-in G1 point each; R compressed): (a device
+    flag to read after a synchronise as _pok_read, the workspace to keep until then)"""
+    from .zksnark import _dev_bytes
+    r_point, code = _codec.decompress_g1(_dev_bytes(r_enc))
+    pok, ws = _msm(torch.cat([base.reshape(-1), moved.reshape(-1), r_point]),
+                   b"".join(v.to_bytes(32, "little") for v in (z, FR - c, FR - 1)), 3)
+    return (pok, code), ws
+
+
+def _pok_read(flag) -> bool:
+    pok, code = flag
+    return _is_inf_out(pok) and not int(code.item())
+
+
 class Receipt:
     """What a contributor publishes next to the new key: the transcript digest h, delta before and after in both
     groups, and the proof of knowledge (R, z) of the factor between them."""
@@ -154,19 +189,12 @@ class Receipt:
     def from_bytes(b) -> "Receipt":
         """Strict: ValueError naming the field for a wrong length, a wrong magic, z >= r or a point that does not
         decode (decoded on the device)."""
-        b = bytes(b)
-        if len(b) != RECEIPT_BYTES:
-            raise ValueError("receipt: length %d, not %d" % (len(b), RECEIPT_BYTES))
-        if b[:8] != MAGIC:
-            raise ValueError("receipt: wrong magic or version")
+        b = _receipt_head(b, MAGIC, RECEIPT_BYTES)
         z = int.from_bytes(b[264:], "little")
         if z >= FR:
             raise ValueError("receipt: z is not below r")
         rec = Receipt(b[8:40], b[40:72], b[72:104], b[104:168], b[168:232], b[232:264], z)
-        for name, type_ in Receipt._FIELDS:
-            code = _decode_code(getattr(rec, name), type_)
-            if code:
-                raise ValueError("receipt: %s does not decode: code %d (%s)" % (name, code, _codec.CODE_NAMES.get(code, "?")))
+        _require_points((name, getattr(rec, name), type_) for name, type_ in Receipt._FIELDS)
         return rec
 
     def body(self) -> bytes:
@@ -254,7 +282,7 @@ def verify_contribution(pk_before, pk_after, receipt, *, vk_before=None, vk_afte
     system.  A seeded check is reproducible and so unsound against anyone who knows the seed: tests only.
     stage_ms: None, or a dict that receives the times of the stages compare, scale, msms, pairings in ms (the call
     then synchronises between them)."""
-    from .zksnark import VerificationKey, _dev_bytes
+    from .zksnark import VerificationKey
     T = {"compare": 0.0, "scale": 0.0, "msms": 0.0, "pairings": 0.0}
     t0 = [time.perf_counter()]
 
@@ -314,11 +342,8 @@ def verify_contribution(pk_before, pk_after, receipt, *, vk_before=None, vk_afte
     s_old, ws1 = _msm(torch.cat([pk_before.delta_abc_g1.reshape(-1), pk_before.query_h.reshape(-1)]), rho, n)
     s_new, ws2 = _msm(torch.cat([pk_after.delta_abc_g1.reshape(-1), pk_after.query_h.reshape(-1)]), rho, n)
     # 6 pok (its MSM with the two above)
-    c = _challenge(rec.body(), rec.r)
-    r_point, code = _codec.decompress_g1(_dev_bytes(rec.r))
-    pok, ws3 = _msm(torch.cat([pk_before.delta_g1.reshape(-1), pk_after.delta_g1.reshape(-1), r_point]),
-                    b"".join(v.to_bytes(32, "little") for v in (rec.z, FR - c, FR - 1)), 3)
-    inf_old, inf_new, pok_ok = _is_inf_out(s_old), _is_inf_out(s_new), _is_inf_out(pok) and not int(code.item())
+    pok, ws3 = _pok_holds(pk_before.delta_g1, pk_after.delta_g1, rec.r, rec.z, _challenge(rec.body(), rec.r))
+    inf_old, inf_new, pok_ok = _is_inf_out(s_old), _is_inf_out(s_new), _pok_read(pok)
     lap("msms")
     if inf_old or inf_new:
         return no("vectors")

@@ -30,15 +30,19 @@ struct ScaleSchedule {
   u32 w[SCALE_MAX_STEPS / 8];
   int32_t len;
 };
-OZK_HD u32 scale_step(const ScaleSchedule& s, int i) { return (s.w[i >> 3] >> (4 * (i & 7))) & 15u; }
+// (any schedule: a struct with SCALE_MAX_STEPS / 8 words behind .w and a .len; points_mul.cuh keeps its words in LDS)
+template <class S>
+OZK_HD u32 scale_step(const S& s, int i) { return (s.w[i >> 3] >> (4 * (i & 7))) & 15u; }
 
 // ---------------------------------------------------------------------------------------------- recoding
-// (on the host for ozk_points_scale_dev, on the device for the per-twiddle schedules of ec_fft.cuh)
+// (on the host for ozk_points_scale_dev, on the device for the per-twiddle schedules of ec_fft.cuh and the per-point
+// ones of points_mul.cuh)
 // Joint sparse form (Solinas 2001) of two non-negative integers below 2^256, least significant column first, each
 // column's signs flipped where its integer is to be subtracted (neg1 / neg2).  u = a mods 4 for an odd a, negated
 // when a = +-3 (mod 8) and b = 2 (mod 4): then (a - u) / 2 is odd exactly when b / 2 is, so that non-zero columns
 // pair up.  sum u_i 2^i = a whatever the choice of sign, which is all the ladder needs.
-OZK_HD void scale_jsf(const u32 (&a_in)[8], bool neg1, const u32 (&b_in)[8], bool neg2, ScaleSchedule& s) {
+template <class S>
+OZK_HD void scale_jsf(const u32 (&a_in)[8], bool neg1, const u32 (&b_in)[8], bool neg2, S& s) {
   u32 v[2][9];
   for (int i = 0; i < 8; i++) {
     v[0][i] = a_in[i];
@@ -71,7 +75,8 @@ OZK_HD void scale_jsf(const u32 (&a_in)[8], bool neg1, const u32 (&b_in)[8], boo
   s.len = len;
 }
 // k < r (the caller's check).  G1: the GLV halves jointly; G2: k alone.
-OZK_HD void scale_recode(const u32 (&k)[8], bool glv, ScaleSchedule& s) {
+template <class S>
+OZK_HD void scale_recode(const u32 (&k)[8], bool glv, S& s) {
   const u32 zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (!glv) return scale_jsf(k, false, zero, false, s);
   u32 h1[4], h2[4], k1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, k2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -83,12 +88,12 @@ OZK_HD void scale_recode(const u32 (&k)[8], bool glv, ScaleSchedule& s) {
   }
   scale_jsf(k1, neg1, k2, neg2, s);
 }
-inline bool scale_scalar_ok(const u32 (&k)[8]) { return !mp_geq<8>(k, GlvConsts::R32); }
+OZK_HD bool scale_scalar_ok(const u32 (&k)[8]) { return !mp_geq<8>(k, GlvConsts::R32); }
 
 // ---------------------------------------------------------------------------------------------- one point
 // [k] q for the schedule of k.  GLV (G1 only) reads both digits of a step, otherwise the second is never set.
-template <class CV, bool GLV>
-OZK_HD Jac<CV> scale_ladder(const Aff<typename CV::EA>& q, const ScaleSchedule& s) {
+template <class CV, bool GLV, class S>
+OZK_HD Jac<CV> scale_ladder(const Aff<typename CV::EA>& q, const S& s) {
   using EA = typename CV::EA;
   Jac<CV> acc = jac_infinity<CV>();
   if (is_inf(q)) return acc;
@@ -104,7 +109,7 @@ OZK_HD Jac<CV> scale_ladder(const Aff<typename CV::EA>& q, const ScaleSchedule& 
 #pragma unroll 1
   for (int i = s.len - 1; i >= 0; i--) {
     acc = jac_dbl<CV>(acc);
-    const u32 c = scale_step(s, i);   // the same in every lane
+    const u32 c = scale_step(s, i);   // the same in every lane for a shared schedule; a lane's own in points_mul.cuh
     if (c == 0) continue;
     Aff<EA> a;
     bool negate = (c & SCALE_N1) != 0;
@@ -127,8 +132,8 @@ OZK_HD Jac<CV> scale_ladder(const Aff<typename CV::EA>& q, const ScaleSchedule& 
 
 // in: one wire-in point, out: [k] of it as wire-in with Z = 1 (O: (0, 1, 0) / ((0, 0), (1, 0), (0, 0))).  The point
 // is read whole before anything is written, so out may be in.
-template <class CV, bool GLV>
-OZK_HD void scale_point(const u32* in, const ScaleSchedule& s, u32* out) {
+template <class CV, bool GLV, class S>
+OZK_HD void scale_point(const u32* in, const S& s, u32* out) {
   using IO = CurveIO<CV>;
   IO::template write<WireIn>(scale_ladder<CV, GLV>(IO::aff_from_wire(in), s), out);
 }

@@ -226,12 +226,7 @@ class KeyFile:
 
     def verify_digest(self):
         """the SHA-256 of the header against every byte after the header"""
-        sha, off = hashlib.sha256(), HEADER_BYTES
-        while off < self.size:
-            n = min(1 << 24, self.size - off)
-            sha.update(self._read_at(off, n))
-            off += n
-        if sha.digest() != self.header.digest:
+        if digest_from(self._read_at, HEADER_BYTES, self.size) != self.header.digest:
             raise ValueError("digest mismatch: the bytes after the header are not the ones the key was saved with")
 
     def r1cs(self):
@@ -239,6 +234,17 @@ class KeyFile:
         h = self.header
         return tuple(parse_r1cs_section(name, self.read(name), h.num_constraints, h.nv)
                      for name in ("r1cs_a", "r1cs_b", "r1cs_c"))
+
+
+def digest_from(read_at, off, size) -> bytes:
+    """SHA-256 of the bytes [off, size) behind read_at(offset, count), 16 MiB at a time (the key file's digest, and
+    the string file's of srs.py)"""
+    sha = hashlib.sha256()
+    while off < size:
+        n = min(1 << 24, size - off)
+        sha.update(read_at(off, n))
+        off += n
+    return sha.digest()
 
 
 def locate(parts, j):

@@ -112,6 +112,7 @@ _SIGS = {
     "ozk_points_decompress_prepared_dev": (ctypes.c_int, [vp, i32, i32, vp, sz, vp, i32, vp]),
     "ozk_groth16_proofs_decompress_dev": (ctypes.c_int, [vp, i32, vp, vp, vp]),
     "ozk_points_scale_dev": (ctypes.c_int, [vp, i32, i32, vp, vp, vp]),
+    "ozk_points_mul_dev": (ctypes.c_int, [vp, vp, i32, i32, vp, vp, vp]),
     "ozk_ec_fft_workspace_bytes": (sz, [i32, i32]),
     "ozk_ec_fft_dev": (ctypes.c_int, [vp, i32, i32, vp, i32, vp, vp, sz, vp]),
     "ozk_sparse_mat_points_workspace_bytes": (sz, [i32, i32]),

@@ -12,22 +12,43 @@ For a domain of size m (a power of two, m >= 2), every array a uint8 CUDA tensor
     beta_tau_g1[i]  = [beta tau^i] g1    0 <= i < m
     beta_g2         = [beta] g2
 
-Out of scope: a file format for the string, phase-1 contributions (re-randomising tau, alpha, beta of an existing
-string) and interoperability with other tools' .ptau files.  There is no CPU path.
+A string starts public and is re-randomised by several parties in turn:
+
+    srs0 = Srs.initial(m)                            # tau = alpha = beta = 1: no secret at all
+    srs1, receipt = srs0.contribute()                # the three factors drawn here and forgotten on return
+    assert verify_contribution(srs0, srs1, receipt)  # anybody
+    srs1.save(path); srs1 = Srs.load(path)           # the OZKSRS v1 file; load decodes, it does not check()
+
+Out of scope: interoperability with other tools' .ptau files and receipts, hash-to-curve, a random beacon and a
+device-side weight stream.  There is no CPU path.
 """
 import ctypes
 import hashlib
+import secrets
+import struct
 import time
 
 import torch
 
 from . import ceremony as _ceremony
 from . import codec as _codec
+from . import keyfile as _keyfile
 from . import lib as _lib
 from .device import VarMsmWorkspace, _ptr, _stream
 from .fft import FR, root_of_unity
 
 G1, G2 = 1, 2
+# phase-1 contributions
+MAGIC = b"OZKC1\x00\x00\x01"
+RECEIPT_BYTES = 432
+CONTRIBUTION_CHECKS = ("receipt_points", "generators", "pok", "wellformed")
+_POK_TAG = b"OZK-phase1-pok"
+_SECRETS = ("tau", "alpha", "beta")
+# the string file: (section, point type, count as a function of m), in file order
+FILE_MAGIC = b"OZKSRS\x00\x01"
+FILE_HEADER_BYTES = 48
+FILE_SECTIONS = (("tau_g1", G1, lambda m: 2 * m + 1), ("alpha_tau_g1", G1, lambda m: m), ("beta_tau_g1", G1, lambda m: m),
+                 ("tau_g2", G2, lambda m: m), ("beta_g2", G2, lambda m: 1))
 CHECKS = ("shape", "powers_g1", "powers_g2", "alpha_powers", "beta_powers", "beta_g2")
 _RHO_TAG = b"OZK-srs-rho"
 
@@ -93,10 +114,101 @@ class Srs:
                                            _ptr(d_sc), _ptr(ws), wsb, _stream()))
             torch.cuda.current_stream().synchronize()
             window = get_window_size(n, G1_WINDOW_TABLE if type_ == G1 else G2_WINDOW_TABLE)
-            return z.batch_msm_dev(z._bit_size(gens[type_]), window, gens[type_], d_sc, type_)
+            bits = z._bit_size(gens[type_])
+            if -(-bits // window) * window < 254:     # a few points take window 1: the plan must still cover a scalar
+                bits = 254
+            return z.batch_msm_dev(bits, window, gens[type_], d_sc, type_)
 
         beta_g2 = z.batch_msm_dev(z._bit_size(gens[G2]), 16, gens[G2], [beta], G2)
         return Srs(m, powers(1, 2 * m + 1, G1), powers(1, m, G2), powers(alpha, m, G1), powers(beta, m, G1), beta_g2)
+
+    @staticmethod
+    def initial(m, generator=None) -> "Srs":
+        """The string of tau = alpha = beta = 1: every entry the generator of its group.  It holds no secret and is
+        the public start of a chain of contributions."""
+        return Srs.from_secrets(m, 1, 1, 1, generator)
+
+    # ------------------------------------------------------------------------ phase 1
+    def contribute(self, tau=None, alpha=None, beta=None, *, nonces=None, previous=b""):
+        """(the string after, the receipt bytes): tau, alpha, beta of this string multiplied by the secrets s, a, b
+        in [1, r) given as `tau`, `alpha`, `beta` (each drawn from `secrets` when None):
+
+            tau_g1[i] times s^i, tau_g2[i] times s^i, alpha_tau_g1[i] times a s^i, beta_tau_g1[i] times b s^i
+            (four mul_points calls over scalars ozk_fr_powers_dev writes on the device), beta_g2 times b
+
+        The scalar buffers are zeroed on the device before they are released.  `previous`: the bytes of the receipt
+        before this one, empty for the first.  `nonces`: the three u of the proofs of knowledge, in [1, r); give them
+        for reproducible receipts in tests only."""
+        s, a, b = (secrets.randbelow(FR - 1) + 1 if v is None else _ceremony._scalar(v, what, 1)
+                   for v, what in zip((tau, alpha, beta), _SECRETS))
+        if nonces is None:
+            nonces = [secrets.randbelow(FR - 1) + 1 for _ in _SECRETS]
+        nonces = [_ceremony._scalar(u, "nonce", 1) for u in nonces]
+        if len(nonces) != 3:
+            raise ValueError("three nonces: one per secret")
+        m = self.m
+        L = _lib.load()
+        spent = []
+
+        def powers(k, n):
+            """k s^i, i < n, on the device"""
+            d_sc = torch.empty(n * 32, dtype=torch.uint8, device="cuda")
+            wsb = int(L.ozk_fr_powers_workspace_bytes(n))
+            ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device="cuda")
+            tb = (ctypes.c_uint8 * 32).from_buffer_copy(s.to_bytes(32, "little"))
+            kb = (ctypes.c_uint8 * 32).from_buffer_copy(k.to_bytes(32, "little"))
+            _lib.check(L.ozk_fr_powers_dev(ctypes.cast(tb, ctypes.c_void_p), ctypes.cast(kb, ctypes.c_void_p), n,
+                                           _ptr(d_sc), _ptr(ws), wsb, _stream()))
+            spent.extend((d_sc, ws))
+            return d_sc
+
+        try:
+            pw = powers(1, 2 * m + 1)
+            new = Srs(m, mul_points(self.tau_g1, pw, G1), mul_points(self.tau_g2, pw[:32 * m], G2),
+                      mul_points(self.alpha_tau_g1, powers(a, m), G1), mul_points(self.beta_tau_g1, powers(b, m), G1),
+                      _ceremony.scale_points(self.beta_g2, b, G2))
+        finally:
+            for t in spent:
+                t.zero_()
+            torch.cuda.current_stream().synchronize()
+            del spent
+        bases = _pok_bases(self)
+        rs = _ceremony._enc(torch.cat([_ceremony.scale_points(p, u, G1) for p, u in zip(bases, nonces)]), G1)
+        pts = _ceremony._enc(torch.cat(bases + _pok_bases(new)), G1)
+        rec = Receipt(m, hashlib.sha256(bytes(previous)).digest(),
+                      [(pts[32 * j:32 * j + 32], pts[96 + 32 * j:128 + 32 * j], rs[32 * j:32 * j + 32], 0) for j in range(3)])
+        for j, (k, u) in enumerate(zip((s, a, b), nonces)):
+            before, after, r, _ = rec.blocks[j]
+            rec.blocks[j] = (before, after, r, (u + rec.challenge(j) * k) % FR)
+        return new, rec.to_bytes()
+
+    # ------------------------------------------------------------------------ file
+    def save(self, path) -> None:
+        """Write the string as an OZKSRS version 1 file: the points compressed on the device,
+        magic | m | SHA-256 of the payload | tau_g1 | alpha_tau_g1 | beta_tau_g1 | tau_g2 | beta_g2."""
+        sections = {name: _ceremony._enc(getattr(self, name).reshape(-1), type_) for name, type_, _ in FILE_SECTIONS}
+        with open(path, "wb") as f:
+            f.write(string_file_bytes(self.m, sections))
+
+    @staticmethod
+    def load(src) -> "Srs":
+        """The string of an OZKSRS file (`src`: a path, bytes, or a binary file object), parsed strictly
+        (parse_string_file) and decoded on the device with ozk_points_decompress_dev; ValueError naming the first
+        section and index whose point does not decode.  load does NOT run check(): the points are on their curves and
+        nothing more is known.  In particular a decoded G2 point is on the twist and not yet in the order-r
+        subgroup.  Run check() on a string somebody else supplies."""
+        from .zksnark import _dev_bytes
+        m, sections = parse_string_file(src)
+        arrays = {}
+        for name, type_, _ in FILE_SECTIONS:
+            arrays[name], codes = _codec._decompress(_dev_bytes(sections[name]), type_, "wire_in")
+            bad = torch.nonzero(codes)
+            if bad.numel():
+                i = int(bad[0].item())
+                code = int(codes[i].item())
+                raise ValueError("section %s: point %d does not decode: code %d (%s)"
+                                 % (name, i, code, _codec.CODE_NAMES.get(code, "?")))
+        return Srs(m, *(arrays[name] for name in ("tau_g1", "tau_g2", "alpha_tau_g1", "beta_tau_g1", "beta_g2")))
 
     # ------------------------------------------------------------------------ check
     def check(self, seed=None, why=None) -> bool:
@@ -193,7 +305,211 @@ def _in_subgroup(points, encodings: bytes) -> bool:
     return minus == bytes(want)
 
 
+# ---------------------------------------------------------------------------- phase 1: receipt and verification
+def _pok_bases(srs):
+    """the three points whose factors a contribution proves knowledge of: tau_g1[1], alpha_tau_g1[0], beta_tau_g1[0]"""
+    return [_point(srs.tau_g1, 1, G1), _point(srs.alpha_tau_g1, 0, G1), _point(srs.beta_tau_g1, 0, G1)]
+
+
+class Receipt:
+    """What a phase-1 contributor publishes next to the new string (432 bytes): m, the transcript digest h, and for
+    each of tau, alpha, beta a block (before, after, R, z): the base before and after and the Schnorr proof of
+    knowledge of the factor between them, exactly as ceremony.Receipt proves its d."""
+
+    def __init__(self, m, h, blocks):
+        """h: 32 bytes; blocks: three (before, after, r: compressed G1, 32 bytes each; z: int)"""
+        self.m, self.h, self.blocks = int(m), bytes(h), [(bytes(x), bytes(y), bytes(r), int(z)) for x, y, r, z in blocks]
+
+    def to_bytes(self) -> bytes:
+        b = MAGIC + struct.pack("<Q", self.m) + self.h + b"".join(
+            x + y + r + z.to_bytes(32, "little") for x, y, r, z in self.blocks)
+        if len(b) != RECEIPT_BYTES:
+            raise ValueError("receipt: a field has the wrong length")
+        return b
+
+    @staticmethod
+    def from_bytes(b) -> "Receipt":
+        """Strict and host-only: ValueError naming the field for a wrong length, a wrong magic, an m that is no power
+        of two >= 2, a z >= r or a point that does not decode."""
+        b = _ceremony._receipt_head(b, MAGIC, RECEIPT_BYTES)
+        m = struct.unpack_from("<Q", b, 8)[0]
+        if m < 2 or m & (m - 1):
+            raise ValueError("receipt: m = %d is not a power of two >= 2" % m)
+        blocks, fields = [], []
+        for j, name in enumerate(_SECRETS):
+            o = 48 + 128 * j
+            z = int.from_bytes(b[o + 96:o + 128], "little")
+            if z >= FR:
+                raise ValueError("receipt: %s_z is not below r" % name)
+            blocks.append((b[o:o + 32], b[o + 32:o + 64], b[o + 64:o + 96], z))
+            fields += [("%s_%s" % (name, part), b[o + 32 * i:o + 32 * i + 32], G1)
+                       for i, part in enumerate(("before", "after", "r"))]
+        _ceremony._require_points(fields)
+        return Receipt(m, b[16:48], blocks)
+
+    def challenge(self, j) -> int:
+        """c_j: what block j's response answers; it binds m, h, all six points and R_j"""
+        body = bytes([j]) + struct.pack("<Q", self.m) + self.h + b"".join(x + y for x, y, _, _ in self.blocks)
+        return _ceremony._challenge(body, self.blocks[j][2], _POK_TAG)
+
+
+def _shaped(srs) -> bool:
+    m = srs.m
+    return m >= 2 and not m & (m - 1) and all(
+        getattr(srs, name).numel() == 96 * type_ * count(m) for name, type_, count in FILE_SECTIONS)
+
+
+def verify_contribution(before, after, receipt, *, seed=None, why=None) -> bool:
+    """True exactly when `after` is `before` after one contribution that `receipt` (a Receipt or its bytes)
+    describes.  The checks run in the order of CONTRIBUTION_CHECKS and the first that fails ends the call with False;
+    `why` (a list) then receives its name.
+
+      receipt_points  both strings have the receipt's m and the lengths that go with it, and the receipt's six points
+                      are the compressed tau_g1[1], alpha_tau_g1[0], beta_tau_g1[0] of the two strings
+      generators      tau_g1[0] and tau_g2[0] equal as compressed encodings
+      pok             z_j before_j - c_j after_j - R_j = O for tau, alpha and beta: three 3-point MSMs
+      wellformed      after.check(seed=seed)
+
+    `before` is taken on trust, or from the step before it (verify_chain)."""
+    def no(name):
+        if why is not None:
+            why.append(name)
+        return False
+
+    rec = receipt if isinstance(receipt, Receipt) else Receipt.from_bytes(receipt)
+    if not (before.m == after.m == rec.m and _shaped(before) and _shaped(after)):
+        return no("receipt_points")
+    b_pts, a_pts = _pok_bases(before), _pok_bases(after)
+    pts = _ceremony._enc(torch.cat(b_pts + a_pts), G1)
+    if any((pts[32 * j:32 * j + 32], pts[96 + 32 * j:128 + 32 * j]) != rec.blocks[j][:2] for j in range(3)):
+        return no("receipt_points")
+    g1 = _ceremony._enc(torch.cat([_point(before.tau_g1, 0, G1), _point(after.tau_g1, 0, G1)]), G1)
+    g2 = _ceremony._enc(torch.cat([_point(before.tau_g2, 0, G2), _point(after.tau_g2, 0, G2)]), G2)
+    if g1[:32] != g1[32:] or g2[:64] != g2[64:]:
+        return no("generators")
+    flags = [_ceremony._pok_holds(b_pts[j], a_pts[j], rec.blocks[j][2], rec.blocks[j][3], rec.challenge(j))
+             for j in range(3)]
+    ok = [_ceremony._pok_read(flag) for flag, _ in flags]
+    del flags
+    if not all(ok):
+        return no("pok")
+    if not after.check(seed=seed):
+        return no("wellformed")
+    return True
+
+
+def verify_chain(strings, receipts, *, seed=None, why=None) -> bool:
+    """strings[0] .. strings[k] and the k receipts between them: every step passes verify_contribution, the first
+    receipt's h is the SHA-256 of the empty string and every later one's that of the receipt before it (`why`
+    receives "chain" for a broken link, else the failed check of the step)."""
+    strings = list(strings)
+    raw = [r.to_bytes() if isinstance(r, Receipt) else bytes(r) for r in receipts]
+    if len(strings) != len(raw) + 1 or not raw:
+        raise ValueError("k receipts go with k + 1 strings, k >= 1")
+    previous = b""
+    for i, b in enumerate(raw):
+        rec = Receipt.from_bytes(b)
+        if rec.h != hashlib.sha256(previous).digest():
+            if why is not None:
+                why.append("chain")
+            return False
+        if not verify_contribution(strings[i], strings[i + 1], rec, seed=seed, why=why):
+            return False
+        previous = b
+    return True
+
+
+# ---------------------------------------------------------------------------- the string file (host only)
+def string_file_size(m) -> int:
+    return FILE_HEADER_BYTES + sum(32 * type_ * count(m) for _, type_, count in FILE_SECTIONS)
+
+
+def string_file_bytes(m, sections) -> bytes:
+    """The OZKSRS version 1 file of a string: `sections` maps every name of FILE_SECTIONS to its compressed points."""
+    m = int(m)
+    if m < 2 or m & (m - 1):
+        raise ValueError("the domain size must be a power of two >= 2, not %d" % m)
+    for name, type_, count in FILE_SECTIONS:
+        if len(sections[name]) != 32 * type_ * count(m):
+            raise ValueError("section %s: %d bytes, m says %d" % (name, len(sections[name]), 32 * type_ * count(m)))
+    payload = b"".join(bytes(sections[name]) for name, _, _ in FILE_SECTIONS)
+    return FILE_MAGIC + struct.pack("<Q", m) + hashlib.sha256(payload).digest() + payload
+
+
+def parse_string_file(src):
+    """(m, {section: compressed points}) of an OZKSRS file, strictly: ValueError for a wrong magic or version, an m
+    that is no power of two >= 2, a length that does not follow from m, a digest mismatch.  `src`: a path, bytes, or
+    a binary file object (seek, read).  Host only; the points are not decoded here."""
+    own = None
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        f = _keyfile._Bytes(bytes(src))
+    elif hasattr(src, "read"):
+        f = src
+    else:
+        f = own = open(src, "rb")
+    try:
+        size = f.seek(0, 2)
+
+        def read_at(off, n):
+            f.seek(off)
+            out = f.read(n)
+            if len(out) != n:
+                raise ValueError("truncated file: %d bytes at offset %d, %d read" % (n, off, len(out)))
+            return out
+
+        head = read_at(0, min(FILE_HEADER_BYTES, size))
+        if len(head) < 8 or head[:7] != FILE_MAGIC[:7]:
+            raise ValueError("header: not a string file (wrong magic)")
+        if head[7] != FILE_MAGIC[7]:
+            raise ValueError("header: string file version %d, this library reads version 1 (wrong magic)" % head[7])
+        if len(head) < FILE_HEADER_BYTES:
+            raise ValueError("header: truncated file (length %d, the header alone is %d)" % (len(head), FILE_HEADER_BYTES))
+        m = struct.unpack_from("<Q", head, 8)[0]
+        if m < 2 or m & (m - 1):
+            raise ValueError("header: m = %d is not a power of two >= 2" % m)
+        if size != string_file_size(m):
+            raise ValueError("length %d, m = %d says %d" % (size, m, string_file_size(m)))
+        if _keyfile.digest_from(read_at, FILE_HEADER_BYTES, size) != head[16:48]:
+            raise ValueError("digest mismatch: the bytes after the header are not the ones the string was saved with")
+        sections, off = {}, FILE_HEADER_BYTES
+        for name, type_, count in FILE_SECTIONS:
+            n = 32 * type_ * count(m)
+            sections[name] = read_at(off, n)
+            off += n
+        return m, sections
+    finally:
+        if own is not None:
+            own.close()
+
+
 # ---------------------------------------------------------------------------- point kernels
+def mul_points(points, scalars, type_, codes=False):
+    """[k_i] P_i for the n wire-in points of `points` and the n scalars of `scalars` (n x 32 bytes little-endian on
+    the device, as ozk_fr_powers_dev writes them): n wire-in points with Z = 1 (ozk_points_mul_dev).  A scalar >= r
+    gives infinity for that point alone; codes=True returns (points, n int32 codes), 1 for such a point.  Exact for
+    every point of the curve or twist.  Asynchronous on the current stream."""
+    if type_ not in (G1, G2):
+        raise ValueError("type_ must be 1 (G1) or 2 (G2)")
+    for t, what in ((points, "points"), (scalars, "scalars")):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8):
+            raise ValueError("%s must be a uint8 tensor" % what)
+    rec = 96 * type_
+    if points.numel() == 0 or points.numel() % rec:
+        raise ValueError("points: %d bytes are not a whole number of %d-byte records" % (points.numel(), rec))
+    n = points.numel() // rec
+    if scalars.numel() != 32 * n:
+        raise ValueError("%d points need %d bytes of scalars, not %d" % (n, 32 * n, scalars.numel()))
+    L = _lib.load()
+    _codec._count(points, rec, "points")
+    _codec._count(scalars, 32, "scalars")
+    points, scalars = points.contiguous(), scalars.contiguous()
+    out = torch.empty_like(points)
+    d_codes = torch.empty(n, dtype=torch.int32, device=points.device) if codes else None
+    _lib.check(L.ozk_points_mul_dev(_ptr(points), _ptr(scalars), n, type_, _ptr(out),
+                                    None if d_codes is None else _ptr(d_codes), _stream()))
+    return (out, d_codes) if codes else out
+
+
 def ec_fft(points, type_, omega, inverse=False) -> torch.Tensor:
     """The radix-2 transform of n = 2^k wire-in points in the exponent (ozk_ec_fft_dev): out[j] = sum_i
     [omega^(i j)] in[i]; inverse=True uses omega^-1 and multiplies by 1 / n.  A new tensor, Z = 1."""
