@@ -466,6 +466,42 @@ int ozk_fr_poly_eval_dev(const void* d_coeffs, int32_t npolys, int32_t len, int6
                          const uint8_t* r_host32, void* d_out, void* d_workspace, size_t workspace_bytes,
                          void* stream);
 
+/* KZG openings over Fr (csrc/kzg.cuh): the quotient (p(X) - p(z)) / (X - z) and the value p(z)
+ * of npolys rows at once, and a weighted sum of rows.  Elements are 32-byte little-endian and 16-byte aligned, all in
+ * HBM except omega; a value >= r is REDUCED mod r on load (coefficients, evaluations, points and weights alike), and
+ * every output is canonical.  Strides count elements.
+ *   ozk_fr_poly_open_dev      coefficient form.  Row y: p = the len coefficients at d_coeffs + 32 y poly_stride,
+ *                             z = d_points[y]; d_values[y] = p(z), and the row at d_quot + 32 y quot_stride holds
+ *                             q_0 .. q_{len-2} with q_{j-1} = p_j + z q_j, and element len - 1 = 0: an MSM scalar vector
+ *                             of the same length over the same bases.  poly_stride is 0 (ONE polynomial opened at npolys
+ *                             points) or >= len; quot_stride >= len, and elements of a row beyond len are not touched.
+ *                             1 <= len, 1 <= npolys, npolys len <= 2^28.  d_quot must not overlap d_coeffs (rejected).
+ *                             Workspace: ozk_fr_poly_open_workspace_bytes(npolys, len).
+ *   ozk_fr_evals_open_dev     evaluation form.  Row y holds f_i = p(omega^i), i < n, in natural order; n is a power of
+ *                             two, 2 <= n <= 2^28, npolys n <= 2^28; omega (32-byte LE, host memory, read before the
+ *                             call returns) must have order exactly n (omega^(n/2) = -1 is checked on the host).
+ *                             d_values[y] = p(z) and q_i = (f_i - p(z)) / (omega^i - z), the evaluations of the same
+ *                             quotient; for z = omega^k: d_values[y] = f_k and q_k = -omega^-k sum_{i != k} q_i omega^i,
+ *                             found and finished on the device.  evals_stride is 0 or >= n, quot_stride >= n; d_quot
+ *                             must not overlap d_evals (rejected).
+ *                             Workspace: ozk_fr_evals_open_workspace_bytes(npolys, n).
+ *   ozk_fr_rows_combine_dev   d_out[j] = sum_{i < k} w_i rows[i][j], j < len: row i at d_rows + 32 i row_stride
+ *                             (row_stride >= len), w = the k elements at d_weights.  d_out may be d_rows (the first
+ *                             row); any other overlap is rejected.  k len <= 2^28.
+ * A size function returns 0 for a shape it rejects; the entry points return OZK_E_INVALID for it before any launch (the
+ * shape is checked before the pointers).  All calls are asynchronous on `stream`, allocate nothing and synchronise
+ * nothing. */
+size_t ozk_fr_poly_open_workspace_bytes(int32_t npolys, int32_t len);
+int ozk_fr_poly_open_dev(const void* d_coeffs, int32_t npolys, int32_t len, int64_t poly_stride, const void* d_points,
+                         void* d_quot, int64_t quot_stride, void* d_values, void* d_workspace, size_t workspace_bytes,
+                         void* stream);
+size_t ozk_fr_evals_open_workspace_bytes(int32_t npolys, int32_t n);
+int ozk_fr_evals_open_dev(const void* d_evals, int32_t npolys, int32_t n, int64_t evals_stride,
+                          const uint8_t* omega_host32, const void* d_points, void* d_quot, int64_t quot_stride,
+                          void* d_values, void* d_workspace, size_t workspace_bytes, void* stream);
+int ozk_fr_rows_combine_dev(const void* d_rows, int32_t k, int32_t len, int64_t row_stride, const void* d_weights,
+                            void* d_out, void* stream);
+
 /* ---- batched MSM over shared bases (msm_multi.hip; no counterpart in the reference, whose verifier runs one
  * variable-base MSM per proof): out_i = sum_{j < n} s_ij P_j for k scalar rows over the SAME n bases, G1 only.
  * A window table of every base is built once (ozk_multi_msm_prepare_dev); a run is table gathers and mixed

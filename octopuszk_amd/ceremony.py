@@ -73,14 +73,14 @@ def _challenge(body: bytes, r_enc: bytes, tag=b"OZK-phase2-pok") -> int:
     return int.from_bytes(hashlib.sha256(tag + body + r_enc).digest()[:16], "little") or 1
 
 
-def _weights(seed: bytes, n: int) -> bytes:
+def _weights(seed: bytes, n: int, tag=b"OZK-phase2-rho") -> bytes:
     """n weights in [1, 2^128) as n x 32 bytes little-endian: block j of the stream is SHA-256("OZK-phase2-rho" | seed
-    | j as 8 bytes little-endian), two weights per block"""
+    | j as 8 bytes little-endian), two weights per block (kzg.py: the same under its own tag)"""
     out = bytearray(32 * n)
     pad = bytes(16)
     one = (1).to_bytes(16, "little")
     for j in range((n + 1) // 2):
-        block = hashlib.sha256(b"OZK-phase2-rho" + seed + j.to_bytes(8, "little")).digest()
+        block = hashlib.sha256(tag + seed + j.to_bytes(8, "little")).digest()
         for half in (0, 1):
             i = 2 * j + half
             if i < n:

@@ -1358,3 +1358,4 @@ int ozk_fft_compact_host(const uint8_t* in, int32_t n, const uint8_t* omega, int
 }  // extern "C"
 
 #include "bace.cuh"
+#include "kzg.cuh"

@@ -1,0 +1,432 @@
+"""KZG polynomial commitments over a powers-of-tau string.
+
+    ck = CommitKey.from_srs(srs)                     # tau_g1[:n] as prepared MSM bases
+    vk = VerifyKey.from_srs(srs)                     # tau_g1[0], tau_g2[0], tau_g2[1]; 160 bytes
+    c = ck.commit(coeffs)                            # K rows of n coefficients -> K compressed commitments
+    openings = ck.open(coeffs, [z_0, ..., z_K-1])    # Opening: C | z | y | pi, 128 bytes
+    assert verify(vk, openings[0]) and verify_all(vk, openings)
+
+Polynomials are rows of a uint8 CUDA tensor, 32 bytes little-endian per element, 16-byte aligned: a 1-D tensor is one
+row, a 2-D tensor [K, 32 len] is K rows (the row stride may exceed the row: the caller pads).  A coefficient row has
+exactly the key's n elements (shorter polynomials are zero-padded); an evaluation row has a power of two n <= 2 m of
+them, p(omega_n^i) in natural order, and is committed over the Lagrange form of the string (CommitKey.lagrange).
+
+The commitment is C = [p(tau)] g1; an opening at z is pi = [q(tau)] g1 for q = (p - p(z)) / (X - z), and it verifies when
+e(C - [y] g1 + [z] pi, g2) e(-pi, [tau] g2) = 1.  The quotient comes from ozk_fr_poly_open_dev / ozk_fr_evals_open_dev
+(csrc/kzg.cuh); every group operation is an existing entry point: the variable-base MSM over prepared bases, the group
+FFT, the pairing product and the point codec.
+
+Out of scope: hiding commitments, one proof for several points of one polynomial, degree-bound proofs, G2
+commitments, interoperability with other tools' byte formats.  There is no CPU path.
+"""
+import ctypes
+import hashlib
+import secrets
+
+import torch
+
+from . import ceremony as _ceremony
+from . import codec as _codec
+from . import lib as _lib
+from .device import VarMsmWorkspace, _ptr, _stream, prepare_bases
+from .fft import FR, root_of_unity
+
+G1, G2 = 1, 2
+OPENING_BYTES, VK_BYTES = 128, 160
+_RHO_TAG = b"OZK-kzg-rho"
+_GAMMA_TAG = b"OZK-kzg-gamma"
+_G1_INF = bytes(31) + b"\x40"
+
+
+# ---------------------------------------------------------------------------- argument checks (no library call)
+def _rows(t, what, n=None):
+    """(K, elements per row, row stride in elements) of a tensor of rows; n: the row length the caller requires"""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+        raise TypeError("%s must be a uint8 CUDA tensor" % what)
+    if not t.is_cuda:
+        raise TypeError("%s must be a uint8 CUDA tensor, not one on %s" % (what, t.device))
+    if t.dim() not in (1, 2) or t.numel() == 0:
+        raise ValueError("%s must be one row (1-D) or K rows (2-D), not %d-D" % (what, t.dim()))
+    if t.dim() == 1:
+        t = t.unsqueeze(0)
+    if t.stride(1) != 1 or t.shape[1] % 32 or (t.shape[0] > 1 and (t.stride(0) % 32 or t.stride(0) < t.shape[1])):
+        raise ValueError("%s: rows of whole 32-byte elements, contiguous, at a stride that is a multiple of 32" % what)
+    if t.data_ptr() % 16:
+        raise ValueError("%s is not 16-byte aligned" % what)
+    k, length = t.shape[0], t.shape[1] // 32
+    if n is not None and length != n:
+        raise ValueError("%s: rows of %d elements, the key has n = %d (zero-pad shorter polynomials)" % (what, length, n))
+    return k, length, (t.stride(0) // 32 if k > 1 else length)
+
+
+def _eval_size(length, m):
+    """the size of an evaluation row: a power of two in [2, 2 m]"""
+    if length < 2 or length & (length - 1):
+        raise ValueError("an evaluation row has a power of two >= 2 of elements, not %d" % length)
+    if length > 2 * m:
+        raise ValueError("evaluation rows of %d elements: the string has m = %d and carries at most 2 m" % (length, m))
+    return length
+
+
+def _scalars(values, k, what):
+    """k ints in [0, r) (one int serves k = 1)"""
+    values = [values] if isinstance(values, int) else list(values)
+    if len(values) != k:
+        raise ValueError("%d %s for %d rows" % (len(values), what, k))
+    return [_ceremony._scalar(v, what) for v in values]
+
+
+def _le(values) -> bytes:
+    return b"".join(int(v).to_bytes(32, "little") for v in values)
+
+
+def _ints(b: bytes):
+    return [int.from_bytes(b[i:i + 32], "little") for i in range(0, len(b), 32)]
+
+
+def _vp(b: bytes):
+    return ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p)
+
+
+def _enc_of(b, what, size=32) -> bytes:
+    b = bytes(b)
+    if len(b) != size:
+        raise ValueError("%s: %d bytes, not %d" % (what, len(b), size))
+    return b
+
+
+# ---------------------------------------------------------------------------- bytes
+class Opening:
+    """C | z | y | pi (128 bytes): the compressed commitment, the point, the value, the compressed proof"""
+
+    def __init__(self, c, z, y, pi):
+        self.c, self.pi = _enc_of(c, "opening: C"), _enc_of(pi, "opening: pi")
+        self.z, self.y = _ceremony._scalar(z, "opening: z"), _ceremony._scalar(y, "opening: y")
+
+    def to_bytes(self) -> bytes:
+        return self.c + _le([self.z, self.y]) + self.pi
+
+    @staticmethod
+    def from_bytes(b) -> "Opening":
+        """Strict and host-only: ValueError naming the field for a wrong length, z or y >= r, a point that does not
+        decode."""
+        b = bytes(b)
+        if len(b) != OPENING_BYTES:
+            raise ValueError("opening: length %d, not %d" % (len(b), OPENING_BYTES))
+        z, y = _ints(b[32:96])
+        for name, v in (("z", z), ("y", y)):
+            if v >= FR:
+                raise ValueError("opening: %s is not below r" % name)
+        _require_points((("C", b[:32], G1), ("pi", b[96:], G1)), "opening")
+        return Opening(b[:32], z, y, b[96:])
+
+
+def _require_points(fields, owner):
+    for name, enc, type_ in fields:
+        code = _ceremony._decode_code(enc, type_)
+        if code:
+            raise ValueError("%s: %s does not decode: code %d (%s)" % (owner, name, code, _codec.CODE_NAMES.get(code, "?")))
+
+
+def _g2_in_subgroup(points, encodings: bytes) -> bool:
+    from .srs import _in_subgroup
+    return _in_subgroup(points, encodings)
+
+
+class VerifyKey:
+    """g1 = tau_g1[0], g2 = tau_g2[0], tau_g2 = tau_g2[1]: 32 | 64 | 64 bytes, compressed as DESIGN.md section 13"""
+
+    def __init__(self, g1, g2, tau_g2):
+        self.g1 = _enc_of(g1, "verification key: g1")
+        self.g2, self.tau_g2 = _enc_of(g2, "verification key: g2", 64), _enc_of(tau_g2, "verification key: tau_g2", 64)
+        self._points = None
+
+    @staticmethod
+    def from_srs(srs) -> "VerifyKey":
+        e1 = _ceremony._enc(srs.tau_g1.reshape(-1)[:96], G1)
+        e2 = _ceremony._enc(srs.tau_g2.reshape(-1)[:384], G2)
+        return VerifyKey(e1, e2[:64], e2[64:])
+
+    def to_bytes(self) -> bytes:
+        return self.g1 + self.g2 + self.tau_g2
+
+    @staticmethod
+    def from_bytes(b) -> "VerifyKey":
+        """Strict: ValueError naming the field for a wrong length, a point that does not decode or is infinity (host
+        checks), then for a G2 point outside the order-r subgroup ([r - 1] P = -P on the device, as Srs.check)."""
+        b = bytes(b)
+        if len(b) != VK_BYTES:
+            raise ValueError("verification key: length %d, not %d" % (len(b), VK_BYTES))
+        fields = (("g1", b[:32], G1), ("g2", b[32:96], G2), ("tau_g2", b[96:], G2))
+        _require_points(fields, "verification key")
+        for name, enc, _ in fields:
+            if enc[-1] & 0x40:
+                raise ValueError("verification key: %s is the point at infinity" % name)
+        vk = VerifyKey(b[:32], b[32:96], b[96:])
+        for i, name in enumerate(("g2", "tau_g2")):
+            if not _g2_in_subgroup(vk.points()[1][192 * i:192 * (i + 1)], fields[1 + i][1]):
+                raise ValueError("verification key: %s is not in the order-r subgroup" % name)
+        return vk
+
+    def points(self):
+        """(g1: one wire-in point, g2 | tau_g2: two wire-in points) on the device, decoded once"""
+        if self._points is None:
+            from .zksnark import _dev_bytes
+            p1, c1 = _codec.decompress_g1(_dev_bytes(self.g1))
+            p2, c2 = _codec.decompress_g2(_dev_bytes(self.g2 + self.tau_g2))
+            if int(c1.any().item()) or int(c2.any().item()):
+                raise ValueError("verification key: a point does not decode")
+            self._points = (p1, p2)
+        return self._points
+
+
+# ---------------------------------------------------------------------------- the committer
+class CommitKey:
+    """The first n powers of a string as prepared bases of the variable-base MSM, and (built on first use) the
+    Lagrange form of its first n_e powers for every evaluation-row size n_e used."""
+
+    def __init__(self, tau_g1, n, m):
+        self.n, self.m = int(n), int(m)
+        self._tau_g1 = tau_g1          # wire-in, at least min(2 m, all) points: the source of the Lagrange forms
+        self._bases = None
+        self._lagrange = {}
+        self._msm = {}
+
+    @staticmethod
+    def from_srs(srs, n=None) -> "CommitKey":
+        have = 2 * int(srs.m) + 1
+        n = have if n is None else int(n)
+        if not 1 <= n <= have:
+            raise ValueError("n = %d: a string of m = %d carries %d powers in G1" % (n, srs.m, have))
+        return CommitKey(srs.tau_g1.reshape(-1), n, srs.m)
+
+    # ---- bases
+    def bases(self):
+        if self._bases is None:
+            self._bases = prepare_bases(self._tau_g1[:96 * self.n].contiguous(), self.n, G1)
+        return self._bases
+
+    def lagrange(self, n):
+        """prepared bases of L_i(tau) g1, i < n, for the domain of omega_n: the inverse group transform of tau_g1[:n]"""
+        n = _eval_size(int(n), self.m)
+        if n not in self._lagrange:
+            from .srs import ec_fft
+            pts = ec_fft(self._tau_g1[:96 * n].contiguous(), G1, root_of_unity(n), inverse=True)
+            self._lagrange[n] = prepare_bases(pts, n, G1)
+        return self._lagrange[n]
+
+    def _msms(self, bases, n, scalars, k, stride):
+        """k MSMs of n scalars each (row y at element y stride of `scalars`) over prepared bases -> k x 32 bytes"""
+        if n not in self._msm:
+            self._msm[n] = VarMsmWorkspace(n, G1)
+        ws = self._msm[n]
+        flat = scalars.reshape(-1) if scalars.is_contiguous() else None
+        outs = []
+        for y in range(k):
+            row = flat[32 * y * stride:32 * (y * stride + n)] if flat is not None else scalars[y].contiguous()
+            outs.append(ws.run(bases, row, prepared=True).clone())
+        return _ceremony._bytes(_codec.compress_g1(torch.cat(outs), "wire_out"))
+
+    # ---- commit
+    def commit(self, coeffs) -> list:
+        """K rows of n coefficients -> K compressed commitments (one MSM per row)"""
+        k, _, stride = _rows(coeffs, "coeffs", self.n)
+        enc = self._msms(self.bases(), self.n, _as2d(coeffs), k, stride)
+        return [enc[32 * i:32 * i + 32] for i in range(k)]
+
+    def commit_evals(self, evals) -> list:
+        """K rows of evaluations on the domain of omega_n -> the commitments of their interpolants"""
+        k, n, stride = _rows(evals, "evals")
+        _eval_size(n, self.m)
+        enc = self._msms(self.lagrange(n), n, _as2d(evals), k, stride)
+        return [enc[32 * i:32 * i + 32] for i in range(k)]
+
+    # ---- open
+    def _openings(self, commitments, zs, quot, n, bases, values):
+        k = len(zs)
+        pis = self._msms(bases, n, quot, k, n)
+        ys = _ints(_ceremony._bytes(values))
+        return [Opening(commitments[i], zs[i], ys[i], pis[32 * i:32 * i + 32]) for i in range(k)]
+
+    def open(self, coeffs, z) -> list:
+        """K rows and K points -> K openings (row i at z_i)"""
+        k, _, stride = _rows(coeffs, "coeffs", self.n)
+        zs = _scalars(z, k, "points")
+        quot, values = poly_open(_as2d(coeffs), k, self.n, stride, zs)
+        return self._openings(self.commit(coeffs), zs, quot, self.n, self.bases(), values)
+
+    def open_many_points(self, coeffs, points) -> list:
+        """ONE polynomial opened at K points (poly_stride = 0): K openings with the same C"""
+        k, _, _ = _rows(coeffs, "coeffs", self.n)
+        if k != 1:
+            raise ValueError("open_many_points takes one row")
+        points = [points] if isinstance(points, int) else list(points)
+        zs = _scalars(points, len(points), "points")
+        quot, values = poly_open(_as2d(coeffs), len(zs), self.n, 0, zs)
+        return self._openings(self.commit(coeffs) * len(zs), zs, quot, self.n, self.bases(), values)
+
+    def open_evals(self, evals, z) -> list:
+        """K evaluation rows and K points -> K openings; pi is committed over the Lagrange form"""
+        k, n, stride = _rows(evals, "evals")
+        _eval_size(n, self.m)
+        zs = _scalars(z, k, "points")
+        quot, values = evals_open(_as2d(evals), k, n, stride, zs)
+        return self._openings(self.commit_evals(evals), zs, quot, n, self.lagrange(n), values)
+
+    def open_combined(self, coeffs, z):
+        """K polynomials at ONE point with one proof: (the K commitments, the K values, pi).  The rows are combined
+        with the weights gamma^i (combine_challenge) by ozk_fr_rows_combine_dev and the combination is opened at z."""
+        from .bace import fr_poly_eval
+        k, _, stride = _rows(coeffs, "coeffs", self.n)
+        z = _ceremony._scalar(z, "the point")
+        rows = _as2d(coeffs)
+        if k > 1 and stride != self.n:
+            rows = rows.contiguous()
+        commitments = self.commit(coeffs)
+        values = _ints(_ceremony._bytes(fr_poly_eval(rows.reshape(-1), z, k)))
+        gamma = combine_challenge(z, commitments, values)
+        combined = rows_combine(rows, k, self.n, self.n, [pow(gamma, i, FR) for i in range(k)])
+        quot, _ = poly_open(combined.unsqueeze(0), 1, self.n, self.n, [z])
+        return commitments, values, self._msms(self.bases(), self.n, quot, 1, self.n)
+
+
+def _as2d(t):
+    return t.unsqueeze(0) if t.dim() == 1 else t
+
+
+# ---------------------------------------------------------------------------- the Fr kernels
+def poly_open(coeffs, k, n, stride, zs):
+    """ozk_fr_poly_open_dev on k rows (stride 0: one row at k points): (quotient rows [k, 32 n], values [32 k]) on the
+    device.  Synchronises (the workspace dies here)."""
+    from .zksnark import _dev_bytes
+    L = _lib.load()
+    quot = torch.empty((k, 32 * n), dtype=torch.uint8, device=coeffs.device)
+    values = torch.empty(32 * k, dtype=torch.uint8, device=coeffs.device)
+    wsb = int(L.ozk_fr_poly_open_workspace_bytes(k, n))
+    ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=coeffs.device)
+    pts = _dev_bytes(_le(zs))
+    _lib.check(L.ozk_fr_poly_open_dev(_ptr(coeffs), k, n, stride, _ptr(pts), _ptr(quot), n, _ptr(values), _ptr(ws),
+                                      ws.numel(), _stream()))
+    torch.cuda.current_stream().synchronize()
+    return quot, values
+
+
+def evals_open(evals, k, n, stride, zs):
+    """ozk_fr_evals_open_dev on k evaluation rows over the domain of omega_n: (quotient rows, values) on the device"""
+    from .zksnark import _dev_bytes
+    L = _lib.load()
+    quot = torch.empty((k, 32 * n), dtype=torch.uint8, device=evals.device)
+    values = torch.empty(32 * k, dtype=torch.uint8, device=evals.device)
+    wsb = int(L.ozk_fr_evals_open_workspace_bytes(k, n))
+    ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=evals.device)
+    pts = _dev_bytes(_le(zs))
+    _lib.check(L.ozk_fr_evals_open_dev(_ptr(evals), k, n, stride, _vp(_le([root_of_unity(n)])), _ptr(pts), _ptr(quot), n,
+                                       _ptr(values), _ptr(ws), ws.numel(), _stream()))
+    torch.cuda.current_stream().synchronize()
+    return quot, values
+
+
+def rows_combine(rows, k, n, stride, weights):
+    """sum_i w_i rows[i] as a new row of n elements (ozk_fr_rows_combine_dev)"""
+    from .zksnark import _dev_bytes
+    L = _lib.load()
+    out = torch.empty(32 * n, dtype=torch.uint8, device=rows.device)
+    w = _dev_bytes(_le(weights))
+    _lib.check(L.ozk_fr_rows_combine_dev(_ptr(rows), k, n, stride, _ptr(w), _ptr(out), _stream()))
+    torch.cuda.current_stream().synchronize()
+    return out
+
+
+# ---------------------------------------------------------------------------- verification
+def combine_challenge(z, commitments, values) -> int:
+    """gamma: the first 16 bytes, little-endian, of SHA-256("OZK-kzg-gamma" | K as 8 bytes LE | z | the K compressed
+    commitments | the K values); 1 if they are zero"""
+    h = hashlib.sha256(_GAMMA_TAG + len(commitments).to_bytes(8, "little") + _le([z]) + b"".join(commitments)
+                       + _le(values)).digest()
+    return int.from_bytes(h[:16], "little") or 1
+
+
+def _pairing_holds(lhs_out, neg_weight_pi, pi_is_inf, vk) -> bool:
+    """e(lhs, g2) e(-P, tau_g2) = 1 for lhs (wire-out) and P (wire-in, to be negated).  The pairing kernels take O as
+    the affine (0, 1), which is no neutral element, so a pair whose G1 point is O is left out here: its factor is 1."""
+    from .zksnark import wire_out_to_in
+    lhs_inf = _ceremony._is_inf_out(lhs_out)
+    if lhs_inf or pi_is_inf:
+        return lhs_inf and pi_is_inf      # one factor alone is e(X, Q) with X != O: not 1
+    neg = _ceremony.scale_points(neg_weight_pi, FR - 1, G1)
+    return _ceremony._pairs_are_one(torch.cat([wire_out_to_in(lhs_out, G1), neg]), vk.points()[1])
+
+
+def _decoded(encs):
+    """the wire-in points of compressed G1 encodings, or None when one does not decode"""
+    from .zksnark import _dev_bytes
+    pts, codes = _codec.decompress_g1(_dev_bytes(b"".join(encs)))
+    return None if int(codes.any().item()) else pts
+
+
+def verify(vk, opening) -> bool:
+    """e(C - [y] g1 + [z] pi, g2) e(-pi, tau_g2) = 1: one 3-point MSM and one product of two pairings"""
+    o = opening if isinstance(opening, Opening) else Opening.from_bytes(opening)
+    pts = _decoded([o.c, o.pi])
+    if pts is None:
+        return False
+    lhs, ws = _ceremony._msm(torch.cat([pts[:96], vk.points()[0], pts[96:]]), _le([1, (FR - o.y) % FR, o.z]), 3)
+    ok = _pairing_holds(lhs, pts[96:], o.pi == _G1_INF, vk)
+    del ws
+    return ok
+
+
+def verify_all(vk, openings, seed=None) -> bool:
+    """All K openings at once with weights rho_i in [1, 2^128) (the SHA-256 counter stream of ceremony.py under this
+    module's tag; `seed` None draws 32 bytes from the system, a given seed is for tests only):
+        e(sum rho_i (C_i - [y_i] g1 + [z_i] pi_i), g2) e(-sum rho_i pi_i, tau_g2) = 1
+    as one MSM of 2 K + 1 points, one of K points and one pairing product."""
+    os_ = [o if isinstance(o, Opening) else Opening.from_bytes(o) for o in openings]
+    k = len(os_)
+    if k == 0:
+        return True
+    seed = secrets.token_bytes(32) if seed is None else _ceremony._seed_bytes(seed)
+    rho = _ints(_ceremony._weights(seed, k, _RHO_TAG))
+    pts = _decoded([o.c for o in os_] + [o.pi for o in os_])
+    if pts is None:
+        return False
+    sc = rho + [r * o.z % FR for r, o in zip(rho, os_)] + [-sum(r * o.y for r, o in zip(rho, os_)) % FR]
+    lhs, ws1 = _msm(torch.cat([pts, vk.points()[0]]), _le(sc), 2 * k + 1)
+    ps, ws2 = _msm(pts[96 * k:], _le(rho), k)
+    from .zksnark import wire_out_to_in
+    ok = _pairing_holds(lhs, wire_out_to_in(ps, G1), _ceremony._is_inf_out(ps), vk)
+    del ws1, ws2
+    return ok
+
+
+def _msm(bases, scalar_bytes, n):
+    from .zksnark import _dev_bytes
+    ws = VarMsmWorkspace(n, G1)
+    return ws.run(bases.contiguous(), _dev_bytes(scalar_bytes)), ws
+
+
+def verify_each(vk, openings, seed=None) -> list:
+    """One verdict per opening: the batch check first, single checks only when it fails"""
+    openings = list(openings)
+    if verify_all(vk, openings, seed):
+        return [True] * len(openings)
+    return [verify(vk, o) for o in openings]
+
+
+def verify_combined(vk, commitments, z, values, pi) -> bool:
+    """The proof of open_combined: sum gamma^i C_i opens to sum gamma^i y_i at z"""
+    commitments = [_enc_of(c, "commitment") for c in commitments]
+    z = _ceremony._scalar(z, "the point")
+    values = _scalars(values, len(commitments), "values")
+    pi = _enc_of(pi, "pi")
+    if not commitments:
+        raise ValueError("no commitment")
+    gamma = combine_challenge(z, commitments, values)
+    pw = [pow(gamma, i, FR) for i in range(len(commitments))]
+    pts = _decoded(commitments)
+    if pts is None:
+        return False
+    c, ws = _msm(pts, _le(pw), len(commitments))
+    c_enc = _ceremony._bytes(_codec.compress_g1(c, "wire_out"))
+    del ws
+    return verify(vk, Opening(c_enc, z, sum(w * y for w, y in zip(pw, values)) % FR, pi))

@@ -102,6 +102,11 @@ _SIGS = {
     "ozk_bace_result_dev": (ctypes.c_int, [vp, i32, i32, vp, vp, sz, vp]),
     "ozk_fr_poly_eval_workspace_bytes": (sz, [i32]),
     "ozk_fr_poly_eval_dev": (ctypes.c_int, [vp, i32, i32, ctypes.c_int64, vp, vp, vp, sz, vp]),
+    "ozk_fr_poly_open_workspace_bytes": (sz, [i32, i32]),
+    "ozk_fr_poly_open_dev": (ctypes.c_int, [vp, i32, i32, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, vp, sz, vp]),
+    "ozk_fr_evals_open_workspace_bytes": (sz, [i32, i32]),
+    "ozk_fr_evals_open_dev": (ctypes.c_int, [vp, i32, i32, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, vp, vp, sz, vp]),
+    "ozk_fr_rows_combine_dev": (ctypes.c_int, [vp, i32, i32, ctypes.c_int64, vp, vp, vp]),
     "ozk_multi_msm_table_bytes": (sz, [i32, i32]),
     "ozk_multi_msm_prepare_dev": (ctypes.c_int, [vp, i32, i32, vp, sz, vp, sz, vp]),
     "ozk_multi_msm_workspace_bytes": (sz, [i32, i32, i32]),
