@@ -502,6 +502,35 @@ int ozk_fr_evals_open_dev(const void* d_evals, int32_t npolys, int32_t n, int64_
 int ozk_fr_rows_combine_dev(const void* d_rows, int32_t k, int32_t len, int64_t row_stride, const void* d_weights,
                             void* d_out, void* stream);
 
+/* KZG set openings over Fr (csrc/kzg_set.cuh): for every row the quotient (p - I) / Z_S by the
+ * vanishing polynomial Z_S = prod (X - z_i) of t pairwise distinct points, I the interpolant of p on them, and the t
+ * values p(z_i).  Elements, reduction on load, canonical outputs, strides and the row layout are those of the block
+ * above.  The points are npolys x t elements in HOST memory (32-byte LE, row y uses its own t), read before the call
+ * returns; points of a row that are not pairwise distinct mod r are rejected on the host.
+ *   ozk_fr_poly_open_set_dev   coefficient form, 1 <= t <= 32.  d_values[y t + i] = p(z_i); the row at
+ *                              d_quot + 32 y quot_stride holds q_0 .. q_{len-t-1}, then zeros up to element len - 1 (all
+ *                              zeros when len <= t): an MSM scalar vector over the same bases.  Dividing by the linear
+ *                              factors in turn, every stage on the lane's registers: a row is read twice and written
+ *                              once whatever t.  With t = 1 the bytes are those of ozk_fr_poly_open_dev.  npolys len and
+ *                              npolys t <= 2^28; d_quot must not overlap d_coeffs (rejected).
+ *                              Workspace: ozk_fr_poly_open_set_workspace_bytes(npolys, len, t).
+ *   ozk_fr_evals_open_set_dev  evaluation form, 1 <= t <= 8, n and omega as ozk_fr_evals_open_dev.  q_i = (f_i -
+ *                              I(omega^i)) / Z_S(omega^i), one inversion of Z_S(omega^i) per element.  EVERY point must lie
+ *                              outside the domain: z^n = 1 is tested on the host and rejected (open such a set in
+ *                              coefficient form).  With t = 1 the bytes are those of ozk_fr_evals_open_dev.
+ *                              Workspace: ozk_fr_evals_open_set_workspace_bytes(npolys, n, t).
+ * Size functions and rejections as above: 0 and OZK_E_INVALID before any launch, the shape (t included) before the
+ * pointers.  Asynchronous on `stream`; nothing is allocated or synchronised. */
+size_t ozk_fr_poly_open_set_workspace_bytes(int32_t npolys, int32_t len, int32_t t);
+int ozk_fr_poly_open_set_dev(const void* d_coeffs, int32_t npolys, int32_t len, int64_t poly_stride, int32_t t,
+                             const uint8_t* points_host, void* d_quot, int64_t quot_stride, void* d_values,
+                             void* d_workspace, size_t workspace_bytes, void* stream);
+size_t ozk_fr_evals_open_set_workspace_bytes(int32_t npolys, int32_t n, int32_t t);
+int ozk_fr_evals_open_set_dev(const void* d_evals, int32_t npolys, int32_t n, int64_t evals_stride,
+                              const uint8_t* omega_host32, int32_t t, const uint8_t* points_host, void* d_quot,
+                              int64_t quot_stride, void* d_values, void* d_workspace, size_t workspace_bytes,
+                              void* stream);
+
 /* ---- batched MSM over shared bases (msm_multi.hip; no counterpart in the reference, whose verifier runs one
  * variable-base MSM per proof): out_i = sum_{j < n} s_ij P_j for k scalar rows over the SAME n bases, G1 only.
  * A window table of every base is built once (ozk_multi_msm_prepare_dev); a run is table gathers and mixed

@@ -16,8 +16,16 @@ e(C - [y] g1 + [z] pi, g2) e(-pi, [tau] g2) = 1.  The quotient comes from ozk_fr
 (csrc/kzg.cuh); every group operation is an existing entry point: the variable-base MSM over prepared bases, the group
 FFT, the pairing product and the point codec.
 
-Out of scope: hiding commitments, one proof for several points of one polynomial, degree-bound proofs, G2
-commitments, interoperability with other tools' byte formats.  There is no CPU path.
+Several points of one polynomial under ONE proof: for S = (z_1 .. z_t), I the interpolant of
+p on S and Z_S = prod (X - z_i), the proof is pi = [q(tau)] g1 for q = (p - I) / Z_S (ozk_fr_poly_open_set_dev /
+ozk_fr_evals_open_set_dev, csrc/kzg_set.cuh), accepted when e(C - [I(tau)] g1, g2) e(-pi, [Z_S(tau)] g2) = 1.
+
+    svk = SetVerifyKey.from_srs(srs, t_max)          # tau_g1[:t_max], tau_g2[:t_max + 1]
+    ops = ck.open_set(coeffs, [z_1, ..., z_t])       # SetOpening: C | t | z | y | pi, 68 + 64 t bytes; one per row
+    assert verify_set(svk, ops[0]) and verify_set_all(svk, ops)
+
+Out of scope: hiding commitments, different point sets per polynomial under one proof, whole-coset openings,
+degree-bound proofs, G2 commitments, interoperability with other tools' byte formats.  There is no CPU path.
 """
 import ctypes
 import hashlib
@@ -36,6 +44,9 @@ OPENING_BYTES, VK_BYTES = 128, 160
 _RHO_TAG = b"OZK-kzg-rho"
 _GAMMA_TAG = b"OZK-kzg-gamma"
 _G1_INF = bytes(31) + b"\x40"
+SET_T_MAX, SET_EVALS_T_MAX = 32, 8        # KZG_SET_T, KZG_SET_EV_T of csrc/kzg_set.cuh
+_SET_RHO_TAG = b"OZK-kzg-set-rho"
+_SET_GAMMA_TAG = b"OZK-kzg-set-gamma"
 
 
 # ---------------------------------------------------------------------------- argument checks (no library call)
@@ -289,6 +300,52 @@ class CommitKey:
         quot, _ = poly_open(combined.unsqueeze(0), 1, self.n, self.n, [z])
         return commitments, values, self._msms(self.bases(), self.n, quot, 1, self.n)
 
+    # ---- open at a set of points with one proof
+    def _set_openings(self, commitments, sets, quot, n, bases, values):
+        k, t = len(sets), len(sets[0])
+        pis = self._msms(bases, n, quot, k, n)
+        ys = _ints(_ceremony._bytes(values))
+        return [SetOpening(commitments[i], sets[i], ys[t * i:t * (i + 1)], pis[32 * i:32 * i + 32]) for i in range(k)]
+
+    def open_set(self, coeffs, points) -> list:
+        """K rows, and one list of t points shared by all rows or K lists of t -> K SetOpenings: one kernel call for all
+        rows, one MSM per quotient row"""
+        k, _, stride = _rows(coeffs, "coeffs", self.n)
+        sets = _point_sets(points, k, min(SET_T_MAX, self.m - 1), "the string has m = %d" % self.m)
+        quot, values = poly_open_set(_as2d(coeffs), k, self.n, stride, sets)
+        return self._set_openings(self.commit(coeffs), sets, quot, self.n, self.bases(), values)
+
+    def open_set_evals(self, evals, points) -> list:
+        """The same over K evaluation rows; every point must lie outside the domain (open an in-domain set in
+        coefficient form); pi is committed over the Lagrange form"""
+        k, n, stride = _rows(evals, "evals")
+        _eval_size(n, self.m)
+        sets = _point_sets(points, k, min(SET_EVALS_T_MAX, self.m - 1), "the string has m = %d" % self.m)
+        for row in sets:
+            for z in row:
+                if pow(z, n, FR) == 1:
+                    raise ValueError("the point %d lies in the domain of %d elements: open such a set in coefficient form"
+                                     % (z, n))
+        quot, values = evals_open_set(_as2d(evals), k, n, stride, sets)
+        return self._set_openings(self.commit_evals(evals), sets, quot, n, self.lagrange(n), values)
+
+    def open_set_combined(self, coeffs, points):
+        """K polynomials at ONE shared set with one proof: (the K commitments, the K rows of t values, pi).  The rows
+        are combined with the weights gamma^i (set_combine_challenge) and the combination is opened at the set."""
+        from .bace import fr_poly_eval
+        k, _, stride = _rows(coeffs, "coeffs", self.n)
+        points = _point_sets(points, 1, min(SET_T_MAX, self.m - 1), "the string has m = %d" % self.m, shared=True)[0]
+        rows = _as2d(coeffs)
+        if k > 1 and stride != self.n:
+            rows = rows.contiguous()
+        commitments = self.commit(coeffs)
+        at = [_ints(_ceremony._bytes(fr_poly_eval(rows.reshape(-1), z, k))) for z in points]
+        values = [[col[i] for col in at] for i in range(k)]
+        gamma = set_combine_challenge(points, commitments, values)
+        combined = rows_combine(rows, k, self.n, self.n, [pow(gamma, i, FR) for i in range(k)])
+        quot, _ = poly_open_set(combined.unsqueeze(0), 1, self.n, self.n, [points])
+        return commitments, values, self._msms(self.bases(), self.n, quot, 1, self.n)
+
 
 def _as2d(t):
     return t.unsqueeze(0) if t.dim() == 1 else t
@@ -430,3 +487,321 @@ def verify_combined(vk, commitments, z, values, pi) -> bool:
     c_enc = _ceremony._bytes(_codec.compress_g1(c, "wire_out"))
     del ws
     return verify(vk, Opening(c_enc, z, sum(w * y for w, y in zip(pw, values)) % FR, pi))
+
+
+# ============================================================================ several points under one proof (section 23)
+def _point_sets(points, k, t_max, why, shared=False):
+    """k tuples of t pairwise distinct ints in [0, r), 1 <= t <= t_max, from one list of t points (shared by the k
+    rows) or, unless `shared`, k lists of t"""
+    if isinstance(points, (int, str, bytes)) or not hasattr(points, "__iter__"):
+        raise TypeError("points must be a list of points, or one list per row")
+    points = list(points)
+    if not points:
+        raise ValueError("an empty set of points (1 <= t)")
+    nested = [hasattr(p, "__iter__") and not isinstance(p, (str, bytes)) for p in points]
+    if any(nested) and (shared or not all(nested)):
+        raise ValueError("points: one list of points%s" % ("" if shared else ", or one list per row, not a mix"))
+    sets = [list(p) for p in points] if nested[0] else [points] * k
+    if len(sets) != k:
+        raise ValueError("%d lists of points for %d rows" % (len(sets), k))
+    t = len(sets[0])
+    if any(len(row) != t for row in sets):
+        raise ValueError("ragged lists of points: every row takes the same number t")
+    if not 1 <= t <= t_max:
+        raise ValueError("t = %d points: 1 <= t <= %d here (%s)" % (t, t_max, why))
+    sets = [tuple(_ceremony._scalar(z, "a point") for z in row) for row in sets]
+    for row in sets:
+        if len(set(row)) != t:
+            raise ValueError("repeated points in a set: %s" % (row,))
+    return sets
+
+
+def _vanishing(points):
+    """the t + 1 coefficients of Z_S = prod (X - z_i), lowest first"""
+    z = [1]
+    for p in points:
+        z = [((z[j - 1] if j else 0) - p * (z[j] if j < len(z) else 0)) % FR for j in range(len(z) + 1)]
+    return z
+
+
+def _interpolant(points, values):
+    """the t coefficients of the polynomial of degree < t through (z_i, y_i), in host integers (t is small): the
+    Lagrange numerators are Z_S / (X - z_i) by synthetic division, their denominators the numerators at z_i"""
+    t = len(points)
+    zs = _vanishing(points)
+    out = [0] * t
+    for zi, yi in zip(points, values):
+        num, acc = [0] * t, 0
+        for j in range(t, 0, -1):
+            acc = (zs[j] + zi * acc) % FR
+            num[j - 1] = acc
+        den = 0
+        for c in reversed(num):
+            den = (den * zi + c) % FR
+        s = yi * pow(den, -1, FR) % FR
+        for j in range(t):
+            out[j] = (out[j] + s * num[j]) % FR
+    return out
+
+
+class SetOpening:
+    """C 32 | t uint32 LE | z 32 t | y 32 t | pi 32 (68 + 64 t bytes): the compressed commitment, the points, the
+    values at them, the compressed proof"""
+
+    def __init__(self, c, points, values, pi):
+        self.c, self.pi = _enc_of(c, "set opening: C"), _enc_of(pi, "set opening: pi")
+        self.points = tuple(_ceremony._scalar(z, "set opening: z") for z in points)
+        self.values = tuple(_ceremony._scalar(y, "set opening: y") for y in values)
+        if not 1 <= len(self.points) <= SET_T_MAX:
+            raise ValueError("set opening: t = %d, not in [1, %d]" % (len(self.points), SET_T_MAX))
+        if len(self.values) != len(self.points):
+            raise ValueError("set opening: %d values for %d points" % (len(self.values), len(self.points)))
+        if len(set(self.points)) != len(self.points):
+            raise ValueError("set opening: z has repeated points")
+
+    @property
+    def t(self):
+        return len(self.points)
+
+    def to_bytes(self) -> bytes:
+        return self.c + self.t.to_bytes(4, "little") + _le(self.points) + _le(self.values) + self.pi
+
+    @staticmethod
+    def from_bytes(b) -> "SetOpening":
+        """Strict and host-only: ValueError naming the field for a wrong length, t outside [1, 32], z or y >= r,
+        repeated points, a point that does not decode."""
+        b = bytes(b)
+        if len(b) < 36:
+            raise ValueError("set opening: length %d, too short for C and t" % len(b))
+        t = int.from_bytes(b[32:36], "little")
+        if not 1 <= t <= SET_T_MAX:
+            raise ValueError("set opening: t = %d, not in [1, %d]" % (t, SET_T_MAX))
+        if len(b) != 68 + 64 * t:
+            raise ValueError("set opening: length %d, not %d for t = %d" % (len(b), 68 + 64 * t, t))
+        zs, ys = _ints(b[36:36 + 32 * t]), _ints(b[36 + 32 * t:36 + 64 * t])
+        for name, vs in (("z", zs), ("y", ys)):
+            if any(v >= FR for v in vs):
+                raise ValueError("set opening: %s is not below r" % name)
+        if len(set(zs)) != t:
+            raise ValueError("set opening: z has repeated points")
+        _require_points((("C", b[:32], G1), ("pi", b[-32:], G1)), "set opening")
+        return SetOpening(b[:32], zs, ys, b[-32:])
+
+
+class SetVerifyKey:
+    """tau_g1[:t_max] and tau_g2[:t_max + 1]: what the verifier of openings at up to t_max points commits I and Z_S
+    with.  Bytes: t_max uint32 LE | 32 t_max | 64 (t_max + 1), compressed as DESIGN.md section 13."""
+
+    def __init__(self, t_max, g1s, g2s):
+        self.t_max = int(t_max)
+        if not 1 <= self.t_max <= SET_T_MAX:
+            raise ValueError("set verification key: t_max = %d, not in [1, %d]" % (self.t_max, SET_T_MAX))
+        self.g1s = _enc_of(g1s, "set verification key: tau_g1", 32 * self.t_max)
+        self.g2s = _enc_of(g2s, "set verification key: tau_g2", 64 * (self.t_max + 1))
+        self._points = None
+
+    @staticmethod
+    def from_srs(srs, t_max) -> "SetVerifyKey":
+        t_max = int(t_max)
+        if not 1 <= t_max <= min(SET_T_MAX, int(srs.m) - 1):
+            raise ValueError("t_max = %d: a string of m = %d carries m powers in G2, so 1 <= t_max <= %d"
+                             % (t_max, srs.m, min(SET_T_MAX, int(srs.m) - 1)))
+        e1 = _ceremony._enc(srs.tau_g1.reshape(-1)[:96 * t_max].contiguous(), G1)
+        e2 = _ceremony._enc(srs.tau_g2.reshape(-1)[:192 * (t_max + 1)].contiguous(), G2)
+        return SetVerifyKey(t_max, e1, e2)
+
+    def to_bytes(self) -> bytes:
+        return self.t_max.to_bytes(4, "little") + self.g1s + self.g2s
+
+    @staticmethod
+    def from_bytes(b) -> "SetVerifyKey":
+        """Strict, as VerifyKey.from_bytes: ValueError naming the field for a wrong length, t_max outside [1, 32], a
+        point that does not decode or is infinity (host checks), then for a G2 point outside the order-r subgroup (on
+        the device)."""
+        b = bytes(b)
+        if len(b) < 4:
+            raise ValueError("set verification key: length %d, too short for t_max" % len(b))
+        t_max = int.from_bytes(b[:4], "little")
+        if not 1 <= t_max <= SET_T_MAX:
+            raise ValueError("set verification key: t_max = %d, not in [1, %d]" % (t_max, SET_T_MAX))
+        if len(b) != 4 + 32 * t_max + 64 * (t_max + 1):
+            raise ValueError("set verification key: length %d, not %d for t_max = %d"
+                             % (len(b), 4 + 32 * t_max + 64 * (t_max + 1), t_max))
+        g1s, g2s = b[4:4 + 32 * t_max], b[4 + 32 * t_max:]
+        fields = [("tau_g1[%d]" % i, g1s[32 * i:32 * i + 32], G1) for i in range(t_max)]
+        fields += [("tau_g2[%d]" % i, g2s[64 * i:64 * i + 64], G2) for i in range(t_max + 1)]
+        _require_points(fields, "set verification key")
+        for name, enc, _ in fields:
+            if enc[-1] & 0x40:
+                raise ValueError("set verification key: %s is the point at infinity" % name)
+        vk = SetVerifyKey(t_max, g1s, g2s)
+        for i in range(t_max + 1):
+            if not _g2_in_subgroup(vk.points()[1][192 * i:192 * (i + 1)], g2s[64 * i:64 * i + 64]):
+                raise ValueError("set verification key: tau_g2[%d] is not in the order-r subgroup" % i)
+        return vk
+
+    def points(self):
+        """(tau_g1[:t_max], tau_g2[:t_max + 1]) as wire-in points on the device, decoded once"""
+        if self._points is None:
+            from .zksnark import _dev_bytes
+            p1, c1 = _codec.decompress_g1(_dev_bytes(self.g1s))
+            p2, c2 = _codec.decompress_g2(_dev_bytes(self.g2s))
+            if int(c1.any().item()) or int(c2.any().item()):
+                raise ValueError("set verification key: a point does not decode")
+            self._points = (p1, p2)
+        return self._points
+
+
+def poly_open_set(coeffs, k, n, stride, sets):
+    """ozk_fr_poly_open_set_dev on k rows, row y at the t points sets[y]: (quotient rows [k, 32 n], values [32 k t]) on
+    the device.  Synchronises (the workspace dies here)."""
+    L = _lib.load()
+    t = len(sets[0])
+    quot = torch.empty((k, 32 * n), dtype=torch.uint8, device=coeffs.device)
+    values = torch.empty(32 * k * t, dtype=torch.uint8, device=coeffs.device)
+    wsb = int(L.ozk_fr_poly_open_set_workspace_bytes(k, n, t))
+    ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=coeffs.device)
+    pts = _le([z for row in sets for z in row])
+    _lib.check(L.ozk_fr_poly_open_set_dev(_ptr(coeffs), k, n, stride, t, _vp(pts), _ptr(quot), n, _ptr(values), _ptr(ws),
+                                          ws.numel(), _stream()))
+    torch.cuda.current_stream().synchronize()
+    return quot, values
+
+
+def evals_open_set(evals, k, n, stride, sets):
+    """ozk_fr_evals_open_set_dev on k evaluation rows over the domain of omega_n: (quotient rows, values)"""
+    L = _lib.load()
+    t = len(sets[0])
+    quot = torch.empty((k, 32 * n), dtype=torch.uint8, device=evals.device)
+    values = torch.empty(32 * k * t, dtype=torch.uint8, device=evals.device)
+    wsb = int(L.ozk_fr_evals_open_set_workspace_bytes(k, n, t))
+    ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=evals.device)
+    pts = _le([z for row in sets for z in row])
+    _lib.check(L.ozk_fr_evals_open_set_dev(_ptr(evals), k, n, stride, _vp(_le([root_of_unity(n)])), t, _vp(pts),
+                                           _ptr(quot), n, _ptr(values), _ptr(ws), ws.numel(), _stream()))
+    torch.cuda.current_stream().synchronize()
+    return quot, values
+
+
+def set_combine_challenge(points, commitments, values) -> int:
+    """gamma: the first 16 bytes, little-endian, of SHA-256("OZK-kzg-set-gamma" | K as 8 bytes LE | t as 8 bytes LE | the
+    t points | the K compressed commitments | the K rows of t values); 1 if they are zero"""
+    h = hashlib.sha256(_SET_GAMMA_TAG + len(commitments).to_bytes(8, "little") + len(points).to_bytes(8, "little")
+                       + _le(points) + b"".join(commitments) + _le([v for row in values for v in row])).digest()
+    return int.from_bytes(h[:16], "little") or 1
+
+
+def _set_opening(vk, o):
+    o = o if isinstance(o, SetOpening) else SetOpening.from_bytes(o)
+    if o.t > vk.t_max:
+        raise ValueError("an opening at t = %d points: the key covers t_max = %d" % (o.t, vk.t_max))
+    return o
+
+
+def _g2_msm(bases, scalars, n):
+    """(sum s_i Q_i as a wire-in G2 point, whether it is O, the workspace)"""
+    from .srs import _msm as _msm_typed
+    from .zksnark import _dev_bytes, wire_out_to_in
+    out, ws = _msm_typed(bases, _dev_bytes(_le(scalars)), n, G2)
+    return wire_out_to_in(out, G2), not bool(out.view(6, 64)[4:].any().item()), ws
+
+
+def _pairs_hold(pairs) -> bool:
+    """prod e(P_i, Q_i) = 1 over (P wire-in G1, whether P is O, Q wire-in G2); a pair whose G1 point is O is left out
+    (_pairing_holds: the kernels take O as an affine point, which is no neutral element), and one pair alone is
+    e(P, Q) with P != O and Q != O of order r: not 1"""
+    live = [(p, q) for p, inf, q in pairs if not inf]
+    if len(live) < 2:
+        return not live
+    return _ceremony._pairs_are_one(torch.cat([p for p, _ in live]), torch.cat([q for _, q in live]))
+
+
+def verify_set(vk, opening) -> bool:
+    """e(C - [I(tau)] g1, g2) e(-pi, [Z_S(tau)] g2) = 1: one G1 MSM of t + 1 points (C with scalar 1, tau_g1[:t] with the
+    coefficients of -I), one G2 MSM of t + 1 points and one product of two pairings.  I and Z_S come from (z_i, y_i) in
+    host integers.  lhs = pi = O is accepted (a polynomial of degree < t), one of them O alone is not, and neither is
+    [Z_S(tau)] g2 = O."""
+    return _verify_sets(vk, [_set_opening(vk, opening)], [1])
+
+
+def verify_set_all(vk, openings, seed=None) -> bool:
+    """All K openings at once with weights rho_i in [1, 2^128) (the stream of ceremony.py under this module's set tag;
+    `seed` as verify_all).  Openings are grouped by identical point tuple D:
+        e(sum rho_i (C_i - [I_i(tau)] g1), g2) prod_D e(-sum_{i in D} rho_i pi_i, [Z_D(tau)] g2) = 1
+    as one G1 MSM of K + t points, one of |D| points and one G2 MSM of t + 1 points per distinct set, and one pairing
+    product."""
+    os_ = [_set_opening(vk, o) for o in openings]
+    if not os_:
+        return True
+    seed = secrets.token_bytes(32) if seed is None else _ceremony._seed_bytes(seed)
+    return _verify_sets(vk, os_, _ints(_ceremony._weights(seed, len(os_), _SET_RHO_TAG)))
+
+
+def _verify_sets(vk, os_, rho) -> bool:
+    """the equation of verify_set_all over parsed openings with the weights rho"""
+    from .zksnark import wire_out_to_in
+    k = len(os_)
+    pts = _decoded([o.c for o in os_] + [o.pi for o in os_])
+    if pts is None:
+        return False
+    g1s, g2s = vk.points()
+    t_top = max(o.t for o in os_)
+    minus_i = [0] * t_top
+    groups = {}
+    for i, o in enumerate(os_):
+        groups.setdefault(o.points, []).append(i)
+    for points, members in groups.items():
+        # interpolation is linear in the values: one interpolant per distinct set, of the weighted sums
+        ys = [sum(rho[i] * os_[i].values[j] for i in members) % FR for j in range(len(points))]
+        for j, c in enumerate(_interpolant(points, ys)):
+            minus_i[j] = (minus_i[j] - c) % FR
+    keep = []
+    lhs, ws = _msm(torch.cat([pts[:96 * k], g1s[:96 * t_top]]), _le(rho + minus_i), k + t_top)
+    keep.append(ws)
+    pairs = [(wire_out_to_in(lhs, G1), _ceremony._is_inf_out(lhs), g2s[:192])]
+    for points, members in groups.items():
+        zq, zq_inf, ws = _g2_msm(g2s[:192 * (len(points) + 1)], _vanishing(points), len(points) + 1)
+        keep.append(ws)
+        if zq_inf:
+            return False
+        ps, ws = _msm(torch.cat([pts[96 * (k + i):96 * (k + i + 1)] for i in members]), _le([rho[i] for i in members]),
+                      len(members))
+        keep.append(ws)
+        inf = _ceremony._is_inf_out(ps)
+        neg = None if inf else _ceremony.scale_points(wire_out_to_in(ps, G1), FR - 1, G1)
+        pairs.append((neg, inf, zq))
+    ok = _pairs_hold(pairs)
+    torch.cuda.current_stream().synchronize()
+    del keep
+    return ok
+
+
+def verify_set_each(vk, openings, seed=None) -> list:
+    """One verdict per opening: the batch check first, single checks only when it fails"""
+    openings = list(openings)
+    if verify_set_all(vk, openings, seed):
+        return [True] * len(openings)
+    return [verify_set(vk, o) for o in openings]
+
+
+def verify_set_combined(vk, commitments, points, values, pi) -> bool:
+    """The proof of open_set_combined: sum gamma^i C_i opens to (sum gamma^i y_ij)_j at the set"""
+    commitments = [_enc_of(c, "commitment") for c in commitments]
+    if not commitments:
+        raise ValueError("no commitment")
+    points = _point_sets(points, 1, vk.t_max, "the key covers t_max = %d" % vk.t_max, shared=True)[0]
+    values = [list(row) for row in values]
+    if len(values) != len(commitments) or any(len(row) != len(points) for row in values):
+        raise ValueError("values: %d rows of %d for %d commitments" % (len(values), len(points), len(commitments)))
+    values = [_scalars(row, len(points), "values") for row in values]
+    pi = _enc_of(pi, "pi")
+    gamma = set_combine_challenge(points, commitments, values)
+    pw = [pow(gamma, i, FR) for i in range(len(commitments))]
+    pts = _decoded(commitments)
+    if pts is None:
+        return False
+    c, ws = _msm(pts, _le(pw), len(commitments))
+    c_enc = _ceremony._bytes(_codec.compress_g1(c, "wire_out"))
+    del ws
+    ys = [sum(w * row[j] for w, row in zip(pw, values)) % FR for j in range(len(points))]
+    return verify_set(vk, SetOpening(c_enc, points, ys, pi))
