@@ -246,6 +246,9 @@ int ozk_var_msm_glv(int32_t n);
  * the MSM down the chunked path): the call waits for the device and reads the flag from the MSM's sorted set, so ask
  * before the next MSM sorts into the same buffers. */
 int ozk_var_msm_last_l1_path(void);
+/* Which form of the window sums the calling thread's last variable-base tail launched: 1 = by bucket rows and columns
+ * (G1, throughput shape, OZK_MSM_TAIL_RC), 0 = the fused / serial levels, -1 = no call yet.  For tests and profiles. */
+int ozk_var_msm_last_tail_form(void);
 
 /* Synthetic inputs for benchmarks / full-size tests (BASELINE.md config 2 generator):
  * writes n G1 bases P_i = k_i * G, k_i = splitmix64(seed + i) (k_i = 1 if that is 0), in the

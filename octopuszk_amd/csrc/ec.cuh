@@ -274,6 +274,58 @@ OZK_HD Xyzz<CV> xyzz_madd_lazy(const Xyzz<CV>& p, const Aff<typename CV::EA>& q,
   return out;
 }
 
+// +-q as an XYZZ point (ZZ = ZZZ = 1, or 0 for the infinity marker): the first entry of a run
+template <class CV>
+OZK_HD Xyzz<CV> xyzz_from_affine_signed(const Aff<typename CV::EA>& q, bool negate) {
+  if (is_inf(q)) return xyzz_from_affine<CV>(q);
+  Aff<typename CV::EA> qs = q;
+  qs.y = typename CV::EA(reduce_to<17>(normalise(select_el(negate, neg_nc(q.y), q.y))));
+  return xyzz_from_affine<CV>(qs);
+}
+
+// mmadd-2008-s: affine + affine into XYZZ, the second entry of a run.  `p` is what xyzz_from_affine_signed returned:
+// ZZ = ZZZ = 1 and X, Y within the affine bound EA, or infinity.  With Z1 = 1 the U2 = x2 ZZ1 and S2 = y2 ZZZ1 of
+// xyzz_madd_lazy are x2 and y2, and ZZ3 = PP, ZZZ3 = PPP: 4M + 2S against 8M + 2S.  Lazy carries as there (P, R and X3
+// are carried: they are squared or stored); base field only.  Bounds from X1, Y1, x2 < 17/16 p and +-y2 < 33/16 p:
+// P < 49/16 p, R < 65/16 p, PP, PPP, Q < 17/16 p, X3 < 18/16 + 2 + 4 p = 114/16 p, Y3 < 20/16 p: loop values of CV.
+template <class CV>
+OZK_HD Xyzz<CV> xyzz_add_affine2_lazy(const Xyzz<CV>& p, const Aff<typename CV::EA>& q, bool negate) {
+  if (is_inf(q)) return p;
+  if (is_inf(p)) return xyzz_from_affine_signed<CV>(q, negate);
+  using EA = typename CV::EA;
+  EA X1, Y1;   // the affine coordinates p was made from (narrower than the accumulator's types)
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    X1.l[i] = p.X.l[i];
+    Y1.l[i] = p.Y.l[i];
+  }
+  const auto yq = select_el(negate, neg_nc(q.y), q.y);  // +-y, loose
+  const auto P = sub(q.x, X1);
+  const auto R = sub(yq, Y1);
+  const auto PP = sqr(P);
+  if (is_zero(PP)) {
+    if (is_zero(R)) {  // P == +-Q
+      Aff<EA> qs = q;
+      qs.y = EA(reduce_to<17>(normalise(yq)));
+      return xyzz_dbl_affine<CV>(qs);
+    }
+    Xyzz<CV> z = p;  // P == -(+-Q): infinity
+    z.ZZ = typename CV::XZZ(el_zero(q.x));
+    z.ZZZ = typename CV::XZZZ(el_zero(q.x));
+    return z;
+  }
+  const auto PPP = mul(P, PP);
+  const auto Q = mul(X1, PP);
+  const auto X3 = sub_sub2(sqr(R), PPP, Q);
+  const auto Y3 = mul2(sub_nc(Q, X3), R, neg_nc(Y1), PPP);
+  Xyzz<CV> out;
+  out.X = typename CV::XX(X3);
+  out.Y = typename CV::XY(Y3);
+  out.ZZ = typename CV::XZZ(PP);
+  out.ZZZ = typename CV::XZZZ(PPP);
+  return out;
+}
+
 // dbl-2008-s-1: XYZZ doubling (a = 0).  6M + 4S... used only when a general addition meets P == Q.
 template <class CV>
 OZK_HD Xyzz<CV> xyzz_dbl(const Xyzz<CV>& p) {
@@ -333,6 +385,20 @@ OZK_HD Jac<CV> xyzz_to_jac(const Xyzz<CV>& p) {
   r.X = typename CV::EX(mul(p.X, p.ZZ));
   r.Y = typename CV::EY(mul(p.Y, p.ZZZ));
   r.Z = typename CV::EZ(p.ZZ);
+  return r;
+}
+
+// Jacobian -> XYZZ within the accumulator's bounds: (X, Y, Z^2, Z^3).  1M + 1S and three reductions (base field; the
+// targets are the bounds of CV::XY / XZZ / XZZZ, which the conversions below check).  Only the bucket records that a
+// Jacobian kernel wrote (curve.cuh TAG_JAC) take it.
+template <class CV>
+OZK_HD Xyzz<CV> jac_to_xyzz(const Jac<CV>& p) {
+  const auto zz = sqr(p.Z);
+  Xyzz<CV> r;
+  r.X = typename CV::XX(p.X);
+  r.Y = typename CV::XY(reduce_to<52>(p.Y));
+  r.ZZ = typename CV::XZZ(reduce_to<17>(zz));
+  r.ZZZ = typename CV::XZZZ(reduce_to<17>(mul(zz, p.Z)));
   return r;
 }
 

@@ -487,6 +487,18 @@ OZK_HD auto sub_nc(const Fe<P, B1>& a, const Fe<P, B2>& b) {
   for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + (P::BIAS[K][i] - b.l[i]);
   return r;
 }
+// a - b + K p carried, a loose: limbs stay below LU 2^28 + 2^30 < 2^32 on the way
+template <class P, int B1, int LU, int B2>
+OZK_HD auto sub(const FeL<P, B1, LU>& a, const Fe<P, B2>& b) {
+  constexpr int K = B2 / 16 + 1;
+  static_assert(K <= FE_MAXK, "sub bias table too small");
+  static_assert(LU <= 11, "loose minuend too wide for a 32-bit limb");
+  Fe<P, B1 + 16 * K> r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + (P::BIAS[K][i] - b.l[i]);
+  fe_carry(r);
+  return r;
+}
 // a - b - 2 c with ONE carry pass at the end (the X3 = R^2 - PPP - 2 Q of the addition formulas): limbs stay below
 // 2^29 + 2^30 + 2 2^30 < 2^32 on the way
 template <class P, int B1, int B2, int B3>

@@ -30,6 +30,7 @@ constexpr int KNOB_STRING = KNOB_COMPUTED + 1;  // a string, read with knob_str(
   X(MSM_L1_WHOLE, "OZK_MSM_L1_WHOLE", 1, "G1 level 1 by whole buckets on lane groups: 0 never, 1 on every plan that can take it (unset: where it pays)") \
   X(MSM_L1_ROUNDS, "OZK_MSM_L1_ROUNDS", 2, "most rounds of resident workgroups level 1 is rounded up to; 0: no rounding") \
   X(MSM_TAIL_MODE, "OZK_MSM_TAIL_MODE", -1, "0 / 1: force the latency / throughput shape of the window sums")            \
+  X(MSM_TAIL_RC, "OZK_MSM_TAIL_RC", -1, "1: G1 throughput window sums by bucket rows and columns wherever the buffers take them (0 / unset: the serial levels)") \
   X(MSM_SMALL_SORT, "OZK_MSM_SMALL_SORT", 1, "0: small MSMs take the two-level sort too")                                \
   X(MSM_S_LAT, "OZK_MSM_S_LAT", KNOB_COMPUTED, "buckets per lane in a latency tail's fused first level (default: 8 G1, 4 G2)") \
   X(MSM_FIN_MAX, "OZK_MSM_FIN_MAX", 4, "elements per window left to the final one-wave kernel, 1..16")                   \

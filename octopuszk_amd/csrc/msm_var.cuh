@@ -34,6 +34,7 @@
 #include "curve.cuh"
 #include "glv.cuh"
 #include "l1_whole.h"
+#include "wsum_rc.h"
 
 namespace ozk {
 
@@ -56,6 +57,7 @@ struct MsmPlan {
   int S_lat;       // buckets per lane in the fused first window-sum level of a latency-mode tail
   int fin_max;     // window-sum elements per window left to k_finalize
   int tail_mode;   // -1: as the caller asks; 0 / 1: latency / throughput shape forced
+  int tail_rc;     // 1: G1 throughput window sums by bucket rows and columns wherever they fit the tail buffers (wsum_rc.h)
   int l1_whole;    // 1: level 1 by whole buckets on lane groups where the data allow it (G1; k_bucket_items, k_l1_whole)
   int l1_gtop;     // lanes per bucket of the top window on that path (l1_whole.h WholeGeom::g_top)
 };
@@ -1409,8 +1411,8 @@ __device__ __forceinline__ Xyzz<CV> xyzz_quad_swap(const Xyzz<CV>& a) {
 
 // k_l1_whole: lane t serves part g of G of one item (l1_whole.h whole_lane_map / whole_part) with the software-
 // pipelined gather of the chunked loop (segreduce_lane: record one entry ahead through the buffer resource, index
-// word two ahead, look-ahead unconditional and clamped) and xyzz_madd_lazy from the point at infinity: no bucket id
-// is read, nothing is compared.  Then log2 G steps of the complete xyzz_add over the group (an empty part, a
+// word two ahead, look-ahead unconditional and clamped) and xyzz_madd_lazy, the first two entries peeled (a copy, then
+// the affine + affine xyzz_add_affine2_lazy): no bucket id is read, nothing is compared.  Then log2 G steps of the complete xyzz_add over the group (an empty part, a
 // doubling and P + (-P) included), and lane 0 of the group stores the bucket.  Count 0 writes nothing: the window
 // sums skip such buckets by their count.  Lanes past the grid's end stay in the kernel as empty parts, so that every
 // lane of a wave is active at the exchange.  `clk`: as k_segreduce.
@@ -1443,13 +1445,28 @@ k_l1_whole(const uint4* __restrict__ items, const uint2* __restrict__ sent, cons
     u32 v_next = idx_c[n_e > 1u ? 2 : 0];
     const __amdgpu_buffer_rsrc_t table = Acc::table_rsrc(pts_in);
     typename Acc::Raw r = Acc::load_raw_buf(table, v_cur);
-    for (u32 k = 0; k < n_e; k++) {
-      const bool negate = (v_cur & SIDX_NEG) != 0;
+    // one step of the gather: entry k's point and sign out, record k + 1 and index word k + 2 requested
+    bool negate;
+    auto take = [&](u32 k) {
+      negate = (v_cur & SIDX_NEG) != 0;
       const auto q = Acc::decode_unsigned(r);
       const u32 k2 = (k + 2 < n_e) ? k + 2 : n_e - 1;
       r = Acc::load_raw_buf(table, v_next);
       v_cur = v_next;
       v_next = idx_c[2 * (size_t)k2];
+      return q;
+    };
+    // entry 0 is a copy, entry 1 meets an accumulator with ZZ = ZZZ = 1 (4M + 2S), the rest is the mixed addition
+    {
+      const auto q = take(0u);
+      a = xyzz_from_affine_signed<CV>(q, negate);
+    }
+    if (n_e > 1u) {
+      const auto q = take(1u);
+      a = xyzz_add_affine2_lazy(a, q, negate);
+    }
+    for (u32 k = 2; k < n_e; k++) {
+      const auto q = take(k);
       a = xyzz_madd_lazy(a, q, negate);
     }
   }
@@ -1610,6 +1627,106 @@ k_wsum_fused(const u32* __restrict__ buckets, const u32* __restrict__ hist, int 
   if (l == 0) {
     IO::store_jac(ws, A_out + ((size_t)w * m_out + j) * IO::JAC_WORDS);
     IO::store_jac(run, R_out + ((size_t)w * m_out + j) * IO::JAC_WORDS);
+  }
+}
+
+// ------------------------------------------------------------------ window sums by bucket rows and columns
+// The THROUGHPUT tail of G1 (wsum_rc.h): every bucket enters the plain sum of its row and the plain sum of its column,
+// each one XYZZ accumulator under the complete xyzz_add (12M + 2S, no conversion to Jacobian: 28 multiplications per
+// bucket against ~36 of the serial levels), and only the row and column sums are weighted.  Both kernels are built
+// to fit the 128 VGPRs a SIMD has left beside three level-1 waves: one accumulator, one addition inlined once (the
+// row and the column pass are two turns of one loop), the operand read where it is used.
+template <class CV>
+__device__ __forceinline__ Xyzz<CV> load_rec_as_xyzz(const u32* p) {
+  using IO = CurveIO<CV>;
+  if (p[IO::REC_TAG] == IO::TAG_JAC) return jac_to_xyzz<CV>(IO::load_jac(p));
+  return IO::load_xyzz(p);
+}
+
+// lane t of window w: row part t into row_out, column part t into col_out (XYZZ records, slot w * slots + t).
+// Buckets whose count is 0 were never written and are skipped.
+template <class CV>
+__global__ void __launch_bounds__(256)
+k_rc_partial(const u32* __restrict__ buckets, const u32* __restrict__ hist, RcGeom geo, int W,
+             u32* __restrict__ row_out, u32* __restrict__ col_out) {
+  using IO = CurveIO<CV>;
+  const int per = rc_partial_lanes(geo);
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= per * W) return;
+  const int w = t / per, i = t - w * per;
+  const size_t base = (size_t)w << geo.cb;
+#pragma unroll 1
+  for (int pass = 0; pass < 2; pass++) {
+    const int slots = pass ? rc_col_slots(geo) : rc_row_slots(geo);
+    if (i >= slots) continue;
+    u32 first;
+    int n;
+    if (pass) rc_col_part(geo, i, RC_CHUNK, &first, &n);
+    else rc_row_part(geo, i, RC_CHUNK, &first, &n);
+    const u32 stride = pass ? (u32)geo.cols : 1u;
+    Xyzz<CV> a = xyzz_from_affine<CV>(IO::aff_infinity());
+#pragma unroll 1
+    for (int k = 0; k < n; k++) {
+      const size_t b = base + first + (size_t)k * stride;
+      if (hist[b] != 0) a = xyzz_add(a, load_rec_as_xyzz<CV>(buckets + b * IO::REC_WORDS));
+    }
+    IO::store_rec_xyzz(a, (pass ? col_out : row_out) + ((size_t)w * slots + i) * IO::REC_WORDS);
+  }
+}
+
+// lane (w, list, e), e < m = 2^s: the sum of the slots of row e (list 0) or column e (list 1) as window-sum element
+// e of list 2 w + list: (A, R) = (infinity, sum), Jacobian, the layout k_rc_wave reads.  Rows past the last one (cb
+// odd: half as many rows as columns) are padded with infinity.
+template <class CV>
+__global__ void __launch_bounds__(256)
+k_rc_reduce(const u32* __restrict__ row_in, const u32* __restrict__ col_in, RcGeom geo, int W,
+            u32* __restrict__ A_out, u32* __restrict__ R_out) {
+  using IO = CurveIO<CV>;
+  __builtin_amdgcn_s_setprio(3);   // (as the serial levels it replaces: k_wsum)
+  const int m = geo.cols;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 2 * m * W) return;
+  const int v = t / m, e = t - v * m;   // list 2 w + (0: rows, 1: columns)
+  const int w = v >> 1, list = v & 1;
+  Xyzz<CV> a = xyzz_from_affine<CV>(IO::aff_infinity());
+  if (list == 1 || e < geo.rows) {
+    int col, first, stride, n;
+    rc_reduce_part(geo, list ? geo.rows + e : e, &col, &first, &stride, &n);
+    const u32* src = (col ? col_in : row_in) + (size_t)w * (col ? rc_col_slots(geo) : rc_row_slots(geo)) * IO::REC_WORDS;
+#pragma unroll 1
+    for (int k = 0; k < n; k++) a = xyzz_add(a, IO::load_xyzz(src + (size_t)(first + k * stride) * IO::REC_WORDS));
+  }
+  IO::store_jac(jac_infinity<CV>(), A_out + (size_t)t * IO::JAC_WORDS);
+  IO::store_jac(xyzz_to_jac(a), R_out + (size_t)t * IO::JAC_WORDS);
+}
+
+// The weighted sums: the wave-cooperative level (wave_combine) over the 2 W lists of m_in elements, rows with
+// g_row (2^s r R_r at the first level), columns with g_col (q C_q).  The last level (m_out = 1) leaves the two
+// elements of window w side by side, (A_row, R_row) and (A_col, infinity): k_finalize's sum A_0 + A_1 + sd (R_0 + R_1)
+// with m = 2 is then sum_b (b + sd) B_b, R_row being the sum of all buckets — as R_col is, which is why it is dropped.
+template <class CV>
+__global__ void __launch_bounds__(64)
+k_rc_wave(const u32* __restrict__ A_in, const u32* __restrict__ R_in, int m_in, int g_row, int g_col,
+          u32* __restrict__ A_out, u32* __restrict__ R_out, int m_out, int lists) {
+  using IO = CurveIO<CV>;
+  __builtin_amdgcn_s_setprio(3);
+  const int wave = blockIdx.x;
+  if (wave >= m_out * lists) return;
+  const int v = wave / m_out, j = wave - v * m_out;
+  const int l = threadIdx.x & 63;
+  const int e = j * 64 + l;
+  int valid = m_in - j * 64;
+  if (valid > 64) valid = 64;
+  Jac<CV> A = jac_infinity<CV>(), T = jac_infinity<CV>();
+  if (e < m_in) {
+    A = IO::load_jac(A_in + ((size_t)v * m_in + e) * IO::JAC_WORDS);
+    T = IO::load_jac(R_in + ((size_t)v * m_in + e) * IO::JAC_WORDS);
+  }
+  wave_combine<CV>(A, T, l, valid, (v & 1) ? g_col : g_row);
+  if (l == 0) {
+    if (m_out == 1 && (v & 1)) T = jac_infinity<CV>();
+    IO::store_jac(A, A_out + ((size_t)v * m_out + j) * IO::JAC_WORDS);
+    IO::store_jac(T, R_out + ((size_t)v * m_out + j) * IO::JAC_WORDS);
   }
 }
 

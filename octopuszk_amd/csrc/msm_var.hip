@@ -874,6 +874,8 @@ int ozk_var_msm_last_l1_path(void) {
   return bad ? 0 : 1;
 }
 
+int ozk_var_msm_last_tail_form(void) { return g_tail_form_last; }
+
 const char* ozk_last_error(void) { return err_buf(); }
 int ozk_version(void) { return 2; }
 int ozk_device_count(void) {

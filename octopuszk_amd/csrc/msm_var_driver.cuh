@@ -179,6 +179,8 @@ static MsmPlan make_plan(int n) {
   if (p.fin_max > 16) p.fin_max = 16;
   p.tail_mode = knob(K_MSM_TAIL_MODE);
   if (p.tail_mode != 0 && p.tail_mode != 1) p.tail_mode = -1;
+  p.tail_rc = knob(K_MSM_TAIL_RC);
+  if (p.tail_rc != 1) p.tail_rc = 0;
   p.l1_whole = 0;   // (plan_for: G1 only)
   p.l1_gtop = WHOLE_G;
   return p;
@@ -636,6 +638,51 @@ int var_msm_head(const MsmPlan& p, const void* d_bases, const void* d_scalars, v
   return var_msm_accum<CV>(p, w, rb.sorted, w + rb.sorted + rb.sort_ws, rb.accum_ws, tail, tail_bytes, st, prepared);
 }
 
+// THROUGHPUT window sums by bucket rows and columns (wsum_rc.h; kernels in msm_var.cuh), G1 only.  No buffer grows
+// for it: the XYZZ partial sums of rows and columns go into wA[0] / wR[0], the row and column sums as window-sum
+// elements into wA[1] / wR[1] (2 W lists of 2^s), and the wave levels alternate between the two pairs as ever.
+// It runs only where OZK_MSM_TAIL_RC=1 asks for it and those fit the arrays the plan sized for the serial levels
+// (W 2^cb / S Jacobian elements each).  It is NOT the default: at 2^20 pairs it executes 4.3 M fewer vector
+// instructions per MSM than the serial levels (28.6 M against 32.9 M) and both of its wide kernels fit the 128
+// registers a SIMD has left beside three level-1 waves — and exactly that costs more than it saves: with tail waves
+// resident beside it on every CU, level 1 stretches from 1.21 to 1.30 ms and the bench falls 5 %
+// (profiles/r09_ab_tail_rowcol.txt).
+inline thread_local int g_tail_form_last = -1;   // ozk_var_msm_last_tail_form: 1 rows / columns, 0 the other forms
+template <class CV>
+bool tail_rc_applies(const MsmPlan& p, const MsmLayout& L) {
+  using IO = CurveIO<CV>;
+  if (p.tail_rc != 1) return false;
+  const RcGeom geo = rc_geom(p.cb);
+  const size_t have = L.m1 * IO::JAC_WORDS;   // words per window of each of wA[k], wR[k]
+  return (size_t)rc_row_slots(geo) * IO::REC_WORDS <= have && (size_t)rc_col_slots(geo) * IO::REC_WORDS <= have &&
+         (size_t)2 * geo.cols * IO::JAC_WORDS <= have;
+}
+template <class CV>
+int var_msm_tail_rc(const MsmPlan& p, const MsmLayout& L, void* d_out, hipStream_t st, hipEvent_t order_ev) {
+  const int TB = 256;
+  const RcGeom geo = rc_geom(p.cb);
+  const int lanes1 = rc_partial_lanes(geo) * p.W, lanes2 = 2 * geo.cols * p.W;
+  hipLaunchKernelGGL((k_rc_partial<CV>), dim3((lanes1 + TB - 1) / TB), dim3(TB), 0, st, (const u32*)L.buckets,
+                     (const u32*)L.hist_t, geo, p.W, L.wA[0], L.wR[0]);
+  hipLaunchKernelGGL((k_rc_reduce<CV>), dim3((lanes2 + TB - 1) / TB), dim3(TB), 0, st, (const u32*)L.wA[0],
+                     (const u32*)L.wR[0], geo, p.W, L.wA[1], L.wR[1]);
+  if (order_ev) OZK_HIP(hipEventRecord(order_ev, st));   // (where var_msm_tail records it: behind the throughput-shaped part)
+  int m_in = geo.cols, g_row = geo.s, g_col = 0, k = 1;
+  while (m_in > 1) {
+    const int m_out = (m_in + 63) / 64;
+    hipLaunchKernelGGL((k_rc_wave<CV>), dim3(m_out * 2 * p.W), dim3(64), 0, st, (const u32*)L.wA[k], (const u32*)L.wR[k],
+                       m_in, g_row, g_col, L.wA[k ^ 1], L.wR[k ^ 1], m_out, 2 * p.W);
+    m_in = m_out;
+    g_row += 6;
+    g_col += 6;
+    k ^= 1;
+  }
+  // two elements per window, (A_row, R_row) and (A_col, infinity); the doublings 2^g act on infinity only
+  hipLaunchKernelGGL((k_finalize<CV>), dim3(1), dim3(64), 0, st, L.wA[k], L.wR[k], 2, 0, p.W, p.c, p.sd, (u32*)d_out);
+  OZK_HIP(hipGetLastError());
+  return OZK_OK;
+}
+
 // Tail phase: the latency-bound remainder (wave-cooperative window-sum levels, Horner over the
 // windows, affine normalisation).  Reads only the tail buffers; writes the wire-out result.
 template <class CV>
@@ -649,6 +696,13 @@ int var_msm_tail(const MsmPlan& p, void* tail, size_t tail_bytes, void* d_out, h
   // the shape the caller asks for unless the plan forces one; LATENCY: fused first level (as wide as the plan says
   // when the caller asked for that shape itself), no serial levels
   const int shape = p.tail_mode >= 0 ? p.tail_mode : mode;
+  g_tail_form_last = 0;
+  if constexpr (std::is_same<CV, G1Cfg>::value) {
+    if (shape == TAIL_THROUGHPUT && tail_rc_applies<CV>(p, L)) {
+      g_tail_form_last = 1;
+      return var_msm_tail_rc<CV>(p, L, d_out, st, order_ev);
+    }
+  }
   const bool fused = shape == TAIL_LATENCY;
   const int S0 = fused && mode == TAIL_LATENCY ? p.S_lat : p.S;
   launch_wsum0<CV>(p, L, st, S0, fused);

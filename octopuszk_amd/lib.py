@@ -36,6 +36,7 @@ _SIGS = {
     "ozk_var_msm_plan": (ctypes.c_int, [i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
     "ozk_var_msm_glv": (ctypes.c_int, [i32]),
     "ozk_var_msm_last_l1_path": (ctypes.c_int, []),
+    "ozk_var_msm_last_tail_form": (ctypes.c_int, []),
     "ozk_gen_bases_dev": (ctypes.c_int, [ctypes.c_uint64, i32, i32, vp, vp]),
     "ozk_var_msm_stage_bytes": (ctypes.c_int, [i32, i32, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(sz)]),
     "ozk_var_msm_sort_dev": (ctypes.c_int, [vp, i32, vp, i32, i32, vp, sz, vp, sz, vp]),
