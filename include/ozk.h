@@ -673,6 +673,39 @@ int ozk_sparse_mat_points_dev(const void* d_row_ptr, const void* d_index, const 
 int ozk_points_add_dev(const void* d_a, const void* d_b, int32_t n, int32_t type, int32_t negate_b, void* d_out,
                        void* stream);
 
+/* ---- n sums of products of points and scalars (points_mac.hip; no counterpart in the
+ * reference): out[i] = sum over v < terms of [k_v[i]] P_v[i], G1.  The middle step of KZG openings at every coset at
+ * once (octopuszk_amd/kzg.py OpenAllKey): the points are fixed per key and prepared once, the scalars change per call.
+ * A lane keeps one Jacobian accumulator for its output: one doubling chain of at most 128 steps and one inversion
+ * whatever `terms` is, against `terms` of each for ozk_points_mul_dev calls joined by ozk_points_add_dev.
+ *   ozk_points_mac_prepared_bytes / ozk_points_mac_workspace_bytes
+ *               192 terms n / 68 terms n bytes; 0 for a shape or type the calls refuse.
+ *   ozk_points_mac_prepare_dev
+ *     d_in        terms x n wire-in G1 points, term-major (term v's n points contiguous), any Z, Z = 0 is infinity,
+ *                 read exactly as ozk_points_scale_dev reads them
+ *     d_prepared  prepared_bytes >= ozk_points_mac_prepared_bytes(terms, n, type): per point x, beta x, beta^2 x, y
+ *                 and the two coordinates of P - phi(P), canonical Montgomery words, element-major so that
+ *                 neighbouring lanes read neighbouring elements; infinity is six zero elements.  Valid for calls with
+ *                 the same terms and n.
+ *   ozk_points_mac_dev
+ *     d_scalars   terms x n x 32 bytes little-endian in DEVICE memory, term-major, as ozk_points_mul_dev takes them
+ *     d_out       n wire-in points exactly as ozk_points_mul_dev writes them (Z = 1, canonical; its infinity)
+ *     d_codes     NULL, or n x int32: 0, or 1 for a lane one of whose scalars was >= r; that lane is written as
+ *                 infinity and its neighbours are not affected
+ *     d_workspace workspace_bytes >= ozk_points_mac_workspace_bytes(terms, n, type): the digit schedules (the GLV
+ *                 halves in joint sparse form, 16 words and a length per scalar), which a first kernel writes and the
+ *                 accumulating kernel streams; no buffer may overlap another.
+ * Every addition is complete: equal points among the terms, P with -P, infinity as any or every term, k = 0 and
+ * k = r - 1 are exact.  1 <= terms <= 32, 1 <= n <= 2^24, type OZK_G1 only (OZK_G2 is OZK_E_INVALID).  A null pointer,
+ * a buffer that is not 4-byte aligned, a shape out of range, a buffer that is too small: OZK_E_INVALID with nothing
+ * enqueued.  Asynchronous on `stream`; they allocate nothing. */
+size_t ozk_points_mac_prepared_bytes(int32_t terms, int32_t n, int32_t type);
+int ozk_points_mac_prepare_dev(const void* d_in, int32_t terms, int32_t n, int32_t type, void* d_prepared,
+                               size_t prepared_bytes, void* stream);
+size_t ozk_points_mac_workspace_bytes(int32_t terms, int32_t n, int32_t type);
+int ozk_points_mac_dev(const void* d_prepared, const void* d_scalars, int32_t terms, int32_t n, int32_t type,
+                       void* d_out, int32_t* d_codes, void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,8 +24,17 @@ ozk_fr_evals_open_set_dev, csrc/kzg_set.cuh), accepted when e(C - [I(tau)] g1, g
     ops = ck.open_set(coeffs, [z_1, ..., z_t])       # SetOpening: C | t | z | y | pi, 68 + 64 t bytes; one per row
     assert verify_set(svk, ops[0]) and verify_set_all(svk, ops)
 
-Out of scope: hiding commitments, different point sets per polynomial under one proof, whole-coset openings,
-degree-bound proofs, G2 commitments, interoperability with other tools' byte formats.  There is no CPU path.
+Every point of the evaluation domain, or every coset of it, at once (the FK20 construction): for
+n a power of two, l a power of two dividing n and r = n / l, the r proofs of the cosets S_k = (omega^(k + r j), j < l),
+each the pi of open_set(coeffs, S_k) (of open(coeffs, omega^k) for l = 1), from l transforms over Fr, one
+multiply-accumulate kernel over points (ozk_points_mac_dev) and two group FFTs, instead of r quotients and r MSMs.
+
+    ak = OpenAllKey.from_srs(srs, n, coset=l)        # the l prepared tables of one (n, l)
+    all_ = ak.open_all(coeffs)[0]                    # AllOpenings: c, values (n x 32 B on the device), proofs (r x 32 B)
+    assert verify_set(svk, all_.opening(k))          # an Opening for l = 1, a SetOpening for l > 1
+
+Out of scope: hiding commitments, different point sets per polynomial under one proof, degree-bound proofs, G2
+commitments, interoperability with other tools' byte formats.  There is no CPU path.
 """
 import ctypes
 import hashlib
@@ -805,3 +814,167 @@ def verify_set_combined(vk, commitments, points, values, pi) -> bool:
     del ws
     ys = [sum(w * row[j] for w, row in zip(pw, values)) % FR for j in range(len(points))]
     return verify_set(vk, SetOpening(c_enc, points, ys, pi))
+
+
+# ============================================================================ every coset at once (section 25)
+ALL_COSETS = (1, 2, 4, 8, 16, 32)     # coset sizes l: up to the t of a set opening (SET_T_MAX)
+ALL_MAX_TRANSFORM = 1 << 22           # the largest group FFT (ozk_ec_fft_dev); the construction runs one of 2 n / l
+_G1_INF_WIRE = bytes(32) + (1).to_bytes(32, "little") + bytes(32)
+
+
+def points_mac_prepare(points, terms, n):
+    """terms x n wire-in G1 points, term-major -> the prepared table of ozk_points_mac_dev (ozk_points_mac_prepare_dev).
+    Asynchronous on the current stream."""
+    L = _lib.load()
+    points = points.contiguous()
+    if _codec._count(points, 96, "points") != terms * n:
+        raise ValueError("%d x %d points need %d bytes, not %d" % (terms, n, 96 * terms * n, points.numel()))
+    nbytes = int(L.ozk_points_mac_prepared_bytes(terms, n, G1))
+    table = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=points.device)
+    _lib.check(L.ozk_points_mac_prepare_dev(_ptr(points), terms, n, G1, _ptr(table), table.numel(), _stream()))
+    return table
+
+
+def points_mac(table, scalars, terms, n, codes=False, workspace=None):
+    """out[i] = sum_v [k_v[i]] P_v[i] over a prepared table and terms x n scalars (32 bytes little-endian, term-major,
+    on the device): n wire-in points, Z = 1 (ozk_points_mac_dev); codes=True returns (points, n int32 codes), 1 for a
+    lane with a scalar >= r.  Asynchronous on the current stream when the caller passes (and keeps) the workspace,
+    else it synchronises: the workspace dies here."""
+    L = _lib.load()
+    scalars = scalars.contiguous()
+    if scalars.numel() != 32 * terms * n:
+        raise ValueError("%d x %d scalars need %d bytes, not %d" % (terms, n, 32 * terms * n, scalars.numel()))
+    out = torch.empty(96 * n, dtype=torch.uint8, device=scalars.device)
+    d_codes = torch.empty(n, dtype=torch.int32, device=scalars.device) if codes else None
+    ws = workspace
+    if ws is None:
+        ws = torch.empty(max(int(L.ozk_points_mac_workspace_bytes(terms, n, G1)), 256), dtype=torch.uint8,
+                         device=scalars.device)
+    _lib.check(L.ozk_points_mac_dev(_ptr(table), _ptr(scalars), terms, n, G1, _ptr(out),
+                                    None if d_codes is None else _ptr(d_codes), _ptr(ws), ws.numel(), _stream()))
+    if workspace is None:
+        torch.cuda.current_stream().synchronize()
+    return (out, d_codes) if codes else out
+
+
+def fr_fft(values, n, omega, out=None):
+    """The transform of n = 2^k elements of Fr (32 bytes little-endian each) on the device: out[j] = sum_i
+    omega^(i j) in[i], canonical (ozk_fft_compact_dev).  Synchronises (the workspace dies here)."""
+    L = _lib.load()
+    if out is None:
+        out = torch.empty(32 * n, dtype=torch.uint8, device=values.device)
+    ws = torch.empty(max(int(L.ozk_fft_workspace_bytes(n)), 256), dtype=torch.uint8, device=values.device)
+    _lib.check(L.ozk_fft_compact_dev(_ptr(values), n, _vp(_le([omega])), _ptr(out), _ptr(ws), ws.numel(), _stream()))
+    torch.cuda.current_stream().synchronize()
+    return out
+
+
+class AllOpenings:
+    """What open_all returns per polynomial: c (the compressed commitment), values (n x 32 bytes on the device, p(omega^i)
+    in natural order) and proofs (r x 32 bytes on the device, compressed as DESIGN.md section 13; proof k is that of the
+    coset S_k = (omega^(k + r j), j < l))."""
+
+    def __init__(self, c, values, proofs, n, coset):
+        self.c, self.values, self.proofs = _enc_of(c, "commitment"), values, proofs
+        self.n, self.coset, self.cosets = int(n), int(coset), int(n) // int(coset)
+        self._host = None
+
+    def opening(self, k):
+        """the Opening at omega^k (coset size 1) or the SetOpening at S_k, points in the order j = 0 .. l - 1"""
+        k = int(k)
+        if not 0 <= k < self.cosets:
+            raise ValueError("coset %d: there are %d" % (k, self.cosets))
+        if self._host is None:
+            self._host = (_ints(_ceremony._bytes(self.values)), _ceremony._bytes(self.proofs))
+        ys, pis = self._host
+        omega, pi = root_of_unity(self.n), pis[32 * k:32 * k + 32]
+        if self.coset == 1:
+            return Opening(self.c, pow(omega, k, FR), ys[k], pi)
+        at = [k + self.cosets * j for j in range(self.coset)]
+        return SetOpening(self.c, [pow(omega, i, FR) for i in at], [ys[i] for i in at], pi)
+
+
+class OpenAllKey:
+    """One (n, l): the l tables X_v = ECFFT_2r(tau_g1[l (r - 1 - j) + v], j < r, then r points at infinity) in the
+    prepared form of ozk_points_mac_dev, built on first use, and a CommitKey for the commitments."""
+
+    def __init__(self, tau_g1, n, coset, commit_key):
+        self.n, self.coset, self.cosets = int(n), int(coset), int(n) // int(coset)
+        self._tau_g1, self._ck, self._tables = tau_g1, commit_key, None
+
+    @staticmethod
+    def from_srs(srs, n, coset=1, commit_key=None) -> "OpenAllKey":
+        n, coset = int(n), int(coset)
+        have = 2 * int(srs.m) + 1
+        if n < 2 or n & (n - 1):
+            raise ValueError("n = %d: a power of two >= 2" % n)
+        if n > have:
+            raise ValueError("n = %d: a string of m = %d carries %d powers in G1" % (n, srs.m, have))
+        if coset not in ALL_COSETS or coset > n:
+            raise ValueError("coset = %d: one of %s, at most n = %d" % (coset, ALL_COSETS, n))
+        if 2 * (n // coset) > ALL_MAX_TRANSFORM:
+            raise ValueError("n / coset = %d: the group FFT of twice that exceeds 2^22 points" % (n // coset))
+        if commit_key is not None and commit_key.n != n:
+            raise ValueError("the commit key has n = %d, not %d" % (commit_key.n, n))
+        flat = srs.tau_g1.reshape(-1)
+        return OpenAllKey(flat, n, coset, commit_key if commit_key is not None else CommitKey(flat, n, srs.m))
+
+    def tables(self):
+        """the prepared tables, l x 2r points (None for r = 1: the one proof is O)"""
+        if self._tables is None and self.cosets > 1:
+            from .srs import ec_fft
+            l, r = self.coset, self.cosets
+            powers = self._tau_g1[:96 * self.n].view(r, l, 96)              # power l i + v at [i, v]
+            inf = torch.frombuffer(bytearray(_G1_INF_WIRE), dtype=torch.uint8).to(powers.device)
+            x = torch.cat([powers.flip(0).transpose(0, 1), inf.expand(l, r, 96)], dim=1).contiguous()
+            w2 = root_of_unity(2 * r)
+            big = torch.cat([ec_fft(x[v].reshape(-1), G1, w2) for v in range(l)])
+            self._tables = points_mac_prepare(big, l, 2 * r)
+            torch.cuda.current_stream().synchronize()
+        return self._tables
+
+    # ---- the stages of one row (tools/kzg_all_bench.py times each)
+    def values(self, row):
+        """p(omega^i), i < n: one transform over Fr"""
+        return fr_fft(row, self.n, root_of_unity(self.n))
+
+    def coefficient_ffts(self, row):
+        """c_v = FFT_2r(p[l i + v], i < r, then r zeros), v < l: l x 2r elements, term-major"""
+        l, r = self.coset, self.cosets
+        padded = torch.zeros((l, 2 * r, 32), dtype=torch.uint8, device=row.device)
+        padded[:, :r] = row.view(r, l, 32).transpose(0, 1)
+        out = torch.empty((l, 64 * r), dtype=torch.uint8, device=row.device)
+        w2 = root_of_unity(2 * r)
+        for v in range(l):
+            fr_fft(padded[v].reshape(-1), 2 * r, w2, out[v])
+        return out
+
+    def mac(self, c):
+        """U[i] = sum_v [c_v[i]] X_v[i], i < 2r"""
+        return points_mac(self.tables(), c.reshape(-1), self.coset, 2 * self.cosets)
+
+    def upper_half(self, u):
+        """H = the upper half of the inverse group FFT of U (its last element is O by construction)"""
+        from .srs import ec_fft
+        return ec_fft(u, G1, root_of_unity(2 * self.cosets), inverse=True)[96 * self.cosets:].contiguous()
+
+    def proofs_of(self, h):
+        """(pi_0 .. pi_{r-1}) = ECFFT_r(H) with the root omega^l, as wire-in points"""
+        from .srs import ec_fft
+        return ec_fft(h, G1, root_of_unity(self.cosets))
+
+    def open_all(self, coeffs) -> list:
+        """K rows of n coefficients -> K AllOpenings.  No point leaves the device between the stages."""
+        k, _, _ = _rows(coeffs, "coeffs", self.n)
+        rows = _as2d(coeffs)
+        commitments = self._ck.commit(coeffs)
+        out = []
+        for y in range(k):
+            row = rows[y]
+            if self.cosets == 1:
+                proofs = torch.frombuffer(bytearray(_G1_INF), dtype=torch.uint8).to(row.device)
+            else:
+                h = self.upper_half(self.mac(self.coefficient_ffts(row)))
+                proofs = _codec.compress_g1(self.proofs_of(h))
+            out.append(AllOpenings(commitments[y], self.values(row), proofs, self.n, self.coset))
+        return out

@@ -128,6 +128,10 @@ _SIGS = {
     "ozk_sparse_mat_points_workspace_bytes": (sz, [i32, i32]),
     "ozk_sparse_mat_points_dev": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, sz, vp]),
     "ozk_points_add_dev": (ctypes.c_int, [vp, vp, i32, i32, i32, vp, vp]),
+    "ozk_points_mac_prepared_bytes": (sz, [i32, i32, i32]),
+    "ozk_points_mac_prepare_dev": (ctypes.c_int, [vp, i32, i32, i32, vp, sz, vp]),
+    "ozk_points_mac_workspace_bytes": (sz, [i32, i32, i32]),
+    "ozk_points_mac_dev": (ctypes.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]),
 }
 
 
