@@ -9,7 +9,6 @@ C(beta(r)) at one random r.  Field: BN254 Fr (the reference's test uses a 180-bi
 
 Tensors live on the current device and work on the current stream.
 """
-import ctypes
 import secrets
 
 import numpy as np
@@ -17,8 +16,10 @@ import torch
 
 from . import lib as _lib
 from .device import _ptr, _stream
-from .fft import FR
-from .zksnark import fr_random, lowest_power_of_two
+from .fft import FR, fr_random, lowest_power_of_two
+from .vectors import fr_poly_eval
+from .wire import host_bytes, ints32, le32
+from .wire import vp as _vp
 
 MAX_D = 1 << 28     # the 2-adicity of Fr
 OP_INPUT, OP_CONST, OP_ADD, OP_MUL = 0, 1, 2, 3
@@ -196,14 +197,6 @@ class Circuit:
 
 
 # ---------------------------------------------------------------------------------------------- device helpers
-def _le32(values) -> bytes:
-    return b"".join((int(v) % FR).to_bytes(32, "little") for v in values)
-
-
-def _vp(b):
-    return ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p)
-
-
 def _check_shape(circuit, num_inputs):
     n, N = circuit.input_size, int(num_inputs)
     if n <= 0:
@@ -235,34 +228,13 @@ def _inputs_dev(inputs, count):
     inputs = list(inputs)
     if len(inputs) != count:
         raise ValueError("inputs: %d values, expected %d" % (len(inputs), count))
-    return torch.from_numpy(np.frombuffer(_le32(inputs), dtype=np.uint8).copy()).cuda()
+    return torch.from_numpy(np.frombuffer(le32(int(v) % FR for v in inputs), dtype=np.uint8).copy()).cuda()
 
 
 def _program_args(circuit):
     prog, n_slots, consts = circuit.compile()
-    cb = _le32(consts) if consts else b"\x00" * 32
+    cb = le32(c % FR for c in consts) if consts else b"\x00" * 32
     return np.ascontiguousarray(prog), n_slots, cb, len(consts)
-
-
-def _ints(t):
-    raw = bytes(t.cpu().numpy().tobytes())
-    return [int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(len(raw) // 32)]
-
-
-def fr_poly_eval(coeffs, r, npolys=1):
-    """sum_i c_yi r^i for npolys polynomials of equal length stored back to back in a uint8 CUDA tensor (32-byte LE
-    canonical coefficients): a CUDA tensor of npolys x 32 bytes."""
-    L = _lib.load()
-    total = coeffs.numel() // 32
-    if coeffs.numel() % 32 or total % npolys or total == 0:
-        raise ValueError("coefficients do not split into %d polynomials" % npolys)
-    length = total // npolys
-    out = torch.empty(npolys * 32, dtype=torch.uint8, device=coeffs.device)
-    ws = torch.empty(int(L.ozk_fr_poly_eval_workspace_bytes(npolys)), dtype=torch.uint8, device=coeffs.device)
-    rb = (int(r) % FR).to_bytes(32, "little")
-    _lib.check(L.ozk_fr_poly_eval_dev(_ptr(coeffs), npolys, length, length, _vp(rb), _ptr(out), _ptr(ws), ws.numel(),
-                                      _stream()))
-    return out
 
 
 # ---------------------------------------------------------------------------------------------- prover / verifier
@@ -317,7 +289,7 @@ class Verifier:
 
     def claim(self, r):
         """The proof polynomial at r (NaiveEvaluation.parallelEvaluatePolynomial)."""
-        return _ints(fr_poly_eval(self.proof, r))[0]
+        return ints32(host_bytes(fr_poly_eval(self.proof, r)))[0]
 
     def verify_proof(self, seed=None, challenge=None):
         """Verifier.verifyProof: accept exactly when proof(r) == C(beta_1(r), ..., beta_n(r)), comparing field values
@@ -333,7 +305,7 @@ class Verifier:
         else:
             r = secrets.randbelow(FR)
         beta = self.columns_at(r)
-        want = _ints(NaiveEvaluator._evaluate(self.circuit, beta, 1))[0]
+        want = ints32(host_bytes(NaiveEvaluator._evaluate(self.circuit, beta, 1)))[0]
         return self.claim(r) == want
 
     def get_result(self):

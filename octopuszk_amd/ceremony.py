@@ -12,19 +12,20 @@ and t of serial_setup_generate stay known to whoever ran it, and there is no pha
 The receipt (296 bytes) chains to the one before through h = SHA-256(previous receipt) and carries a Schnorr proof of
 knowledge of d over the base delta_g1-before.  There is no CPU path.
 """
-import ctypes
 import hashlib
-import os
 import secrets
 import time
 
+import numpy as np
 import torch
 
 from . import codec as _codec
-from . import lib as _lib
-from . import pairing as _pairing
-from .device import VarMsmWorkspace, _ptr, _stream
+from . import transcript as _transcript
+from . import vectors as _vectors
+from . import wire as _wire
 from .fft import FR
+from .vectors import scale_points
+from .zksnark import ProvingKey, VerificationKey
 
 G1, G2 = 1, 2
 MAGIC = b"OZKC2\x00\x00\x01"
@@ -33,136 +34,32 @@ CHECKS = ("receipt_deltas", "unchanged", "delta_wellformed", "delta_ratio", "vec
 _UNCHANGED_G1 = ("alpha_g1", "beta_g1", "query_a", "query_b_g1")
 _UNCHANGED_G2 = ("beta_g2", "query_b_g2")
 _SHARED = _UNCHANGED_G1 + _UNCHANGED_G2 + ("r1cs",)
-_GT_ONE = (1).to_bytes(32, "little") + bytes(352)
-
-
-def _scalar(k, what, lo=0):
-    k = int(k)
-    if not lo <= k < FR:
-        raise ValueError("%s must lie in [%d, r)" % (what, lo))
-    return k
-
-
-def scale_points(points, k, type_) -> torch.Tensor:
-    """[k] P for every wire-in point P of `points` (a uint8 CUDA tensor, n x 96 bytes for type_ 1 = G1, n x 192 for
-    2 = G2, any Z) and one int k in [0, r): n wire-in points with Z = 1, infinity as (0, 1, 0) / ((0, 0), (1, 0),
-    (0, 0)).  Exact for every point of the curve (of the twist, inside the order-r subgroup or not).  Asynchronous on
-    the current stream."""
-    k = _scalar(k, "the scalar")
-    if type_ not in (G1, G2):
-        raise ValueError("type_ must be 1 (G1) or 2 (G2)")
-    L = _lib.load()
-    n = _codec._count(points, 96 * type_, "points")
-    points = points.contiguous()
-    out = torch.empty_like(points)
-    kb = (ctypes.c_uint8 * 32).from_buffer_copy(k.to_bytes(32, "little"))   # read before the call returns
-    _lib.check(L.ozk_points_scale_dev(_ptr(points), n, type_, ctypes.cast(kb, ctypes.c_void_p), _ptr(out), _stream()))
-    return out
-
-
-def _bytes(t) -> bytes:
-    return bytes(t.cpu().numpy())
+_POK_TAG = b"OZK-phase2-pok"
+_RHO_TAG = b"OZK-phase2-rho"
 
 
 def _enc(points, type_) -> bytes:
-    return _bytes((_codec.compress_g1 if type_ == G1 else _codec.compress_g2)(points))
+    return _wire.host_bytes((_codec.compress_g1 if type_ == G1 else _codec.compress_g2)(points))
 
 
-def _challenge(body: bytes, r_enc: bytes, tag=b"OZK-phase2-pok") -> int:
+def _challenge(body: bytes, r_enc: bytes) -> int:
     """the 128-bit Schnorr challenge of a receipt, never zero (srs.py: the same under the phase-1 tag)"""
-    return int.from_bytes(hashlib.sha256(tag + body + r_enc).digest()[:16], "little") or 1
-
-
-def _weights(seed: bytes, n: int, tag=b"OZK-phase2-rho") -> bytes:
-    """n weights in [1, 2^128) as n x 32 bytes little-endian: block j of the stream is SHA-256("OZK-phase2-rho" | seed
-    | j as 8 bytes little-endian), two weights per block (kzg.py: the same under its own tag)"""
-    out = bytearray(32 * n)
-    pad = bytes(16)
-    one = (1).to_bytes(16, "little")
-    for j in range((n + 1) // 2):
-        block = hashlib.sha256(tag + seed + j.to_bytes(8, "little")).digest()
-        for half in (0, 1):
-            i = 2 * j + half
-            if i < n:
-                w = block[16 * half:16 * half + 16]
-                out[32 * i:32 * i + 32] = (w if w != pad else one) + pad
-    return bytes(out)
-
-
-def _seed_bytes(seed) -> bytes:
-    if seed is None:
-        return os.urandom(32)
-    if isinstance(seed, (bytes, bytearray)):
-        return bytes(seed)
-    return int(seed).to_bytes(32, "little")
+    return _transcript.challenge128(_POK_TAG, body, r_enc)
 
 
 # ---------------------------------------------------------------------------- receipt
-FQ = 21888242871839275222246405745257275088696311157297823662689037894645226208583
-_INV82 = pow(82, -1, FQ)
-_TWIST_B = (27 * _INV82 % FQ, -3 * _INV82 % FQ)   # 3 / (9 + u) = 3 (9 - u) / 82
-
-
-def _is_square(v) -> bool:
-    return v % FQ == 0 or pow(v, (FQ - 1) // 2, FQ) == 1
-
-
-def _decode_code(enc: bytes, type_) -> int:
-    """The code the strict decoder of section 13 gives one compressed point (0 ok, 1 range, 2 infinity, 3 no point),
-    in host integers: a receipt is five points, parsed where there may be no GPU.  Existence of y only: a square in
-    Fq2 is an element whose norm is a square in Fq."""
-    ylarger, infinity = bool(enc[-1] & 0x80), bool(enc[-1] & 0x40)
-    xs = [int.from_bytes(enc[i:i + 32], "little") for i in range(0, len(enc), 32)]
-    xs[-1] &= (1 << 254) - 1
-    if infinity:
-        return _codec.E_INFINITY if any(xs) or ylarger else _codec.OK
-    if any(x >= FQ for x in xs):
-        return _codec.E_RANGE
-    if type_ == G1:
-        rhs = (xs[0] ** 3 + 3) % FQ
-        on, y_zero = _is_square(rhs), rhs == 0
-    else:
-        a, b = xs
-        a2, b2 = (a * a - b * b) % FQ, 2 * a * b % FQ
-        r0, r1 = (a2 * a - b2 * b + _TWIST_B[0]) % FQ, (a2 * b + b2 * a + _TWIST_B[1]) % FQ
-        on, y_zero = _is_square(r0 * r0 + r1 * r1), r0 == 0 and r1 == 0
-    if not on:
-        return _codec.E_NO_POINT
-    return _codec.E_INFINITY if y_zero and ylarger else _codec.OK
-
-
-def _require_points(fields):
-    """fields: (name, compressed encoding, type_) of a receipt's points; ValueError naming the first that does not
-    decode"""
-    for name, enc, type_ in fields:
-        code = _decode_code(enc, type_)
-        if code:
-            raise ValueError("receipt: %s does not decode: code %d (%s)" % (name, code, _codec.CODE_NAMES.get(code, "?")))
-
-
-def _receipt_head(b, magic, size):
-    """bytes of a receipt with the right length and magic, or ValueError"""
-    b = bytes(b)
-    if len(b) != size:
-        raise ValueError("receipt: length %d, not %d" % (len(b), size))
-    if b[:8] != magic:
-        raise ValueError("receipt: wrong magic or version")
-    return b
-
-
 def _pok_holds(base, moved, r_enc: bytes, z: int, c: int):
     """z base - c moved - R = O as one 3-point MSM (base, moved: one wire-in G1 point each; R compressed): (a device
     flag to read after a synchronise as _pok_read, the workspace to keep until then)"""
-    from .zksnark import _dev_bytes
-    r_point, code = _codec.decompress_g1(_dev_bytes(r_enc))
-    pok, ws = _msm(torch.cat([base.reshape(-1), moved.reshape(-1), r_point]),
-                   b"".join(v.to_bytes(32, "little") for v in (z, FR - c, FR - 1)), 3)
+    r_point, code = _codec.decompress_g1(_wire.dev_bytes(r_enc))
+    pok, ws = _vectors.msm(torch.cat([base.reshape(-1), moved.reshape(-1), r_point]),
+                           _wire.dev_bytes(_wire.le32((z, FR - c, FR - 1))), 3)
     return (pok, code), ws
 
 
 def _pok_read(flag) -> bool:
     pok, code = flag
-    return _is_inf_out(pok) and not int(code.item())
+    return _wire.is_inf_out(pok) and not int(code.item())
 
 
 class Receipt:
@@ -189,12 +86,12 @@ class Receipt:
     def from_bytes(b) -> "Receipt":
         """Strict: ValueError naming the field for a wrong length, a wrong magic, z >= r or a point that does not
         decode (decoded on the device)."""
-        b = _receipt_head(b, MAGIC, RECEIPT_BYTES)
+        b = _codec.receipt_head(b, MAGIC, RECEIPT_BYTES)
         z = int.from_bytes(b[264:], "little")
         if z >= FR:
             raise ValueError("receipt: z is not below r")
         rec = Receipt(b[8:40], b[40:72], b[72:104], b[104:168], b[168:232], b[232:264], z)
-        _require_points((name, getattr(rec, name), type_) for name, type_ in Receipt._FIELDS)
+        _codec.require_points(((name, getattr(rec, name), type_) for name, type_ in Receipt._FIELDS), "receipt")
         return rec
 
     def body(self) -> bytes:
@@ -209,9 +106,8 @@ def contribute(pk, vk=None, d=None, *, nonce=None, previous=b""):
     scale_points call over the whole array; every other field of pk2 is the same tensor object as in pk.  vk2 is vk
     with the new delta_g2 (None for vk None).  `previous`: the bytes of the receipt before this one, empty for the
     first.  `nonce`: the u of the proof of knowledge, in [1, r); give one for reproducible receipts in tests only."""
-    from .zksnark import ProvingKey, VerificationKey
-    d = secrets.randbelow(FR - 1) + 1 if d is None else _scalar(d, "d", 1)
-    u = secrets.randbelow(FR - 1) + 1 if nonce is None else _scalar(nonce, "nonce", 1)
+    d = secrets.randbelow(FR - 1) + 1 if d is None else _wire.scalar_in_range(d, "d", 1)
+    u = secrets.randbelow(FR - 1) + 1 if nonce is None else _wire.scalar_in_range(nonce, "nonce", 1)
     inv_d = pow(d, -1, FR)
     pk2 = ProvingKey()
     for name in _SHARED:
@@ -232,24 +128,7 @@ def contribute(pk, vk=None, d=None, *, nonce=None, previous=b""):
 
 
 # ---------------------------------------------------------------------------- verify
-def _msm(bases, scalars_bytes, n):
-    """sum s_i P_i over n wire-in G1 points through ozk_var_msm_dev: one wire-out point (192 bytes); the workspace is
-    returned too, to be kept until the stream has run"""
-    from .zksnark import _dev_bytes
-    ws = VarMsmWorkspace(n, G1)
-    return ws.run(bases.contiguous(), _dev_bytes(scalars_bytes)), ws
-
-
-def _is_inf_out(p) -> bool:
-    return not bool(p.view(3, 64)[2].any().item())
-
-
-def _pairs_are_one(p_batch, q_batch) -> bool:
-    return _bytes(_pairing.pairing_product(p_batch, q_batch)) == _GT_ONE
-
-
 def _r1cs_equal(a, b) -> bool:
-    import numpy as np
     if (a.num_inputs, a.num_auxiliary) != (b.num_inputs, b.num_auxiliary):
         return False
     for x, y in ((a.A, b.A), (a.B, b.B), (a.C, b.C)):
@@ -282,7 +161,6 @@ def verify_contribution(pk_before, pk_after, receipt, *, vk_before=None, vk_afte
     system.  A seeded check is reproducible and so unsound against anyone who knows the seed: tests only.
     stage_ms: None, or a dict that receives the times of the stages compare, scale, msms, pairings in ms (the call
     then synchronises between them)."""
-    from .zksnark import VerificationKey
     T = {"compare": 0.0, "scale": 0.0, "msms": 0.0, "pairings": 0.0}
     t0 = [time.perf_counter()]
 
@@ -331,27 +209,28 @@ def verify_contribution(pk_before, pk_after, receipt, *, vk_before=None, vk_afte
     neg_d1 = scale_points(pk_before.delta_g1, FR - 1, G1)
     lap("scale")
     # 4 delta_ratio
-    if not _pairs_are_one(torch.cat([pk_after.delta_g1.reshape(-1), neg_d1]),
-                          torch.cat([pk_before.delta_g2.reshape(-1), pk_after.delta_g2.reshape(-1)])):
+    if not _vectors.pairs_are_one(torch.cat([pk_after.delta_g1.reshape(-1), neg_d1]),
+                                  torch.cat([pk_before.delta_g2.reshape(-1), pk_after.delta_g2.reshape(-1)])):
         return no("delta_ratio", "pairings")
     lap("pairings")
     # 5 vectors
     n = n_abc + n_h
-    rho = _weights(_seed_bytes(seed), n)
+    rho = _transcript.weights(_transcript.seed_bytes(seed), n, _RHO_TAG)
     lap("compare")
-    s_old, ws1 = _msm(torch.cat([pk_before.delta_abc_g1.reshape(-1), pk_before.query_h.reshape(-1)]), rho, n)
-    s_new, ws2 = _msm(torch.cat([pk_after.delta_abc_g1.reshape(-1), pk_after.query_h.reshape(-1)]), rho, n)
+    s_old, ws1 = _vectors.msm(torch.cat([pk_before.delta_abc_g1.reshape(-1), pk_before.query_h.reshape(-1)]),
+                              _wire.dev_bytes(rho), n)
+    s_new, ws2 = _vectors.msm(torch.cat([pk_after.delta_abc_g1.reshape(-1), pk_after.query_h.reshape(-1)]),
+                              _wire.dev_bytes(rho), n)
     # 6 pok (its MSM with the two above)
     pok, ws3 = _pok_holds(pk_before.delta_g1, pk_after.delta_g1, rec.r, rec.z, _challenge(rec.body(), rec.r))
-    inf_old, inf_new, pok_ok = _is_inf_out(s_old), _is_inf_out(s_new), _pok_read(pok)
+    inf_old, inf_new, pok_ok = _wire.is_inf_out(s_old), _wire.is_inf_out(s_new), _pok_read(pok)
     lap("msms")
     if inf_old or inf_new:
         return no("vectors")
-    from .zksnark import wire_out_to_in
-    neg_s = scale_points(wire_out_to_in(s_old, G1), FR - 1, G1)
+    neg_s = scale_points(_wire.wire_out_to_in(s_old, G1), FR - 1, G1)
     lap("scale")
-    if not _pairs_are_one(torch.cat([wire_out_to_in(s_new, G1), neg_s]),
-                          torch.cat([pk_after.delta_g2.reshape(-1), pk_before.delta_g2.reshape(-1)])):
+    if not _vectors.pairs_are_one(torch.cat([_wire.wire_out_to_in(s_new, G1), neg_s]),
+                                  torch.cat([pk_after.delta_g2.reshape(-1), pk_before.delta_g2.reshape(-1)])):
         return no("vectors", "pairings")
     lap("pairings")
     if not pok_ok:

@@ -9,6 +9,7 @@ from . import lib as _lib
 FR = 21888242871839275222246405745257275088548364400416034343698204186575808495617  # BN254aFrParameters.java:33
 FR_ROOT = 19103219067921713944291392827692070036145651957329286315305642004821462161904  # :34
 FR_MULT_GEN = 5  # :35
+SEED = 10  # configuration/Configuration.java:52
 
 
 def big_integer_to_byte_array_cgbn(v: int) -> bytes:
@@ -21,6 +22,33 @@ def big_integer_to_byte_array_cgbn(v: int) -> bytes:
 def root_of_unity(order: int) -> int:
     """Fp.rootOfUnity (Fp.java:98-102)."""
     return pow(FR_ROOT, FR // order, FR)
+
+
+def _java_random_next_long(seed: int) -> int:
+    """new java.util.Random(seed).nextLong() (JDK API specification: 48-bit LCG, two signed 32-bit draws)."""
+    mult, mask = 0x5DEECE66D, (1 << 48) - 1
+    st = (seed ^ mult) & mask
+    out = []
+    for _ in range(2):
+        st = (st * mult + 0xB) & mask
+        v = st >> 16
+        out.append(v - (1 << 32) if v >= 1 << 31 else v)
+    v = ((out[0] << 32) + out[1]) & ((1 << 64) - 1)
+    return v - (1 << 64) if v >= 1 << 63 else v
+
+
+def fr_random(seed: int = SEED) -> int:
+    """Fp.random (algebra/fields/Fp.java:72-80): new Fp(new Random(seed).nextLong()) — reduced mod r by the
+    constructor, so every draw with the same seed is the same element."""
+    return _java_random_next_long(seed) % FR
+
+
+def lowest_power_of_two(n: int) -> int:
+    """common/MathUtils.java:20-41."""
+    r = 1
+    while r < n:
+        r <<= 1
+    return r
 
 
 def serial_radix2_fft_native_helper(inputs, omega: bytes, task_id: int) -> bytes:

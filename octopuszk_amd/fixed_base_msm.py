@@ -5,7 +5,8 @@ formats; the natives are the C ABI of libozk_hip.so."""
 import ctypes
 
 from . import lib as _lib
-from .variable_base_msm import big_integer_to_byte_array_cgbn, marshal_scalars
+from .wire import g2_wire, le32
+from .wire import vp as _vp
 
 G1_ITERATION_BATCH = 1 << 23       # FixedBaseMSM.java:200, :333
 G2_ITERATION_BATCH = 1 << 22       # FixedBaseMSM.java:257, :390
@@ -28,10 +29,6 @@ def get_window_size(num_scalars: int, table) -> int:
             window = i + 1
             break
     return window
-
-
-def _vp(b):
-    return ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p)
 
 
 def batch_msm_native_helper(outerc, window_size, out_len, inner_len, batch_size, scalar_size, base: bytes,
@@ -71,9 +68,7 @@ def _be64(b: bytes) -> int:
 
 
 def _base_wire(base, is_g1):
-    if is_g1:
-        return b"".join(big_integer_to_byte_array_cgbn(c) for c in base)
-    return b"".join(big_integer_to_byte_array_cgbn(base[i][j]) for i in range(3) for j in range(2))
+    return le32(base) if is_g1 else g2_wire(base)
 
 
 def _points_be(raw, count, is_g1):
@@ -97,7 +92,7 @@ def batch_msm(scalar_size, window_size, base, scalars, is_g1=True, task_id=0):
     for it in range(0, len(scalars), step):
         sc = scalars[it:it + step]
         raw = batch_msm_native_helper(outerc, window_size, num_windows, 1 << window_size, len(sc), scalar_size,
-                                      bw, marshal_scalars(sc), 1 if is_g1 else 2, task_id)
+                                      bw, le32(sc), 1 if is_g1 else 2, task_id)
         out.extend(_points_be(raw, len(sc), is_g1))
     return out
 
@@ -112,7 +107,7 @@ def batch_msm_partition(scalar_size, window_size, out_size, in_size, base, index
     for it in range(0, len(indexed_scalars), step):
         part = indexed_scalars[it:it + step]
         raw = batch_msm_native_helper(outerc, window_size, out_size, in_size, len(part), scalar_size, bw,
-                                      marshal_scalars([p[1] for p in part]), 1 if is_g1 else 2, task_id)
+                                      le32([p[1] for p in part]), 1 if is_g1 else 2, task_id)
         pts = _points_be(raw, len(part), is_g1)
         out.extend((part[i][0], pts[i]) for i in range(len(part)))
     return out
@@ -130,7 +125,7 @@ def double_batch_msm(out_size1, in_size1, out_size2, in_size2, scalar_size1, win
     for it in range(0, len(scalars), DOUBLE_ITERATION_BATCH):
         sc = scalars[it:it + DOUBLE_ITERATION_BATCH]
         raw = double_batch_msm_native_helper(outerc1, window_size1, outerc2, window_size2, out_size1, in_size1,
-                                             out_size2, in_size2, len(sc), b1, b2, marshal_scalars(sc), 0)
+                                             out_size2, in_size2, len(sc), b1, b2, le32(sc), 0)
         for i in range(len(sc)):
             v = [_be64(raw[(9 * i + k) * 64:(9 * i + k + 1) * 64]) for k in range(9)]
             out.append(((v[0], v[1], v[2]), ((v[3], v[4]), (v[5], v[6]), (v[7], v[8]))))
@@ -141,7 +136,7 @@ def batch_field_msm_partition(base_element, indexed_scalars, task_id=0):
     """FixedBaseMSM.batchFieldMSMPartition (FixedBaseMSM.java:753-785): x_i * base in Fr for a partition's list of
     (index, x_i).  The native's input is the n scalars FOLLOWED BY THE BASE as element n (:765); its output n 64-byte
     big-endian values, which setBigInteger reduces mod r (bn254a/BN254aFields.java:52-54)."""
-    data = marshal_scalars([p[1] for p in indexed_scalars]) + big_integer_to_byte_array_cgbn(base_element)
+    data = le32([p[1] for p in indexed_scalars]) + le32([base_element])
     n = len(indexed_scalars)
     raw = field_batch_msm_native_helper(data, n, task_id)
     return [(indexed_scalars[i][0], _be64(raw[64 * i:64 * (i + 1)]) % FR_MODULUS) for i in range(n)]

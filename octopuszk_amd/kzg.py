@@ -36,8 +36,6 @@ multiply-accumulate kernel over points (ozk_points_mac_dev) and two group FFTs, 
 Out of scope: hiding commitments, different point sets per polynomial under one proof, degree-bound proofs, G2
 commitments, interoperability with other tools' byte formats.  There is no CPU path.
 """
-import ctypes
-import hashlib
 import secrets
 
 import torch
@@ -45,8 +43,13 @@ import torch
 from . import ceremony as _ceremony
 from . import codec as _codec
 from . import lib as _lib
+from . import transcript as _transcript
+from . import vectors as _vectors
+from . import wire as _wire
 from .device import VarMsmWorkspace, _ptr, _stream, prepare_bases
 from .fft import FR, root_of_unity
+from .vectors import ec_fft, fr_fft, fr_poly_eval, points_mac, points_mac_prepare, scale_points
+from .wire import ints32, le32, vp, wire_out_to_in
 
 G1, G2 = 1, 2
 OPENING_BYTES, VK_BYTES = 128, 160
@@ -93,19 +96,7 @@ def _scalars(values, k, what):
     values = [values] if isinstance(values, int) else list(values)
     if len(values) != k:
         raise ValueError("%d %s for %d rows" % (len(values), what, k))
-    return [_ceremony._scalar(v, what) for v in values]
-
-
-def _le(values) -> bytes:
-    return b"".join(int(v).to_bytes(32, "little") for v in values)
-
-
-def _ints(b: bytes):
-    return [int.from_bytes(b[i:i + 32], "little") for i in range(0, len(b), 32)]
-
-
-def _vp(b: bytes):
-    return ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p)
+    return [_wire.scalar_in_range(v, what) for v in values]
 
 
 def _enc_of(b, what, size=32) -> bytes:
@@ -121,10 +112,10 @@ class Opening:
 
     def __init__(self, c, z, y, pi):
         self.c, self.pi = _enc_of(c, "opening: C"), _enc_of(pi, "opening: pi")
-        self.z, self.y = _ceremony._scalar(z, "opening: z"), _ceremony._scalar(y, "opening: y")
+        self.z, self.y = _wire.scalar_in_range(z, "opening: z"), _wire.scalar_in_range(y, "opening: y")
 
     def to_bytes(self) -> bytes:
-        return self.c + _le([self.z, self.y]) + self.pi
+        return self.c + le32([self.z, self.y]) + self.pi
 
     @staticmethod
     def from_bytes(b) -> "Opening":
@@ -133,24 +124,16 @@ class Opening:
         b = bytes(b)
         if len(b) != OPENING_BYTES:
             raise ValueError("opening: length %d, not %d" % (len(b), OPENING_BYTES))
-        z, y = _ints(b[32:96])
+        z, y = ints32(b[32:96])
         for name, v in (("z", z), ("y", y)):
             if v >= FR:
                 raise ValueError("opening: %s is not below r" % name)
-        _require_points((("C", b[:32], G1), ("pi", b[96:], G1)), "opening")
+        _codec.require_points((("C", b[:32], G1), ("pi", b[96:], G1)), "opening")
         return Opening(b[:32], z, y, b[96:])
 
 
-def _require_points(fields, owner):
-    for name, enc, type_ in fields:
-        code = _ceremony._decode_code(enc, type_)
-        if code:
-            raise ValueError("%s: %s does not decode: code %d (%s)" % (owner, name, code, _codec.CODE_NAMES.get(code, "?")))
-
-
 def _g2_in_subgroup(points, encodings: bytes) -> bool:
-    from .srs import _in_subgroup
-    return _in_subgroup(points, encodings)
+    return _vectors.in_subgroup_g2(points, encodings)
 
 
 class VerifyKey:
@@ -178,7 +161,7 @@ class VerifyKey:
         if len(b) != VK_BYTES:
             raise ValueError("verification key: length %d, not %d" % (len(b), VK_BYTES))
         fields = (("g1", b[:32], G1), ("g2", b[32:96], G2), ("tau_g2", b[96:], G2))
-        _require_points(fields, "verification key")
+        _codec.require_points(fields, "verification key")
         for name, enc, _ in fields:
             if enc[-1] & 0x40:
                 raise ValueError("verification key: %s is the point at infinity" % name)
@@ -191,9 +174,8 @@ class VerifyKey:
     def points(self):
         """(g1: one wire-in point, g2 | tau_g2: two wire-in points) on the device, decoded once"""
         if self._points is None:
-            from .zksnark import _dev_bytes
-            p1, c1 = _codec.decompress_g1(_dev_bytes(self.g1))
-            p2, c2 = _codec.decompress_g2(_dev_bytes(self.g2 + self.tau_g2))
+            p1, c1 = _codec.decompress_g1(_wire.dev_bytes(self.g1))
+            p2, c2 = _codec.decompress_g2(_wire.dev_bytes(self.g2 + self.tau_g2))
             if int(c1.any().item()) or int(c2.any().item()):
                 raise ValueError("verification key: a point does not decode")
             self._points = (p1, p2)
@@ -230,12 +212,11 @@ class CommitKey:
         """prepared bases of L_i(tau) g1, i < n, for the domain of omega_n: the inverse group transform of tau_g1[:n]"""
         n = _eval_size(int(n), self.m)
         if n not in self._lagrange:
-            from .srs import ec_fft
             pts = ec_fft(self._tau_g1[:96 * n].contiguous(), G1, root_of_unity(n), inverse=True)
             self._lagrange[n] = prepare_bases(pts, n, G1)
         return self._lagrange[n]
 
-    def _msms(self, bases, n, scalars, k, stride):
+    def _row_msms(self, bases, n, scalars, k, stride):
         """k MSMs of n scalars each (row y at element y stride of `scalars`) over prepared bases -> k x 32 bytes"""
         if n not in self._msm:
             self._msm[n] = VarMsmWorkspace(n, G1)
@@ -245,27 +226,27 @@ class CommitKey:
         for y in range(k):
             row = flat[32 * y * stride:32 * (y * stride + n)] if flat is not None else scalars[y].contiguous()
             outs.append(ws.run(bases, row, prepared=True).clone())
-        return _ceremony._bytes(_codec.compress_g1(torch.cat(outs), "wire_out"))
+        return _wire.host_bytes(_codec.compress_g1(torch.cat(outs), "wire_out"))
 
     # ---- commit
     def commit(self, coeffs) -> list:
         """K rows of n coefficients -> K compressed commitments (one MSM per row)"""
         k, _, stride = _rows(coeffs, "coeffs", self.n)
-        enc = self._msms(self.bases(), self.n, _as2d(coeffs), k, stride)
+        enc = self._row_msms(self.bases(), self.n, _as2d(coeffs), k, stride)
         return [enc[32 * i:32 * i + 32] for i in range(k)]
 
     def commit_evals(self, evals) -> list:
         """K rows of evaluations on the domain of omega_n -> the commitments of their interpolants"""
         k, n, stride = _rows(evals, "evals")
         _eval_size(n, self.m)
-        enc = self._msms(self.lagrange(n), n, _as2d(evals), k, stride)
+        enc = self._row_msms(self.lagrange(n), n, _as2d(evals), k, stride)
         return [enc[32 * i:32 * i + 32] for i in range(k)]
 
     # ---- open
     def _openings(self, commitments, zs, quot, n, bases, values):
         k = len(zs)
-        pis = self._msms(bases, n, quot, k, n)
-        ys = _ints(_ceremony._bytes(values))
+        pis = self._row_msms(bases, n, quot, k, n)
+        ys = ints32(_wire.host_bytes(values))
         return [Opening(commitments[i], zs[i], ys[i], pis[32 * i:32 * i + 32]) for i in range(k)]
 
     def open(self, coeffs, z) -> list:
@@ -296,24 +277,23 @@ class CommitKey:
     def open_combined(self, coeffs, z):
         """K polynomials at ONE point with one proof: (the K commitments, the K values, pi).  The rows are combined
         with the weights gamma^i (combine_challenge) by ozk_fr_rows_combine_dev and the combination is opened at z."""
-        from .bace import fr_poly_eval
         k, _, stride = _rows(coeffs, "coeffs", self.n)
-        z = _ceremony._scalar(z, "the point")
+        z = _wire.scalar_in_range(z, "the point")
         rows = _as2d(coeffs)
         if k > 1 and stride != self.n:
             rows = rows.contiguous()
         commitments = self.commit(coeffs)
-        values = _ints(_ceremony._bytes(fr_poly_eval(rows.reshape(-1), z, k)))
+        values = ints32(_wire.host_bytes(fr_poly_eval(rows.reshape(-1), z, k)))
         gamma = combine_challenge(z, commitments, values)
         combined = rows_combine(rows, k, self.n, self.n, [pow(gamma, i, FR) for i in range(k)])
         quot, _ = poly_open(combined.unsqueeze(0), 1, self.n, self.n, [z])
-        return commitments, values, self._msms(self.bases(), self.n, quot, 1, self.n)
+        return commitments, values, self._row_msms(self.bases(), self.n, quot, 1, self.n)
 
     # ---- open at a set of points with one proof (DESIGN.md section 23)
     def _set_openings(self, commitments, sets, quot, n, bases, values):
         k, t = len(sets), len(sets[0])
-        pis = self._msms(bases, n, quot, k, n)
-        ys = _ints(_ceremony._bytes(values))
+        pis = self._row_msms(bases, n, quot, k, n)
+        ys = ints32(_wire.host_bytes(values))
         return [SetOpening(commitments[i], sets[i], ys[t * i:t * (i + 1)], pis[32 * i:32 * i + 32]) for i in range(k)]
 
     def open_set(self, coeffs, points) -> list:
@@ -341,19 +321,18 @@ class CommitKey:
     def open_set_combined(self, coeffs, points):
         """K polynomials at ONE shared set with one proof: (the K commitments, the K rows of t values, pi).  The rows
         are combined with the weights gamma^i (set_combine_challenge) and the combination is opened at the set."""
-        from .bace import fr_poly_eval
         k, _, stride = _rows(coeffs, "coeffs", self.n)
         points = _point_sets(points, 1, min(SET_T_MAX, self.m - 1), "the string has m = %d" % self.m, shared=True)[0]
         rows = _as2d(coeffs)
         if k > 1 and stride != self.n:
             rows = rows.contiguous()
         commitments = self.commit(coeffs)
-        at = [_ints(_ceremony._bytes(fr_poly_eval(rows.reshape(-1), z, k))) for z in points]
+        at = [ints32(_wire.host_bytes(fr_poly_eval(rows.reshape(-1), z, k))) for z in points]
         values = [[col[i] for col in at] for i in range(k)]
         gamma = set_combine_challenge(points, commitments, values)
         combined = rows_combine(rows, k, self.n, self.n, [pow(gamma, i, FR) for i in range(k)])
         quot, _ = poly_open_set(combined.unsqueeze(0), 1, self.n, self.n, [points])
-        return commitments, values, self._msms(self.bases(), self.n, quot, 1, self.n)
+        return commitments, values, self._row_msms(self.bases(), self.n, quot, 1, self.n)
 
 
 def _as2d(t):
@@ -364,13 +343,12 @@ def _as2d(t):
 def poly_open(coeffs, k, n, stride, zs):
     """ozk_fr_poly_open_dev on k rows (stride 0: one row at k points): (quotient rows [k, 32 n], values [32 k]) on the
     device.  Synchronises (the workspace dies here)."""
-    from .zksnark import _dev_bytes
     L = _lib.load()
     quot = torch.empty((k, 32 * n), dtype=torch.uint8, device=coeffs.device)
     values = torch.empty(32 * k, dtype=torch.uint8, device=coeffs.device)
     wsb = int(L.ozk_fr_poly_open_workspace_bytes(k, n))
     ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=coeffs.device)
-    pts = _dev_bytes(_le(zs))
+    pts = _wire.dev_bytes(le32(zs))
     _lib.check(L.ozk_fr_poly_open_dev(_ptr(coeffs), k, n, stride, _ptr(pts), _ptr(quot), n, _ptr(values), _ptr(ws),
                                       ws.numel(), _stream()))
     torch.cuda.current_stream().synchronize()
@@ -379,14 +357,13 @@ def poly_open(coeffs, k, n, stride, zs):
 
 def evals_open(evals, k, n, stride, zs):
     """ozk_fr_evals_open_dev on k evaluation rows over the domain of omega_n: (quotient rows, values) on the device"""
-    from .zksnark import _dev_bytes
     L = _lib.load()
     quot = torch.empty((k, 32 * n), dtype=torch.uint8, device=evals.device)
     values = torch.empty(32 * k, dtype=torch.uint8, device=evals.device)
     wsb = int(L.ozk_fr_evals_open_workspace_bytes(k, n))
     ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=evals.device)
-    pts = _dev_bytes(_le(zs))
-    _lib.check(L.ozk_fr_evals_open_dev(_ptr(evals), k, n, stride, _vp(_le([root_of_unity(n)])), _ptr(pts), _ptr(quot), n,
+    pts = _wire.dev_bytes(le32(zs))
+    _lib.check(L.ozk_fr_evals_open_dev(_ptr(evals), k, n, stride, vp(le32([root_of_unity(n)])), _ptr(pts), _ptr(quot), n,
                                        _ptr(values), _ptr(ws), ws.numel(), _stream()))
     torch.cuda.current_stream().synchronize()
     return quot, values
@@ -394,10 +371,9 @@ def evals_open(evals, k, n, stride, zs):
 
 def rows_combine(rows, k, n, stride, weights):
     """sum_i w_i rows[i] as a new row of n elements (ozk_fr_rows_combine_dev)"""
-    from .zksnark import _dev_bytes
     L = _lib.load()
     out = torch.empty(32 * n, dtype=torch.uint8, device=rows.device)
-    w = _dev_bytes(_le(weights))
+    w = _wire.dev_bytes(le32(weights))
     _lib.check(L.ozk_fr_rows_combine_dev(_ptr(rows), k, n, stride, _ptr(w), _ptr(out), _stream()))
     torch.cuda.current_stream().synchronize()
     return out
@@ -407,26 +383,23 @@ def rows_combine(rows, k, n, stride, weights):
 def combine_challenge(z, commitments, values) -> int:
     """gamma: the first 16 bytes, little-endian, of SHA-256("OZK-kzg-gamma" | K as 8 bytes LE | z | the K compressed
     commitments | the K values); 1 if they are zero"""
-    h = hashlib.sha256(_GAMMA_TAG + len(commitments).to_bytes(8, "little") + _le([z]) + b"".join(commitments)
-                       + _le(values)).digest()
-    return int.from_bytes(h[:16], "little") or 1
+    return _transcript.challenge128(_GAMMA_TAG, len(commitments).to_bytes(8, "little"), le32([z]),
+                                    b"".join(commitments), le32(values))
 
 
 def _pairing_holds(lhs_out, neg_weight_pi, pi_is_inf, vk) -> bool:
     """e(lhs, g2) e(-P, tau_g2) = 1 for lhs (wire-out) and P (wire-in, to be negated).  The pairing kernels take O as
     the affine (0, 1), which is no neutral element, so a pair whose G1 point is O is left out here: its factor is 1."""
-    from .zksnark import wire_out_to_in
-    lhs_inf = _ceremony._is_inf_out(lhs_out)
+    lhs_inf = _wire.is_inf_out(lhs_out)
     if lhs_inf or pi_is_inf:
         return lhs_inf and pi_is_inf      # one factor alone is e(X, Q) with X != O: not 1
-    neg = _ceremony.scale_points(neg_weight_pi, FR - 1, G1)
-    return _ceremony._pairs_are_one(torch.cat([wire_out_to_in(lhs_out, G1), neg]), vk.points()[1])
+    neg = scale_points(neg_weight_pi, FR - 1, G1)
+    return _vectors.pairs_are_one(torch.cat([wire_out_to_in(lhs_out, G1), neg]), vk.points()[1])
 
 
 def _decoded(encs):
     """the wire-in points of compressed G1 encodings, or None when one does not decode"""
-    from .zksnark import _dev_bytes
-    pts, codes = _codec.decompress_g1(_dev_bytes(b"".join(encs)))
+    pts, codes = _codec.decompress_g1(_wire.dev_bytes(b"".join(encs)))
     return None if int(codes.any().item()) else pts
 
 
@@ -436,14 +409,15 @@ def verify(vk, opening) -> bool:
     pts = _decoded([o.c, o.pi])
     if pts is None:
         return False
-    lhs, ws = _ceremony._msm(torch.cat([pts[:96], vk.points()[0], pts[96:]]), _le([1, (FR - o.y) % FR, o.z]), 3)
+    lhs, ws = _vectors.msm(torch.cat([pts[:96], vk.points()[0], pts[96:]]),
+                           _wire.dev_bytes(le32([1, (FR - o.y) % FR, o.z])), 3)
     ok = _pairing_holds(lhs, pts[96:], o.pi == _G1_INF, vk)
     del ws
     return ok
 
 
 def verify_all(vk, openings, seed=None) -> bool:
-    """All K openings at once with weights rho_i in [1, 2^128) (the SHA-256 counter stream of ceremony.py under this
+    """All K openings at once with weights rho_i in [1, 2^128) (the SHA-256 counter stream of transcript.py under this
     module's tag; `seed` None draws 32 bytes from the system, a given seed is for tests only):
         e(sum rho_i (C_i - [y_i] g1 + [z_i] pi_i), g2) e(-sum rho_i pi_i, tau_g2) = 1
     as one MSM of 2 K + 1 points, one of K points and one pairing product."""
@@ -451,24 +425,17 @@ def verify_all(vk, openings, seed=None) -> bool:
     k = len(os_)
     if k == 0:
         return True
-    seed = secrets.token_bytes(32) if seed is None else _ceremony._seed_bytes(seed)
-    rho = _ints(_ceremony._weights(seed, k, _RHO_TAG))
+    seed = secrets.token_bytes(32) if seed is None else _transcript.seed_bytes(seed)
+    rho = ints32(_transcript.weights(seed, k, _RHO_TAG))
     pts = _decoded([o.c for o in os_] + [o.pi for o in os_])
     if pts is None:
         return False
     sc = rho + [r * o.z % FR for r, o in zip(rho, os_)] + [-sum(r * o.y for r, o in zip(rho, os_)) % FR]
-    lhs, ws1 = _msm(torch.cat([pts, vk.points()[0]]), _le(sc), 2 * k + 1)
-    ps, ws2 = _msm(pts[96 * k:], _le(rho), k)
-    from .zksnark import wire_out_to_in
-    ok = _pairing_holds(lhs, wire_out_to_in(ps, G1), _ceremony._is_inf_out(ps), vk)
+    lhs, ws1 = _vectors.msm(torch.cat([pts, vk.points()[0]]), _wire.dev_bytes(le32(sc)), 2 * k + 1)
+    ps, ws2 = _vectors.msm(pts[96 * k:], _wire.dev_bytes(le32(rho)), k)
+    ok = _pairing_holds(lhs, wire_out_to_in(ps, G1), _wire.is_inf_out(ps), vk)
     del ws1, ws2
     return ok
-
-
-def _msm(bases, scalar_bytes, n):
-    from .zksnark import _dev_bytes
-    ws = VarMsmWorkspace(n, G1)
-    return ws.run(bases.contiguous(), _dev_bytes(scalar_bytes)), ws
 
 
 def verify_each(vk, openings, seed=None) -> list:
@@ -482,7 +449,7 @@ def verify_each(vk, openings, seed=None) -> list:
 def verify_combined(vk, commitments, z, values, pi) -> bool:
     """The proof of open_combined: sum gamma^i C_i opens to sum gamma^i y_i at z"""
     commitments = [_enc_of(c, "commitment") for c in commitments]
-    z = _ceremony._scalar(z, "the point")
+    z = _wire.scalar_in_range(z, "the point")
     values = _scalars(values, len(commitments), "values")
     pi = _enc_of(pi, "pi")
     if not commitments:
@@ -492,8 +459,8 @@ def verify_combined(vk, commitments, z, values, pi) -> bool:
     pts = _decoded(commitments)
     if pts is None:
         return False
-    c, ws = _msm(pts, _le(pw), len(commitments))
-    c_enc = _ceremony._bytes(_codec.compress_g1(c, "wire_out"))
+    c, ws = _vectors.msm(pts, _wire.dev_bytes(le32(pw)), len(commitments))
+    c_enc = _wire.host_bytes(_codec.compress_g1(c, "wire_out"))
     del ws
     return verify(vk, Opening(c_enc, z, sum(w * y for w, y in zip(pw, values)) % FR, pi))
 
@@ -518,7 +485,7 @@ def _point_sets(points, k, t_max, why, shared=False):
         raise ValueError("ragged lists of points: every row takes the same number t")
     if not 1 <= t <= t_max:
         raise ValueError("t = %d points: 1 <= t <= %d here (%s)" % (t, t_max, why))
-    sets = [tuple(_ceremony._scalar(z, "a point") for z in row) for row in sets]
+    sets = [tuple(_wire.scalar_in_range(z, "a point") for z in row) for row in sets]
     for row in sets:
         if len(set(row)) != t:
             raise ValueError("repeated points in a set: %s" % (row,))
@@ -559,8 +526,8 @@ class SetOpening:
 
     def __init__(self, c, points, values, pi):
         self.c, self.pi = _enc_of(c, "set opening: C"), _enc_of(pi, "set opening: pi")
-        self.points = tuple(_ceremony._scalar(z, "set opening: z") for z in points)
-        self.values = tuple(_ceremony._scalar(y, "set opening: y") for y in values)
+        self.points = tuple(_wire.scalar_in_range(z, "set opening: z") for z in points)
+        self.values = tuple(_wire.scalar_in_range(y, "set opening: y") for y in values)
         if not 1 <= len(self.points) <= SET_T_MAX:
             raise ValueError("set opening: t = %d, not in [1, %d]" % (len(self.points), SET_T_MAX))
         if len(self.values) != len(self.points):
@@ -573,7 +540,7 @@ class SetOpening:
         return len(self.points)
 
     def to_bytes(self) -> bytes:
-        return self.c + self.t.to_bytes(4, "little") + _le(self.points) + _le(self.values) + self.pi
+        return self.c + self.t.to_bytes(4, "little") + le32(self.points) + le32(self.values) + self.pi
 
     @staticmethod
     def from_bytes(b) -> "SetOpening":
@@ -587,13 +554,13 @@ class SetOpening:
             raise ValueError("set opening: t = %d, not in [1, %d]" % (t, SET_T_MAX))
         if len(b) != 68 + 64 * t:
             raise ValueError("set opening: length %d, not %d for t = %d" % (len(b), 68 + 64 * t, t))
-        zs, ys = _ints(b[36:36 + 32 * t]), _ints(b[36 + 32 * t:36 + 64 * t])
+        zs, ys = ints32(b[36:36 + 32 * t]), ints32(b[36 + 32 * t:36 + 64 * t])
         for name, vs in (("z", zs), ("y", ys)):
             if any(v >= FR for v in vs):
                 raise ValueError("set opening: %s is not below r" % name)
         if len(set(zs)) != t:
             raise ValueError("set opening: z has repeated points")
-        _require_points((("C", b[:32], G1), ("pi", b[-32:], G1)), "set opening")
+        _codec.require_points((("C", b[:32], G1), ("pi", b[-32:], G1)), "set opening")
         return SetOpening(b[:32], zs, ys, b[-32:])
 
 
@@ -639,7 +606,7 @@ class SetVerifyKey:
         g1s, g2s = b[4:4 + 32 * t_max], b[4 + 32 * t_max:]
         fields = [("tau_g1[%d]" % i, g1s[32 * i:32 * i + 32], G1) for i in range(t_max)]
         fields += [("tau_g2[%d]" % i, g2s[64 * i:64 * i + 64], G2) for i in range(t_max + 1)]
-        _require_points(fields, "set verification key")
+        _codec.require_points(fields, "set verification key")
         for name, enc, _ in fields:
             if enc[-1] & 0x40:
                 raise ValueError("set verification key: %s is the point at infinity" % name)
@@ -652,9 +619,8 @@ class SetVerifyKey:
     def points(self):
         """(tau_g1[:t_max], tau_g2[:t_max + 1]) as wire-in points on the device, decoded once"""
         if self._points is None:
-            from .zksnark import _dev_bytes
-            p1, c1 = _codec.decompress_g1(_dev_bytes(self.g1s))
-            p2, c2 = _codec.decompress_g2(_dev_bytes(self.g2s))
+            p1, c1 = _codec.decompress_g1(_wire.dev_bytes(self.g1s))
+            p2, c2 = _codec.decompress_g2(_wire.dev_bytes(self.g2s))
             if int(c1.any().item()) or int(c2.any().item()):
                 raise ValueError("set verification key: a point does not decode")
             self._points = (p1, p2)
@@ -670,8 +636,8 @@ def poly_open_set(coeffs, k, n, stride, sets):
     values = torch.empty(32 * k * t, dtype=torch.uint8, device=coeffs.device)
     wsb = int(L.ozk_fr_poly_open_set_workspace_bytes(k, n, t))
     ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=coeffs.device)
-    pts = _le([z for row in sets for z in row])
-    _lib.check(L.ozk_fr_poly_open_set_dev(_ptr(coeffs), k, n, stride, t, _vp(pts), _ptr(quot), n, _ptr(values), _ptr(ws),
+    pts = le32([z for row in sets for z in row])
+    _lib.check(L.ozk_fr_poly_open_set_dev(_ptr(coeffs), k, n, stride, t, vp(pts), _ptr(quot), n, _ptr(values), _ptr(ws),
                                           ws.numel(), _stream()))
     torch.cuda.current_stream().synchronize()
     return quot, values
@@ -685,8 +651,8 @@ def evals_open_set(evals, k, n, stride, sets):
     values = torch.empty(32 * k * t, dtype=torch.uint8, device=evals.device)
     wsb = int(L.ozk_fr_evals_open_set_workspace_bytes(k, n, t))
     ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=evals.device)
-    pts = _le([z for row in sets for z in row])
-    _lib.check(L.ozk_fr_evals_open_set_dev(_ptr(evals), k, n, stride, _vp(_le([root_of_unity(n)])), t, _vp(pts),
+    pts = le32([z for row in sets for z in row])
+    _lib.check(L.ozk_fr_evals_open_set_dev(_ptr(evals), k, n, stride, vp(le32([root_of_unity(n)])), t, vp(pts),
                                            _ptr(quot), n, _ptr(values), _ptr(ws), ws.numel(), _stream()))
     torch.cuda.current_stream().synchronize()
     return quot, values
@@ -695,9 +661,9 @@ def evals_open_set(evals, k, n, stride, sets):
 def set_combine_challenge(points, commitments, values) -> int:
     """gamma: the first 16 bytes, little-endian, of SHA-256("OZK-kzg-set-gamma" | K as 8 bytes LE | t as 8 bytes LE | the
     t points | the K compressed commitments | the K rows of t values); 1 if they are zero"""
-    h = hashlib.sha256(_SET_GAMMA_TAG + len(commitments).to_bytes(8, "little") + len(points).to_bytes(8, "little")
-                       + _le(points) + b"".join(commitments) + _le([v for row in values for v in row])).digest()
-    return int.from_bytes(h[:16], "little") or 1
+    return _transcript.challenge128(_SET_GAMMA_TAG, len(commitments).to_bytes(8, "little"),
+                                    len(points).to_bytes(8, "little"), le32(points), b"".join(commitments),
+                                    le32([v for row in values for v in row]))
 
 
 def _set_opening(vk, o):
@@ -707,14 +673,6 @@ def _set_opening(vk, o):
     return o
 
 
-def _g2_msm(bases, scalars, n):
-    """(sum s_i Q_i as a wire-in G2 point, whether it is O, the workspace)"""
-    from .srs import _msm as _msm_typed
-    from .zksnark import _dev_bytes, wire_out_to_in
-    out, ws = _msm_typed(bases, _dev_bytes(_le(scalars)), n, G2)
-    return wire_out_to_in(out, G2), not bool(out.view(6, 64)[4:].any().item()), ws
-
-
 def _pairs_hold(pairs) -> bool:
     """prod e(P_i, Q_i) = 1 over (P wire-in G1, whether P is O, Q wire-in G2); a pair whose G1 point is O is left out
     (_pairing_holds: the kernels take O as an affine point, which is no neutral element), and one pair alone is
@@ -722,7 +680,7 @@ def _pairs_hold(pairs) -> bool:
     live = [(p, q) for p, inf, q in pairs if not inf]
     if len(live) < 2:
         return not live
-    return _ceremony._pairs_are_one(torch.cat([p for p, _ in live]), torch.cat([q for _, q in live]))
+    return _vectors.pairs_are_one(torch.cat([p for p, _ in live]), torch.cat([q for _, q in live]))
 
 
 def verify_set(vk, opening) -> bool:
@@ -734,7 +692,7 @@ def verify_set(vk, opening) -> bool:
 
 
 def verify_set_all(vk, openings, seed=None) -> bool:
-    """All K openings at once with weights rho_i in [1, 2^128) (the stream of ceremony.py under this module's set tag;
+    """All K openings at once with weights rho_i in [1, 2^128) (the stream of transcript.py under this module's set tag;
     `seed` as verify_all).  Openings are grouped by identical point tuple D:
         e(sum rho_i (C_i - [I_i(tau)] g1), g2) prod_D e(-sum_{i in D} rho_i pi_i, [Z_D(tau)] g2) = 1
     as one G1 MSM of K + t points, one of |D| points and one G2 MSM of t + 1 points per distinct set, and one pairing
@@ -742,13 +700,12 @@ def verify_set_all(vk, openings, seed=None) -> bool:
     os_ = [_set_opening(vk, o) for o in openings]
     if not os_:
         return True
-    seed = secrets.token_bytes(32) if seed is None else _ceremony._seed_bytes(seed)
-    return _verify_sets(vk, os_, _ints(_ceremony._weights(seed, len(os_), _SET_RHO_TAG)))
+    seed = secrets.token_bytes(32) if seed is None else _transcript.seed_bytes(seed)
+    return _verify_sets(vk, os_, ints32(_transcript.weights(seed, len(os_), _SET_RHO_TAG)))
 
 
 def _verify_sets(vk, os_, rho) -> bool:
     """the equation of verify_set_all over parsed openings with the weights rho"""
-    from .zksnark import wire_out_to_in
     k = len(os_)
     pts = _decoded([o.c for o in os_] + [o.pi for o in os_])
     if pts is None:
@@ -765,20 +722,22 @@ def _verify_sets(vk, os_, rho) -> bool:
         for j, c in enumerate(_interpolant(points, ys)):
             minus_i[j] = (minus_i[j] - c) % FR
     keep = []
-    lhs, ws = _msm(torch.cat([pts[:96 * k], g1s[:96 * t_top]]), _le(rho + minus_i), k + t_top)
+    lhs, ws = _vectors.msm(torch.cat([pts[:96 * k], g1s[:96 * t_top]]), _wire.dev_bytes(le32(rho + minus_i)),
+                           k + t_top)
     keep.append(ws)
-    pairs = [(wire_out_to_in(lhs, G1), _ceremony._is_inf_out(lhs), g2s[:192])]
+    pairs = [(wire_out_to_in(lhs, G1), _wire.is_inf_out(lhs), g2s[:192])]
     for points, members in groups.items():
-        zq, zq_inf, ws = _g2_msm(g2s[:192 * (len(points) + 1)], _vanishing(points), len(points) + 1)
+        zq, ws = _vectors.msm(g2s[:192 * (len(points) + 1)], _wire.dev_bytes(le32(_vanishing(points))),
+                              len(points) + 1, G2)
         keep.append(ws)
-        if zq_inf:
+        if _wire.is_inf_out(zq, G2):
             return False
-        ps, ws = _msm(torch.cat([pts[96 * (k + i):96 * (k + i + 1)] for i in members]), _le([rho[i] for i in members]),
-                      len(members))
+        ps, ws = _vectors.msm(torch.cat([pts[96 * (k + i):96 * (k + i + 1)] for i in members]),
+                              _wire.dev_bytes(le32([rho[i] for i in members])), len(members))
         keep.append(ws)
-        inf = _ceremony._is_inf_out(ps)
-        neg = None if inf else _ceremony.scale_points(wire_out_to_in(ps, G1), FR - 1, G1)
-        pairs.append((neg, inf, zq))
+        inf = _wire.is_inf_out(ps)
+        neg = None if inf else scale_points(wire_out_to_in(ps, G1), FR - 1, G1)
+        pairs.append((neg, inf, wire_out_to_in(zq, G2)))
     ok = _pairs_hold(pairs)
     torch.cuda.current_stream().synchronize()
     del keep
@@ -809,8 +768,8 @@ def verify_set_combined(vk, commitments, points, values, pi) -> bool:
     pts = _decoded(commitments)
     if pts is None:
         return False
-    c, ws = _msm(pts, _le(pw), len(commitments))
-    c_enc = _ceremony._bytes(_codec.compress_g1(c, "wire_out"))
+    c, ws = _vectors.msm(pts, _wire.dev_bytes(le32(pw)), len(commitments))
+    c_enc = _wire.host_bytes(_codec.compress_g1(c, "wire_out"))
     del ws
     ys = [sum(w * row[j] for w, row in zip(pw, values)) % FR for j in range(len(points))]
     return verify_set(vk, SetOpening(c_enc, points, ys, pi))
@@ -820,53 +779,6 @@ def verify_set_combined(vk, commitments, points, values, pi) -> bool:
 ALL_COSETS = (1, 2, 4, 8, 16, 32)     # coset sizes l: up to the t of a set opening (SET_T_MAX)
 ALL_MAX_TRANSFORM = 1 << 22           # the largest group FFT (ozk_ec_fft_dev); the construction runs one of 2 n / l
 _G1_INF_WIRE = bytes(32) + (1).to_bytes(32, "little") + bytes(32)
-
-
-def points_mac_prepare(points, terms, n):
-    """terms x n wire-in G1 points, term-major -> the prepared table of ozk_points_mac_dev (ozk_points_mac_prepare_dev).
-    Asynchronous on the current stream."""
-    L = _lib.load()
-    points = points.contiguous()
-    if _codec._count(points, 96, "points") != terms * n:
-        raise ValueError("%d x %d points need %d bytes, not %d" % (terms, n, 96 * terms * n, points.numel()))
-    nbytes = int(L.ozk_points_mac_prepared_bytes(terms, n, G1))
-    table = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=points.device)
-    _lib.check(L.ozk_points_mac_prepare_dev(_ptr(points), terms, n, G1, _ptr(table), table.numel(), _stream()))
-    return table
-
-
-def points_mac(table, scalars, terms, n, codes=False, workspace=None):
-    """out[i] = sum_v [k_v[i]] P_v[i] over a prepared table and terms x n scalars (32 bytes little-endian, term-major,
-    on the device): n wire-in points, Z = 1 (ozk_points_mac_dev); codes=True returns (points, n int32 codes), 1 for a
-    lane with a scalar >= r.  Asynchronous on the current stream when the caller passes (and keeps) the workspace,
-    else it synchronises: the workspace dies here."""
-    L = _lib.load()
-    scalars = scalars.contiguous()
-    if scalars.numel() != 32 * terms * n:
-        raise ValueError("%d x %d scalars need %d bytes, not %d" % (terms, n, 32 * terms * n, scalars.numel()))
-    out = torch.empty(96 * n, dtype=torch.uint8, device=scalars.device)
-    d_codes = torch.empty(n, dtype=torch.int32, device=scalars.device) if codes else None
-    ws = workspace
-    if ws is None:
-        ws = torch.empty(max(int(L.ozk_points_mac_workspace_bytes(terms, n, G1)), 256), dtype=torch.uint8,
-                         device=scalars.device)
-    _lib.check(L.ozk_points_mac_dev(_ptr(table), _ptr(scalars), terms, n, G1, _ptr(out),
-                                    None if d_codes is None else _ptr(d_codes), _ptr(ws), ws.numel(), _stream()))
-    if workspace is None:
-        torch.cuda.current_stream().synchronize()
-    return (out, d_codes) if codes else out
-
-
-def fr_fft(values, n, omega, out=None):
-    """The transform of n = 2^k elements of Fr (32 bytes little-endian each) on the device: out[j] = sum_i
-    omega^(i j) in[i], canonical (ozk_fft_compact_dev).  Synchronises (the workspace dies here)."""
-    L = _lib.load()
-    if out is None:
-        out = torch.empty(32 * n, dtype=torch.uint8, device=values.device)
-    ws = torch.empty(max(int(L.ozk_fft_workspace_bytes(n)), 256), dtype=torch.uint8, device=values.device)
-    _lib.check(L.ozk_fft_compact_dev(_ptr(values), n, _vp(_le([omega])), _ptr(out), _ptr(ws), ws.numel(), _stream()))
-    torch.cuda.current_stream().synchronize()
-    return out
 
 
 class AllOpenings:
@@ -885,7 +797,7 @@ class AllOpenings:
         if not 0 <= k < self.cosets:
             raise ValueError("coset %d: there are %d" % (k, self.cosets))
         if self._host is None:
-            self._host = (_ints(_ceremony._bytes(self.values)), _ceremony._bytes(self.proofs))
+            self._host = (ints32(_wire.host_bytes(self.values)), _wire.host_bytes(self.proofs))
         ys, pis = self._host
         omega, pi = root_of_unity(self.n), pis[32 * k:32 * k + 32]
         if self.coset == 1:
@@ -922,7 +834,6 @@ class OpenAllKey:
     def tables(self):
         """the prepared tables, l x 2r points (None for r = 1: the one proof is O)"""
         if self._tables is None and self.cosets > 1:
-            from .srs import ec_fft
             l, r = self.coset, self.cosets
             powers = self._tau_g1[:96 * self.n].view(r, l, 96)              # power l i + v at [i, v]
             inf = torch.frombuffer(bytearray(_G1_INF_WIRE), dtype=torch.uint8).to(powers.device)
@@ -955,12 +866,10 @@ class OpenAllKey:
 
     def upper_half(self, u):
         """H = the upper half of the inverse group FFT of U (its last element is O by construction)"""
-        from .srs import ec_fft
         return ec_fft(u, G1, root_of_unity(2 * self.cosets), inverse=True)[96 * self.cosets:].contiguous()
 
     def proofs_of(self, h):
         """(pi_0 .. pi_{r-1}) = ECFFT_r(H) with the root omega^l, as wire-in points"""
-        from .srs import ec_fft
         return ec_fft(h, G1, root_of_unity(self.cosets))
 
     def open_all(self, coeffs) -> list:

@@ -10,17 +10,10 @@ import ctypes
 import torch
 
 from . import lib as _lib
+from . import wire as _wire
 from .device import _ptr, _stream
 
 G1_BYTES, G2_BYTES, GT_BYTES = 96, 192, 384
-
-
-def _count(t, rec, what):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8):
-        raise TypeError("%s must be a uint8 CUDA tensor" % what)
-    if t.numel() == 0 or t.numel() % rec:
-        raise ValueError("%s: %d bytes are not a whole number of %d-byte records" % (what, t.numel(), rec))
-    return t.numel() // rec
 
 
 class PreparedG2:
@@ -29,7 +22,7 @@ class PreparedG2:
     def __init__(self, q_batch):
         L = _lib.load()
         q_batch = q_batch.contiguous()
-        self.n = _count(q_batch, G2_BYTES, "Q")
+        self.n = _wire.count(q_batch, G2_BYTES, "Q")
         self.bytes = int(L.ozk_pairing_g2_prepared_bytes(self.n))
         self.data = torch.empty(self.bytes, dtype=torch.uint8, device=q_batch.device)
         _lib.check(L.ozk_pairing_g2_prepare_dev(_ptr(q_batch), self.n, _ptr(self.data), self.bytes, _stream()))
@@ -45,13 +38,13 @@ def reduced_pairing(p_batch, q_batch) -> torch.Tensor:
     current stream; returns the n x 384-byte GT tensor."""
     L = _lib.load()
     p_batch = p_batch.contiguous()
-    n = _count(p_batch, G1_BYTES, "P")
+    n = _wire.count(p_batch, G1_BYTES, "P")
     if isinstance(q_batch, PreparedG2):
         prepared, q = 1, q_batch.data
         nq = q_batch.n
     else:
         prepared, q = 0, q_batch.contiguous()
-        nq = _count(q, G2_BYTES, "Q")
+        nq = _wire.count(q, G2_BYTES, "Q")
     if nq != n:
         raise ValueError("%d G1 points against %d G2 points" % (n, nq))
     out = torch.empty(n * GT_BYTES, dtype=torch.uint8, device=p_batch.device)
@@ -64,8 +57,8 @@ def groth16_verify(alpha_beta, gamma_prep: PreparedG2, delta_prep: PreparedG2, d
     k x 192-byte evaluationABC points, both in wire-out format; alpha_beta one GT value (384 B)."""
     L = _lib.load()
     d_proofs, d_abc = d_proofs.contiguous(), d_abc.contiguous()
-    k = _count(d_proofs, 768, "proofs")
-    if _count(d_abc, 192, "evaluationABC") != k:
+    k = _wire.count(d_proofs, 768, "proofs")
+    if _wire.count(d_abc, 192, "evaluationABC") != k:
         raise ValueError("one evaluationABC point per proof")
     if gamma_prep.n != 1 or delta_prep.n != 1 or alpha_beta.numel() != GT_BYTES:
         raise ValueError("one prepared gamma, one prepared delta and one GT value")
@@ -80,13 +73,13 @@ def pairing_product(p_batch, q_batch) -> torch.Tensor:
     Inputs as for reduced_pairing.  Asynchronous on the current stream."""
     L = _lib.load()
     p_batch = p_batch.contiguous()
-    n = _count(p_batch, G1_BYTES, "P")
+    n = _wire.count(p_batch, G1_BYTES, "P")
     if isinstance(q_batch, PreparedG2):
         prepared, q = 1, q_batch.data
         nq = q_batch.n
     else:
         prepared, q = 0, q_batch.contiguous()
-        nq = _count(q, G2_BYTES, "Q")
+        nq = _wire.count(q, G2_BYTES, "Q")
     if nq != n:
         raise ValueError("%d G1 points against %d G2 points" % (n, nq))
     out = torch.empty(GT_BYTES, dtype=torch.uint8, device=p_batch.device)
@@ -99,7 +92,7 @@ def gt_pow(gt_batch, exponents) -> torch.Tensor:
     list of ints or an n x 32-byte little-endian uint8 CUDA tensor.  Asynchronous on the current stream."""
     L = _lib.load()
     gt_batch = gt_batch.contiguous()
-    n = _count(gt_batch, GT_BYTES, "GT")
+    n = _wire.count(gt_batch, GT_BYTES, "GT")
     if not isinstance(exponents, torch.Tensor):
         exponents = list(exponents)
         if any(not 0 <= int(e) < 1 << 256 for e in exponents):
@@ -108,7 +101,7 @@ def gt_pow(gt_batch, exponents) -> torch.Tensor:
         exponents = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(gt_batch.device) if raw else \
             torch.empty(0, dtype=torch.uint8, device=gt_batch.device)
     exponents = exponents.contiguous()
-    if _count(exponents, 32, "exponents") != n:
+    if _wire.count(exponents, 32, "exponents") != n:
         raise ValueError("one exponent per GT value")
     out = torch.empty_like(gt_batch)
     _lib.check(L.ozk_gt_pow_dev(_ptr(gt_batch), _ptr(exponents), n, _ptr(out), _stream()))
@@ -120,7 +113,7 @@ def wellformed(d_proofs) -> torch.Tensor:
     A and C on the curve, B on the twist and in the order-r subgroup, no point at infinity.  Asynchronous."""
     L = _lib.load()
     d_proofs = d_proofs.contiguous()
-    k = _count(d_proofs, 768, "proofs")
+    k = _wire.count(d_proofs, 768, "proofs")
     flags = torch.empty(k, dtype=torch.int32, device=d_proofs.device)
     _lib.check(L.ozk_groth16_wellformed_dev(_ptr(d_proofs), k, _ptr(flags), _stream()))
     return flags
@@ -134,9 +127,9 @@ def groth16_verify_rlc(alpha_beta, gamma_prep: PreparedG2, delta_prep: PreparedG
     five stage times in ms (the call then waits for the stream)."""
     L = _lib.load()
     d_proofs, d_inputs, d_r = d_proofs.contiguous(), d_inputs.contiguous(), d_r.contiguous()
-    k = _count(d_proofs, 768, "proofs")
-    n = _count(gamma_abc, G1_BYTES, "gammaABC")
-    if _count(d_inputs, 32 * n, "inputs") != k or _count(d_r, 32, "weights") != k:
+    k = _wire.count(d_proofs, 768, "proofs")
+    n = _wire.count(gamma_abc, G1_BYTES, "gammaABC")
+    if _wire.count(d_inputs, 32 * n, "inputs") != k or _wire.count(d_r, 32, "weights") != k:
         raise ValueError("one row of %d inputs and one weight per proof" % n)
     if gamma_prep.n != 1 or delta_prep.n != 1 or alpha_beta.numel() != GT_BYTES:
         raise ValueError("one prepared gamma, one prepared delta and one GT value")

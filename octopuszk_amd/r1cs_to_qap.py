@@ -6,10 +6,7 @@ import ctypes
 
 from . import lib as _lib
 from .fft import FR, FR_MULT_GEN, root_of_unity
-
-
-def _le32(v: int) -> bytes:
-    return int(v % FR).to_bytes(32, "little")
+from .wire import le32, vp
 
 
 def qap_witness_native_helper(a_eval: bytes, b_eval: bytes, c_eval: bytes, m: int, omega: bytes, g: bytes,
@@ -18,9 +15,6 @@ def qap_witness_native_helper(a_eval: bytes, b_eval: bytes, c_eval: bytes, m: in
     (m + 1) x 32 B LE coefficients of H out."""
     L = _lib.load()
     out = ctypes.create_string_buffer(32 * (m + 1))
-
-    def vp(b):
-        return ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p)
 
     _lib.check(L.ozk_qap_witness_host(vp(a_eval), vp(b_eval), vp(c_eval), m, vp(omega), vp(g), task_id,
                                       ctypes.cast(out, ctypes.c_void_p)))
@@ -33,6 +27,6 @@ def coefficients_h(a_eval, b_eval, c_eval, g: int = FR_MULT_GEN, task_id: int = 
     including the extra input_i * 0 = 0 constraints); returns coefficientsH (domainSize + 1 ints)."""
     m = len(a_eval)
     assert m >= 2 and m & (m - 1) == 0 and len(b_eval) == m and len(c_eval) == m
-    raw = qap_witness_native_helper(b"".join(map(_le32, a_eval)), b"".join(map(_le32, b_eval)),
-                                    b"".join(map(_le32, c_eval)), m, _le32(root_of_unity(m)), _le32(g), task_id)
+    raw = qap_witness_native_helper(le32(v % FR for v in a_eval), le32(v % FR for v in b_eval),
+                                    le32(v % FR for v in c_eval), m, le32([root_of_unity(m)]), le32([g % FR]), task_id)
     return [int.from_bytes(raw[32 * i:32 * (i + 1)], "little") for i in range(m + 1)]

@@ -34,8 +34,14 @@ from . import ceremony as _ceremony
 from . import codec as _codec
 from . import keyfile as _keyfile
 from . import lib as _lib
-from .device import VarMsmWorkspace, _ptr, _stream
-from .fft import FR, root_of_unity
+from . import transcript as _transcript
+from . import vectors as _vectors
+from . import wire as _wire
+from . import zksnark as _zksnark
+from .device import _ptr, _stream
+from .fft import FR, SEED, fr_random, lowest_power_of_two, root_of_unity
+from .fixed_base_msm import G1_WINDOW_TABLE, G2_WINDOW_TABLE, get_window_size
+from .vectors import ec_fft, mul_points, points_add, scale_points, sparse_mat_points
 
 G1, G2 = 1, 2
 # phase-1 contributions
@@ -53,34 +59,9 @@ CHECKS = ("shape", "powers_g1", "powers_g2", "alpha_powers", "beta_powers", "bet
 _RHO_TAG = b"OZK-srs-rho"
 
 
-def _count(t, type_):
-    return t.numel() // (96 * type_)
-
-
 def _point(t, i, type_):
     n = 96 * type_
     return t.reshape(-1)[n * i:n * (i + 1)]
-
-
-def _weights(seed: bytes, n: int) -> bytes:
-    """n weights in [1, 2^128) as n x 32 bytes little-endian: the SHA-256 counter stream of ceremony.py under this
-    module's own tag"""
-    out = bytearray(32 * n)
-    pad = bytes(16)
-    one = (1).to_bytes(16, "little")
-    for j in range((n + 1) // 2):
-        block = hashlib.sha256(_RHO_TAG + seed + j.to_bytes(8, "little")).digest()
-        for half in (0, 1):
-            i = 2 * j + half
-            if i < n:
-                w = block[16 * half:16 * half + 16]
-                out[32 * i:32 * i + 32] = (w if w != pad else one) + pad
-    return bytes(out)
-
-
-def _msm(bases, d_scalars, n, type_):
-    ws = VarMsmWorkspace(n, type_)
-    return ws.run(bases.contiguous(), d_scalars), ws
 
 
 class Srs:
@@ -94,32 +75,30 @@ class Srs:
         """The string of KNOWN secrets tau, alpha, beta in [1, r), over generator * G1_ONE / G2_ONE (the generators of
         serial_setup_generate; default fr_random(SEED)).  For tests, tools and measurements only: whoever calls this
         knows the trapdoor of every key built from the result and can forge proofs for it."""
-        from . import zksnark as z
-        from .fixed_base_msm import G1_WINDOW_TABLE, G2_WINDOW_TABLE, get_window_size
         m = int(m)
         if m < 2 or m & (m - 1):
             raise ValueError("the domain size must be a power of two >= 2, not %d" % m)
-        tau, alpha, beta = (_ceremony._scalar(v, what, 1) for v, what in ((tau, "tau"), (alpha, "alpha"), (beta, "beta")))
-        rnd = z.fr_random(z.SEED) if generator is None else _ceremony._scalar(generator, "generator", 1)
+        tau, alpha, beta = (_wire.scalar_in_range(v, what, 1)
+                            for v, what in ((tau, "tau"), (alpha, "alpha"), (beta, "beta")))
+        rnd = fr_random(SEED) if generator is None else _wire.scalar_in_range(generator, "generator", 1)
         L = _lib.load()
-        gens = {G1: bytes(z.batch_msm_dev(254, 16, z.g1_wire(z.G1_ONE), [rnd], G1).cpu().numpy()),
-                G2: bytes(z.batch_msm_dev(254, 16, z.g2_wire(z.G2_ONE), [rnd], G2).cpu().numpy())}
+        gens = {G1: bytes(_zksnark.batch_msm_dev(254, 16, _wire.g1_wire(_zksnark.G1_ONE), [rnd], G1).cpu().numpy()),
+                G2: bytes(_zksnark.batch_msm_dev(254, 16, _wire.g2_wire(_zksnark.G2_ONE), [rnd], G2).cpu().numpy())}
 
         def powers(k, n, type_):
             d_sc = torch.empty(n * 32, dtype=torch.uint8, device="cuda")
             wsb = int(L.ozk_fr_powers_workspace_bytes(n))
             ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
-            tb, kb = z._le32_one(tau), z._le32_one(k)
-            _lib.check(L.ozk_fr_powers_dev(ctypes.cast(tb, ctypes.c_void_p), ctypes.cast(kb, ctypes.c_void_p), n,
-                                           _ptr(d_sc), _ptr(ws), wsb, _stream()))
+            tb, kb = _wire.le32([tau]), _wire.le32([k])
+            _lib.check(L.ozk_fr_powers_dev(_wire.vp(tb), _wire.vp(kb), n, _ptr(d_sc), _ptr(ws), wsb, _stream()))
             torch.cuda.current_stream().synchronize()
             window = get_window_size(n, G1_WINDOW_TABLE if type_ == G1 else G2_WINDOW_TABLE)
-            bits = z._bit_size(gens[type_])
+            bits = _zksnark._bit_size(gens[type_])
             if -(-bits // window) * window < 254:     # a few points take window 1: the plan must still cover a scalar
                 bits = 254
-            return z.batch_msm_dev(bits, window, gens[type_], d_sc, type_)
+            return _zksnark.batch_msm_dev(bits, window, gens[type_], d_sc, type_)
 
-        beta_g2 = z.batch_msm_dev(z._bit_size(gens[G2]), 16, gens[G2], [beta], G2)
+        beta_g2 = _zksnark.batch_msm_dev(_zksnark._bit_size(gens[G2]), 16, gens[G2], [beta], G2)
         return Srs(m, powers(1, 2 * m + 1, G1), powers(1, m, G2), powers(alpha, m, G1), powers(beta, m, G1), beta_g2)
 
     @staticmethod
@@ -139,11 +118,11 @@ class Srs:
         The scalar buffers are zeroed on the device before they are released.  `previous`: the bytes of the receipt
         before this one, empty for the first.  `nonces`: the three u of the proofs of knowledge, in [1, r); give them
         for reproducible receipts in tests only."""
-        s, a, b = (secrets.randbelow(FR - 1) + 1 if v is None else _ceremony._scalar(v, what, 1)
+        s, a, b = (secrets.randbelow(FR - 1) + 1 if v is None else _wire.scalar_in_range(v, what, 1)
                    for v, what in zip((tau, alpha, beta), _SECRETS))
         if nonces is None:
             nonces = [secrets.randbelow(FR - 1) + 1 for _ in _SECRETS]
-        nonces = [_ceremony._scalar(u, "nonce", 1) for u in nonces]
+        nonces = [_wire.scalar_in_range(u, "nonce", 1) for u in nonces]
         if len(nonces) != 3:
             raise ValueError("three nonces: one per secret")
         m = self.m
@@ -166,14 +145,14 @@ class Srs:
             pw = powers(1, 2 * m + 1)
             new = Srs(m, mul_points(self.tau_g1, pw, G1), mul_points(self.tau_g2, pw[:32 * m], G2),
                       mul_points(self.alpha_tau_g1, powers(a, m), G1), mul_points(self.beta_tau_g1, powers(b, m), G1),
-                      _ceremony.scale_points(self.beta_g2, b, G2))
+                      scale_points(self.beta_g2, b, G2))
         finally:
             for t in spent:
                 t.zero_()
             torch.cuda.current_stream().synchronize()
             del spent
         bases = _pok_bases(self)
-        rs = _ceremony._enc(torch.cat([_ceremony.scale_points(p, u, G1) for p, u in zip(bases, nonces)]), G1)
+        rs = _ceremony._enc(torch.cat([scale_points(p, u, G1) for p, u in zip(bases, nonces)]), G1)
         pts = _ceremony._enc(torch.cat(bases + _pok_bases(new)), G1)
         rec = Receipt(m, hashlib.sha256(bytes(previous)).digest(),
                       [(pts[32 * j:32 * j + 32], pts[96 + 32 * j:128 + 32 * j], rs[32 * j:32 * j + 32], 0) for j in range(3)])
@@ -197,11 +176,10 @@ class Srs:
         section and index whose point does not decode.  load does NOT run check(): the points are on their curves and
         nothing more is known.  In particular a decoded G2 point is on the twist and not yet in the order-r
         subgroup.  Run check() on a string somebody else supplies."""
-        from .zksnark import _dev_bytes
         m, sections = parse_string_file(src)
         arrays = {}
         for name, type_, _ in FILE_SECTIONS:
-            arrays[name], codes = _codec._decompress(_dev_bytes(sections[name]), type_, "wire_in")
+            arrays[name], codes = _codec._decompress(_wire.dev_bytes(sections[name]), type_, "wire_in")
             bad = torch.nonzero(codes)
             if bad.numel():
                 i = int(bad[0].item())
@@ -229,15 +207,13 @@ class Srs:
         The weights come from a SHA-256 counter stream over `seed` (bytes or an int) under this module's own tag; None
         draws 32 bytes from the system.  A seeded check is reproducible and so unsound against anyone who knows the
         seed: tests only."""
-        from .zksnark import _dev_bytes, wire_out_to_in
-
         def no(name):
             if why is not None:
                 why.append(name)
             return False
 
         m = self.m
-        enc, scale, ones = _ceremony._enc, _ceremony.scale_points, _ceremony._pairs_are_one
+        enc, scale, ones = _ceremony._enc, scale_points, _vectors.pairs_are_one
         # 1 shape
         if m < 2 or m & (m - 1):
             return no("shape")
@@ -252,34 +228,35 @@ class Srs:
         e2 = enc(torch.cat([g2, sub]), G2)
         if any(e1[32 * i + 31] & 0x40 for i in range(4)) or any(e2[64 * i + 63] & 0x40 for i in range(3)):
             return no("shape")
-        if not _in_subgroup(sub, e2[64:]):
+        if not _vectors.in_subgroup_g2(sub, e2[64:]):
             return no("shape")
-        rho = _dev_bytes(_weights(_ceremony._seed_bytes(seed), 2 * m))
+        rho = _wire.dev_bytes(_transcript.weights(_transcript.seed_bytes(seed), 2 * m, _RHO_TAG))
         keep = []
 
         def shift_g1(points, n, q_lo, q_hi):
             """sum rho_i points[i] =: S, sum rho_i points[i + 1] =: S', i < n: S != O and e(S', q_lo) e(-S, q_hi) = 1"""
             flat = points.reshape(-1)
-            s_lo, w1 = _msm(flat[:96 * n], rho[:32 * n], n, G1)
-            s_hi, w2 = _msm(flat[96:96 * (n + 1)], rho[:32 * n], n, G1)
+            s_lo, w1 = _vectors.msm(flat[:96 * n], rho[:32 * n], n, G1)
+            s_hi, w2 = _vectors.msm(flat[96:96 * (n + 1)], rho[:32 * n], n, G1)
             keep.extend((w1, w2))
-            if _ceremony._is_inf_out(s_lo):
+            if _wire.is_inf_out(s_lo):
                 return False
-            neg = scale(wire_out_to_in(s_lo, G1), FR - 1, G1)
-            return ones(torch.cat([wire_out_to_in(s_hi, G1), neg]), torch.cat([q_lo, q_hi]))
+            neg = scale(_wire.wire_out_to_in(s_lo, G1), FR - 1, G1)
+            return ones(torch.cat([_wire.wire_out_to_in(s_hi, G1), neg]), torch.cat([q_lo, q_hi]))
 
         # 2 powers_g1
         if not shift_g1(self.tau_g1, 2 * m, g2, tg2):
             return no("powers_g1")
         # 3 powers_g2
-        if not _in_subgroup(self.tau_g2, enc(self.tau_g2, G2)):
+        if not _vectors.in_subgroup_g2(self.tau_g2, enc(self.tau_g2, G2)):
             return no("powers_g2")
         flat = self.tau_g2.reshape(-1)
-        t_lo, w1 = _msm(flat[:192 * (m - 1)], rho[:32 * (m - 1)], m - 1, G2)
-        t_hi, w2 = _msm(flat[192:], rho[:32 * (m - 1)], m - 1, G2)
-        if not bool(t_lo.view(6, 64)[4:].any().item()):
+        t_lo, w1 = _vectors.msm(flat[:192 * (m - 1)], rho[:32 * (m - 1)], m - 1, G2)
+        t_hi, w2 = _vectors.msm(flat[192:], rho[:32 * (m - 1)], m - 1, G2)
+        if _wire.is_inf_out(t_lo, G2):
             return no("powers_g2")
-        if not ones(torch.cat([g1, scale(tg1, FR - 1, G1)]), torch.cat([wire_out_to_in(t_hi, G2), wire_out_to_in(t_lo, G2)])):
+        if not ones(torch.cat([g1, scale(tg1, FR - 1, G1)]),
+                    torch.cat([_wire.wire_out_to_in(t_hi, G2), _wire.wire_out_to_in(t_lo, G2)])):
             return no("powers_g2")
         # 4 alpha_powers, beta_powers
         for name, points in (("alpha_powers", self.alpha_tau_g1), ("beta_powers", self.beta_tau_g1)):
@@ -292,17 +269,6 @@ class Srs:
         torch.cuda.current_stream().synchronize()
         del keep, w1, w2
         return True
-
-
-def _in_subgroup(points, encodings: bytes) -> bool:
-    """every G2 point of `points` (finite or not) satisfies [r - 1] P = -P: the same x, the other y (no twist point
-    has y = 0), O for O"""
-    minus = _ceremony._enc(_ceremony.scale_points(points, FR - 1, G2), G2)
-    want = bytearray(encodings)
-    for i in range(63, len(want), 64):
-        if not want[i] & 0x40:
-            want[i] ^= 0x80
-    return minus == bytes(want)
 
 
 # ---------------------------------------------------------------------------- phase 1: receipt and verification
@@ -331,7 +297,7 @@ class Receipt:
     def from_bytes(b) -> "Receipt":
         """Strict and host-only: ValueError naming the field for a wrong length, a wrong magic, an m that is no power
         of two >= 2, a z >= r or a point that does not decode."""
-        b = _ceremony._receipt_head(b, MAGIC, RECEIPT_BYTES)
+        b = _codec.receipt_head(b, MAGIC, RECEIPT_BYTES)
         m = struct.unpack_from("<Q", b, 8)[0]
         if m < 2 or m & (m - 1):
             raise ValueError("receipt: m = %d is not a power of two >= 2" % m)
@@ -344,13 +310,13 @@ class Receipt:
             blocks.append((b[o:o + 32], b[o + 32:o + 64], b[o + 64:o + 96], z))
             fields += [("%s_%s" % (name, part), b[o + 32 * i:o + 32 * i + 32], G1)
                        for i, part in enumerate(("before", "after", "r"))]
-        _ceremony._require_points(fields)
+        _codec.require_points(fields, "receipt")
         return Receipt(m, b[16:48], blocks)
 
     def challenge(self, j) -> int:
         """c_j: what block j's response answers; it binds m, h, all six points and R_j"""
         body = bytes([j]) + struct.pack("<Q", self.m) + self.h + b"".join(x + y for x, y, _, _ in self.blocks)
-        return _ceremony._challenge(body, self.blocks[j][2], _POK_TAG)
+        return _transcript.challenge128(_POK_TAG, body, self.blocks[j][2])
 
 
 def _shaped(srs) -> bool:
@@ -482,76 +448,6 @@ def parse_string_file(src):
             own.close()
 
 
-# ---------------------------------------------------------------------------- point kernels
-def mul_points(points, scalars, type_, codes=False):
-    """[k_i] P_i for the n wire-in points of `points` and the n scalars of `scalars` (n x 32 bytes little-endian on
-    the device, as ozk_fr_powers_dev writes them): n wire-in points with Z = 1 (ozk_points_mul_dev).  A scalar >= r
-    gives infinity for that point alone; codes=True returns (points, n int32 codes), 1 for such a point.  Exact for
-    every point of the curve or twist.  Asynchronous on the current stream."""
-    if type_ not in (G1, G2):
-        raise ValueError("type_ must be 1 (G1) or 2 (G2)")
-    for t, what in ((points, "points"), (scalars, "scalars")):
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8):
-            raise ValueError("%s must be a uint8 tensor" % what)
-    rec = 96 * type_
-    if points.numel() == 0 or points.numel() % rec:
-        raise ValueError("points: %d bytes are not a whole number of %d-byte records" % (points.numel(), rec))
-    n = points.numel() // rec
-    if scalars.numel() != 32 * n:
-        raise ValueError("%d points need %d bytes of scalars, not %d" % (n, 32 * n, scalars.numel()))
-    L = _lib.load()
-    _codec._count(points, rec, "points")
-    _codec._count(scalars, 32, "scalars")
-    points, scalars = points.contiguous(), scalars.contiguous()
-    out = torch.empty_like(points)
-    d_codes = torch.empty(n, dtype=torch.int32, device=points.device) if codes else None
-    _lib.check(L.ozk_points_mul_dev(_ptr(points), _ptr(scalars), n, type_, _ptr(out),
-                                    None if d_codes is None else _ptr(d_codes), _stream()))
-    return (out, d_codes) if codes else out
-
-
-def ec_fft(points, type_, omega, inverse=False) -> torch.Tensor:
-    """The radix-2 transform of n = 2^k wire-in points in the exponent (ozk_ec_fft_dev): out[j] = sum_i
-    [omega^(i j)] in[i]; inverse=True uses omega^-1 and multiplies by 1 / n.  A new tensor, Z = 1."""
-    L = _lib.load()
-    points = points.contiguous()
-    n = _codec._count(points, 96 * type_, "points")
-    out = torch.empty_like(points)
-    wsb = int(L.ozk_ec_fft_workspace_bytes(n, type_))
-    ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=points.device)
-    ob = (ctypes.c_uint8 * 32).from_buffer_copy(int(omega).to_bytes(32, "little"))
-    _lib.check(L.ozk_ec_fft_dev(_ptr(points), n, type_, ctypes.cast(ob, ctypes.c_void_p), int(bool(inverse)), _ptr(out),
-                                _ptr(ws), ws.numel(), _stream()))
-    torch.cuda.current_stream().synchronize()    # the workspace dies here
-    return out
-
-
-def points_add(a, b, type_, negate_b=False) -> torch.Tensor:
-    """a[i] + b[i], or a[i] - b[i]: n wire-in points, Z = 1 (ozk_points_add_dev).  Asynchronous on the current stream."""
-    L = _lib.load()
-    a, b = a.contiguous(), b.contiguous()
-    n = _codec._count(a, 96 * type_, "points")
-    if b.numel() != a.numel():
-        raise ValueError("two vectors of one length")
-    out = torch.empty_like(a)
-    _lib.check(L.ozk_points_add_dev(_ptr(a), _ptr(b), n, type_, int(bool(negate_b)), _ptr(out), _stream()))
-    return out
-
-
-def sparse_mat_points(mat, points, type_) -> torch.Tensor:
-    """mat (a zksnark._CsrDevice) times a vector of wire-in points: one point per row (ozk_sparse_mat_points_dev)"""
-    L = _lib.load()
-    points = points.contiguous()
-    out = torch.empty(mat.rows * 96 * type_, dtype=torch.uint8, device=points.device)
-    wsb = int(L.ozk_sparse_mat_points_workspace_bytes(mat.n_long, type_))
-    ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=points.device)
-    opt = lambda t: None if t is None else _ptr(t)
-    _lib.check(L.ozk_sparse_mat_points_dev(_ptr(mat.ptr), _ptr(mat.idx), opt(mat.coeff), _ptr(points), mat.rows, type_,
-                                           opt(mat.long), mat.n_long, _ptr(out), _ptr(ws), ws.numel(), _stream()))
-    torch.cuda.current_stream().synchronize()    # the workspace dies here
-    return out
-
-
 # ---------------------------------------------------------------------------- the setup
 def setup_from_srs(r1cs, srs: Srs, log=None):
     """The Groth16 key of `r1cs` instantiated at the tau of `srs`, with gamma = delta = 1 (the shape of Bowe, Gabizon
@@ -560,9 +456,8 @@ def setup_from_srs(r1cs, srs: Srs, log=None):
     pointwise sums.  Returns a CRS with proving_key (and its .r1cs), gamma_g2, gamma_abc_g1, timing and secrets = None.
     ValueError when the string's m is not lowest_power_of_two(num_constraints + num_inputs), and when tau lies in the
     domain (tau^m = 1: tau_g1[m] equals tau_g1[0])."""
-    from . import zksnark as z
     nc, ni, nv = r1cs.num_constraints, r1cs.num_inputs, r1cs.num_variables
-    m = z.lowest_power_of_two(nc + ni)
+    m = lowest_power_of_two(nc + ni)
     if m != srs.m:
         raise ValueError("the circuit needs a string of m = %d, this one has m = %d" % (m, srs.m))
     tm = {}
@@ -578,11 +473,11 @@ def setup_from_srs(r1cs, srs: Srs, log=None):
     if ends[:32] == ends[32:]:
         raise ValueError("tau lies in the domain of size %d (tau_g1[m] = tau_g1[0]): no key can be built at it" % m)
     if getattr(r1cs, "_transposed_dev", None) is None:
-        r1cs._transposed_dev = z.R1CSTransposedDevice(r1cs)
+        r1cs._transposed_dev = _zksnark.R1CSTransposedDevice(r1cs)
     At, Bt, Ct = r1cs._transposed_dev.mats
     t0 = lap("r1cs_transpose_once_host_s", t0)
     omega = root_of_unity(m)
-    pk = z.ProvingKey()
+    pk = _zksnark.ProvingKey()
     # G2 first: its Lagrange array is the largest and has one product
     L2 = ec_fft(srs.tau_g2, G2, omega, inverse=True)
     t0 = lap("fft_g2_s", t0)
@@ -617,7 +512,7 @@ def setup_from_srs(r1cs, srs: Srs, log=None):
     pk.delta_g1 = tau_g1[:96].clone()
     pk.delta_g2 = srs.tau_g2.reshape(-1)[:192].clone()
     pk.r1cs = r1cs
-    crs = z.CRS()
+    crs = _zksnark.CRS()
     crs.proving_key = pk
     crs.gamma_g2 = pk.delta_g2.clone()
     crs.gamma_abc_g1 = abc[:96 * ni].clone()

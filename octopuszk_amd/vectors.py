@@ -1,0 +1,189 @@
+"""One-call wrappers of the library's vector entry points over points and over Fr (include/ozk.h): uint8 CUDA tensors
+in, uint8 CUDA tensors out, on the current stream.  There is no CPU path."""
+import ctypes
+
+import torch
+
+from . import codec as _codec
+from . import lib as _lib
+from . import pairing as _pairing
+from . import wire as _wire
+from .device import VarMsmWorkspace, _ptr, _stream
+from .fft import FR
+
+G1, G2 = 1, 2
+_GT_ONE = (1).to_bytes(32, "little") + bytes(352)
+
+
+# ---------------------------------------------------------------------------- points
+def scale_points(points, k, type_) -> torch.Tensor:
+    """[k] P for every wire-in point P of `points` (a uint8 CUDA tensor, n x 96 bytes for type_ 1 = G1, n x 192 for
+    2 = G2, any Z) and one int k in [0, r): n wire-in points with Z = 1, infinity as (0, 1, 0) / ((0, 0), (1, 0),
+    (0, 0)).  Exact for every point of the curve (of the twist, inside the order-r subgroup or not).  Asynchronous on
+    the current stream."""
+    k = _wire.scalar_in_range(k, "the scalar")
+    if type_ not in (G1, G2):
+        raise ValueError("type_ must be 1 (G1) or 2 (G2)")
+    L = _lib.load()
+    n = _wire.count(points, 96 * type_, "points")
+    points = points.contiguous()
+    out = torch.empty_like(points)
+    kb = (ctypes.c_uint8 * 32).from_buffer_copy(k.to_bytes(32, "little"))   # read before the call returns
+    _lib.check(L.ozk_points_scale_dev(_ptr(points), n, type_, ctypes.cast(kb, ctypes.c_void_p), _ptr(out), _stream()))
+    return out
+
+
+def mul_points(points, scalars, type_, codes=False):
+    """[k_i] P_i for the n wire-in points of `points` and the n scalars of `scalars` (n x 32 bytes little-endian on
+    the device, as ozk_fr_powers_dev writes them): n wire-in points with Z = 1 (ozk_points_mul_dev).  A scalar >= r
+    gives infinity for that point alone; codes=True returns (points, n int32 codes), 1 for such a point.  Exact for
+    every point of the curve or twist.  Asynchronous on the current stream."""
+    if type_ not in (G1, G2):
+        raise ValueError("type_ must be 1 (G1) or 2 (G2)")
+    for t, what in ((points, "points"), (scalars, "scalars")):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8):
+            raise ValueError("%s must be a uint8 tensor" % what)
+    rec = 96 * type_
+    if points.numel() == 0 or points.numel() % rec:
+        raise ValueError("points: %d bytes are not a whole number of %d-byte records" % (points.numel(), rec))
+    n = points.numel() // rec
+    if scalars.numel() != 32 * n:
+        raise ValueError("%d points need %d bytes of scalars, not %d" % (n, 32 * n, scalars.numel()))
+    L = _lib.load()
+    _wire.count(points, rec, "points")
+    _wire.count(scalars, 32, "scalars")
+    points, scalars = points.contiguous(), scalars.contiguous()
+    out = torch.empty_like(points)
+    d_codes = torch.empty(n, dtype=torch.int32, device=points.device) if codes else None
+    _lib.check(L.ozk_points_mul_dev(_ptr(points), _ptr(scalars), n, type_, _ptr(out),
+                                    None if d_codes is None else _ptr(d_codes), _stream()))
+    return (out, d_codes) if codes else out
+
+
+def ec_fft(points, type_, omega, inverse=False) -> torch.Tensor:
+    """The radix-2 transform of n = 2^k wire-in points in the exponent (ozk_ec_fft_dev): out[j] = sum_i
+    [omega^(i j)] in[i]; inverse=True uses omega^-1 and multiplies by 1 / n.  A new tensor, Z = 1."""
+    L = _lib.load()
+    points = points.contiguous()
+    n = _wire.count(points, 96 * type_, "points")
+    out = torch.empty_like(points)
+    wsb = int(L.ozk_ec_fft_workspace_bytes(n, type_))
+    ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=points.device)
+    ob = (ctypes.c_uint8 * 32).from_buffer_copy(int(omega).to_bytes(32, "little"))
+    _lib.check(L.ozk_ec_fft_dev(_ptr(points), n, type_, ctypes.cast(ob, ctypes.c_void_p), int(bool(inverse)), _ptr(out),
+                                _ptr(ws), ws.numel(), _stream()))
+    torch.cuda.current_stream().synchronize()    # the workspace dies here
+    return out
+
+
+def points_add(a, b, type_, negate_b=False) -> torch.Tensor:
+    """a[i] + b[i], or a[i] - b[i]: n wire-in points, Z = 1 (ozk_points_add_dev).  Asynchronous on the current stream."""
+    L = _lib.load()
+    a, b = a.contiguous(), b.contiguous()
+    n = _wire.count(a, 96 * type_, "points")
+    if b.numel() != a.numel():
+        raise ValueError("two vectors of one length")
+    out = torch.empty_like(a)
+    _lib.check(L.ozk_points_add_dev(_ptr(a), _ptr(b), n, type_, int(bool(negate_b)), _ptr(out), _stream()))
+    return out
+
+
+def sparse_mat_points(mat, points, type_) -> torch.Tensor:
+    """mat (a zksnark._CsrDevice) times a vector of wire-in points: one point per row (ozk_sparse_mat_points_dev)"""
+    L = _lib.load()
+    points = points.contiguous()
+    out = torch.empty(mat.rows * 96 * type_, dtype=torch.uint8, device=points.device)
+    wsb = int(L.ozk_sparse_mat_points_workspace_bytes(mat.n_long, type_))
+    ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=points.device)
+    opt = lambda t: None if t is None else _ptr(t)
+    _lib.check(L.ozk_sparse_mat_points_dev(_ptr(mat.ptr), _ptr(mat.idx), opt(mat.coeff), _ptr(points), mat.rows, type_,
+                                           opt(mat.long), mat.n_long, _ptr(out), _ptr(ws), ws.numel(), _stream()))
+    torch.cuda.current_stream().synchronize()    # the workspace dies here
+    return out
+
+
+def points_mac_prepare(points, terms, n):
+    """terms x n wire-in G1 points, term-major -> the prepared table of ozk_points_mac_dev (ozk_points_mac_prepare_dev).
+    Asynchronous on the current stream."""
+    L = _lib.load()
+    points = points.contiguous()
+    if _wire.count(points, 96, "points") != terms * n:
+        raise ValueError("%d x %d points need %d bytes, not %d" % (terms, n, 96 * terms * n, points.numel()))
+    nbytes = int(L.ozk_points_mac_prepared_bytes(terms, n, G1))
+    table = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=points.device)
+    _lib.check(L.ozk_points_mac_prepare_dev(_ptr(points), terms, n, G1, _ptr(table), table.numel(), _stream()))
+    return table
+
+
+def points_mac(table, scalars, terms, n, codes=False, workspace=None):
+    """out[i] = sum_v [k_v[i]] P_v[i] over a prepared table and terms x n scalars (32 bytes little-endian, term-major,
+    on the device): n wire-in points, Z = 1 (ozk_points_mac_dev); codes=True returns (points, n int32 codes), 1 for a
+    lane with a scalar >= r.  Asynchronous on the current stream when the caller passes (and keeps) the workspace,
+    else it synchronises: the workspace dies here."""
+    L = _lib.load()
+    scalars = scalars.contiguous()
+    if scalars.numel() != 32 * terms * n:
+        raise ValueError("%d x %d scalars need %d bytes, not %d" % (terms, n, 32 * terms * n, scalars.numel()))
+    out = torch.empty(96 * n, dtype=torch.uint8, device=scalars.device)
+    d_codes = torch.empty(n, dtype=torch.int32, device=scalars.device) if codes else None
+    ws = workspace
+    if ws is None:
+        ws = torch.empty(max(int(L.ozk_points_mac_workspace_bytes(terms, n, G1)), 256), dtype=torch.uint8,
+                         device=scalars.device)
+    _lib.check(L.ozk_points_mac_dev(_ptr(table), _ptr(scalars), terms, n, G1, _ptr(out),
+                                    None if d_codes is None else _ptr(d_codes), _ptr(ws), ws.numel(), _stream()))
+    if workspace is None:
+        torch.cuda.current_stream().synchronize()
+    return (out, d_codes) if codes else out
+
+
+def msm(bases, d_scalars, n, type_=1):
+    """sum s_i P_i over n wire-in points through ozk_var_msm_dev: one wire-out point (192 bytes for G1, 384 for G2);
+    the workspace is returned too, to be kept until the stream has run"""
+    ws = VarMsmWorkspace(n, type_)
+    return ws.run(bases.contiguous(), d_scalars), ws
+
+
+def in_subgroup_g2(points, encodings: bytes) -> bool:
+    """every G2 point of `points` (finite or not) satisfies [r - 1] P = -P: the same x, the other y (no twist point
+    has y = 0), O for O"""
+    minus = _wire.host_bytes(_codec.compress_g2(scale_points(points, FR - 1, G2)))
+    want = bytearray(encodings)
+    for i in range(63, len(want), 64):
+        if not want[i] & 0x40:
+            want[i] ^= 0x80
+    return minus == bytes(want)
+
+
+def pairs_are_one(p_batch, q_batch) -> bool:
+    return _wire.host_bytes(_pairing.pairing_product(p_batch, q_batch)) == _GT_ONE
+
+
+# ---------------------------------------------------------------------------- Fr
+def fr_fft(values, n, omega, out=None):
+    """The transform of n = 2^k elements of Fr (32 bytes little-endian each) on the device: out[j] = sum_i
+    omega^(i j) in[i], canonical (ozk_fft_compact_dev).  Synchronises (the workspace dies here)."""
+    L = _lib.load()
+    if out is None:
+        out = torch.empty(32 * n, dtype=torch.uint8, device=values.device)
+    ws = torch.empty(max(int(L.ozk_fft_workspace_bytes(n)), 256), dtype=torch.uint8, device=values.device)
+    _lib.check(L.ozk_fft_compact_dev(_ptr(values), n, _wire.vp(_wire.le32([omega])), _ptr(out), _ptr(ws), ws.numel(),
+                                     _stream()))
+    torch.cuda.current_stream().synchronize()
+    return out
+
+
+def fr_poly_eval(coeffs, r, npolys=1):
+    """sum_i c_yi r^i for npolys polynomials of equal length stored back to back in a uint8 CUDA tensor (32-byte LE
+    canonical coefficients): a CUDA tensor of npolys x 32 bytes."""
+    L = _lib.load()
+    total = coeffs.numel() // 32
+    if coeffs.numel() % 32 or total % npolys or total == 0:
+        raise ValueError("coefficients do not split into %d polynomials" % npolys)
+    length = total // npolys
+    out = torch.empty(npolys * 32, dtype=torch.uint8, device=coeffs.device)
+    ws = torch.empty(int(L.ozk_fr_poly_eval_workspace_bytes(npolys)), dtype=torch.uint8, device=coeffs.device)
+    rb = (int(r) % FR).to_bytes(32, "little")
+    _lib.check(L.ozk_fr_poly_eval_dev(_ptr(coeffs), npolys, length, length, _wire.vp(rb), _ptr(out), _ptr(ws),
+                                      ws.numel(), _stream()))
+    return out

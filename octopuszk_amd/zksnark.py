@@ -36,14 +36,18 @@ import time
 import numpy as np
 import torch
 
-from . import lib as _lib
+from . import codec as _codec
 from . import device as _dev
+from . import keyfile as _keyfile
+from . import lib as _lib
+from . import pairing as _pairing
 from .device import _ptr, _stream, prepare_bases
 from .distributed import shard_range
-from .fft import FR, FR_MULT_GEN, root_of_unity
+from .fft import FR, FR_MULT_GEN, SEED, fr_random, lowest_power_of_two, root_of_unity
 from .fixed_base_msm import G1_WINDOW_TABLE, G2_WINDOW_TABLE, get_window_size
+from .wire import dev_bytes, g1_wire, g2_wire, host_bytes, ints32, upload, vp, wire_out_to_in
+from .wire import le32 as _le32
 
-SEED = 10  # configuration/Configuration.java:52
 G1_ONE = (1, 2, 1)  # BN254aG1Parameters.java:23-24
 G2_ONE = (  # BN254aG2Parameters.java:25-32
     (10857046999023057135944570762232829481370756359578518086990519993285655852781,
@@ -51,66 +55,6 @@ G2_ONE = (  # BN254aG2Parameters.java:25-32
     (8495653923123431417604973247489272438418190587263600148770280649306958101930,
      4082367875863433681332203403145435568316851327593401208105741076214120093531),
     (1, 0))
-
-
-# ---------------------------------------------------------------------------- small helpers
-def _java_random_next_long(seed: int) -> int:
-    """new java.util.Random(seed).nextLong() (JDK API specification: 48-bit LCG, two signed 32-bit draws)."""
-    mult, mask = 0x5DEECE66D, (1 << 48) - 1
-    st = (seed ^ mult) & mask
-    out = []
-    for _ in range(2):
-        st = (st * mult + 0xB) & mask
-        v = st >> 16
-        out.append(v - (1 << 32) if v >= 1 << 31 else v)
-    v = ((out[0] << 32) + out[1]) & ((1 << 64) - 1)
-    return v - (1 << 64) if v >= 1 << 63 else v
-
-
-def fr_random(seed: int = SEED) -> int:
-    """Fp.random (algebra/fields/Fp.java:72-80): new Fp(new Random(seed).nextLong()) — reduced mod r by the
-    constructor, so every draw with the same seed is the same element."""
-    return _java_random_next_long(seed) % FR
-
-
-def lowest_power_of_two(n: int) -> int:
-    """common/MathUtils.java:20-41."""
-    r = 1
-    while r < n:
-        r <<= 1
-    return r
-
-
-def _le32(values) -> bytes:
-    return b"".join(int(v).to_bytes(32, "little") for v in values)
-
-
-def _upload(a: np.ndarray) -> torch.Tensor:
-    """A host TEMPORARY to the device.  Large ones go through pinned memory: handed a pageable range, the HIP runtime
-    registers it with the kernel driver, and when the freed range is later recycled and unmapped the driver evicts all
-    GPU queues of the process for 10-30 ms — a stall that would land in some later proof."""
-    a = np.ascontiguousarray(a)
-    t = torch.from_numpy(a if a.flags.writeable else a.copy())
-    return (t.pin_memory() if t.numel() * t.element_size() >= (1 << 20) else t).cuda()
-
-
-def _dev_bytes(b: bytes) -> torch.Tensor:
-    return _upload(np.frombuffer(b, dtype=np.uint8))
-
-
-def g1_wire(P) -> bytes:
-    return _le32(P)
-
-
-def g2_wire(P) -> bytes:
-    return _le32(P[i][j] for i in range(3) for j in range(2))
-
-
-def wire_out_to_in(out: torch.Tensor, type_: int) -> torch.Tensor:
-    """One point in the natives' return layout (64-byte LE coordinates, upper half zero) -> the 32-byte
-    coordinates they take as input (VariableBaseMSM.java:221-228 vs :239-258)."""
-    k = 3 if type_ == 1 else 6
-    return out.view(k, 64)[:, :32].reshape(-1).contiguous()
 
 
 # ---------------------------------------------------------------------------- R1CS (CSR arrays)
@@ -222,10 +166,10 @@ class _CsrDevice:
         assert ptr[-1] == len(idx) < 1 << 32
         long_rows = np.nonzero(np.diff(ptr) > 64)[0].astype(np.uint32)
         self.rows, self.n_long = len(ptr) - 1, len(long_rows)
-        self.ptr = _upload(ptr.astype(np.uint32).view(np.uint8))
-        self.idx = _upload(idx.astype(np.uint32).view(np.uint8))
-        self.coeff = None if val is None else _dev_bytes(_le32(int(v) % FR for v in val))
-        self.long = _upload(long_rows.view(np.uint8)) if self.n_long else None
+        self.ptr = upload(ptr.astype(np.uint32).view(np.uint8))
+        self.idx = upload(idx.astype(np.uint32).view(np.uint8))
+        self.coeff = None if val is None else dev_bytes(_le32(int(v) % FR for v in val))
+        self.long = upload(long_rows.view(np.uint8)) if self.n_long else None
 
     @staticmethod
     def workspace(mats):
@@ -352,15 +296,6 @@ def r1cs_to_qap_relation(r1cs: R1CSRelation, t: int) -> QAPRelation:
 
 
 # ---------------------------------------------------------------------------- QAP instance at t (device)
-def _le32_one(v: int):
-    return ctypes.create_string_buffer(int(v % FR).to_bytes(32, "little"), 32)
-
-
-def _ints_from_dev(t: torch.Tensor):
-    raw = bytes(t.cpu().numpy())
-    return [int.from_bytes(raw[k:k + 32], "little") for k in range(0, len(raw), 32)]
-
-
 class R1CSTransposedDevice:
     """The constraint matrices TRANSPOSED, resident in HBM as CSR: row j = the terms (constraint i, coefficient) of
     variable j, with the `input_i * 0 = 0` rows R1CStoQAPRelation adds to A (R1CStoQAP.java:52-55: At[i] gets the
@@ -392,15 +327,15 @@ class QAPRelationDevice:
     def __init__(self):
         self._cache = {}
 
-    def _ints(self, name):
+    def _host(self, name):
         if name not in self._cache:
-            self._cache[name] = _ints_from_dev(getattr(self, "d_" + name))
+            self._cache[name] = ints32(host_bytes(getattr(self, "d_" + name)))
         return self._cache[name]
 
-    At = property(lambda self: self._ints("At"))
-    Bt = property(lambda self: self._ints("Bt"))
-    Ct = property(lambda self: self._ints("Ct"))
-    Ht = property(lambda self: self._ints("Ht"))
+    At = property(lambda self: self._host("At"))
+    Bt = property(lambda self: self._host("Bt"))
+    Ct = property(lambda self: self._host("Ct"))
+    Ht = property(lambda self: self._host("Ht"))
 
 
 def r1cs_to_qap_relation_dev(r1cs: R1CSRelation, t: int, transposed: R1CSTransposedDevice = None) -> QAPRelationDevice:
@@ -420,8 +355,8 @@ def r1cs_to_qap_relation_dev(r1cs: R1CSRelation, t: int, transposed: R1CSTranspo
     d_zt = torch.empty(32, dtype=torch.uint8, device="cuda")
     wsb = int(L.ozk_qap_lagrange_workspace_bytes(m))
     ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
-    tb, ob = _le32_one(t), _le32_one(root_of_unity(m))
-    _lib.check(L.ozk_qap_lagrange_dev(ctypes.cast(tb, ctypes.c_void_p), ctypes.cast(ob, ctypes.c_void_p), m, _ptr(d_lag),
+    tb, ob = _le32([t % FR]), _le32([root_of_unity(m)])
+    _lib.check(L.ozk_qap_lagrange_dev(vp(tb), vp(ob), m, _ptr(d_lag),
                                       _ptr(d_zt), _ptr(ws), wsb, st))
     outs = []
     for mat in T.mats:
@@ -432,8 +367,8 @@ def r1cs_to_qap_relation_dev(r1cs: R1CSRelation, t: int, transposed: R1CSTranspo
     q.d_Ht = torch.empty((m + 1) * 32, dtype=torch.uint8, device="cuda")
     pwb = int(L.ozk_fr_powers_workspace_bytes(m + 1))
     pws = torch.empty(pwb, dtype=torch.uint8, device="cuda")
-    one = _le32_one(1)
-    _lib.check(L.ozk_fr_powers_dev(ctypes.cast(tb, ctypes.c_void_p), ctypes.cast(one, ctypes.c_void_p), m + 1, _ptr(q.d_Ht),
+    one = _le32([1])
+    _lib.check(L.ozk_fr_powers_dev(vp(tb), vp(one), m + 1, _ptr(q.d_Ht),
                                    _ptr(pws), pwb, st))
     torch.cuda.current_stream().synchronize()       # the host buffers and workspaces above die here
     q.Zt = int.from_bytes(bytes(d_zt.cpu().numpy()), "little")
@@ -452,8 +387,8 @@ def batch_msm_dev(scalar_size: int, window_size: int, base_wire: bytes, scalars,
     outerc = (scalar_size + window_size - 1) // window_size   # FixedBaseMSM.java:212
     if outerc * window_size < 254:
         raise _lib.OzkError("window plan covers %d bits of a 254-bit scalar" % (outerc * window_size))
-    d_base = _dev_bytes(base_wire)
-    d_sc = scalars if on_device else _dev_bytes(_le32(scalars))
+    d_base = dev_bytes(base_wire)
+    d_sc = scalars if on_device else dev_bytes(_le32(scalars))
     out = torch.empty(n * (96 if type_ == 1 else 192), dtype=torch.uint8, device="cuda")
     wsb = int(L.ozk_fixed_batch_msm_workspace_bytes(outerc, window_size, n, type_))
     ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
@@ -476,7 +411,7 @@ class _LazyScalars(dict):
     def __getitem__(self, k):
         v = dict.__getitem__(self, k)
         if isinstance(v, torch.Tensor):
-            v = _ints_from_dev(v)
+            v = ints32(host_bytes(v))
             dict.__setitem__(self, k, v)
         return v
 
@@ -491,7 +426,6 @@ def _r1cs_from_key_file(kf) -> R1CSRelation:
 
 
 def _key_point_failure(section, index, code):
-    from . import codec as _codec
     return ValueError("proving key: section %s, point %d does not decode: code %d (%s)"
                       % (section, index, code, _codec.CODE_NAMES.get(code, "?")))
 
@@ -513,8 +447,6 @@ class ProvingKey:
 
     def to_bytes(self) -> bytes:
         """The key file: every point compressed on the device (32 bytes per G1 point, 64 per G2), and the R1CS."""
-        from . import codec as _codec
-        from . import keyfile as _keyfile
         r1cs = self.r1cs
         sections = {}
         for name in _PK_G1 + _PK_G2:
@@ -530,13 +462,12 @@ class ProvingKey:
 
     @staticmethod
     def _from_key_file(kf, verify_digest) -> "ProvingKey":
-        from . import codec as _codec
         if verify_digest:
             kf.verify_digest()
         pk = ProvingKey()
         pk.r1cs = _r1cs_from_key_file(kf)
         for name in _PK_G1 + _PK_G2:
-            pts, codes = (_codec.decompress_g1 if name in _PK_G1 else _codec.decompress_g2)(_dev_bytes(kf.read(name)), "wire_in")
+            pts, codes = (_codec.decompress_g1 if name in _PK_G1 else _codec.decompress_g2)(dev_bytes(kf.read(name)), "wire_in")
             bad = _first_failure(codes)
             if bad:
                 raise _key_point_failure(name, *bad)
@@ -548,12 +479,10 @@ class ProvingKey:
         """The key of a key file, its points decoded on the device into wire-in tensors, with pk.r1cs: what
         serial_setup_generate returns as crs.proving_key.  ValueError for a malformed file (keyfile.py names what is
         wrong) and for a point that does not decode (section, index and codec.CODE_NAMES[code])."""
-        from . import keyfile as _keyfile
         return ProvingKey._from_key_file(_keyfile.KeyFile(b), verify_digest)
 
     @staticmethod
     def load(path, verify_digest=True) -> "ProvingKey":
-        from . import keyfile as _keyfile
         kf = _keyfile.KeyFile(path)
         try:
             return ProvingKey._from_key_file(kf, verify_digest)
@@ -604,13 +533,12 @@ def serial_setup_generate(r1cs: R1CSRelation, seed: int = SEED, log=None) -> CRS
         k3 = torch.empty(96, dtype=torch.uint8, device="cuda")
         d_gamma_abc = torch.empty(ni * 32, dtype=torch.uint8, device="cuda")
         d_delta_abc = torch.empty((nv - ni) * 32, dtype=torch.uint8, device="cuda")
-        kb, ka = _le32_one(beta), _le32_one(alpha)
+        kb, ka = _le32([beta]), _le32([alpha])
         for lo, cnt, kk, out in ((0, ni, inv_gamma, d_gamma_abc), (ni, nv - ni, inv_delta, d_delta_abc)):
             if cnt > 0:
-                kkb = _le32_one(kk)
+                kkb = _le32([kk])
                 _lib.check(L.ozk_fr_lincomb3_dev(_ptr(qap.d_At) + 32 * lo, _ptr(qap.d_Bt) + 32 * lo, _ptr(qap.d_Ct) + 32 * lo,
-                                                 cnt, ctypes.cast(kb, ctypes.c_void_p), ctypes.cast(ka, ctypes.c_void_p),
-                                                 ctypes.cast(kkb, ctypes.c_void_p), _ptr(out), _ptr(k3), _stream()))
+                                                 cnt, vp(kb), vp(ka), vp(kkb), _ptr(out), _ptr(k3), _stream()))
                 torch.cuda.current_stream().synchronize()
         gamma_abc, delta_abc = d_gamma_abc, d_delta_abc
         non_zero_at = int((qap.d_At.view(nv, 32) != 0).any(dim=1).sum().item())
@@ -651,8 +579,8 @@ def serial_setup_generate(r1cs: R1CSRelation, seed: int = SEED, log=None) -> CRS
         ht_scalars = torch.empty((qap.degree + 1) * 32, dtype=torch.uint8, device="cuda")
         pwb = int(L.ozk_fr_powers_workspace_bytes(qap.degree + 1))
         pws = torch.empty(pwb, dtype=torch.uint8, device="cuda")
-        tb, kb2 = _le32_one(t), _le32_one(inv_delta_zt)
-        _lib.check(L.ozk_fr_powers_dev(ctypes.cast(tb, ctypes.c_void_p), ctypes.cast(kb2, ctypes.c_void_p), qap.degree + 1,
+        tb, kb2 = _le32([t]), _le32([inv_delta_zt])
+        _lib.check(L.ozk_fr_powers_dev(vp(tb), vp(kb2), qap.degree + 1,
                                        _ptr(ht_scalars), _ptr(pws), pwb, _stream()))
         torch.cuda.current_stream().synchronize()
     else:
@@ -709,10 +637,9 @@ class Proof:
 
     def to_bytes(self) -> bytes:
         """The 128-byte compressed form A (32) | B (64) | C (32) of DESIGN.md section 13, encoded on the device."""
-        from . import codec as _codec
-        a = _codec.compress_g1(_dev_bytes(bytes(self.g_a)), "wire_out")
-        b = _codec.compress_g2(_dev_bytes(bytes(self.g_b)), "wire_out")
-        c = _codec.compress_g1(_dev_bytes(bytes(self.g_c)), "wire_out")
+        a = _codec.compress_g1(dev_bytes(bytes(self.g_a)), "wire_out")
+        b = _codec.compress_g2(dev_bytes(bytes(self.g_b)), "wire_out")
+        c = _codec.compress_g1(dev_bytes(bytes(self.g_c)), "wire_out")
         return bytes(torch.cat([a, b, c]).cpu().numpy())
 
     @staticmethod
@@ -725,19 +652,17 @@ class Proof:
 
 
 def _decode_failure(what, index, code):
-    from . import codec as _codec
     return ValueError("%s %s does not decode: code %d (%s)" % (what, index, code, _codec.CODE_NAMES.get(code, "?")))
 
 
 def proofs_from_bytes(buf) -> list:
     """The proofs of K x 128 compressed bytes, decoded in one launch.  ValueError on the first proof with a point that
     does not decode."""
-    from . import codec as _codec
     buf = bytes(buf)
     if not buf or len(buf) % 128:
         raise ValueError("%d bytes are not a whole number of 128-byte proofs" % len(buf))
     k = len(buf) // 128
-    enc = _dev_bytes(buf).view(k, 128)
+    enc = dev_bytes(buf).view(k, 128)
     # the three points apart, so that a failure can name its point (the proof entry reports one code per proof)
     parts = (("A", _codec.decompress_g1(enc[:, :32], "wire_out")), ("B", _codec.decompress_g2(enc[:, 32:96], "wire_out")),
              ("C", _codec.decompress_g1(enc[:, 96:], "wire_out")))
@@ -827,8 +752,6 @@ class ShardedProver:
         default (None) checks it when world = 1 and not when world > 1, where the point of a rank is not to read the
         other ranks' rows; pass True to check it on a rank all the same.
         `timing` (optional dict) receives read_s, upload_s and decode_s, wall times with a synchronise between."""
-        from . import codec as _codec
-        from . import keyfile as _keyfile
         kf = _keyfile.KeyFile(path_or_file)
         T = {"read_s": 0.0, "upload_s": 0.0, "decode_s": 0.0}
         try:
@@ -845,7 +768,7 @@ class ShardedProver:
                 t0 = time.perf_counter()
                 enc, parts = kf.read_joined(names, lo, hi)
                 t1 = time.perf_counter()
-                d_enc = _dev_bytes(enc)
+                d_enc = dev_bytes(enc)
                 torch.cuda.synchronize()
                 t2 = time.perf_counter()
                 prepared, codes = _codec.decompress_prepared(d_enc, type_, check_subgroup)
@@ -858,7 +781,7 @@ class ShardedProver:
                     raise _key_point_failure(*_keyfile.locate(parts, bad[0]), bad[1])
                 setattr(self, attr, prepared)
             # deltaG1 once more as a wire-in point: a base of the 3-term MSM behind every rank's share of C
-            delta, codes = _codec.decompress_g1(_dev_bytes(kf.read("delta_g1")), "wire_in")
+            delta, codes = _codec.decompress_g1(dev_bytes(kf.read("delta_g1")), "wire_in")
             bad = _first_failure(codes)
             if bad:
                 raise _key_point_failure("delta_g1", *bad)
@@ -924,21 +847,21 @@ class ShardedProver:
         assert full_bytes.size == self.nv * 32
         return full_bytes
 
-    def _upload_witness(self, full_bytes, seed):
+    def _witness_upload(self, full_bytes, seed):
         """What _enqueue works on, in HBM: the assignment, this rank's slices of z ++ [1, r] and z ++ [1, s], the
         scalars of C's 3-term share, and the zeroed record."""
         r = fr_random(seed)                                      # SerialProver.java:58-59
         s = fr_random(seed)
         lo, hi = self.plan["A"]
         d_full = torch.from_numpy(full_bytes).cuda()
-        tails = _dev_bytes(_le32([1, r, 1, s] + c_share_scalars(r, s, self.rank)))
+        tails = dev_bytes(_le32([1, r, 1, s] + c_share_scalars(r, s, self.rank)))
         d_sc_r = torch.cat((d_full, tails[:64]))[32 * lo:32 * hi]
         d_sc_s = torch.cat((d_full, tails[64:128]))[32 * lo:32 * hi]
         rec = torch.zeros(RECORD_BYTES, dtype=torch.uint8, device="cuda")
         return d_full, d_sc_r, d_sc_s, tails[128:], rec
 
     def _enqueue(self, d_full, d_sc_r, d_sc_s, d_fin_sc, rec, mark=None):
-        """One proof's device work over the tensors of _upload_witness, asynchronous: on return the current stream is behind
+        """One proof's device work over the tensors of _witness_upload, asynchronous: on return the current stream is behind
         all of it, and `rec` will hold A_r | B_r | C_r.  mark(name, stream), if given, is called where the device
         work starts, where the witness map, the L and H MSMs and the record are done (timing events)."""
         L = _lib.load()
@@ -1010,7 +933,7 @@ class ShardedProver:
         C_r = L_r + H_r + s A_r + r B1_r (- rs deltaG1 on rank 0).  `timing` (optional dict) receives the stage
         times of the device work from its start: witness map done, L and H MSMs done, record done."""
         t0 = time.perf_counter()
-        up = self._upload_witness(self._marshal(primary, auxiliary, full_bytes), seed)
+        up = self._witness_upload(self._marshal(primary, auxiliary, full_bytes), seed)
         at = {}
 
         def mark(name, stream):
@@ -1028,7 +951,7 @@ class ShardedProver:
 
     def coefficients_h(self):
         """coefficientsH of the last proof (m + 1 ints), for checks."""
-        return _ints_from_dev(self.d_h)
+        return ints32(host_bytes(self.d_h))
 
 
 class SerialProver(ShardedProver):
@@ -1053,7 +976,7 @@ class SerialProver(ShardedProver):
         full_bytes = self._marshal(primary, auxiliary, full_bytes)
         T["marshal_assignment_host_ms"] = (time.perf_counter() - t0) * 1e3
         t1 = time.perf_counter()
-        up = self._upload_witness(full_bytes, seed)
+        up = self._witness_upload(full_bytes, seed)
         torch.cuda.synchronize()
         T["upload_ms"] = (time.perf_counter() - t1) * 1e3
         t2 = time.perf_counter()
@@ -1073,7 +996,6 @@ class VerificationKey:
     (their Miller-loop line coefficients, computed once per key)."""
 
     def __init__(self, alpha_g1_beta_g2, gamma_g2, delta_g2, gamma_abc_g1):
-        from . import pairing as _pairing
         self.alpha_g1_beta_g2 = alpha_g1_beta_g2
         self.gamma_g2, self.delta_g2, self.gamma_abc_g1 = gamma_g2, delta_g2, gamma_abc_g1
         self.num_inputs = gamma_abc_g1.numel() // 96
@@ -1085,24 +1007,22 @@ class VerificationKey:
     def evaluation_abc(self, primary) -> torch.Tensor:
         """sum primary_i gammaABC_i (Verifier.java:45-47, VariableBaseMSM.serialMSM) through the variable-base MSM;
         192-byte wire-out point, asynchronous on the current stream"""
-        from . import device as _device
         if len(primary) != self.num_inputs:
             raise ValueError("%d primary inputs for a key of %d" % (len(primary), self.num_inputs))
         if self._msm is None:
-            self._msm = _device.VarMsmWorkspace(self.num_inputs, 1)
-        return self._msm.run(self.gamma_abc_g1, _dev_bytes(_le32(primary))).clone()
+            self._msm = _dev.VarMsmWorkspace(self.num_inputs, 1)
+        return self._msm.run(self.gamma_abc_g1, dev_bytes(_le32(primary))).clone()
 
     def evaluation_abc_batch(self, primaries) -> torch.Tensor:
         """evaluation_abc of every row of `primaries`, concatenated (K x 192 bytes, byte for byte what K calls of
         evaluation_abc return), through the shared-base batched MSM: the window table of gammaABC is built at the
         first call and kept with the key.  Asynchronous on the current stream."""
-        from . import device as _device
         for primary in primaries:
             if len(primary) != self.num_inputs:
                 raise ValueError("%d primary inputs for a key of %d" % (len(primary), self.num_inputs))
         if self._multi is None:
-            self._multi = _device.SharedBaseMsm(self.gamma_abc_g1, self.num_inputs)
-        return self._multi.run(_dev_bytes(b"".join(_le32(primary) for primary in primaries)), len(primaries))
+            self._multi = _dev.SharedBaseMsm(self.gamma_abc_g1, self.num_inputs)
+        return self._multi.run(dev_bytes(b"".join(_le32(primary) for primary in primaries)), len(primaries))
 
 
     MAGIC = b"OZKVK\x00\x00\x01"   # five letters, two zero bytes, format version 1
@@ -1110,7 +1030,6 @@ class VerificationKey:
     def to_bytes(self) -> bytes:
         """magic and version (8) | num_inputs u32 | 4 bytes of padding | alphaG1betaG2 (384, as the device holds it) |
         gammaG2 (64) | deltaG2 (64) | gammaABC (32 each), the points compressed"""
-        from . import codec as _codec
         g2 = _codec.compress_g2(torch.cat([self.gamma_g2.reshape(-1), self.delta_g2.reshape(-1)]))
         abc = _codec.compress_g1(self.gamma_abc_g1)
         body = torch.cat([self.alpha_g1_beta_g2.reshape(-1), g2, abc])
@@ -1120,14 +1039,13 @@ class VerificationKey:
     def from_bytes(b) -> "VerificationKey":
         """The key of to_bytes; the points are decoded on the device and the prepared lines of gamma and delta rebuilt
         by the constructor.  ValueError on a bad header or length and on any point that does not decode."""
-        from . import codec as _codec
         b = bytes(b)
         if len(b) < 16 or b[:8] != VerificationKey.MAGIC or b[12:16] != bytes(4):
             raise ValueError("not a verification key (bad magic, version or padding)")
         n = int.from_bytes(b[8:12], "little")
         if n < 1 or len(b) != 16 + 384 + 128 + 32 * n:
             raise ValueError("a verification key of %d inputs is %d bytes, not %d" % (n, 528 + 32 * n, len(b)))
-        body = _dev_bytes(b[16:])
+        body = dev_bytes(b[16:])
         g2, c2 = _codec.decompress_g2(body[384:512])
         abc, c1 = _codec.decompress_g1(body[512:])
         for i, code in enumerate(torch.cat([c2, c1]).cpu().tolist()):
@@ -1140,7 +1058,6 @@ class VerificationKey:
 def verification_key(crs: CRS) -> VerificationKey:
     """The verification key of a CRS from serial_setup_generate (SerialSetup.java:159-164): alphaG1betaG2 =
     reducedPairing(alphaG1, betaG2) computed on the device."""
-    from . import pairing as _pairing
     pk = crs.proving_key
     alpha_beta = _pairing.reduced_pairing(pk.alpha_g1, pk.beta_g2)
     return VerificationKey(alpha_beta, crs.gamma_g2, pk.delta_g2, crs.gamma_abc_g1)
@@ -1198,7 +1115,7 @@ class Verifier:
         if len(primaries) != len(proofs) or not proofs:
             raise ValueError("one primary input per proof, at least one proof")
         abc = Verifier._evaluation_abc(vk, primaries, abc)
-        recs = _dev_bytes(b"".join(proof_record(p) for p in proofs))
+        recs = dev_bytes(b"".join(proof_record(p) for p in proofs))
         return Verifier._records_verdicts(vk, recs, abc)
 
     @staticmethod
@@ -1218,7 +1135,6 @@ class Verifier:
     @staticmethod
     def _records_verdicts(vk: VerificationKey, recs, abc_points) -> list:
         """K records on the device (768 bytes each) and their evaluationABC points to K verdicts"""
-        from . import pairing as _pairing
         ok = _pairing.groth16_verify(vk.alpha_g1_beta_g2, vk.gamma_prep, vk.delta_prep, recs, abc_points)
         return [bool(v) for v in ok.cpu().tolist()]
 
@@ -1227,7 +1143,6 @@ class Verifier:
         """The randomized check over the well-formed proofs: (verdict, covered flags), verdict 1 / 0 / -1 as
         ozk_groth16_verify_rlc_dev returns it.  The proofs are `proofs`, or, with proofs None, the records `recs`
         already on the device (768 bytes each)."""
-        from . import pairing as _pairing
         k = len(proofs) if recs is None else recs.numel() // RECORD_BYTES
         if len(primaries) != k or not k:
             raise ValueError("one primary input per proof, at least one proof")
@@ -1236,9 +1151,9 @@ class Verifier:
         weights = b"".join((rng.randrange(1, 1 << 128)).to_bytes(32, "little") for _ in range(k))
         t0 = time.perf_counter()
         if recs is None:
-            recs = _dev_bytes(b"".join(proof_record(p) for p in proofs))
-        d_inputs = _dev_bytes(b"".join(rows))
-        d_r = _dev_bytes(weights)
+            recs = dev_bytes(b"".join(proof_record(p) for p in proofs))
+        d_inputs = dev_bytes(b"".join(rows))
+        d_r = dev_bytes(weights)
         if stage_ms is not None:
             torch.cuda.synchronize()
             stage_ms["upload"] = (time.perf_counter() - t0) * 1e3
@@ -1305,10 +1220,9 @@ class Verifier:
     @staticmethod
     def _decode_records(buf, k, stage_ms=None):
         """(K x 768 record bytes on the device as a (K, 768) tensor, the K codes as a list)"""
-        from . import codec as _codec
         t0 = time.perf_counter()
         if not isinstance(buf, torch.Tensor):
-            buf = _dev_bytes(bytes(buf)) if len(buf) else torch.empty(0, dtype=torch.uint8)
+            buf = dev_bytes(bytes(buf)) if len(buf) else torch.empty(0, dtype=torch.uint8)
         if buf.numel() != 128 * k or not k:
             raise ValueError("one 128-byte proof per primary input, at least one proof (%d bytes for %d)"
                              % (buf.numel(), k))

@@ -246,22 +246,22 @@ def test_receipt_parsing_is_strict(label):
 
 def test_host_decode_codes_match_the_codec_model():
     """the receipt parser's own point check against tests/codec_ref.py, every malformed class"""
-    from octopuszk_amd import ceremony
+    from octopuszk_amd import codec
     for type_ in (1, 2):
         encs, bad = cases.encodings(type_, 80, seed=9)
         assert len({cls for cls, _ in bad.values()}) >= 5
         for e in encs:
-            assert ceremony._decode_code(e, type_) == cases.decode(type_, e)[0], e.hex()
+            assert codec.decode_code(e, type_) == cases.decode(type_, e)[0], e.hex()
 
 
 def test_weight_stream_matches_the_model():
-    from octopuszk_amd import ceremony
+    from octopuszk_amd import ceremony, transcript
     for n in (1, 2, 5, 64):
-        raw = ceremony._weights(SEED, n)
+        raw = transcript.weights(SEED, n, ceremony._RHO_TAG)
         got = [int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(n)]
         assert got == cref.weights(SEED, n) and all(1 <= w < 1 << 128 for w in got)
     assert cref.weights(SEED, 5) == cref.weights(SEED, 6)[:5] and cref.weights(SEED, 4) != cref.weights(b"other", 4)
-    assert ceremony._seed_bytes(5) == (5).to_bytes(32, "little") and len(ceremony._seed_bytes(None)) == 32
+    assert transcript.seed_bytes(5) == (5).to_bytes(32, "little") and len(transcript.seed_bytes(None)) == 32
 
 
 def test_bad_scalars_raise_before_any_library_call(monkeypatch):

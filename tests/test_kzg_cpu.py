@@ -161,7 +161,7 @@ def test_verify_key_bytes_round_trip_and_failures(monkeypatch):
     tau_g1, (g2, tau_g2) = kr.string(1, 9)
     b = kr.vk_bytes(tau_g1[0], g2, tau_g2)
     assert len(b) == kzg.VK_BYTES == kr.VK_BYTES
-    # the subgroup test runs on the device (srs._in_subgroup): here the model's stands in for it, fed by what
+    # the subgroup test runs on the device (vectors.in_subgroup_g2): here the model's stands in for it, fed by what
     # from_bytes hands it
     monkeypatch.setattr(kzg.VerifyKey, "points", lambda self: (None, bytes(384)))
     monkeypatch.setattr(kzg, "_g2_in_subgroup", _subgroup_model)
@@ -189,9 +189,9 @@ def test_verify_key_bytes_round_trip_and_failures(monkeypatch):
 
 
 def test_streams_match_the_model():
-    from octopuszk_amd import ceremony, kzg
+    from octopuszk_amd import kzg, transcript
     seed = bytes(range(32))
-    assert kr.ints(ceremony._weights(seed, 5, kzg._RHO_TAG)) == kr.rho(seed, 5)
+    assert kr.ints(transcript.weights(seed, 5, kzg._RHO_TAG)) == kr.rho(seed, 5)
     assert kr.rho(seed, 5) != cref.weights(seed, 5)
     cs = [kr.le(i + 1) for i in range(3)]
     assert kzg.combine_challenge(7, cs, [1, 2, 3]) == kr.gamma(7, cs, [1, 2, 3])

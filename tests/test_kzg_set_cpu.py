@@ -264,7 +264,7 @@ def test_set_verify_key_bytes_round_trip_and_failures(monkeypatch):
     tau_g1, tau_g2 = ks.string(t_max, 9)
     b = ks.vk_bytes(tau_g1, tau_g2)
     assert len(b) == 4 + 32 * t_max + 64 * (t_max + 1)
-    # the subgroup test runs on the device (srs._in_subgroup): here the model's stands in for it, fed by what
+    # the subgroup test runs on the device (vectors.in_subgroup_g2): here the model's stands in for it, fed by what
     # from_bytes hands it
     monkeypatch.setattr(kzg.SetVerifyKey, "points", lambda self: (None, bytes(192 * (self.t_max + 1))))
     monkeypatch.setattr(kzg, "_g2_in_subgroup", _subgroup_model)
@@ -296,10 +296,10 @@ def test_set_verify_key_bytes_round_trip_and_failures(monkeypatch):
 
 
 def test_streams_match_literal_recomputation():
-    from octopuszk_amd import ceremony, kzg
+    from octopuszk_amd import kzg, transcript
     seed = bytes(range(32))
     assert kzg._SET_RHO_TAG == b"OZK-kzg-set-rho" and kzg._SET_GAMMA_TAG == b"OZK-kzg-set-gamma"
-    got = kr.ints(ceremony._weights(seed, 5, kzg._SET_RHO_TAG))
+    got = kr.ints(transcript.weights(seed, 5, kzg._SET_RHO_TAG))
     blocks = [hashlib.sha256(b"OZK-kzg-set-rho" + seed + j.to_bytes(8, "little")).digest() for j in range(3)]
     want = [int.from_bytes(blk[h:h + 16], "little") or 1 for blk in blocks for h in (0, 16)][:5]
     assert got == want == ks.rho(seed, 5) and got != kr.rho(seed, 5)

@@ -197,7 +197,7 @@ def test_argument_errors_without_a_device():
             srs.Srs.from_secrets(m, TAU, ALPHA, BETA)
     assert srs.CHECKS == ("shape", "powers_g1", "powers_g2", "alpha_powers", "beta_powers", "beta_g2")
     # the weight stream has its own tag: it is not the stream of a phase-2 check over the same seed
-    from octopuszk_amd import ceremony
-    assert srs._weights(b"s", 3) != ceremony._weights(b"s", 3)
-    w = srs._weights(b"s", 3)
+    from octopuszk_amd import ceremony, transcript
+    assert transcript.weights(b"s", 3, srs._RHO_TAG) != transcript.weights(b"s", 3, ceremony._RHO_TAG)
+    w = transcript.weights(b"s", 3, srs._RHO_TAG)
     assert len(w) == 96 and all(w[32 * i + 16:32 * i + 32] == bytes(16) and any(w[32 * i:32 * i + 16]) for i in range(3))

@@ -87,9 +87,10 @@ def _multi_msm(quick):
 
 def _batched_stages(z, pa, vk, prims, proofs):
     """device time of the two stages of verify_batch(abc="batched") on inputs already in HBM"""
+    from octopuszk_amd import wire
     k = len(proofs)
-    d_rows = z._dev_bytes(b"".join(z._le32(p) for p in prims))
-    recs = z._dev_bytes(b"".join(z.proof_record(p) for p in proofs))
+    d_rows = wire.dev_bytes(b"".join(wire.le32(p) for p in prims))
+    recs = wire.dev_bytes(b"".join(z.proof_record(p) for p in proofs))
     abc = vk.evaluation_abc_batch(prims[:1])   # (the table exists from here on)
     t_abc = _timed(lambda: vk._multi.run(d_rows, k), 5)
     abc = vk._multi.run(d_rows, k)
@@ -99,13 +100,13 @@ def _batched_stages(z, pa, vk, prims, proofs):
 
 def _compressed(z, vk, prims, proof, k, t_all):
     """the compressed-proof path at K = k: decoding alone, verify_all_bytes, and the Python-integer baseline"""
-    from octopuszk_amd import codec
+    from octopuszk_amd import codec, wire
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import codec_ref
     one = proof.to_bytes()
     assert z.proof_record(z.Proof.from_bytes(one)) == z.proof_record(proof)
     buf = one * k
-    d_buf = z._dev_bytes(buf)
+    d_buf = wire.dev_bytes(buf)
     recs, codes = codec.decompress_proofs(d_buf)
     assert not codes.any().item()
     t_dec = _timed(lambda: codec.decompress_proofs(d_buf), 5)

@@ -32,7 +32,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
 
 import kzg_bench as kb  # noqa: E402
-from octopuszk_amd import codec, kzg, lib as _lib  # noqa: E402
+from octopuszk_amd import codec, kzg, lib as _lib, vectors  # noqa: E402
 from octopuszk_amd import device as dev  # noqa: E402
 from octopuszk_amd.device import _ptr, _stream  # noqa: E402
 from octopuszk_amd.fft import FR, root_of_unity  # noqa: E402
@@ -105,7 +105,7 @@ def mac_against_chain(terms, log, reps):
     L = _lib.load()
     points = dev.gen_g1_bases(terms * n, seed=23)
     scalars = kb._random_rows(1, terms * n, 7).reshape(-1)
-    table = kzg.points_mac_prepare(points, terms, n)
+    table = vectors.points_mac_prepare(points, terms, n)
     ws = torch.empty(int(L.ozk_points_mac_workspace_bytes(terms, n, 1)), dtype=torch.uint8, device="cuda")
     out = torch.empty(96 * n, dtype=torch.uint8, device="cuda")
     acc, prod = torch.empty_like(out), torch.empty_like(out)

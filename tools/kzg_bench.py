@@ -7,7 +7,6 @@ G1 MSM of the same n through the existing entry point.  One JSON line.
 The string is built from a known tau (G1 powers and two G2 points only), so every opening verifies.
 """
 import argparse
-import ctypes
 import json
 import os
 import statistics
@@ -21,7 +20,7 @@ if ROOT not in sys.path:
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from octopuszk_amd import kzg, lib as _lib  # noqa: E402
+from octopuszk_amd import kzg, lib as _lib, wire  # noqa: E402
 from octopuszk_amd import zksnark as z  # noqa: E402
 from octopuszk_amd.device import VarMsmWorkspace, _ptr, _stream  # noqa: E402
 from octopuszk_amd.fft import FR, root_of_unity  # noqa: E402
@@ -39,13 +38,12 @@ class _String:
         d_sc = torch.empty(n * 32, dtype=torch.uint8, device="cuda")
         wsb = int(L.ozk_fr_powers_workspace_bytes(n))
         ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
-        tb, kb = z._le32_one(TAU), z._le32_one(1)
-        _lib.check(L.ozk_fr_powers_dev(ctypes.cast(tb, ctypes.c_void_p), ctypes.cast(kb, ctypes.c_void_p), n, _ptr(d_sc),
-                                       _ptr(ws), wsb, _stream()))
+        tb, kb = wire.le32([TAU]), wire.le32([1])
+        _lib.check(L.ozk_fr_powers_dev(wire.vp(tb), wire.vp(kb), n, _ptr(d_sc), _ptr(ws), wsb, _stream()))
         torch.cuda.synchronize()
         self.m = m
-        self.tau_g1 = z.batch_msm_dev(254, get_window_size(n, G1_WINDOW_TABLE), z.g1_wire(z.G1_ONE), d_sc, 1)
-        self.tau_g2 = z.batch_msm_dev(254, 16, z.g2_wire(z.G2_ONE), [1, TAU], 2)
+        self.tau_g1 = z.batch_msm_dev(254, get_window_size(n, G1_WINDOW_TABLE), wire.g1_wire(z.G1_ONE), d_sc, 1)
+        self.tau_g2 = z.batch_msm_dev(254, 16, wire.g2_wire(z.G2_ONE), [1, TAU], 2)
 
 
 def _median_ms(fn, reps):
@@ -101,16 +99,16 @@ def run(log, reps, kbatch):
     # the kernels alone
     quot = torch.empty(n * 32, dtype=torch.uint8, device="cuda")
     val = torch.empty(32, dtype=torch.uint8, device="cuda")
-    pts = z._dev_bytes(kzg._le(zpt))
+    pts = wire.dev_bytes(wire.le32(zpt))
     wsb = int(L.ozk_fr_poly_open_workspace_bytes(1, n))
     ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device="cuda")
     res["poly_open_kernel_ms"] = _event_ms(lambda: _lib.check(L.ozk_fr_poly_open_dev(
         _ptr(rows), 1, n, n, _ptr(pts), _ptr(quot), n, _ptr(val), _ptr(ws), ws.numel(), _stream())), reps)
     wsb = int(L.ozk_fr_evals_open_workspace_bytes(1, n))
     ws2 = torch.empty(max(wsb, 256), dtype=torch.uint8, device="cuda")
-    om = kzg._le([root_of_unity(n)])
+    om = wire.le32([root_of_unity(n)])
     res["evals_open_kernel_ms"] = _event_ms(lambda: _lib.check(L.ozk_fr_evals_open_dev(
-        _ptr(rows), 1, n, n, kzg._vp(om), _ptr(pts), _ptr(quot), n, _ptr(val), _ptr(ws2), ws2.numel(), _stream())), reps)
+        _ptr(rows), 1, n, n, wire.vp(om), _ptr(pts), _ptr(quot), n, _ptr(val), _ptr(ws2), ws2.numel(), _stream())), reps)
     # the lone MSM of the same n over the same prepared bases
     msm = VarMsmWorkspace(n, 1)
     res["msm_ms"] = _event_ms(lambda: msm.run(ck.bases(), rows.reshape(-1), prepared=True), reps)

@@ -20,7 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
 
 import kzg_bench as kb  # noqa: E402
-from octopuszk_amd import kzg, lib as _lib  # noqa: E402
+from octopuszk_amd import kzg, lib as _lib, wire  # noqa: E402
 from octopuszk_amd import zksnark as z  # noqa: E402
 from octopuszk_amd.device import VarMsmWorkspace, _ptr, _stream  # noqa: E402
 from octopuszk_amd.fft import FR, root_of_unity  # noqa: E402
@@ -31,7 +31,7 @@ class _String(kb._String):
 
     def __init__(self, m):
         super().__init__(m)
-        self.tau_g2 = z.batch_msm_dev(254, 16, z.g2_wire(z.G2_ONE), [pow(kb.TAU, i, FR) for i in range(33)], 2)
+        self.tau_g2 = z.batch_msm_dev(254, 16, wire.g2_wire(z.G2_ONE), [pow(kb.TAU, i, FR) for i in range(33)], 2)
 
 
 def _points(t, salt=0):
@@ -53,18 +53,18 @@ def run(log, reps, kbatch, ts):
     val = torch.empty(32 * 32, dtype=torch.uint8, device="cuda")
     wsb = int(L.ozk_fr_poly_open_workspace_bytes(1, n))
     ws1 = torch.empty(max(wsb, 256), dtype=torch.uint8, device="cuda")
-    om = kzg._le([root_of_unity(n)])
+    om = wire.le32([root_of_unity(n)])
     msm = VarMsmWorkspace(n, 1)
     res["msm_ms"] = kb._event_ms(lambda: msm.run(ck.bases(), rows.reshape(-1), prepared=True), reps)
     for t in ts:
         pts = _points(t)
-        host = kzg._le(pts)
-        d_pts = z._dev_bytes(host)
+        host = wire.le32(pts)
+        d_pts = wire.dev_bytes(host)
         r = {}
         wsb = int(L.ozk_fr_poly_open_set_workspace_bytes(1, n, t))
         ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device="cuda")
         r["poly_open_set_kernel_ms"] = kb._event_ms(lambda: _lib.check(L.ozk_fr_poly_open_set_dev(
-            _ptr(rows), 1, n, n, t, kzg._vp(host), _ptr(quot), n, _ptr(val), _ptr(ws), ws.numel(), _stream())), reps)
+            _ptr(rows), 1, n, n, t, wire.vp(host), _ptr(quot), n, _ptr(val), _ptr(ws), ws.numel(), _stream())), reps)
 
         def chain():
             # t divisions by one linear factor each, the quotient of one the dividend of the next
@@ -79,7 +79,7 @@ def run(log, reps, kbatch, ts):
             wsb = int(L.ozk_fr_evals_open_set_workspace_bytes(1, n, t))
             ws2 = torch.empty(max(wsb, 256), dtype=torch.uint8, device="cuda")
             r["evals_open_set_kernel_ms"] = kb._event_ms(lambda: _lib.check(L.ozk_fr_evals_open_set_dev(
-                _ptr(rows), 1, n, n, kzg._vp(om), t, kzg._vp(host), _ptr(quot), n, _ptr(val), _ptr(ws2), ws2.numel(),
+                _ptr(rows), 1, n, n, wire.vp(om), t, wire.vp(host), _ptr(quot), n, _ptr(val), _ptr(ws2), ws2.numel(),
                 _stream())), reps)
             assert kzg.verify_set(vk, ck.open_set_evals(rows, pts)[0])
         r["open_set_ms"] = kb._median_ms(lambda: ck.open_set(rows, pts), reps)

@@ -15,7 +15,6 @@ contribute, save, load and verify_contribution; compares ozk_points_mul_dev with
 ozk_sparse_mat_points_dev over the same points and scalars; builds a key from the contributed string, proves and
 verifies; and writes profiles/srs_contribute_2pLOGN.json with the counted figure next to each measured one.  It exits
 non-zero unless the contribution verifies, the two routes agree, the new kernel is the faster and the proof verifies."""
-import ctypes
 import json
 import os
 import secrets
@@ -94,7 +93,7 @@ def _timed(fn, repeat=1):
 
 
 def measure(logn):
-    from octopuszk_amd import ceremony, srs
+    from octopuszk_amd import srs, vectors, wire
     from octopuszk_amd import lib as _lib
     from octopuszk_amd import zksnark as z
     from octopuszk_amd.device import _ptr, _stream
@@ -114,28 +113,28 @@ def measure(logn):
         d_sc = torch.empty(n * 32, dtype=torch.uint8, device="cuda")
         wsb = int(L.ozk_fr_powers_workspace_bytes(n))
         ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device="cuda")
-        _lib.check(L.ozk_fr_powers_dev(ctypes.cast(z._le32_one(s), ctypes.c_void_p), ctypes.cast(z._le32_one(k), ctypes.c_void_p),
-                                       n, _ptr(d_sc), _ptr(ws), wsb, _stream()))
+        _lib.check(L.ozk_fr_powers_dev(wire.vp(wire.le32([s])), wire.vp(wire.le32([k])), n, _ptr(d_sc), _ptr(ws), wsb,
+                                       _stream()))
         torch.cuda.synchronize()
         return d_sc
 
     # the five scalings, one by one (warm the kernels on a few points first)
     pw, pa, pb = powers(1, 2 * m + 1), powers(a, m), powers(b, m)
-    srs.mul_points(before.tau_g1.reshape(-1)[:96 * 64], pw[:32 * 64], 1)
-    srs.mul_points(before.tau_g2.reshape(-1)[:192 * 64], pw[:32 * 64], 2)
+    vectors.mul_points(before.tau_g1.reshape(-1)[:96 * 64], pw[:32 * 64], 1)
+    vectors.mul_points(before.tau_g2.reshape(-1)[:192 * 64], pw[:32 * 64], 2)
     for name, points, sc, type_, n in (("tau_g1", before.tau_g1, pw, 1, 2 * m + 1), ("tau_g2", before.tau_g2, pw[:32 * m], 2, m),
                                        ("alpha_tau_g1", before.alpha_tau_g1, pa, 1, m), ("beta_tau_g1", before.beta_tau_g1, pb, 1, m)):
-        _, dt = _timed(lambda: srs.mul_points(points, sc, type_), repeat=2)
+        _, dt = _timed(lambda: vectors.mul_points(points, sc, type_), repeat=2)
         stage("mul_" + name, dt, n, G1_MULS if type_ == 1 else G2_MULS)
-    _, dt = _timed(lambda: ceremony.scale_points(before.beta_g2, b, 2), repeat=2)
+    _, dt = _timed(lambda: vectors.scale_points(before.beta_g2, b, 2), repeat=2)
     stage("scale_beta_g2", dt, 1)
     # the comparison: the diagonal matrix of the same scalars over the same points
     n = min(m, 1 << 20)
-    ks = z._ints_from_dev(pa[:32 * n])
+    ks = wire.ints32(wire.host_bytes(pa[:32 * n]))
     mat = z._CsrDevice(np.arange(n + 1, dtype=np.int64), np.arange(n, dtype=np.int64), np.array(ks, dtype=object))
     pts = before.alpha_tau_g1.reshape(-1)[:96 * n]
-    new, t_new = _timed(lambda: srs.mul_points(pts, pa[:32 * n], 1), repeat=3)
-    old, t_old = _timed(lambda: srs.sparse_mat_points(mat, pts, 1), repeat=3)
+    new, t_new = _timed(lambda: vectors.mul_points(pts, pa[:32 * n], 1), repeat=3)
+    old, t_old = _timed(lambda: vectors.sparse_mat_points(mat, pts, 1), repeat=3)
     res["comparison"] = {"points": n, "points_mul_s": round(t_new, 5), "diagonal_sparse_mat_points_s": round(t_old, 5),
                          "ratio": round(t_old / t_new, 3), "counted_ratio": round(254 * 18 / G1_MULS, 2),
                          "bit_equal": bool(torch.equal(new, old))}
