@@ -166,9 +166,10 @@ OZK_BIG Fe12 f12_prod_range(const u32* f_in, long stride, long lo, long hi) {
   return acc;
 }
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) && !defined(OZK_BV_NO_KERNELS)
 // ---------------------------------------------------------------------------------------------- kernels
-// (miller, g1_affine, g2_affine: pairing.hip)
+// (miller, g1_affine, g2_affine: pairing.hip; tests/native/towercheck.hip, which has none of them, defines
+// OZK_BV_NO_KERNELS and takes the arithmetic above alone)
 
 __global__ __launch_bounds__(64) void k_wellformed(const u32* __restrict__ recs, int k, int32_t* __restrict__ ok) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

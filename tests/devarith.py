@@ -20,8 +20,9 @@ ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "native", "devcheck.hip")
 LIB = os.path.join(HERE, "native", "_devcheck.so")
 CSRC = os.path.join(ROOT, "octopuszk_amd", "csrc")
-DEPS = [SRC] + [os.path.join(CSRC, f) for f in ("fp29.cuh", "fq2.cuh", "ec.cuh", "quad.cuh", "curve.cuh",
-                                                 "consts_gen.h", "mad_chain_gen.h")]
+DEPS = [SRC, os.path.join(HERE, "native", "devcheck_common.h")] + [
+    os.path.join(CSRC, f) for f in ("fp29.cuh", "fq2.cuh", "ec.cuh", "quad.cuh", "curve.cuh", "consts_gen.h",
+                                    "mad_chain_gen.h")]
 
 W = 29
 MASK = (1 << W) - 1
@@ -266,6 +267,15 @@ def fq2_expect(name, v):
     if name == "fq2_sub_sub2":
         a, b, c = el(0), el(1), el(2)
         return F.sub(F.sub(a, b), F.add(c, c))
+    if name == "fq2_scale":                       # the scalar is one Fq operand after the element
+        return mont((el(0)[0] * v[2] % Q, el(0)[1] * v[2] % Q))
+    if name == "fq2_inv":                         # (x R)^-1 R^2 = x^-1 R; zero gives zero
+        a = el(0)
+        return a if F.is_zero(a) else tuple(c * RQ % Q * RQ % Q for c in F.inv(a))
+    if name == "fq2_is_zero":
+        return [int(F.is_zero(el(0)))]
+    if name == "fq2_reduce_to":
+        return el(0)
     raise KeyError(name)
 
 

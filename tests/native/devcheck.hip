@@ -3,77 +3,14 @@
 // laws (quad.cuh DPP broadcasts, fq2.cuh lane pair / octet shuffles).  Compiled with the library's own hipcc flags
 // (octopuszk_amd/build.py HIPCC_FLAGS), never linked into libozk_hip.so; driven by tests/test_device_arith_gpu.py.
 //
-// Every operation is a struct: `In` lists its operand types, run() applies it.  Each lane reads its operands as raw
-// 9-limb records (operand k of lane i at in[(k * n + i) * 9]), applies the operation once and writes the raw limbs
-// of every output element (out[(i * NOUT + j) * 9]).  dc_info() reports each operand's and each output's bound from
-// the C++ types themselves (decltype of run()), so the test checks what the type claims, not a copy of it.
+// The record layout, the bound reports and the launcher are devcheck_common.h's (shared with towercheck.hip); this
+// file holds the operation lists and the records of the types only it uses (lane-pair Fq2, points).
 #include "../../octopuszk_amd/csrc/fq2.cuh"
-#include <string.h>
-#include <type_traits>
-using namespace ozk;
+#include "devcheck_common.h"
 
-namespace {
-
-// ---- bounds of a type: element count, and per element (value bound in sixteenths of p, limb bound LU in units of
-// 2^28; LU 2 = normalised).  Special kinds: B = 0 a bool (word 0), B = -1 eight packed words, B = -2 a wire operand.
-struct Wire {
-  u32 w[8];
-};
-struct Words {
-  u32 w[8];
-};
-struct Flag {
-  bool v;
-};
-template <class T>
-struct Bnd;
-template <class P, int B>
-struct Bnd<Fe<P, B>> {
-  static constexpr int N = 1;
-  static void get(int* b, int* l) { b[0] = B, l[0] = 2; }
-};
-template <class P, int B, int L>
-struct Bnd<FeL<P, B, L>> {
-  static constexpr int N = 1;
-  static void get(int* b, int* l) { b[0] = B, l[0] = L; }
-};
-template <int B>
-struct Bnd<Fe2<B>> {
-  static constexpr int N = 2;
-  static void get(int* b, int* l) { b[0] = b[1] = B, l[0] = l[1] = 2; }
-};
+namespace dc {
 template <int B>
 struct Bnd<Fe2L<B>> : Bnd<Fe2<B>> {};
-template <>
-struct Bnd<bool> {
-  static constexpr int N = 1;
-  static void get(int* b, int* l) { b[0] = 0, l[0] = 0; }
-};
-template <>
-struct Bnd<Flag> : Bnd<bool> {};
-template <>
-struct Bnd<Words> {
-  static constexpr int N = 1;
-  static void get(int* b, int* l) { b[0] = -1, l[0] = 0; }
-};
-template <>
-struct Bnd<Wire> {
-  static constexpr int N = 1;
-  static void get(int* b, int* l) { b[0] = -2, l[0] = 0; }
-};
-template <class A, class B>
-struct Pair2 {  // two elements written one after the other (a point's coordinates)
-  A a;
-  B b;
-};
-template <class A, class B>
-struct Bnd<Pair2<A, B>> {
-  static constexpr int N = Bnd<A>::N + Bnd<B>::N;
-  static void get(int* b, int* l) {
-    Bnd<A>::get(b, l);
-    Bnd<B>::get(b + Bnd<A>::N, l + Bnd<A>::N);
-  }
-};
 template <class CV>
 struct Bnd<Jac<CV>> : Bnd<Pair2<typename CV::EX, Pair2<typename CV::EY, typename CV::EZ>>> {};
 template <class CV>
@@ -82,90 +19,8 @@ struct Bnd<Xyzz<CV>>
 template <class EA>
 struct Bnd<Aff<EA>> : Bnd<Pair2<EA, EA>> {};
 
-template <class... T>
-struct TL {
-  static constexpr int N = (0 + ... + Bnd<T>::N);
-  static void get(int* b, int* l) {
-    int k = 0;
-    ((Bnd<T>::get(b + k, l + k), k += Bnd<T>::N), ...);
-  }
-};
-
-// ---- raw record <-> typed value (device side)
-template <class T>
-struct Raw;
-template <class P, int B>
-struct Raw<Fe<P, B>> {
-  static __device__ Fe<P, B> ld(const u32* const* x) {
-    Fe<P, B> r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = x[0][i];
-    return r;
-  }
-  static __device__ void st(const Fe<P, B>& v, u32* o) {
-#pragma unroll
-    for (int i = 0; i < 9; i++) o[i] = v.l[i];
-  }
-};
-template <class P, int B, int L>
-struct Raw<FeL<P, B, L>> {
-  static __device__ FeL<P, B, L> ld(const u32* const* x) {
-    FeL<P, B, L> r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = x[0][i];
-    return r;
-  }
-  static __device__ void st(const FeL<P, B, L>& v, u32* o) {
-#pragma unroll
-    for (int i = 0; i < 9; i++) o[i] = v.l[i];
-  }
-};
-template <template <int> class E, int B>
-struct RawFq2 {
-  static __device__ E<B> ld(const u32* const* x) {
-    E<B> r;
-    r.c0 = Raw<Fe<FqParams, B>>::ld(x);
-    r.c1 = Raw<Fe<FqParams, B>>::ld(x + 1);
-    return r;
-  }
-  static __device__ void st(const E<B>& v, u32* o) {
-    Raw<Fe<FqParams, B>>::st(v.c0, o);
-    Raw<Fe<FqParams, B>>::st(v.c1, o + 9);
-  }
-};
-template <int B>
-struct Raw<Fe2<B>> : RawFq2<Fe2, B> {};
 template <int B>
 struct Raw<Fe2L<B>> : RawFq2<Fe2L, B> {};
-template <>
-struct Raw<bool> {
-  static __device__ void st(bool v, u32* o) {
-    o[0] = v ? 1u : 0u;
-#pragma unroll
-    for (int i = 1; i < 9; i++) o[i] = 0;
-  }
-};
-template <>
-struct Raw<Flag> {
-  static __device__ Flag ld(const u32* const* x) { return Flag{x[0][0] != 0}; }
-};
-template <>
-struct Raw<Words> {
-  static __device__ void st(const Words& v, u32* o) {
-#pragma unroll
-    for (int i = 0; i < 8; i++) o[i] = v.w[i];
-    o[8] = 0;
-  }
-};
-template <>
-struct Raw<Wire> {
-  static __device__ Wire ld(const u32* const* x) {
-    Wire r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) r.w[i] = x[0][i];
-    return r;
-  }
-};
 template <class CV>
 struct Raw<Jac<CV>> {
   static constexpr int NX = Bnd<typename CV::EX>::N, NY = Bnd<typename CV::EY>::N;
@@ -208,36 +63,10 @@ struct Raw<Aff<EA>> {
     return r;
   }
 };
+}  // namespace dc
+using namespace dc;
 
-template <class T>
-__device__ T ld(const u32* const* x) {
-  return Raw<T>::ld(x);
-}
-
-// ---- the operations.  D(NAME, GROUP, OPERANDS..., BODY over a0, a1, ...) defines one; GROUP is the number of lanes
-// that hold one case (1, or 2 / 4 / 8 for the lane-pair, quad and octet code).
-#define COMMA ,
-#define DC_A(k, T) const auto a##k = ld<T>(x + off[k]);
-template <int G, class... T>
-struct OpBase {
-  using In = TL<T...>;
-  static constexpr int GROUP = G;
-  static constexpr int PARAM = 0;  // csub's K
-  static __device__ void offsets(int (&off)[8]) {
-    int k = 0, o = 0;
-    ((off[k++] = o, o += Bnd<T>::N), ...);
-  }
-};
-
-#define DC_OP(ID, NAME, G, ARGS, ...)                                                 \
-  struct ID : OpBase<G, __VA_ARGS__> {                                               \
-    static constexpr const char* name = NAME;                                        \
-    static __device__ auto run(const u32* const* x) {                                \
-      int off[8];                                                                    \
-      OpBase<G, __VA_ARGS__>::offsets(off);                                          \
-      ARGS                                                                           \
-    }                                                                                \
-  };
+namespace {
 
 constexpr int SLACK = MONT_SLACK;
 constexpr int isqrt_c(int v) {
@@ -379,6 +208,16 @@ template <int B1, int B2>
 DC_OP(Fq2PairMul, "fq2_mul", 2, DC_A(0, Fe2L<B1>) DC_A(1, Fe2L<B2>) return mul(a0, a1);, Fe2L<B1>, Fe2L<B2>)
 template <int B>
 DC_OP(Fq2PairSqr, "fq2_sqr", 2, DC_A(0, Fe2L<B>) return sqr(a0);, Fe2L<B>)
+// the forms the pairing tower (fq12.cuh) instantiates beside the products
+template <int B>
+DC_OP(Fq2Scale, "fq2_scale", 1, DC_A(0, Fe2<B>) DC_A(1, Fe<FqParams COMMA 16>) return scale(a0, a1);, Fe2<B>,
+      Fe<FqParams, 16>)
+template <int B>
+DC_OP(Fq2Inv, "fq2_inv", 1, DC_A(0, Fe2<B>) return inv(a0);, Fe2<B>)
+template <int B>
+DC_OP(Fq2IsZero, "fq2_is_zero", 1, DC_A(0, Fe2<B>) return is_zero(a0);, Fe2<B>)
+template <int TB, int B>
+DC_OP(Fq2ReduceTo, "fq2_reduce_to", 1, DC_A(0, Fe2<B>) return reduce_to<TB>(a0);, Fe2<B>)
 DC_OP(G1MaddLazy, "g1_xyzz_madd", 1,
       DC_A(0, Xyzz<G1Cfg>) DC_A(1, Aff<G1Cfg::EA>) DC_A(2, Flag) return xyzz_madd_lazy(a0, a1, a2.v);, Xyzz<G1Cfg>,
       Aff<G1Cfg::EA>, Flag)
@@ -393,72 +232,10 @@ using ExtList = TL<Fq2Mul<32, 32>, Fq2Mul<144, 112>, Fq2Mul<176, 80>, Fq2Sqr<32>
                    Fq2MulLz<144, 32>, Fq2SqrLz<32>, Fq2MulsubLz<32, 32, 80, 32>, Fq2MulsubLz<32, 32, 80, 17>,
                    Fq2SubSub2<32, 32, 32>, Fq2SubSub2<32, 32, 17>, Fq2PairMul<32, 32>, Fq2PairMul<112, 32>,
                    Fq2PairMul<144, 32>, Fq2PairSqr<32>, Fq2PairSqr<112>, G1MaddLazy, G1QuadDbl, G1QuadAdd, G2OctetDbl,
-                   G2OctetAdd>;
-
-template <class L>
-struct Nth;
-template <class... T>
-struct Nth<TL<T...>> {
-  static constexpr int N = sizeof...(T);
-};
-template <int I, class L>
-struct At;
-template <int I, class H, class... T>
-struct At<I, TL<H, T...>> : At<I - 1, TL<T...>> {};
-template <class H, class... T>
-struct At<0, TL<H, T...>> {
-  using type = H;
-};
-
-template <class Op>
-using OutT = std::decay_t<decltype(Op::run(nullptr))>;
-
-template <class Op>
-__global__ void k_op(const u32* __restrict__ in, u32* __restrict__ out, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  // a lane past the end still runs (on a copy of lane 0's operands) so that no lane group is split, but writes nothing
-  const int src = i < n ? i : 0;
-  constexpr int NIN = Op::In::N;
-  const u32* x[NIN];
-#pragma unroll
-  for (int k = 0; k < NIN; k++) x[k] = in + ((size_t)k * n + src) * 9;
-  const auto r = Op::run(x);
-  if (i < n) Raw<OutT<Op>>::st(r, out + (size_t)i * Bnd<OutT<Op>>::N * 9);
-}
-
-template <class L, int I = 0>
-int launch(int idx, const u32* in, u32* out, int n, hipStream_t s) {
-  if constexpr (I == Nth<L>::N) {
-    return -1;
-  } else {
-    if (idx != I) return launch<L, I + 1>(idx, in, out, n, s);
-    using Op = typename At<I, L>::type;
-    (void)hipGetLastError();  // drop a stale error left by somebody else's call
-    constexpr int BLOCK = 256;
-    hipLaunchKernelGGL(k_op<Op>, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, in, out, n);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-  }
-}
-
-// info: [GROUP, NIN, NOUT, PARAM, in bounds (NIN), in LU (NIN), out bounds (NOUT), out LU (NOUT)]
-template <class L, int I = 0>
-int info(int idx, char* name, int* v) {
-  if constexpr (I == Nth<L>::N) {
-    return -1;
-  } else {
-    if (idx != I) return info<L, I + 1>(idx, name, v);
-    using Op = typename At<I, L>::type;
-    constexpr int NIN = Op::In::N, NOUT = Bnd<OutT<Op>>::N;
-    strcpy(name, Op::name);
-    v[0] = Op::GROUP;
-    v[1] = NIN;
-    v[2] = NOUT;
-    v[3] = Op::PARAM;
-    Op::In::get(v + 4, v + 4 + NIN);
-    Bnd<OutT<Op>>::get(v + 4 + 2 * NIN, v + 4 + 2 * NIN + NOUT);
-    return 0;
-  }
-}
+                   G2OctetAdd,
+                   // the tower's Fq2 instantiations (appended: the cases above are seeded by their index)
+                   Fq2Mul<32, 64>, Fq2Mul<32, 80>, Fq2Mul<64, 64>, Fq2Scale<32>, Fq2Scale<64>, Fq2Inv<32>,
+                   Fq2IsZero<32>, Fq2IsZero<80>, Fq2ReduceTo<32, 64>, Fq2ReduceTo<32, 112>>;
 
 }  // namespace
 
@@ -477,10 +254,11 @@ extern "C" int dc_info(int field, int idx, char* name, int* v) {
 // in: NIN x n records of 9 words, out: n x NOUT records of 9 words, both device buffers; n a multiple of the group
 extern "C" int dc_run(int field, int idx, const void* in, void* out, int n, void* stream) {
   const hipStream_t s = (hipStream_t)stream;
+  constexpr int BLOCK = 256, LB = 1024;  // 256 lanes per block, no launch bound below the compiler's default
   if (n <= 0) return -3;
-  if (field == 0) return launch<FieldOps<FqParams>::List>(idx, (const u32*)in, (u32*)out, n, s);
-  if (field == 1) return launch<FieldOps<FrParams>::List>(idx, (const u32*)in, (u32*)out, n, s);
-  if (field == 2) return launch<ExtList>(idx, (const u32*)in, (u32*)out, n, s);
+  if (field == 0) return launch<FieldOps<FqParams>::List, LB>(idx, (const u32*)in, (u32*)out, nullptr, n, BLOCK, s);
+  if (field == 1) return launch<FieldOps<FrParams>::List, LB>(idx, (const u32*)in, (u32*)out, nullptr, n, BLOCK, s);
+  if (field == 2) return launch<ExtList, LB>(idx, (const u32*)in, (u32*)out, nullptr, n, BLOCK, s);
   return -1;
 }
 // the constants the input builders need from the headers: MONT_SLACK, FE_MAXK

@@ -26,7 +26,8 @@ def test_harness_cross_compiles_and_reports_its_operations(dc):
                 assert B in (0, -1, -2) or (1 <= B <= 16 * dc.dc_const(1) and 2 <= LU <= 15)
     for n in ("mul", "sqr", "mul2", "mul4", "mulsub", "add", "dbl", "sub", "neg", "csub", "reduce_to", "reduce_q",
               "canonical", "canonical_q", "unpack", "pack", "inv", "is_zero", "eq", "normalise", "sub_sub2",
-              "fq2_mul", "fq2_sqr", "fq2_mulsub", "fq2_sub_sub2", "g1_xyzz_madd", "g1_jac_dbl", "g1_jac_add",
+              "fq2_mul", "fq2_sqr", "fq2_mulsub", "fq2_sub_sub2", "fq2_scale", "fq2_inv", "fq2_is_zero",
+              "fq2_reduce_to", "g1_xyzz_madd", "g1_jac_dbl", "g1_jac_add",
               "g2_jac_dbl", "g2_jac_add"):
         assert n in names, n
 
@@ -44,6 +45,38 @@ def test_extreme_products_sit_at_the_static_assert_limit(dc):
             best[op.name] = max(best.get(op.name, 0), s)
     for n, s in best.items():
         assert s == E or (n != "mul4" and s > E * 0.99), (n, s, E)
+
+
+def test_the_tower_instantiations_of_fq2_are_listed(dc):
+    """the Fq2 forms fq12.cuh instantiates beside those the group laws use, at their bounds"""
+    have = {(op.name, tuple(B for B, _ in op.ins[::2])) for op in da.ops(dc, 2) if op.name.startswith("fq2_")}
+    for want in (("fq2_mul", (32, 64)), ("fq2_mul", (32, 80)), ("fq2_mul", (64, 64)), ("fq2_scale", (32, 16)),
+                 ("fq2_scale", (64, 16)), ("fq2_inv", (32,)), ("fq2_is_zero", (32,)), ("fq2_is_zero", (80,)),
+                 ("fq2_reduce_to", (64,)), ("fq2_reduce_to", (112,))):
+        assert want in have, want
+    for op in da.ops(dc, 2):
+        if op.name in ("fq2_scale", "fq2_inv", "fq2_reduce_to"):
+            assert op.outs == [(32, 2), (32, 2)], op.id
+
+
+def test_fq2_zero_reaches_inv_and_is_zero_in_every_spelling(dc):
+    for op in da.ops(dc, 2):
+        if op.name in ("fq2_inv", "fq2_is_zero"):
+            cols = da.operand_sets(op, 4096, seed=100 + op.idx)          # as test_device_arith_gpu.py draws them
+            rows = {(da.from_limbs(a), da.from_limbs(b)) for a, b in zip(*cols)}
+            assert {(0, 0), (0, o.Q), (o.Q, 0), (o.Q, o.Q), (1, o.Q), (o.Q, o.Q + 1)} <= rows, op.id
+
+
+def test_fq2_expectations_of_the_tower_forms():
+    R = da.RQ
+    a, k = (12345, 678), 91011
+    am = [c * R % da.Q for c in a]
+    assert da.fq2_expect("fq2_scale", am + [k * R % da.Q]) == tuple(c * k * R % da.Q for c in a)
+    inv = da.fq2_expect("fq2_inv", [am[0] + da.Q, am[1]])
+    assert da.demont(o.Fq2Ops.mul(inv, tuple(am)), o.Fq2Ops) == (R, 0)      # a^-1 R * a R / R = R, the Montgomery one
+    assert da.fq2_expect("fq2_inv", [da.Q, 0]) == (0, 0)
+    assert da.fq2_expect("fq2_is_zero", [da.Q, 0]) == [1] and da.fq2_expect("fq2_is_zero", [da.Q, 1]) == [0]
+    assert da.fq2_expect("fq2_reduce_to", [am[0] + 3 * da.Q, am[1]]) == tuple(am)
 
 
 @pytest.mark.parametrize("field,p", [(0, o.Q), (1, o.R)])
