@@ -182,6 +182,13 @@ def operand_sets(op, n, seed):
         head = [[c[i % ne] for i in range(E)] if ne else c[:E] for c, ne in zip(cols, nedge)]
         cross = [(a, b) for a in cols[0][:nedge[0]] for b in cols[1][:nedge[1]]]
         rng.shuffle(cross)
+        if op.name == "fq2_is_zero" and len(cross) > max(0, n // 2 - E):
+            # is_zero over Fq2 is about (k0 p, k1 p) with k0 != k1 and the pairs one off them: where the cross does
+            # not fit, those pairs go ahead of the cut.  The 4096-case sets the GPU test draws at the bounds it had
+            # before (17, 32, 80, 112) stay as they were; that holds for n = 4096 only: a smaller set, such as the 600
+            # cases the CPU builder tests draw at 80 and 112, is cut earlier and so comes out reordered
+            off = lambda r: min(from_limbs(r) % p, -from_limbs(r) % p)      # noqa: E731
+            cross.sort(key=lambda ab: sum((off(r) > 0) + (off(r) > 1) for r in ab))
         cross = cross[:max(0, n // 2 - E)]
         mid = [[a for a, _ in cross], [b for _, b in cross]] + [[rng.choice(c) for _ in cross] for c in cols[2:]]
         cols = [(h + m + c[ne:])[:n] for h, m, c, ne in zip(head, mid, cols, nedge)]

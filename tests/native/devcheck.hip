@@ -4,65 +4,16 @@
 // (octopuszk_amd/build.py HIPCC_FLAGS), never linked into libozk_hip.so; driven by tests/test_device_arith_gpu.py.
 //
 // The record layout, the bound reports and the launcher are devcheck_common.h's (shared with towercheck.hip); this
-// file holds the operation lists and the records of the types only it uses (lane-pair Fq2, points).
+// file holds the operation lists and the records of the one type only it uses (lane-pair Fq2); the records of points are
+// devcheck_common.h's too.
 #include "../../octopuszk_amd/csrc/fq2.cuh"
 #include "devcheck_common.h"
 
 namespace dc {
 template <int B>
 struct Bnd<Fe2L<B>> : Bnd<Fe2<B>> {};
-template <class CV>
-struct Bnd<Jac<CV>> : Bnd<Pair2<typename CV::EX, Pair2<typename CV::EY, typename CV::EZ>>> {};
-template <class CV>
-struct Bnd<Xyzz<CV>>
-    : Bnd<Pair2<typename CV::XX, Pair2<typename CV::XY, Pair2<typename CV::XZZ, typename CV::XZZZ>>>> {};
-template <class EA>
-struct Bnd<Aff<EA>> : Bnd<Pair2<EA, EA>> {};
-
 template <int B>
 struct Raw<Fe2L<B>> : RawFq2<Fe2L, B> {};
-template <class CV>
-struct Raw<Jac<CV>> {
-  static constexpr int NX = Bnd<typename CV::EX>::N, NY = Bnd<typename CV::EY>::N;
-  static __device__ Jac<CV> ld(const u32* const* x) {
-    Jac<CV> r;
-    r.X = Raw<typename CV::EX>::ld(x);
-    r.Y = Raw<typename CV::EY>::ld(x + NX);
-    r.Z = Raw<typename CV::EZ>::ld(x + NX + NY);
-    return r;
-  }
-  static __device__ void st(const Jac<CV>& v, u32* o) {
-    Raw<typename CV::EX>::st(v.X, o);
-    Raw<typename CV::EY>::st(v.Y, o + 9 * NX);
-    Raw<typename CV::EZ>::st(v.Z, o + 9 * (NX + NY));
-  }
-};
-template <class CV>
-struct Raw<Xyzz<CV>> {
-  static __device__ Xyzz<CV> ld(const u32* const* x) {
-    Xyzz<CV> r;
-    r.X = Raw<typename CV::XX>::ld(x);
-    r.Y = Raw<typename CV::XY>::ld(x + 1);
-    r.ZZ = Raw<typename CV::XZZ>::ld(x + 2);
-    r.ZZZ = Raw<typename CV::XZZZ>::ld(x + 3);
-    return r;
-  }
-  static __device__ void st(const Xyzz<CV>& v, u32* o) {
-    Raw<typename CV::XX>::st(v.X, o);
-    Raw<typename CV::XY>::st(v.Y, o + 9);
-    Raw<typename CV::XZZ>::st(v.ZZ, o + 18);
-    Raw<typename CV::XZZZ>::st(v.ZZZ, o + 27);
-  }
-};
-template <class EA>
-struct Raw<Aff<EA>> {
-  static __device__ Aff<EA> ld(const u32* const* x) {
-    Aff<EA> r;
-    r.x = Raw<EA>::ld(x);
-    r.y = Raw<EA>::ld(x + Bnd<EA>::N);
-    return r;
-  }
-};
 }  // namespace dc
 using namespace dc;
 
@@ -185,7 +136,10 @@ struct FieldOps {
       MulL<SB, 12, SB>, MulL<640, 12, SLACK * 256 / 640>, MulL<320, 10, 16>, MulL<352, 6, 16>, MulL<96, 4, 17>,
       Mul2L<SB2, 6, SB2, SB2, 6, SB2>, Mul2L<112, 4, 17, 64, 8, 17>, MulLL<SB, 4, SB, 6>, MulLL<SB, 2, SB, 12>,
       Mul2LL<SB2, 4, SB2, 3>, Mul4LL<SB4, 2, SB4, 3>, Normalise<320, 15>, Normalise<640, 12>, SubSub2<32, 32, 32>,
-      SubSub2<96, 200, 100>, SubNc<96, 94>, NegNc<94>, AddNc<192, 6, 192, 6>, DblNc<320, 6>>;
+      SubSub2<96, 200, 100>, SubNc<96, 94>, NegNc<94>, AddNc<192, 6, 192, 6>, DblNc<320, 6>,
+      // is_zero at the bounds the group law of ec.cuh hands it H, rh, P, R, PP and Z / ZZ at over the base field
+      // (DESIGN.md lists them; appended: the cases above are seeded by their index)
+      IsZero<24>, IsZero<49>, IsZero<65>, IsZero<78>, IsZero<81>, IsZero<97>, IsZero<113>, IsZero<145>>;
 };
 
 // ---- Fq2 per lane, Fq2 on a lane pair, the G1 hot loop, the lane-quad G1 and lane-octet G2 group laws (Fq only)
@@ -235,7 +189,9 @@ using ExtList = TL<Fq2Mul<32, 32>, Fq2Mul<144, 112>, Fq2Mul<176, 80>, Fq2Sqr<32>
                    G2OctetAdd,
                    // the tower's Fq2 instantiations (appended: the cases above are seeded by their index)
                    Fq2Mul<32, 64>, Fq2Mul<32, 80>, Fq2Mul<64, 64>, Fq2Scale<32>, Fq2Scale<64>, Fq2Inv<32>,
-                   Fq2IsZero<32>, Fq2IsZero<80>, Fq2ReduceTo<32, 64>, Fq2ReduceTo<32, 112>>;
+                   Fq2IsZero<32>, Fq2IsZero<80>, Fq2ReduceTo<32, 64>, Fq2ReduceTo<32, 112>,
+                   // ... and the group law's over Fq2 (G2Cfg): the affine coordinates, Z, R, rh, H, P (appended)
+                   Fq2IsZero<17>, Fq2IsZero<112>, Fq2IsZero<128>, Fq2IsZero<160>, Fq2IsZero<192>, Fq2IsZero<224>>;
 
 }  // namespace
 

@@ -1,5 +1,6 @@
 // TEST INFRASTRUCTURE shared by the device conformance harnesses (devcheck.hip: fp29 / fq2 / ec / quad; towercheck.hip
-// and towercheck_host.cpp: the pairing tower).  Include it after the arithmetic headers under test.
+// and towercheck_host.cpp: the pairing tower; groupcheck.hip and groupcheck_host.cpp: the group law).  Include it after
+// the arithmetic headers under test (fq2.cuh at least: the records of Fe2 and of the points of ec.cuh are here).
 //
 // Every operation is a struct: `In` lists its operand types, run() applies it.  Each lane reads its operands as raw
 // 9-limb records (operand k of lane i at in[(k * n + i) * 9]), applies the operation once and writes the raw limbs
@@ -22,7 +23,8 @@ namespace dc {
 using namespace ozk;
 
 // ---- bounds of a type: element count, and per element (value bound in sixteenths of p, limb bound LU in units of
-// 2^28; LU 2 = normalised).  Special kinds: B = 0 a bool (word 0), B = -1 eight packed words, B = -2 a wire operand.
+// 2^28; LU 2 = normalised).  Special kinds: B = 0 a bool (word 0), B = -1 eight packed words, B = -2 a wire operand,
+// B = -3 an exponent or scalar of LU words.
 struct Wire {
   u32 w[8];
 };
@@ -144,6 +146,7 @@ struct Raw<bool> {
 template <>
 struct Raw<Flag> {
   static DC_FN Flag ld(const u32* const* x) { return Flag{x[0][0] != 0}; }
+  static DC_FN void st(const Flag& v, u32* o) { Raw<bool>::st(v.v, o); }
 };
 template <>
 struct Raw<Words> {
@@ -167,6 +170,82 @@ struct Raw<Pair2<A, B>> {
   static DC_FN void st(const Pair2<A, B>& v, u32* o) {
     Raw<A>::st(v.a, o);
     Raw<B>::st(v.b, o + 9 * Bnd<A>::N);
+  }
+};
+
+// an exponent or scalar of W little-endian words (B = -3, the LU slot holds W)
+template <int W>
+struct Expo {
+  u32 w[8];
+};
+template <int W>
+struct Bnd<Expo<W>> {
+  static constexpr int N = 1;
+  static void get(int* b, int* l) { b[0] = -3, l[0] = W; }
+};
+template <int W>
+struct Raw<Expo<W>> {
+  static DC_FN Expo<W> ld(const u32* const* x) {
+    Expo<W> r;
+    for (int i = 0; i < 8; i++) r.w[i] = x[0][i];
+    return r;
+  }
+};
+
+// ---- points (ec.cuh): the coordinates one after the other, each with as many records as its field has components
+// (one over Fq, two over Fq2 and over the lane-pair Fq2 of the octet code)
+template <class CV>
+struct Bnd<Jac<CV>> : Bnd<Pair2<typename CV::EX, Pair2<typename CV::EY, typename CV::EZ>>> {};
+template <class CV>
+struct Bnd<Xyzz<CV>>
+    : Bnd<Pair2<typename CV::XX, Pair2<typename CV::XY, Pair2<typename CV::XZZ, typename CV::XZZZ>>>> {};
+template <class EA>
+struct Bnd<Aff<EA>> : Bnd<Pair2<EA, EA>> {};
+template <class CV>
+struct Raw<Jac<CV>> {
+  static constexpr int NX = Bnd<typename CV::EX>::N, NY = Bnd<typename CV::EY>::N;
+  static DC_FN Jac<CV> ld(const u32* const* x) {
+    Jac<CV> r;
+    r.X = Raw<typename CV::EX>::ld(x);
+    r.Y = Raw<typename CV::EY>::ld(x + NX);
+    r.Z = Raw<typename CV::EZ>::ld(x + NX + NY);
+    return r;
+  }
+  static DC_FN void st(const Jac<CV>& v, u32* o) {
+    Raw<typename CV::EX>::st(v.X, o);
+    Raw<typename CV::EY>::st(v.Y, o + 9 * NX);
+    Raw<typename CV::EZ>::st(v.Z, o + 9 * (NX + NY));
+  }
+};
+template <class CV>
+struct Raw<Xyzz<CV>> {
+  static constexpr int NX = Bnd<typename CV::XX>::N, NY = Bnd<typename CV::XY>::N, NZ = Bnd<typename CV::XZZ>::N;
+  static DC_FN Xyzz<CV> ld(const u32* const* x) {
+    Xyzz<CV> r;
+    r.X = Raw<typename CV::XX>::ld(x);
+    r.Y = Raw<typename CV::XY>::ld(x + NX);
+    r.ZZ = Raw<typename CV::XZZ>::ld(x + NX + NY);
+    r.ZZZ = Raw<typename CV::XZZZ>::ld(x + NX + NY + NZ);
+    return r;
+  }
+  static DC_FN void st(const Xyzz<CV>& v, u32* o) {
+    Raw<typename CV::XX>::st(v.X, o);
+    Raw<typename CV::XY>::st(v.Y, o + 9 * NX);
+    Raw<typename CV::XZZ>::st(v.ZZ, o + 9 * (NX + NY));
+    Raw<typename CV::XZZZ>::st(v.ZZZ, o + 9 * (NX + NY + NZ));
+  }
+};
+template <class EA>
+struct Raw<Aff<EA>> {
+  static DC_FN Aff<EA> ld(const u32* const* x) {
+    Aff<EA> r;
+    r.x = Raw<EA>::ld(x);
+    r.y = Raw<EA>::ld(x + Bnd<EA>::N);
+    return r;
+  }
+  static DC_FN void st(const Aff<EA>& v, u32* o) {
+    Raw<EA>::st(v.x, o);
+    Raw<EA>::st(v.y, o + 9 * Bnd<EA>::N);
   }
 };
 

@@ -91,24 +91,7 @@ struct Raw<Wire12> {
     return r;
   }
 };
-// an exponent of W little-endian words (B = -3, the LU slot holds W)
-template <int W>
-struct Expo {
-  u32 w[8];
-};
-template <int W>
-struct Bnd<Expo<W>> {
-  static constexpr int N = 1;
-  static void get(int* b, int* l) { b[0] = -3, l[0] = W; }
-};
-template <int W>
-struct Raw<Expo<W>> {
-  static DC_FN Expo<W> ld(const u32* const* x) {
-    Expo<W> r;
-    for (int i = 0; i < 8; i++) r.w[i] = x[0][i];
-    return r;
-  }
-};
+// (an exponent of W little-endian words: devcheck_common.h's Expo<W>)
 
 }  // namespace dc
 
