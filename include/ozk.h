@@ -152,6 +152,21 @@ int ozk_var_msm_tail_dev(int32_t n, int32_t type, void* d_tail, size_t tail_byte
  * ozk_var_msm_stage_bytes gives the sizes of the three buffers. */
 int ozk_var_msm_stage_bytes(int32_t n, int32_t type, size_t* sorted_bytes, size_t* sort_ws_bytes,
                             size_t* accum_ws_bytes);
+/* Where the staged entries put what one stage hands to the next, for tests and diagnostics that read those buffers
+ * back.  Host only (no device is needed); the plan and the layouts are the ones the entries below use, under the
+ * tuning knobs in force.  Fills fields[0 .. OZK_VAR_MSM_STAGE_LAYOUT_FIELDS), `count` being the room in `fields`:
+ *    0 points sorted (n, or 2 n with GLV)   1 glv   2 signed digits   3 c   4 cb (bucket bits per window)   5 W
+ *    6 small_sort (the one-launch sort)   7 L1 (entries per level-1 lane)   8 l1_whole as planned
+ *    9 lo_bits   10 NH (coarse bins per window)   11 nblk (sort chunks)   12 big_thresh (a coarse bin above it is
+ *      split over many blocks)
+ *   13 aff (-1 with prepared != 0: the records are the caller's)   14 hist   15 total   16 sent: byte offsets into the
+ *      sorted set — affine records of AFF_WORDS words, one count per bucket (W << cb of them, bucket id =
+ *      window << cb | bucket), four counters (total[0] = sorted entries), the entries (index | sign << 31, bucket id)
+ *   17 buckets   18 hist_t: byte offsets into the tail buffer — records of REC_WORDS words, the copy of the counts
+ *   19 AFF_WORDS   20 REC_WORDS   21 REC_TAG (word of a bucket record that says XYZZ = 0 or Jacobian = 1)
+ * Bad arguments (n outside [1, 2^24], NULL, count too small, unknown type): OZK_E_INVALID. */
+#define OZK_VAR_MSM_STAGE_LAYOUT_FIELDS 22
+int ozk_var_msm_stage_layout(int32_t n, int32_t type, int32_t prepared, int64_t* fields, int32_t count);
 /* d_bases and prepared as for the head; over prepared bases the sort skips the base conversion */
 int ozk_var_msm_sort_dev(const void* d_bases, int32_t prepared, const void* d_scalars, int32_t n, int32_t type,
                          void* d_sorted, size_t sorted_bytes, void* d_sort_ws, size_t sort_ws_bytes, void* stream);

@@ -57,6 +57,28 @@ int ozk_var_msm_stage_bytes(int32_t n, int32_t type, size_t* sorted_bytes, size_
     return OZK_OK;
   });
 }
+// Where the staged entries put what they hand on, from the plan and the layouts they use themselves (host only: the
+// base pointers are placeholders that nothing dereferences).  Field order: include/ozk.h.
+int ozk_var_msm_stage_layout(int32_t n, int32_t type, int32_t prepared, int64_t* fields, int32_t count) {
+  if (n <= 0 || n > (1 << 24) || !fields || count < OZK_VAR_MSM_STAGE_LAYOUT_FIELDS)
+    return fail(OZK_E_INVALID, "bad argument");
+  return with_plan(n, type, [&](auto t, const MsmPlan& p) {
+    using IO = CurveIO<CV_OF(t)>;
+    uint8_t* const base = (uint8_t*)(uintptr_t)4096;   // any 256-byte aligned non-null address
+    MsmLayout L = make_layout3<CV_OF(t)>(p, base, base, base, nullptr);
+    tail_layout<CV_OF(t)>(p, L, base, ~(size_t)0);
+    auto off = [&](const void* q) { return (int64_t)((const uint8_t*)q - base); };
+    const u32 big_thresh = (u32)(p.n / 64) > SORT_BIG ? (u32)(p.n / 64) : SORT_BIG;   // as var_msm_sort
+    const int64_t v[OZK_VAR_MSM_STAGE_LAYOUT_FIELDS] = {
+        p.n, p.glv, p.sd, p.c, p.cb, p.W, p.small_sort, p.L1, p.l1_whole,
+        L.lo_bits, L.NH, L.nblk, (int64_t)big_thresh,
+        prepared ? -1 : off(L.aff), off(L.hist), off(L.total), off(L.sent),
+        off(L.buckets), off(L.hist_t),
+        IO::AFF_WORDS, IO::REC_WORDS, IO::REC_TAG};
+    for (int i = 0; i < OZK_VAR_MSM_STAGE_LAYOUT_FIELDS; i++) fields[i] = v[i];
+    return OZK_OK;
+  });
+}
 
 int ozk_var_msm_dev(const void* d_bases, const void* d_scalars, int32_t n, int32_t type, void* d_out,
                     void* d_workspace, size_t workspace_bytes, void* stream) {

@@ -39,6 +39,7 @@ _SIGS = {
     "ozk_var_msm_last_tail_form": (ctypes.c_int, []),
     "ozk_gen_bases_dev": (ctypes.c_int, [ctypes.c_uint64, i32, i32, vp, vp]),
     "ozk_var_msm_stage_bytes": (ctypes.c_int, [i32, i32, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(sz)]),
+    "ozk_var_msm_stage_layout": (ctypes.c_int, [i32, i32, i32, ctypes.POINTER(ctypes.c_int64), i32]),
     "ozk_var_msm_sort_dev": (ctypes.c_int, [vp, i32, vp, i32, i32, vp, sz, vp, sz, vp]),
     "ozk_var_msm_accum_dev": (ctypes.c_int, [vp, i32, i32, vp, sz, vp, sz, vp, sz, vp, i32]),
     "ozk_device_cu_count": (ctypes.c_int, []),

@@ -22,8 +22,10 @@ def _entries(L, n, type_, part=0):
     """name -> call of every `*_dev` entry that dispatches on `type`, with otherwise acceptable arguments"""
     one = (ctypes.c_uint8 * 32)(1)      # host memory: the scalar 1 / the root of unity of order 1
     sizes = [ctypes.c_size_t() for _ in range(3)]
+    fields = (ctypes.c_int64 * 22)()
     return {
         "ozk_var_msm_stage_bytes": lambda: L.ozk_var_msm_stage_bytes(n, type_, *[ctypes.byref(s) for s in sizes]),
+        "ozk_var_msm_stage_layout": lambda: L.ozk_var_msm_stage_layout(n, type_, 0, fields, 22),
         "ozk_var_msm_dev": lambda: L.ozk_var_msm_dev(P, Q, n, type_, R, R, BIG, None),
         "ozk_var_msm_prepared_dev": lambda: L.ozk_var_msm_prepared_dev(P, Q, n, type_, R, R, BIG, None),
         "ozk_var_msm_prepare_dev": lambda: L.ozk_var_msm_prepare_dev(P, n, type_, R, BIG, None),
