@@ -549,6 +549,37 @@ int ozk_fr_evals_open_set_dev(const void* d_evals, int32_t npolys, int32_t n, in
                               int64_t quot_stride, void* d_values, void* d_workspace, size_t workspace_bytes,
                               void* stream);
 
+/* KZG multi-openings over Fr (csrc/kzg_multi.cuh): what a prover that opens many polynomials,
+ * each at its own set of points, needs beside the entry points above.  Elements, reduction on load, canonical outputs
+ * and strides are those of the two blocks above.
+ *   ozk_fr_rows_combine_groups_dev
+ *                              d_out[g][j] = sum_{i : group(i) = g} w_i rows[i][j] for g < groups, j < len: row i at
+ *                              d_rows + 32 i row_stride, output row g at d_out + 32 g out_stride (both strides >= len;
+ *                              elements of an output row beyond len are not touched), w = the k elements at d_weights.
+ *                              group_of_row_host: k int32 values in [0, groups) in HOST memory, read before the call
+ *                              returns; the groups may interleave in any way, and a group with no row yields a zero
+ *                              row.  1 <= k <= 256, 1 <= groups <= 32, k len <= 2^28.  d_out must not overlap d_rows
+ *                              (rejected).  Every input element is read once and every output element written once,
+ *                              whatever the grouping.  With groups = 1 the bytes are those of ozk_fr_rows_combine_dev.
+ *                              No workspace.
+ *   ozk_fr_poly_eval_set_dev   d_values[y t + i] = p_y(z_yi), 1 <= t <= 32: the values of ozk_fr_poly_open_set_dev
+ *                              without a quotient, from one read of every row.  The points are npolys x t elements in
+ *                              HOST memory, laid out and read as there, but the points of a row need NOT be distinct:
+ *                              a repeated point gives a repeated value.  poly_stride is 0 (ONE polynomial at npolys
+ *                              sets) or >= len; npolys len and npolys t <= 2^28; d_values must not overlap d_coeffs
+ *                              (rejected).  For pairwise distinct points the bytes are the values of
+ *                              ozk_fr_poly_open_set_dev.
+ *                              Workspace: ozk_fr_poly_eval_set_workspace_bytes(npolys, len, t).
+ * Size functions and rejections as above: 0 and OZK_E_INVALID before any launch, the shape (k, groups and t included)
+ * before the pointers, then the group ids.  Asynchronous on `stream`; nothing is allocated or synchronised. */
+int ozk_fr_rows_combine_groups_dev(const void* d_rows, int32_t k, int32_t len, int64_t row_stride, const void* d_weights,
+                                   const int32_t* group_of_row_host, int32_t groups, void* d_out, int64_t out_stride,
+                                   void* stream);
+size_t ozk_fr_poly_eval_set_workspace_bytes(int32_t npolys, int32_t len, int32_t t);
+int ozk_fr_poly_eval_set_dev(const void* d_coeffs, int32_t npolys, int32_t len, int64_t poly_stride, int32_t t,
+                             const uint8_t* points_host, void* d_values, void* d_workspace, size_t workspace_bytes,
+                             void* stream);
+
 /* ---- batched MSM over shared bases (msm_multi.hip; no counterpart in the reference, whose verifier runs one
  * variable-base MSM per proof): out_i = sum_{j < n} s_ij P_j for k scalar rows over the SAME n bases, G1 only.
  * A window table of every base is built once (ozk_multi_msm_prepare_dev); a run is table gathers and mixed

@@ -33,8 +33,16 @@ multiply-accumulate kernel over points (ozk_points_mac_dev) and two group FFTs, 
     all_ = ak.open_all(coeffs)[0]                    # AllOpenings: c, values (n x 32 B on the device), proofs (r x 32 B)
     assert verify_set(svk, all_.opening(k))          # an Opening for l = 1, a SetOpening for l > 1
 
-Out of scope: hiding commitments, different point sets per polynomial under one proof, degree-bound proofs, G2
-commitments, interoperability with other tools' byte formats.  There is no CPU path.
+Many polynomials, each at its own set of points, under ONE proof of two G1 points (the
+two-element scheme of Boneh, Drake, Fisch and Gabizon): the verifier holds the plain VerifyKey and runs two pairings
+whatever the sets.  The rows of every distinct set are summed by ozk_fr_rows_combine_groups_dev and the values come
+from ozk_fr_poly_eval_set_dev (csrc/kzg_multi.cuh); the divisions are those of the sections above.
+
+    mo = ck.open_multi(coeffs, [[z], [z, z w], [z]]) # MultiOpening: K | per row C, t, z, y | W | W'
+    assert verify_multi(vk, mo) and verify_multi_all(vk, [mo])
+
+Out of scope: hiding commitments, degree-bound proofs, multi-openings of evaluation rows, G2 commitments,
+interoperability with other tools' byte formats.  There is no CPU path.
 """
 import secrets
 
@@ -334,6 +342,57 @@ class CommitKey:
         quot, _ = poly_open_set(combined.unsqueeze(0), 1, self.n, self.n, [points])
         return commitments, values, self._row_msms(self.bases(), self.n, quot, 1, self.n)
 
+    # ---- open many rows, each at its own set, with one proof
+    def open_multi(self, coeffs, point_sets, commitments=None) -> "MultiOpening":
+        """K rows, row i at its own set point_sets[i] of t_i points, under ONE proof of two G1 points (DESIGN.md section
+        28): the values from one ozk_fr_poly_eval_set_dev call (from one ozk_fr_poly_eval_dev call per point where every
+        set lies inside one of at most 8 points), the sums F_g = sum_{i in g} gamma^i f_i of the rows of
+        every distinct set from one ozk_fr_rows_combine_groups_dev call, one ozk_fr_poly_open_set_dev call per distinct
+        set size for h = sum_g (F_g - I_g) / Z_{S_g} and W = [h(tau)] g1, then L = sum_g c_g F_g - Z_T(z) h opened at z for
+        W'.  1 <= K <= 256, 1 <= t_i <= 32 (whatever the string's m), at most 32 distinct sets.  `commitments`: the K
+        compressed commitments, for a caller who holds them already (else K MSMs)."""
+        k, _, stride = _rows(coeffs, "coeffs", self.n)
+        sets = _multi_sets(point_sets, "point_sets", k)
+        groups, group_of = _multi_groups(sets, MULTI_SETS_MAX)
+        if commitments is not None:
+            commitments = [_enc_of(c, "commitment") for c in commitments]
+            if len(commitments) != k:
+                raise ValueError("%d commitments for %d rows" % (len(commitments), k))
+        rows, n, ng = _as2d(coeffs), self.n, len(groups)
+        if commitments is None:
+            commitments = self.commit(coeffs)
+        t_top = max(len(row) for row in sets)
+        union = groups[-1] if all(set(g) <= set(groups[-1]) for g in groups) else None
+        if union is not None and t_top <= MULTI_EVAL_CALLS_T:
+            # every set lies inside the largest one (z and z omega): one pass of ozk_fr_poly_eval_dev per point over
+            # all rows measured faster than the set kernel for up to 8 points (DESIGN.md section 28)
+            at = dict(zip(union, poly_eval_points(rows, k, n, stride, union)))
+            values = [tuple(at[z][i] for z in row) for i, row in enumerate(sets)]
+        else:
+            # short sets are padded with their first point; the values of the padding are dropped
+            padded = [row + (row[0],) * (t_top - len(row)) for row in sets]
+            ys = ints32(_wire.host_bytes(poly_eval_set(rows, k, n, stride, padded)))
+            values = [tuple(ys[t_top * i:t_top * i + len(row)]) for i, row in enumerate(sets)]
+        gamma, digest = _multi_gamma(commitments, sets, values)
+        # rows 0 .. G - 1: the F_g; row G: h
+        buf = torch.empty((ng + 1, 32 * n), dtype=torch.uint8, device=rows.device)
+        rows_combine_groups(rows, k, n, stride, [pow(gamma, i, FR) for i in range(k)], group_of, ng, buf, n)
+        quot = torch.empty((ng, 32 * n), dtype=torch.uint8, device=rows.device)
+        a = 0
+        while a < ng:                                                   # the groups of one size are neighbours
+            b = a + 1
+            while b < ng and len(groups[b]) == len(groups[a]):
+                b += 1
+            poly_open_set(buf[a:b], b - a, n, n, groups[a:b], quot[a:b])
+            a = b
+        rows_combine(quot, ng, n, n, [1] * ng, buf[ng])
+        w = self._row_msms(self.bases(), n, buf[ng:], 1, n)
+        z = _multi_z(digest, w)
+        c, _, _, z_t = _multi_at(sets, values, groups, group_of, gamma, z)
+        combined = rows_combine(buf, ng + 1, n, n, c + [(FR - z_t) % FR])
+        quot2, _ = poly_open(combined.unsqueeze(0), 1, n, n, [z])
+        return MultiOpening(commitments, sets, values, w, self._row_msms(self.bases(), n, quot2, 1, n))
+
 
 def _as2d(t):
     return t.unsqueeze(0) if t.dim() == 1 else t
@@ -369,10 +428,11 @@ def evals_open(evals, k, n, stride, zs):
     return quot, values
 
 
-def rows_combine(rows, k, n, stride, weights):
-    """sum_i w_i rows[i] as a new row of n elements (ozk_fr_rows_combine_dev)"""
+def rows_combine(rows, k, n, stride, weights, out=None):
+    """sum_i w_i rows[i] as a row of n elements, a new one unless `out` is given (ozk_fr_rows_combine_dev)"""
     L = _lib.load()
-    out = torch.empty(32 * n, dtype=torch.uint8, device=rows.device)
+    if out is None:
+        out = torch.empty(32 * n, dtype=torch.uint8, device=rows.device)
     w = _wire.dev_bytes(le32(weights))
     _lib.check(L.ozk_fr_rows_combine_dev(_ptr(rows), k, n, stride, _ptr(w), _ptr(out), _stream()))
     torch.cuda.current_stream().synchronize()
@@ -627,12 +687,13 @@ class SetVerifyKey:
         return self._points
 
 
-def poly_open_set(coeffs, k, n, stride, sets):
-    """ozk_fr_poly_open_set_dev on k rows, row y at the t points sets[y]: (quotient rows [k, 32 n], values [32 k t]) on
-    the device.  Synchronises (the workspace dies here)."""
+def poly_open_set(coeffs, k, n, stride, sets, quot=None):
+    """ozk_fr_poly_open_set_dev on k rows, row y at the t points sets[y]: (quotient rows [k, 32 n], new ones unless
+    `quot` is given, values [32 k t]) on the device.  Synchronises (the workspace dies here)."""
     L = _lib.load()
     t = len(sets[0])
-    quot = torch.empty((k, 32 * n), dtype=torch.uint8, device=coeffs.device)
+    if quot is None:
+        quot = torch.empty((k, 32 * n), dtype=torch.uint8, device=coeffs.device)
     values = torch.empty(32 * k * t, dtype=torch.uint8, device=coeffs.device)
     wsb = int(L.ozk_fr_poly_open_set_workspace_bytes(k, n, t))
     ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=coeffs.device)
@@ -887,3 +948,261 @@ class OpenAllKey:
                 proofs = _codec.compress_g1(self.proofs_of(h))
             out.append(AllOpenings(commitments[y], self.values(row), proofs, self.n, self.coset))
         return out
+
+
+# ============================================================================ many polynomials, each at its own set (section 28)
+MULTI_K_MAX, MULTI_SETS_MAX = 256, 32     # KZG_MULTI_ROWS, KZG_MULTI_GROUPS of csrc/kzg_multi.cuh
+MULTI_EVAL_CALLS_T = 8                    # up to here t passes of ozk_fr_poly_eval_dev beat the set kernel (measured)
+_MULTI_GAMMA_TAG = b"OZK-kzg-multi-gamma"
+_MULTI_Z_TAG = b"OZK-kzg-multi-z"
+_MULTI_RHO_TAG = b"OZK-kzg-multi-rho"
+
+
+def _multi_sets(point_sets, what, k=None):
+    """K tuples of t_i pairwise distinct ints in [0, r), 1 <= K <= 256 (k when the caller has K rows), 1 <= t_i <= 32"""
+    if isinstance(point_sets, (int, str, bytes)) or not hasattr(point_sets, "__iter__"):
+        raise TypeError("%s must be one list of points per row" % what)
+    sets = list(point_sets)
+    if k is not None and len(sets) != k:
+        raise ValueError("%d lists of points for %d rows" % (len(sets), k))
+    if not 1 <= len(sets) <= MULTI_K_MAX:
+        raise ValueError("K = %d rows: 1 <= K <= %d" % (len(sets), MULTI_K_MAX))
+    out = []
+    for row in sets:
+        if isinstance(row, (int, str, bytes)) or not hasattr(row, "__iter__"):
+            raise ValueError("%s: one list of points per row, not a mix of lists and points" % what)
+        row = tuple(row)
+        if not 1 <= len(row) <= SET_T_MAX:
+            raise ValueError("t = %d points: 1 <= t <= %d" % (len(row), SET_T_MAX))
+        row = tuple(_wire.scalar_in_range(z, "%s: z" % what) for z in row)
+        if len(set(row)) != len(row):
+            raise ValueError("%s: z has repeated points in a set: %s" % (what, row))
+        out.append(row)
+    return out
+
+
+def _multi_values(values, sets, what):
+    """K tuples of t_i ints in [0, r), one value per point"""
+    values = [tuple(row) for row in values]
+    if len(values) != len(sets) or any(len(ys) != len(row) for ys, row in zip(values, sets)):
+        raise ValueError("%s: the values are not one per point" % what)
+    return [tuple(_wire.scalar_in_range(y, "%s: y" % what) for y in ys) for ys in values]
+
+
+def _multi_groups(sets, limit=None):
+    """(the distinct sets, smallest first and each as its first row wrote it; the group of every row): two rows are of
+    one group when their sets hold the same points in any order"""
+    first = {}
+    for row in sets:
+        first.setdefault(frozenset(row), row)
+    if limit is not None and len(first) > limit:
+        raise ValueError("%d distinct sets of points: at most %d" % (len(first), limit))
+    keys = sorted(first, key=len)                                   # (stable: sets of one size stay in row order)
+    index = {key: g for g, key in enumerate(keys)}
+    return [first[key] for key in keys], [index[frozenset(row)] for row in sets]
+
+
+def _multi_at(sets, values, groups, group_of, gamma, z):
+    """What prover and verifier derive at z, in host integers: c_g = Z_{T \\ S_g}(z) per group (T the union of the
+    sets; the empty product is 1), the weight gamma^i c_{g(i)} of every row, sum_i gamma^i c_{g(i)} r_i(z) for r_i the
+    interpolant of row i's values on its set, and Z_T(z)"""
+    union = list(dict.fromkeys(p for s in groups for p in s))
+
+    def z_over(points):
+        acc = 1
+        for p in points:
+            acc = acc * (z - p) % FR
+        return acc
+
+    c = [z_over([p for p in union if p not in s]) for s in map(frozenset, groups)]
+    weights, at_z, g = [], 0, 1
+    for row, ys, grp in zip(sets, values, group_of):
+        weights.append(g * c[grp] % FR)
+        r_at = 0
+        for coeff in reversed(_interpolant(row, ys)):
+            r_at = (r_at * z + coeff) % FR
+        at_z = (at_z + weights[-1] * r_at) % FR
+        g = g * gamma % FR
+    return c, weights, at_z, z_over(union)
+
+
+def _multi_gamma(commitments, sets, values) -> tuple:
+    """(gamma, the digest D that z is drawn over) of checked arguments"""
+    parts = [len(sets).to_bytes(8, "little")]
+    for c, row, ys in zip(commitments, sets, values):
+        parts += [len(row).to_bytes(8, "little"), le32(row), c, le32(ys)]
+    return _transcript.challenge128(_MULTI_GAMMA_TAG, *parts), _transcript.digest(_MULTI_GAMMA_TAG, *parts)
+
+
+def _multi_z(digest, w) -> int:
+    return _transcript.challenge128(_MULTI_Z_TAG, digest, w)
+
+
+def multi_challenges(commitments, point_sets, values, w) -> tuple:
+    """(gamma, z).  gamma: the first 16 bytes, little-endian, of D = SHA-256("OZK-kzg-multi-gamma" | K as 8 bytes LE |
+    per row: t_i as 8 bytes LE, its t_i points, its compressed commitment, its t_i values); z: the first 16 bytes of
+    SHA-256("OZK-kzg-multi-z" | D | the compressed W); either is 1 if those bytes are zero"""
+    commitments = [_enc_of(c, "commitment") for c in commitments]
+    sets = _multi_sets(point_sets, "point_sets", len(commitments))
+    gamma, digest = _multi_gamma(commitments, sets, _multi_values(values, sets, "values"))
+    return gamma, _multi_z(digest, _enc_of(w, "W"))
+
+
+class MultiOpening:
+    """K uint32 LE | per row: C 32 | t uint32 LE | z 32 t | y 32 t | then W 32 | W' 32: the compressed commitments, every
+    row's points and the values at them, and the two compressed proof points"""
+
+    def __init__(self, commitments, point_sets, values, w, w2):
+        self.commitments = tuple(_enc_of(c, "multi opening: C") for c in commitments)
+        self.point_sets = tuple(_multi_sets(point_sets, "multi opening", len(self.commitments)))
+        self.values = tuple(_multi_values(values, self.point_sets, "multi opening"))
+        self.w, self.w2 = _enc_of(w, "multi opening: W"), _enc_of(w2, "multi opening: W'")
+
+    @property
+    def k(self):
+        return len(self.commitments)
+
+    def to_bytes(self) -> bytes:
+        rows = [c + len(zs).to_bytes(4, "little") + le32(zs) + le32(ys)
+                for c, zs, ys in zip(self.commitments, self.point_sets, self.values)]
+        return self.k.to_bytes(4, "little") + b"".join(rows) + self.w + self.w2
+
+    @staticmethod
+    def from_bytes(b) -> "MultiOpening":
+        """Strict and host-only: ValueError naming the field for a wrong length, K outside [1, 256], a t outside
+        [1, 32], z or y >= r, a repeated point within a row, a point that does not decode."""
+        b = bytes(b)
+        if len(b) < 4:
+            raise ValueError("multi opening: length %d, too short for K" % len(b))
+        k = int.from_bytes(b[:4], "little")
+        if not 1 <= k <= MULTI_K_MAX:
+            raise ValueError("multi opening: K = %d, not in [1, %d]" % (k, MULTI_K_MAX))
+        at, cs, sets, values = 4, [], [], []
+        for i in range(k):
+            if len(b) < at + 36:
+                raise ValueError("multi opening: length %d, too short for C and t of row %d" % (len(b), i))
+            t = int.from_bytes(b[at + 32:at + 36], "little")
+            if not 1 <= t <= SET_T_MAX:
+                raise ValueError("multi opening: t = %d in row %d, not in [1, %d]" % (t, i, SET_T_MAX))
+            if len(b) < at + 36 + 64 * t:
+                raise ValueError("multi opening: length %d, too short for the %d points of row %d" % (len(b), t, i))
+            cs.append(b[at:at + 32])
+            sets.append(ints32(b[at + 36:at + 36 + 32 * t]))
+            values.append(ints32(b[at + 36 + 32 * t:at + 36 + 64 * t]))
+            at += 36 + 64 * t
+        if len(b) != at + 64:
+            raise ValueError("multi opening: length %d, not %d for these K and t" % (len(b), at + 64))
+        for name, rows in (("z", sets), ("y", values)):
+            if any(v >= FR for row in rows for v in row):
+                raise ValueError("multi opening: %s is not below r" % name)
+        if any(len(set(row)) != len(row) for row in sets):
+            raise ValueError("multi opening: z has repeated points")
+        fields = [("C[%d]" % i, c, G1) for i, c in enumerate(cs)] + [("W", b[at:at + 32], G1), ("W'", b[at + 32:], G1)]
+        _codec.require_points(fields, "multi opening")
+        return MultiOpening(cs, sets, values, b[at:at + 32], b[at + 32:])
+
+
+def poly_eval_set(coeffs, k, n, stride, sets):
+    """ozk_fr_poly_eval_set_dev on k rows, row y at the t points sets[y] (which may repeat): values [32 k t] on the
+    device.  Synchronises (the workspace dies here)."""
+    L = _lib.load()
+    t = len(sets[0])
+    values = torch.empty(32 * k * t, dtype=torch.uint8, device=coeffs.device)
+    wsb = int(L.ozk_fr_poly_eval_set_workspace_bytes(k, n, t))
+    ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=coeffs.device)
+    pts = le32([z for row in sets for z in row])
+    _lib.check(L.ozk_fr_poly_eval_set_dev(_ptr(coeffs), k, n, stride, t, vp(pts), _ptr(values), _ptr(ws), ws.numel(),
+                                          _stream()))
+    torch.cuda.current_stream().synchronize()
+    return values
+
+
+def poly_eval_points(coeffs, k, n, stride, points):
+    """every one of k rows at every point: one ozk_fr_poly_eval_dev call per point -> per point, the k values as ints"""
+    L = _lib.load()
+    out = torch.empty(32 * k * len(points), dtype=torch.uint8, device=coeffs.device)
+    ws = torch.empty(max(int(L.ozk_fr_poly_eval_workspace_bytes(k)), 256), dtype=torch.uint8, device=coeffs.device)
+    for i, z in enumerate(points):
+        _lib.check(L.ozk_fr_poly_eval_dev(_ptr(coeffs), k, n, stride, vp(le32([z])), _ptr(out[32 * k * i:]), _ptr(ws),
+                                          ws.numel(), _stream()))
+    ys = ints32(_wire.host_bytes(out))
+    return [ys[k * i:k * (i + 1)] for i in range(len(points))]
+
+
+def rows_combine_groups(rows, k, n, stride, weights, group_of, groups, out, out_stride):
+    """out[g] = sum_{i : group_of[i] = g} w_i rows[i] for g < groups (ozk_fr_rows_combine_groups_dev)"""
+    L = _lib.load()
+    w = _wire.dev_bytes(le32(weights))
+    ids = b"".join(int(g).to_bytes(4, "little", signed=True) for g in group_of)
+    _lib.check(L.ozk_fr_rows_combine_groups_dev(_ptr(rows), k, n, stride, _ptr(w), vp(ids), groups, _ptr(out), out_stride,
+                                                _stream()))
+    torch.cuda.current_stream().synchronize()
+    return out
+
+
+def _multi_terms(o):
+    """the scalars of one opening's check: (of every C_i, of g1, of W, of W')"""
+    gamma, z = multi_challenges(o.commitments, o.point_sets, o.values, o.w)
+    groups, group_of = _multi_groups(o.point_sets)
+    _, weights, at_z, z_t = _multi_at(o.point_sets, o.values, groups, group_of, gamma, z)
+    return weights, (FR - at_z) % FR, (FR - z_t) % FR, z
+
+
+def _multi_opening(o):
+    return o if isinstance(o, MultiOpening) else MultiOpening.from_bytes(o)
+
+
+def verify_multi(vk, opening) -> bool:
+    """With F = sum_i gamma^i c_{g(i)} C_i - [sum_i gamma^i c_{g(i)} r_i(z)] g1 - [Z_T(z)] W:
+        e(F + [z] W', g2) e(-W', tau_g2) = 1
+    as one G1 MSM of K + 3 points (the C_i, g1, W, W') and one product of two pairings, over the plain VerifyKey;
+    everything else is host integers.  Both G1 points O is accepted, one of them alone is not."""
+    o = _multi_opening(opening)
+    k = o.k
+    pts = _decoded(list(o.commitments) + [o.w, o.w2])
+    if pts is None:
+        return False
+    weights, s_g1, s_w, z = _multi_terms(o)
+    lhs, ws = _vectors.msm(torch.cat([pts[:96 * k], vk.points()[0], pts[96 * k:]]),
+                           _wire.dev_bytes(le32(weights + [s_g1, s_w, z])), k + 3)
+    ok = _pairing_holds(lhs, pts[96 * (k + 1):], o.w2 == _G1_INF, vk)
+    del ws
+    return ok
+
+
+def verify_multi_all(vk, openings, seed=None) -> bool:
+    """All M openings at once with weights rho_m in [1, 2^128) (the stream of transcript.py under this module's multi
+    tag; `seed` as verify_all):
+        e(sum_m rho_m (F_m + [z_m] W'_m), g2) e(-sum_m rho_m W'_m, tau_g2) = 1
+    as one G1 MSM over every commitment, W and W' of the batch and g1, one of the M points W'_m, and one product of
+    two pairings."""
+    os_ = [_multi_opening(o) for o in openings]
+    if not os_:
+        return True
+    seed = secrets.token_bytes(32) if seed is None else _transcript.seed_bytes(seed)
+    rho = ints32(_transcript.weights(seed, len(os_), _MULTI_RHO_TAG))
+    pts = _decoded([c for o in os_ for c in o.commitments] + [o.w for o in os_] + [o.w2 for o in os_])
+    if pts is None:
+        return False
+    sc_c, sc_w, sc_w2, sc_g1 = [], [], [], 0
+    for r, o in zip(rho, os_):
+        weights, s_g1, s_w, z = _multi_terms(o)
+        sc_c += [r * x % FR for x in weights]
+        sc_w.append(r * s_w % FR)
+        sc_w2.append(r * z % FR)
+        sc_g1 = (sc_g1 + r * s_g1) % FR
+    total = len(sc_c) + 2 * len(os_)
+    lhs, ws1 = _vectors.msm(torch.cat([pts, vk.points()[0]]), _wire.dev_bytes(le32(sc_c + sc_w + sc_w2 + [sc_g1])),
+                            total + 1)
+    ps, ws2 = _vectors.msm(pts[96 * (total - len(os_)):], _wire.dev_bytes(le32(rho)), len(os_))
+    ok = _pairing_holds(lhs, wire_out_to_in(ps, G1), _wire.is_inf_out(ps), vk)
+    del ws1, ws2
+    return ok
+
+
+def verify_multi_each(vk, openings, seed=None) -> list:
+    """One verdict per opening: the batch check first, single checks only when it fails"""
+    openings = list(openings)
+    if verify_multi_all(vk, openings, seed):
+        return [True] * len(openings)
+    return [verify_multi(vk, o) for o in openings]

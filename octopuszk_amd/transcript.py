@@ -20,9 +20,14 @@ def weights(seed: bytes, n: int, tag: bytes) -> bytes:
     return bytes(out)
 
 
+def digest(tag: bytes, *parts) -> bytes:
+    """SHA-256(tag | the parts): what a later challenge of the same transcript hashes in place of the parts"""
+    return hashlib.sha256(tag + b"".join(parts)).digest()
+
+
 def challenge128(tag: bytes, *parts) -> int:
     """the first 16 bytes, little-endian, of SHA-256(tag | the parts); 1 if they are zero"""
-    return int.from_bytes(hashlib.sha256(tag + b"".join(parts)).digest()[:16], "little") or 1
+    return int.from_bytes(digest(tag, *parts)[:16], "little") or 1
 
 
 def seed_bytes(seed) -> bytes:
