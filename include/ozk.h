@@ -580,6 +580,54 @@ int ozk_fr_poly_eval_set_dev(const void* d_coeffs, int32_t npolys, int32_t len, 
                              const uint8_t* points_host, void* d_values, void* d_workspace, size_t workspace_bytes,
                              void* stream);
 
+/* The Fr kernels of the PLONK prover (csrc/plonk.cuh).  Elements, reduction on load, canonical
+ * outputs and strides are those of the KZG blocks above; every scalar argument is 32-byte little-endian in HOST memory,
+ * taken mod r and read before the call returns.
+ *   ozk_fr_rows_coset_dev      d_out[y][i] = c s^i rows[y][i] for i < len and 0 for len <= i < out_len: row y at
+ *                              d_rows + 32 y row_stride (>= len), output row y at d_out + 32 y out_stride (>= out_len;
+ *                              elements of an output row beyond out_len are not touched).  One call is the way into a
+ *                              coset (s = g, zero-extended to the size of the transform that follows), the way out of
+ *                              one (s = 1 / g, c = 1 / size) and the 1 / n of an inverse transform (s = 1).
+ *                              1 <= k, 1 <= len <= out_len, k out_len <= 2^28.  d_out may be d_rows itself when
+ *                              out_len = len and the strides agree; any other overlap is rejected.  No table of len
+ *                              powers is written: the workspace holds 256 + ceil(out_len / 1024) elements.
+ *                              Workspace: ozk_fr_rows_coset_workspace_bytes(k, len, out_len).
+ *   ozk_fr_perm_product_dev    The permutation grand product.  d_wires and d_sigma each hold three rows of len elements
+ *                              at `stride` (>= len); the identity label of cell (j, i) is k_j omega^i, k_host96 the
+ *                              three k_j.  d_z[0] = 1 and
+ *                                d_z[i] = prod_{m < i} prod_j (w_jm + beta k_j omega^m + gamma) / (w_jm + beta s_jm + gamma),
+ *                              *d_total (one element) the product over all len rows, *d_zero_dens (int32) the number of
+ *                              rows whose denominator is zero: such a row's factor is taken as 1, and the other rows
+ *                              are exact.  1 <= len <= 2^28, a power of two or not.  d_z, d_total and d_zero_dens must
+ *                              not overlap d_wires, d_sigma or one another (rejected).  Every wire and sigma element
+ *                              is read twice (once when len <= 1024) and d_z is written once.
+ *                              Workspace: ozk_fr_perm_product_workspace_bytes(len).
+ *   ozk_plonk_quotient_dev     d_out[i] = t(g omega_4n^i), i < 4 n, for
+ *                                t = (qL a + qR b + qO c + qM a b + qC + PI + alpha P1 + alpha^2 (Z - 1) L_1) / Z_H,
+ *                                P1 = Z (a + beta X + gamma)(b + beta k_1 X + gamma)(c + beta k_2 X + gamma)
+ *                                     - Z(omega X)(a + beta s1 + gamma)(b + beta s2 + gamma)(c + beta s3 + gamma).
+ *                              d_wit: the five rows a, b, c, Z, PI of 4 n values on the coset, at wit_stride; d_key: the
+ *                              ten rows qL, qR, qO, qM, qC, s1, s2, s3, L_1 and the coset points themselves, at
+ *                              key_stride (both >= 4 n).  k_host96: (k_0, k_1, k_2), of which k_1 and k_2 are used;
+ *                              zh_inv_host128: the four values 1 / (g^n i4^m - 1), m < 4, i4 = omega_4n^n, which are
+ *                              all that 1 / Z_H takes on the coset (point i has m = i mod 4); Z(omega X) is Z at
+ *                              index (i + 4) mod 4 n.  n a power of two, 2 <= n, 4 n <= 2^28.  d_out must not overlap
+ *                              d_wit or d_key (rejected).  Every input is read once (Z twice), d_out written once.
+ *                              No workspace.
+ * Size functions and rejections as above: 0 and OZK_E_INVALID before any launch, the shape before the pointers.
+ * Asynchronous on `stream`; nothing is allocated or synchronised. */
+size_t ozk_fr_rows_coset_workspace_bytes(int32_t k, int32_t len, int32_t out_len);
+int ozk_fr_rows_coset_dev(const void* d_rows, int32_t k, int32_t len, int64_t row_stride, const uint8_t* s_host32,
+                          const uint8_t* c_host32, void* d_out, int32_t out_len, int64_t out_stride, void* d_workspace,
+                          size_t workspace_bytes, void* stream);
+size_t ozk_fr_perm_product_workspace_bytes(int32_t len);
+int ozk_fr_perm_product_dev(const void* d_wires, const void* d_sigma, int32_t len, int64_t stride, const uint8_t* omega_host32,
+                            const uint8_t* k_host96, const uint8_t* beta_host32, const uint8_t* gamma_host32, void* d_z,
+                            void* d_total, int32_t* d_zero_dens, void* d_workspace, size_t workspace_bytes, void* stream);
+int ozk_plonk_quotient_dev(const void* d_wit, int64_t wit_stride, const void* d_key, int64_t key_stride, int32_t n,
+                           const uint8_t* alpha_host32, const uint8_t* beta_host32, const uint8_t* gamma_host32,
+                           const uint8_t* k_host96, const uint8_t* zh_inv_host128, void* d_out, void* stream);
+
 /* ---- batched MSM over shared bases (msm_multi.hip; no counterpart in the reference, whose verifier runs one
  * variable-base MSM per proof): out_i = sum_{j < n} s_ij P_j for k scalar rows over the SAME n bases, G1 only.
  * A window table of every base is built once (ozk_multi_msm_prepare_dev); a run is table gathers and mixed

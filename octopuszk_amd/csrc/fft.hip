@@ -1361,3 +1361,4 @@ int ozk_fft_compact_host(const uint8_t* in, int32_t n, const uint8_t* omega, int
 #include "kzg.cuh"
 #include "kzg_set.cuh"
 #include "kzg_multi.cuh"
+#include "plonk.cuh"

@@ -41,6 +41,8 @@ from ozk_fr_poly_eval_set_dev (csrc/kzg_multi.cuh); the divisions are those of t
     mo = ck.open_multi(coeffs, [[z], [z, z w], [z]]) # MultiOpening: K | per row C, t, z, y | W | W'
     assert verify_multi(vk, mo) and verify_multi_all(vk, [mo])
 
+A proof system over these openings, with no per-circuit secrets: the `plonk` package.
+
 Out of scope: hiding commitments, degree-bound proofs, multi-openings of evaluation rows, G2 commitments,
 interoperability with other tools' byte formats.  There is no CPU path.
 """
@@ -112,6 +114,12 @@ def _enc_of(b, what, size=32) -> bytes:
     if len(b) != size:
         raise ValueError("%s: %d bytes, not %d" % (what, len(b), size))
     return b
+
+
+def require_g1(fields, owner):
+    """fields: (name, compressed G1 encoding) of the points of a byte format built on this module (`owner`); ValueError
+    naming the first that does not decode.  Strict and host-only, as the from_bytes here."""
+    _codec.require_points([(name, enc, G1) for name, enc in fields], owner)
 
 
 # ---------------------------------------------------------------------------- bytes

@@ -116,6 +116,11 @@ _SIGS = {
     "ozk_fr_rows_combine_groups_dev": (ctypes.c_int, [vp, i32, i32, ctypes.c_int64, vp, vp, i32, vp, ctypes.c_int64, vp]),
     "ozk_fr_poly_eval_set_workspace_bytes": (sz, [i32, i32, i32]),
     "ozk_fr_poly_eval_set_dev": (ctypes.c_int, [vp, i32, i32, ctypes.c_int64, i32, vp, vp, vp, sz, vp]),
+    "ozk_fr_rows_coset_workspace_bytes": (sz, [i32, i32, i32]),
+    "ozk_fr_rows_coset_dev": (ctypes.c_int, [vp, i32, i32, ctypes.c_int64, vp, vp, vp, i32, ctypes.c_int64, vp, sz, vp]),
+    "ozk_fr_perm_product_workspace_bytes": (sz, [i32]),
+    "ozk_fr_perm_product_dev": (ctypes.c_int, [vp, vp, i32, ctypes.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "ozk_plonk_quotient_dev": (ctypes.c_int, [vp, ctypes.c_int64, vp, ctypes.c_int64, i32, vp, vp, vp, vp, vp, vp, vp]),
     "ozk_multi_msm_table_bytes": (sz, [i32, i32]),
     "ozk_multi_msm_prepare_dev": (ctypes.c_int, [vp, i32, i32, vp, sz, vp, sz, vp]),
     "ozk_multi_msm_workspace_bytes": (sz, [i32, i32, i32]),

@@ -1,0 +1,130 @@
+"""Circuits of the PLONK prover: gates over variables, host only."""
+import numpy as np
+
+from ..fft import FR, FR_MULT_GEN, root_of_unity
+
+K = (1, FR_MULT_GEN, FR_MULT_GEN * FR_MULT_GEN)      # the cosets of the three wire columns' identity labels
+N_MAX = 1 << 26                                      # the quotient's coset has 4 n <= 2^28 points
+
+
+class Circuit:
+    """n = 2^k >= 2 gates.  selectors: the five columns qL, qR, qO, qM, qC of n ints; wires: the three columns a, b, c of
+    n variable numbers (two cells naming one variable are copy-constrained); the first n_public rows are the public
+    inputs: qL = 1, every other selector 0, the input in column a."""
+
+    def __init__(self, n, selectors, wires, n_public=0):
+        n, n_public = int(n), int(n_public)
+        if n < 2 or n & (n - 1) or n > N_MAX:
+            raise ValueError("n = %d: a power of two in [2, 2^26]" % n)
+        selectors, wires = [list(col) for col in selectors], [list(col) for col in wires]
+        if len(selectors) != 5 or len(wires) != 3 or any(len(col) != n for col in selectors + wires):
+            raise ValueError("five selector columns and three wire columns of n = %d rows" % n)
+        if not 0 <= n_public <= n:
+            raise ValueError("n_public = %d: at most n = %d" % (n_public, n))
+        self.n, self.n_public = n, n_public
+        self.selectors = [[int(v) % FR for v in col] for col in selectors]
+        self.wires = [[int(v) for v in col] for col in wires]
+        if any(v < 0 for col in self.wires for v in col):
+            raise ValueError("a variable number is negative")
+        self.n_vars = 1 + max(v for col in self.wires for v in col)
+        self._index = None
+        for i in range(n_public):
+            if [col[i] for col in self.selectors] != [1, 0, 0, 0, 0]:
+                raise ValueError("row %d is a public input: qL = 1 and every other selector 0" % i)
+
+    def permutation(self):
+        """sigma over the cells j n + i: the cells of one variable, in increasing order, form one cycle"""
+        n = self.n
+        cells = {}
+        for j, col in enumerate(self.wires):
+            for i, v in enumerate(col):
+                cells.setdefault(v, []).append(j * n + i)
+        sigma = [0] * (3 * n)
+        for members in cells.values():
+            for at, cell in enumerate(members):
+                sigma[cell] = members[(at + 1) % len(members)]
+        return sigma
+
+    def sigma_labels(self):
+        """the three rows s1, s2, s3: cell (j, i) carries the identity label k_j' omega^i' of the cell sigma maps it to"""
+        n, powers = self.n, [1]
+        omega = root_of_unity(n)
+        for _ in range(n - 1):
+            powers.append(powers[-1] * omega % FR)
+        sigma = self.permutation()
+        return [[K[sigma[j * n + i] // n] * powers[sigma[j * n + i] % n] % FR for i in range(n)] for j in range(3)]
+
+    def checked_assignment(self, assignment):
+        """one int in [0, r) per variable"""
+        values = [int(v) for v in assignment]
+        if len(values) != self.n_vars:
+            raise ValueError("%d values for %d variables" % (len(values), self.n_vars))
+        if any(not 0 <= v < FR for v in values):
+            raise ValueError("a value does not lie in [0, r)")
+        return values
+
+    def wire_values(self, assignment):
+        """the three columns of values under one Fr value per variable"""
+        values = self.checked_assignment(assignment)
+        return [[values[v] for v in col] for col in self.wires]
+
+    def wire_index(self):
+        """the three wire columns as one [3, n] index array, built once"""
+        if self._index is None:
+            self._index = np.array(self.wires, dtype=np.int64)
+        return self._index
+
+
+class Builder:
+    """Collects variables and gates; build() puts the public inputs first and pads with empty gates to a power of two.
+    A variable used in several cells is copy-constrained by that alone."""
+
+    def __init__(self):
+        self._n_vars, self._public, self._gates = 0, [], []
+
+    def var(self) -> int:
+        self._n_vars += 1
+        return self._n_vars - 1
+
+    def public(self) -> int:
+        v = self.var()
+        self._public.append(v)
+        return v
+
+    def _known(self, *vs):
+        for v in vs:
+            if not (isinstance(v, int) and 0 <= v < self._n_vars):
+                raise ValueError("%r is no variable of this builder" % (v,))
+
+    def gate(self, ql, qr, qo, qm, qc, a, b, c):
+        """ql a + qr b + qo c + qm a b + qc = 0"""
+        self._known(a, b, c)
+        self._gates.append(((ql, qr, qo, qm, qc), (a, b, c)))
+
+    def mul(self, x, y, out):
+        self.gate(0, 0, -1, 1, 0, x, y, out)
+
+    def add(self, x, y, out):
+        self.gate(1, 1, -1, 0, 0, x, y, out)
+
+    def constant(self, x, value):
+        """x = value"""
+        self.gate(1, 0, 0, 0, -int(value), x, x, x)
+
+    def assert_equal(self, u, v):
+        """u = v, as the gate u - v = 0"""
+        self.gate(1, -1, 0, 0, 0, u, v, u)
+
+    def build(self) -> Circuit:
+        rows = [((1, 0, 0, 0, 0), (v, v, v)) for v in self._public] + self._gates
+        if self._n_vars == 0:
+            raise ValueError("a circuit needs a variable")
+        n = 2
+        while n < len(rows):
+            n *= 2
+        rows += [((0, 0, 0, 0, 0), (0, 0, 0))] * (n - len(rows))
+        circuit = Circuit(n, [[q[k] for q, _ in rows] for k in range(5)], [[w[k] for _, w in rows] for k in range(3)],
+                          len(self._public))
+        if circuit.n_vars != self._n_vars:
+            raise ValueError("variable %d is in no gate" % circuit.n_vars)
+        return circuit

@@ -187,3 +187,49 @@ def fr_poly_eval(coeffs, r, npolys=1):
     _lib.check(L.ozk_fr_poly_eval_dev(_ptr(coeffs), npolys, length, length, _wire.vp(rb), _ptr(out), _ptr(ws),
                                       ws.numel(), _stream()))
     return out
+
+
+def fr_rows_coset(rows, k, length, stride, s, c=1, out=None, out_len=None, out_stride=None):
+    """out[y][i] = c s^i rows[y][i] for i < length, zero up to out_len (ozk_fr_rows_coset_dev): k rows at `stride`
+    elements -> k rows of out_len (default length) at out_stride (default out_len), new ones unless `out` is given;
+    out may be `rows` itself when the lengths and strides agree.  Synchronises (the workspace dies here)."""
+    L = _lib.load()
+    out_len = length if out_len is None else int(out_len)
+    out_stride = out_len if out_stride is None else int(out_stride)
+    if out is None:
+        out = torch.empty((k, 32 * out_stride), dtype=torch.uint8, device=rows.device)
+    ws = torch.empty(max(int(L.ozk_fr_rows_coset_workspace_bytes(k, length, out_len)), 256), dtype=torch.uint8,
+                     device=rows.device)
+    _lib.check(L.ozk_fr_rows_coset_dev(_ptr(rows), k, length, stride, _wire.vp(_wire.le32([int(s) % FR])),
+                                       _wire.vp(_wire.le32([int(c) % FR])), _ptr(out), out_len, out_stride, _ptr(ws),
+                                       ws.numel(), _stream()))
+    torch.cuda.current_stream().synchronize()
+    return out
+
+
+def fr_perm_product(wires, sigma, length, stride, omega, ks, beta, gamma):
+    """The permutation grand product of three wire rows and three sigma rows of `length` elements at `stride`
+    (ozk_fr_perm_product_dev; cell (j, i) has the identity label ks[j] omega^i): (z, `length` x 32 bytes on the device
+    with z[0] = 1; the product over all rows as an int; the number of rows with a zero denominator).  Synchronises."""
+    L = _lib.load()
+    z = torch.empty(32 * length, dtype=torch.uint8, device=wires.device)
+    tail = torch.empty(48, dtype=torch.uint8, device=wires.device)         # the total, then the count
+    ws = torch.empty(max(int(L.ozk_fr_perm_product_workspace_bytes(length)), 256), dtype=torch.uint8, device=wires.device)
+    le = lambda vs: _wire.vp(_wire.le32([int(v) % FR for v in vs]))
+    _lib.check(L.ozk_fr_perm_product_dev(_ptr(wires), _ptr(sigma), length, stride, le([omega]), le(ks), le([beta]),
+                                         le([gamma]), _ptr(z), _ptr(tail), _ptr(tail[32:]), _ptr(ws), ws.numel(),
+                                         _stream()))
+    host = _wire.host_bytes(tail)
+    return z, int.from_bytes(host[:32], "little"), int.from_bytes(host[32:36], "little", signed=True)
+
+
+def plonk_quotient(wit, wit_stride, key, key_stride, n, alpha, beta, gamma, ks, zh_inv, out=None):
+    """t on the coset of 4 n points from the five witness rows and the ten key rows (ozk_plonk_quotient_dev): 4 n x 32
+    bytes on the device, a new tensor unless `out` is given.  Asynchronous on the current stream."""
+    L = _lib.load()
+    if out is None:
+        out = torch.empty(32 * 4 * n, dtype=torch.uint8, device=wit.device)
+    le = lambda vs: _wire.vp(_wire.le32([int(v) % FR for v in vs]))
+    _lib.check(L.ozk_plonk_quotient_dev(_ptr(wit), wit_stride, _ptr(key), key_stride, n, le([alpha]), le([beta]),
+                                        le([gamma]), le(ks), le(zh_inv), _ptr(out), _stream()))
+    return out
