@@ -335,7 +335,7 @@ static int bace_upload_program(const BaceLayout& L, const int32_t* program, int 
 
 // the constant block L.cst: 1/N (Montgomery), 1/D (plain), 1 (plain), and r (Montgomery) when r_host32 is given
 static int bace_upload_consts(const BaceLayout& L, int N, int D, const uint8_t* r_host32, hipStream_t st) {
-  BaceWords c;
+  FrWords<4> c;
   memset(c.w, 0, sizeof(c.w));
   u32 t[8];
   bace_inv_pow2_host(ilog2((uint32_t)N), true, t);
@@ -344,7 +344,7 @@ static int bace_upload_consts(const BaceLayout& L, int N, int D, const uint8_t* 
   memcpy(c.w + 8, t, 32);
   c.w[16] = 1;
   if (r_host32) memcpy(c.w + 24, r_host32, 32);
-  hipLaunchKernelGGL(k_bace_put, dim3(1), dim3(64), 0, st, c, 32, L.cst);
+  hipLaunchKernelGGL(k_fr_put<4>, dim3(1), dim3(64), 0, st, c, 32, L.cst);
   if (r_host32) hipLaunchKernelGGL(k_to_mont_inplace, dim3(1), dim3(64), 0, st, L.cst + 24, 1);
   OZK_HIP(hipGetLastError());
   return OZK_OK;
@@ -465,9 +465,7 @@ int ozk_fr_poly_eval_dev(const void* d_coeffs, int32_t npolys, int32_t len, int6
   hipStream_t st = (hipStream_t)stream;
   u32* partial = (u32*)d_workspace;
   u32* r = (u32*)((uint8_t*)d_workspace + pad256((size_t)npolys * 256 * 32));
-  BaceWords c;
-  memcpy(c.w, r_host32, 32);
-  hipLaunchKernelGGL(k_bace_put, dim3(1), dim3(64), 0, st, c, 8, r);
+  fr_put_element(r_host32, r, st);
   hipLaunchKernelGGL(k_to_mont_inplace, dim3(1), dim3(64), 0, st, r, 1);
   bace_poly_eval((const u32*)d_coeffs, (size_t)poly_stride * 8, len, npolys, r, partial, (u32*)d_out, st);
   OZK_HIP(hipGetLastError());

@@ -743,23 +743,12 @@ static int qap_build_tables(const DomainTables& t, int m, const uint8_t* omega_h
   return OZK_OK;
 }
 
-// small host values reach the device as kernel arguments (captured at launch: no host buffer has to outlive the
-// call).  BACE's constants and roots of unity, which are temporaries of its host code, go up this way (bace.cuh).
-struct BaceWords {
-  u32 w[32];
-};
-__global__ void k_bace_put(BaceWords c, int nw, u32* __restrict__ dst) {
-  for (int i = threadIdx.x; i < nw; i += blockDim.x) dst[i] = c.w[i];
-}
-
 // enqueues the build of a domain's tables into `t`: the witness map's when g is given, else the transform's twiddles
 static int tables_build(const DomainTables& t, int n, const uint8_t* omega, const uint8_t* g, bool by_value, hipStream_t st) {
   if (g) return qap_build_tables(t, n, omega, g, st);
   hip_clear_stale();   // (ozk_common.h: a stale error of the calling thread is not this call's)
   if (by_value) {
-    BaceWords c;
-    memcpy(c.w, omega, 32);
-    hipLaunchKernelGGL(k_bace_put, dim3(1), dim3(64), 0, st, c, 8, t.consts->omega);
+    fr_put_element(omega, t.consts->omega, st);
   } else {
     OZK_HIP(hipMemcpyAsync(t.consts->omega, omega, 32, hipMemcpyHostToDevice, st));
   }

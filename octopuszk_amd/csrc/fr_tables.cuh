@@ -1,5 +1,6 @@
-// What the Fr kernels of fft.hip and bace.cuh share: element I/O, exponentiation by a word, the two-level power
-// table, and the description of one domain's tables.  Included by fft.hip only.
+// What the Fr kernels of fft.hip and bace.cuh share: element I/O, host words in kernel arguments, exponentiation by a
+// word, the two-level power table, and the description of one domain's tables.  Included by
+// fft.hip only.
 #pragma once
 #include "curve.cuh"
 #include "ozk_common.h"
@@ -34,6 +35,27 @@ __device__ __forceinline__ Fe<FrP, B> fr_load(const u32* src) {
 template <int B>
 __device__ __forceinline__ void fr_to_wire(const Fe<FrP, B>& v, u32* dst) {
   ElemTraits<Fe<FrP, B>>::to_wire(v, dst);
+}
+
+// ---- host words in the kernel arguments ------------------------------------------------------------------------
+// Small host values reach the device as kernel arguments (captured at launch: no host buffer has to outlive the
+// call): N elements of 8 packed words.  A kernel takes single elements this way (FrArg), and k_fr_put writes a batch
+// to device memory: BACE's constants and roots of unity, which are temporaries of its host code, a domain's omega, the
+// points of a set opening.
+template <int N>
+struct FrWords {
+  u32 w[8 * N];
+};
+using FrArg = FrWords<1>;
+template <int N>
+__global__ void __launch_bounds__(256) k_fr_put(FrWords<N> c, int nw, u32* __restrict__ dst) {
+  for (int i = threadIdx.x; i < nw; i += blockDim.x) dst[i] = c.w[i];
+}
+// one element of host memory to dst
+inline void fr_put_element(const uint8_t* host32, u32* dst, hipStream_t st) {
+  FrArg c;
+  memcpy(c.w, host32, 32);
+  hipLaunchKernelGGL(k_fr_put<1>, dim3(1), dim3(64), 0, st, c, 8, dst);
 }
 
 // base^e (base in Montgomery form, any bound the multiplier takes): 32 squarings, a product per set bit

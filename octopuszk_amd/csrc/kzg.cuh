@@ -1,14 +1,14 @@
 // The Fr kernels of KZG openings: the quotient (p(X) - p(z)) / (X - z) with the value p(z),
 // in coefficient form and in evaluation form, and a weighted sum of rows.  Included at the end of fft.hip (it uses that
-// unit's element I/O, power table and block sum); the per-lane pieces above the kernels compile for the host too
-// (tests/native/kzg_hostcheck.cpp).
+// unit's element I/O, power table and block sum).  The per-lane pieces, the staged tile, the scan and the entry checks
+// are fr_rows.cuh's; the pieces compile for the host too (tests/native/kzg_hostcheck.cpp).
 //
 // Every value in HBM is 32 bytes LE, plain (non-Montgomery); inputs are taken mod r, outputs are canonical.
 //
 // Coefficient form.  h_j = p_j + z h_{j+1}, h_len = 0 is Horner's rule run from the top: y = h_0 and q_{j-1} = h_j.
 // A workgroup stages a tile of KZG_TILE coefficients in LDS (coalesced 32-byte reads), a lane runs the recurrence over
 // its KZG_L consecutive elements of the tile (kzg_piece, carry 0), and the carry into every lane,
-// S_l = a_l + z^L S_{l+1}, is a suffix scan over the workgroup (kzg_wg_scan: log2 256 steps, one product each).  The
+// S_l = a_l + z^L S_{l+1}, is a suffix scan over the workgroup (fr_wg_scan: log2 256 steps, one product each).  The
 // lane then runs the recurrence again from its carry and the tile goes out through LDS, coalesced.  With more than
 // one tile per row a first pass leaves every tile's value at z in the workspace, one workgroup per row scans them
 // (the same scan with z^T), and the tile pass starts from the carry into its tile.
@@ -25,132 +25,24 @@
 //   domain); bytes: 32 read + 32 written in the first pass, 64 read + 32 written in the second.
 #pragma once
 #include "fp29.cuh"
+#include "fr_rows.cuh"
 
 namespace ozk {
 
-using FrP = FrParams;
-
-constexpr int KZG_WG = 256;                    // lanes of a workgroup
-constexpr int KZG_L = 4;                       // consecutive coefficients of a lane
-constexpr int KZG_TILE = KZG_WG * KZG_L;       // coefficients of a workgroup: 33 KiB of LDS + 9 KiB of scan
-constexpr int KZG_INV_BATCH = 8;               // differences sharing one inversion
-using KzgV = Fe<FrP, 32>;
-
-// ---- the per-lane pieces ----
-// h_i = p_i + z h_{i+1} for i = n - 1 .. 0 with h_n = carry; returns h_0.  p, carry, h: plain; z: Montgomery form.
-// n <= N, the length the loop is unrolled for (a kernel's lanes run n = N, so that p and h stay in registers).
-// KEEP: the h_i are written to h, which may not alias p; else h is not touched (the value alone).
-template <int N, bool KEEP>
-OZK_HD KzgV kzg_piece(const Fe<FrP, 16>* p, int n, const Fe<FrP, 16>& z, const KzgV& carry, KzgV* h) {
-  KzgV c = carry;
-#pragma unroll
-  for (int k = 0; k < N; k++) {
-    const int i = N - 1 - k;
-    if (i < n) {
-      c = KzgV(reduce_to<32>(add(p[i], mul(z, c))));
-      if (KEEP) h[i] = c;
-    }
-  }
-  return c;
-}
-// a + m s: the value of a piece followed by what lies above it (m = z^(length of the piece), Montgomery form)
-OZK_HD KzgV kzg_compose(const KzgV& a, const KzgV& m, const KzgV& s) {
-  return KzgV(reduce_to<32>(add(a, mul(m, s))));
-}
-// out_k = 1 / d_k for k < n <= BATCH (Montgomery form in and out), 0 for d_k = 0: one inversion for the chunk
-template <int BATCH>
-OZK_HD void kzg_chunk_inverses(const KzgV* d, int n, KzgV* out) {
-  KzgV prefix[BATCH];
-  KzgV run = KzgV(fe_one<FrP>());
-#pragma unroll
-  for (int k = 0; k < BATCH; k++) {
-    if (k < n && !is_zero(d[k])) run = KzgV(mul(run, d[k]));
-    prefix[k] = run;
-  }
-  KzgV invrun = inv(run);
-#pragma unroll
-  for (int k = BATCH - 1; k >= 0; k--) {
-    if (k >= n) continue;
-    if (is_zero(d[k])) {
-      out[k] = KzgV(fe_zero<FrP>());
-      continue;
-    }
-    out[k] = k > 0 ? KzgV(mul(invrun, prefix[k - 1])) : invrun;
-    invrun = KzgV(mul(invrun, d[k]));
-  }
-}
-
 #if defined(__HIPCC__)
 // ---- coefficient form ----
-struct KzgRow {        // per row, Montgomery form, canonical
-  u32 z[8], zl[8], zt[8];   // z, z^KZG_L, z^KZG_TILE
-};
 __global__ void __launch_bounds__(64) k_kzg_open_consts(const u32* __restrict__ points, int npolys, KzgRow* __restrict__ rows) {
   const int y = blockIdx.x * blockDim.x + threadIdx.x;
   if (y >= npolys) return;
-  using E16 = ElemTraits<Fe<FrP, 16>>;
-  const auto z = ElemTraits<Fe<FrP, 17>>::from_wire(points + (size_t)y * 8);
-  E16::store(canonical(z), rows[y].z);
-  E16::store(canonical(fe_pow_u32(z, KZG_L)), rows[y].zl);
-  E16::store(canonical(fe_pow_u32(z, KZG_TILE)), rows[y].zt);
+  kzg_row_consts(ElemTraits<Fe<FrP, 17>>::from_wire(points + (size_t)y * 8), rows + y, nullptr);
 }
-
-// element e of a staged tile, word w: word-major, a pad word every 32 elements, so that the lanes of a wave hit
-// distinct banks both when they touch consecutive elements and when they touch elements KZG_L apart
-constexpr int KZG_TILE_PAD = KZG_TILE + KZG_TILE / 32;
-constexpr int KZG_TILE_WORDS = 8 * KZG_TILE_PAD;
-__device__ __forceinline__ int kzg_at(int e, int w) { return w * KZG_TILE_PAD + e + (e >> 5); }
 
 // the tile's coefficients (canonical; zero beyond len) into LDS, then the lane's own KZG_L of them
 __device__ __forceinline__ void kzg_tile_load(const u32* __restrict__ row, int len, int t, u32* tile, Fe<FrP, 16> (&p)[KZG_L]) {
-#pragma unroll
-  for (int i = 0; i < KZG_L; i++) {
-    const int e = i * KZG_WG + threadIdx.x;
-    const long long j = (long long)t * KZG_TILE + e;
-    u32 o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (j < len) pack(canonical(fr_load<85>(row + (size_t)j * 8)), o);
-#pragma unroll
-    for (int w = 0; w < 8; w++) tile[kzg_at(e, w)] = o[w];
-  }
+  fr_tile_fill<KZG_WG, KZG_L>(row, len, t, tile);
   block_sync();
 #pragma unroll
-  for (int i = 0; i < KZG_L; i++) {
-    u32 o[8];
-#pragma unroll
-    for (int w = 0; w < 8; w++) o[w] = tile[kzg_at(threadIdx.x * KZG_L + i, w)];
-    p[i] = unpack<FrP, 16>(o);
-  }
-}
-// S_l = a_l + m S_{l+1} over the lanes of the workgroup, S_256 = 0 (m: Montgomery form).  Returns the lane's S_l and
-// leaves every S in `part` (limb-major, 9 x 256 words) behind a barrier.
-__device__ __forceinline__ KzgV kzg_wg_scan(KzgV a, KzgV m, u32* part) {
-  const int l = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < 9; i++) part[i * KZG_WG + l] = a.l[i];
-  block_sync();
-  for (int d = 1; d < KZG_WG; d <<= 1) {
-    KzgV s = KzgV(fe_zero<FrP>());
-    if (l + d < KZG_WG) {
-#pragma unroll
-      for (int i = 0; i < 9; i++) s.l[i] = part[i * KZG_WG + l + d];
-    }
-    block_sync();
-    a = kzg_compose(a, m, s);
-#pragma unroll
-    for (int i = 0; i < 9; i++) part[i * KZG_WG + l] = a.l[i];
-    block_sync();
-    m = KzgV(sqr(m));
-  }
-  return a;
-}
-// what lies above lane l after the scan: S_{l+1}, or `above` (what lies above the workgroup) for the last lane
-__device__ __forceinline__ KzgV kzg_scan_next(const u32* part, const KzgV& above) {
-  KzgV s = above;
-  if (threadIdx.x + 1 < KZG_WG) {
-#pragma unroll
-    for (int i = 0; i < 9; i++) s.l[i] = part[i * KZG_WG + threadIdx.x + 1];
-  }
-  return s;
+  for (int i = 0; i < KZG_L; i++) p[i] = fr_tile_get(tile, threadIdx.x * KZG_L + i);
 }
 
 // first pass (rows of several tiles): the value of tile t of row y at z, to agg[y nt + t]
@@ -163,7 +55,7 @@ __global__ void __launch_bounds__(KZG_WG) k_kzg_open_tiles(const u32* __restrict
   Fe<FrP, 16> p[KZG_L];
   kzg_tile_load(coeffs + (size_t)y * poly_cs, len, t, tile, p);
   const KzgV a = kzg_piece<KZG_L, false>(p, KZG_L, E16::load(rows[y].z), KzgV(fe_zero<FrP>()), nullptr);
-  const KzgV s = kzg_wg_scan(a, KzgV(E16::load(rows[y].zl)), part);
+  const KzgV s = fr_wg_scan<KZG_WG, true>(a, FrScanAffine{KzgV(E16::load(rows[y].zl))}, part);
   if (threadIdx.x == 0) fr_store(canonical(s), agg + (size_t)blockIdx.x * 8);
 }
 // second pass, one workgroup per row: carry[y nt + t] = h at the first coefficient of tile t + 1, 256 tiles at a time
@@ -171,22 +63,9 @@ __global__ void __launch_bounds__(KZG_WG) k_kzg_open_tiles(const u32* __restrict
 __global__ void __launch_bounds__(KZG_WG) k_kzg_open_carries(const u32* __restrict__ agg, int nt, const KzgRow* __restrict__ rows,
                                                             u32* __restrict__ carry) {
   __shared__ u32 part[9 * KZG_WG];
-  using E16 = ElemTraits<Fe<FrP, 16>>;
-  const int y = blockIdx.x, l = threadIdx.x;
-  const KzgV m = KzgV(E16::load(rows[y].zt));
-  KzgV above = KzgV(fe_zero<FrP>());
-  for (int base = (nt - 1) / KZG_WG * KZG_WG; base >= 0; base -= KZG_WG) {
-    const int t = base + l;
-    KzgV a = KzgV(fe_zero<FrP>());
-    if (t < nt) a = KzgV(fr_load<16>(agg + ((size_t)y * nt + t) * 8));
-    if (l == KZG_WG - 1) a = kzg_compose(a, m, above);
-    kzg_wg_scan(a, m, part);
-    const KzgV c = kzg_scan_next(part, above);
-    if (t < nt) fr_store(canonical(c), carry + ((size_t)y * nt + t) * 8);
-#pragma unroll
-    for (int i = 0; i < 9; i++) above.l[i] = part[i * KZG_WG];
-    block_sync();
-  }
+  const size_t y = blockIdx.x;
+  const FrScanAffine op{KzgV(ElemTraits<Fe<FrP, 16>>::load(rows[y].zt))};
+  fr_carries_scan<KZG_WG, true>(agg + y * nt * 8, nt, op, carry + y * nt * 8, part);
 }
 // the tile pass: quotient and value.  carry: null when every row is one tile.
 __global__ void __launch_bounds__(KZG_WG) k_kzg_open_apply(const u32* __restrict__ coeffs, size_t poly_cs, int len, int nt,
@@ -204,32 +83,17 @@ __global__ void __launch_bounds__(KZG_WG) k_kzg_open_apply(const u32* __restrict
   if (carry) above = KzgV(fr_load<16>(carry + (size_t)blockIdx.x * 8));
   KzgV a = kzg_piece<KZG_L, false>(p, KZG_L, z, KzgV(fe_zero<FrP>()), nullptr);
   if (l == KZG_WG - 1) a = kzg_compose(a, zl, above);
-  kzg_wg_scan(a, zl, part);
+  fr_wg_scan<KZG_WG, true>(a, FrScanAffine{zl}, part);
   KzgV h[KZG_L];
-  kzg_piece<KZG_L, true>(p, KZG_L, z, kzg_scan_next(part, above), h);
+  kzg_piece<KZG_L, true>(p, KZG_L, z, fr_scan_neighbour<KZG_WG, true>(part, above), h);
   // (a lane overwrites the elements it alone has read)
 #pragma unroll
-  for (int i = 0; i < KZG_L; i++) {
-    u32 o[8];
-    pack(canonical(h[i]), o);
-#pragma unroll
-    for (int w = 0; w < 8; w++) tile[kzg_at(l * KZG_L + i, w)] = o[w];
-  }
+  for (int i = 0; i < KZG_L; i++) fr_tile_put(tile, l * KZG_L + i, canonical(h[i]));
   block_sync();
   // q_j = h_{j+1}: element e of the tile receives h of element e + 1, the last one what lies above the tile
   u32 top[8];
   pack(canonical(above), top);
-  u32* qrow = quot + (size_t)y * quot_cs;
-#pragma unroll
-  for (int i = 0; i < KZG_L; i++) {
-    const int e = i * KZG_WG + l;
-    const long long j = (long long)t * KZG_TILE + e;
-    if (j >= len) continue;
-    u32 o[8];
-#pragma unroll
-    for (int w = 0; w < 8; w++) o[w] = e + 1 < KZG_TILE ? tile[kzg_at(e + 1, w)] : top[w];
-    fr_store_words(o, qrow + (size_t)j * 8);
-  }
+  fr_tile_store<KZG_WG, KZG_L>(tile, t, len, 1, top, 0, quot + (size_t)y * quot_cs);
   if (t == 0 && l == 0) fr_store(canonical(h[0]), values + (size_t)y * 8);
 }
 
@@ -365,8 +229,6 @@ __global__ void __launch_bounds__(256) k_fr_rows_combine(const u32* rows, int k,
 }
 
 // ---- host side ----
-constexpr long long KZG_MAX_ELEMS = 1ll << 28;
-
 struct KzgOpenLayout {
   KzgRow* rows;
   u32 *agg, *carry;
@@ -406,18 +268,6 @@ static KzgEvLayout kzg_ev_layout(int npolys, int n, void* wsp) {
   L.bytes = b.off;
   return L;
 }
-static bool kzg_shape_ok(int npolys, int len) {
-  return npolys >= 1 && len >= 1 && (long long)npolys * len <= KZG_MAX_ELEMS;
-}
-// rows of `len` elements, row y at base + 32 y stride bytes: the bytes they span
-static size_t kzg_span(int npolys, int len, long long stride) {
-  return ((size_t)(npolys - 1) * (size_t)stride + (size_t)len) * 32;
-}
-static bool kzg_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
-}
-static bool kzg_misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
 #endif  // __HIPCC__
 
 }  // namespace ozk
@@ -439,13 +289,12 @@ int ozk_fr_poly_open_dev(const void* d_coeffs, int32_t npolys, int32_t len, int6
   if ((poly_stride != 0 && poly_stride < len) || quot_stride < len)
     return fail(OZK_E_INVALID, "bad strides: poly_stride %lld (0 or >= len), quot_stride %lld (>= len), len %d",
                 (long long)poly_stride, (long long)quot_stride, len);
-  if (!d_coeffs || !d_points || !d_quot || !d_values || !d_workspace) return fail(OZK_E_INVALID, "null pointer argument");
-  if (kzg_misaligned16(d_coeffs) || kzg_misaligned16(d_points) || kzg_misaligned16(d_quot) || kzg_misaligned16(d_values))
-    return fail(OZK_E_INVALID, "elements must be 16-byte aligned");
+  if (int rc = fr_check_pointers(d_coeffs, d_points, d_quot, d_values, d_workspace)) return rc;
+  if (int rc = fr_check_aligned16(d_coeffs, d_points, d_quot, d_values)) return rc;
   if (kzg_overlap(d_coeffs, kzg_span(npolys, len, poly_stride), d_quot, kzg_span(npolys, len, quot_stride)))
     return fail(OZK_E_INVALID, "d_quot overlaps d_coeffs");
   const KzgOpenLayout L = kzg_open_layout(npolys, len, d_workspace);
-  if (workspace_bytes < L.bytes) return fail(OZK_E_INVALID, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+  if (int rc = fr_check_workspace(L.bytes, workspace_bytes)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const u32* c = (const u32*)d_coeffs;
   const size_t pcs = (size_t)poly_stride * 8, qcs = (size_t)quot_stride * 8;
@@ -477,32 +326,18 @@ int ozk_fr_evals_open_dev(const void* d_evals, int32_t npolys, int32_t n, int64_
   if ((evals_stride != 0 && evals_stride < n) || quot_stride < n)
     return fail(OZK_E_INVALID, "bad strides: evals_stride %lld (0 or >= n), quot_stride %lld (>= n), n %d",
                 (long long)evals_stride, (long long)quot_stride, n);
-  if (!d_evals || !omega_host32 || !d_points || !d_quot || !d_values || !d_workspace)
-    return fail(OZK_E_INVALID, "null pointer argument");
-  if (kzg_misaligned16(d_evals) || kzg_misaligned16(d_points) || kzg_misaligned16(d_quot) || kzg_misaligned16(d_values))
-    return fail(OZK_E_INVALID, "elements must be 16-byte aligned");
+  if (int rc = fr_check_pointers(d_evals, omega_host32, d_points, d_quot, d_values, d_workspace)) return rc;
+  if (int rc = fr_check_aligned16(d_evals, d_points, d_quot, d_values)) return rc;
   if (kzg_overlap(d_evals, kzg_span(npolys, n, evals_stride), d_quot, kzg_span(npolys, n, quot_stride)))
     return fail(OZK_E_INVALID, "d_quot overlaps d_evals");
-  BaceWords om;
-  memset(om.w, 0, sizeof(om.w));
-  memcpy(om.w, omega_host32, 32);
-  {
-    // omega has order exactly n when omega^(n / 2) = -1
-    u32 w[8], o[8];
-    memcpy(w, omega_host32, 32);
-    Fe<FrP, 32> t = Fe<FrP, 32>(to_mont<FrP>(w));
-    for (int k = n; k > 2; k >>= 1) t = Fe<FrP, 32>(sqr(t));
-    from_mont(Fe<FrP, 32>(reduce_to<32>(add(t, fe_one<FrP>()))), o);
-    u32 any = 0;
-    for (int i = 0; i < 8; i++) any |= o[i];
-    if (any) return fail(OZK_E_INVALID, "omega does not have order %d (omega^(n/2) != -1)", n);
-  }
+  if (!fr_omega_has_order(omega_host32, n))
+    return fail(OZK_E_INVALID, "omega does not have order %d (omega^(n/2) != -1)", n);
   const KzgEvLayout L = kzg_ev_layout(npolys, n, d_workspace);
-  if (workspace_bytes < L.bytes) return fail(OZK_E_INVALID, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+  if (int rc = fr_check_workspace(L.bytes, workspace_bytes)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const u32* f = (const u32*)d_evals;
   const size_t ecs = (size_t)evals_stride * 8, qcs = (size_t)quot_stride * 8;
-  hipLaunchKernelGGL(k_bace_put, dim3(1), dim3(64), 0, st, om, 8, L.omega);
+  fr_put_element(omega_host32, L.omega, st);
   const PowTable pt = PowTable::upto(n);
   pt.build(L.omega, L.pw, st);
   hipLaunchKernelGGL(k_kzg_ev_consts, dim3((npolys + 63) / 64), dim3(64), 0, st, (const u32*)d_points, npolys, n, L.rows,
@@ -525,9 +360,8 @@ int ozk_fr_rows_combine_dev(const void* d_rows, int32_t k, int32_t len, int64_t 
   hip_clear_stale();
   if (k < 1 || len < 1 || row_stride < len || (long long)k * len > KZG_MAX_ELEMS)
     return fail(OZK_E_INVALID, "bad shape: %d rows of %d elements, stride %lld", k, len, (long long)row_stride);
-  if (!d_rows || !d_weights || !d_out) return fail(OZK_E_INVALID, "null pointer argument");
-  if (kzg_misaligned16(d_rows) || kzg_misaligned16(d_weights) || kzg_misaligned16(d_out))
-    return fail(OZK_E_INVALID, "elements must be 16-byte aligned");
+  if (int rc = fr_check_pointers(d_rows, d_weights, d_out)) return rc;
+  if (int rc = fr_check_aligned16(d_rows, d_weights, d_out)) return rc;
   if (d_out != d_rows && kzg_overlap(d_rows, kzg_span(k, len, row_stride), d_out, (size_t)len * 32))
     return fail(OZK_E_INVALID, "d_out overlaps d_rows (it may only be the first row itself)");
   hipLaunchKernelGGL(k_fr_rows_combine, dim3((len + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const u32*)d_rows, k,

@@ -48,31 +48,18 @@ __global__ void __launch_bounds__(256) k_fr_rows_combine_groups(const u32* __res
 // without the table of divided differences
 __global__ void __launch_bounds__(64) k_kzg_eval_set_consts(const u32* __restrict__ points, long long np,
                                                             KzgRow* __restrict__ rows, KzgSetPows* __restrict__ pows) {
-  using E16 = ElemTraits<Fe<FrP, 16>>;
   const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= np) return;
-  const auto z = ElemTraits<Fe<FrP, 17>>::from_wire(points + g * 8);
-  E16::store(canonical(z), rows[g].z);
-  KzgV m = fe_pow_u32(z, KZG_L);
-  E16::store(canonical(m), rows[g].zl);
-#pragma unroll 1
-  for (int d = 0; d < KZG_SCAN_STEPS; d++) {
-    E16::store(canonical(m), pows[g].m[d]);
-    m = KzgV(sqr(m));
-  }
-  E16::store(canonical(m), rows[g].zt);
+  kzg_row_consts(ElemTraits<Fe<FrP, 17>>::from_wire(points + g * 8), rows + g, pows + g);
 }
-// one lane per row and point: p(z) = (the value of tile 0) + z^KZG_TILE (the tail above it), k_kzg_set_mix's value
+// one lane per row and point: p(z) = (the value of tile 0) + z^KZG_TILE (the tail above it), as k_kzg_set_mix leaves it
 __global__ void __launch_bounds__(256) k_kzg_eval_set_values(const u32* __restrict__ agg, const u32* __restrict__ tails, int nt,
                                                              long long np, const KzgRow* __restrict__ rows,
                                                              u32* __restrict__ values) {
-  using E16 = ElemTraits<Fe<FrP, 16>>;
   const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= np) return;
   const size_t at = (size_t)g * nt;
-  fr_store(canonical(kzg_compose(KzgV(fr_load<16>(agg + at * 8)), KzgV(E16::load(rows[g].zt)),
-                                 KzgV(fr_load<16>(tails + at * 8)))),
-           values + (size_t)g * 8);
+  kzg_row_value(agg + at * 8, tails + at * 8, rows[g], values + (size_t)g * 8);
 }
 
 // ---- host side ----
@@ -119,9 +106,8 @@ int ozk_fr_rows_combine_groups_dev(const void* d_rows, int32_t k, int32_t len, i
   if (row_stride < len || out_stride < len)
     return fail(OZK_E_INVALID, "bad strides: row_stride %lld, out_stride %lld (both >= len), len %d", (long long)row_stride,
                 (long long)out_stride, len);
-  if (!d_rows || !d_weights || !group_of_row_host || !d_out) return fail(OZK_E_INVALID, "null pointer argument");
-  if (kzg_misaligned16(d_rows) || kzg_misaligned16(d_weights) || kzg_misaligned16(d_out))
-    return fail(OZK_E_INVALID, "elements must be 16-byte aligned");
+  if (int rc = fr_check_pointers(d_rows, d_weights, group_of_row_host, d_out)) return rc;
+  if (int rc = fr_check_aligned16(d_rows, d_weights, d_out)) return rc;
   if (kzg_overlap(d_rows, kzg_span(k, len, row_stride), d_out, kzg_span(groups, len, out_stride)))
     return fail(OZK_E_INVALID, "d_out overlaps d_rows");
   KzgGroupIds ids;
@@ -153,12 +139,12 @@ int ozk_fr_poly_eval_set_dev(const void* d_coeffs, int32_t npolys, int32_t len, 
     return fail(OZK_E_INVALID, "bad set: %d points a row (1 <= t <= %d, npolys t <= 2^28)", t, KZG_SET_T);
   if (poly_stride != 0 && poly_stride < len)
     return fail(OZK_E_INVALID, "bad stride: poly_stride %lld (0 or >= len), len %d", (long long)poly_stride, len);
-  if (!d_coeffs || !points_host || !d_values || !d_workspace) return fail(OZK_E_INVALID, "null pointer argument");
-  if (kzg_misaligned16(d_coeffs) || kzg_misaligned16(d_values)) return fail(OZK_E_INVALID, "elements must be 16-byte aligned");
+  if (int rc = fr_check_pointers(d_coeffs, points_host, d_values, d_workspace)) return rc;
+  if (int rc = fr_check_aligned16(d_coeffs, d_values)) return rc;
   if (kzg_overlap(d_coeffs, kzg_span(npolys, len, poly_stride), d_values, (size_t)npolys * t * 32))
     return fail(OZK_E_INVALID, "d_values overlaps d_coeffs");
   const KzgEvalSetLayout L = kzg_eval_set_layout(npolys, len, t, d_workspace);
-  if (workspace_bytes < L.bytes) return fail(OZK_E_INVALID, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+  if (int rc = fr_check_workspace(L.bytes, workspace_bytes)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const long long np = (long long)npolys * t;
   kzg_set_upload(points_host, (size_t)np, L.pts, st);

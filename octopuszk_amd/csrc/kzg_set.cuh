@@ -1,7 +1,7 @@
 // The Fr kernels of KZG set openings: the quotient (p - I) / Z_S for S = (z_0 .. z_{t-1}),
 // Z_S = prod (X - z_i) and I the interpolant of p on S, with the values p(z_i), in coefficient form and in evaluation
-// form.  Included at the end of fft.hip after kzg.cuh, whose tiles, scan and chunk inversion it builds on; the
-// per-lane pieces above the kernels compile for the host too (tests/native/kzg_set_hostcheck.cpp).
+// form.  Included at the end of fft.hip after kzg.cuh; it builds on the tiles, scan and chunk inversion of
+// fr_rows.cuh.  The per-lane pieces above the kernels compile for the host too (tests/native/kzg_set_hostcheck.cpp).
 //
 // Coefficient form.  Dividing by (X - z_0), .., (X - z_{t-1}) in turn is t runs of the recurrence of section 22,
 // stage s over the output of stage s - 1: h^s_j = h^(s-1)_j + z_s h^s_(j+1), h^(-1) = p.  Position j holds h_j at
@@ -34,7 +34,6 @@ namespace ozk {
 
 constexpr int KZG_SET_T = 32;       // points of a set, coefficient form
 constexpr int KZG_SET_EV_T = 8;     // points of a set, evaluation form
-constexpr int KZG_SCAN_STEPS = 8;   // log2 KZG_WG
 
 // ---- the per-lane pieces ----
 // a canonical element as 8 packed words, word by word (these pieces compile without the device's element I/O)
@@ -59,20 +58,10 @@ OZK_HD KzgV kzg_set_pow(const Fe<FrP, 16>& z, int e) {
   }
   return r;
 }
-// one stage over a lane's piece, in place or for its value alone: h_i = v_i + z h_{i+1}, h_n = carry; returns h_0.
-// v, carry: plain; z: Montgomery form.  n <= N as kzg_piece.
+// one stage over a lane's piece, in place or for its value alone: kzg_piece with the piece as its own output
 template <int N, bool KEEP>
 OZK_HD KzgV kzg_set_piece(KzgV* v, int n, const Fe<FrP, 16>& z, const KzgV& carry) {
-  KzgV c = carry;
-#pragma unroll
-  for (int k = 0; k < N; k++) {
-    const int i = N - 1 - k;
-    if (i < n) {
-      c = KzgV(reduce_to<32>(add(v[i], mul(z, c))));
-      if (KEEP) v[i] = c;
-    }
-  }
-  return c;
+  return kzg_piece<N, KEEP>(v, n, z, carry, v);
 }
 // row s of the table starts at entry s (s + 1) / 2 and has s + 1 entries
 OZK_HD int kzg_set_tab_at(int s, int i) { return s * (s + 1) / 2 + i; }
@@ -143,27 +132,18 @@ inline bool kzg_set_distinct(const u32* pts, int n) {
 }
 
 #if defined(__HIPCC__)
-// ---- host points to the device: kernel arguments, as k_bace_put, 96 elements a launch ----
+// ---- host points to the device: kernel arguments (k_fr_put), 96 elements a launch ----
 constexpr int KZG_SET_PUT = 96;
-struct KzgSetWords {
-  u32 w[8 * KZG_SET_PUT];
-};
-__global__ void __launch_bounds__(256) k_kzg_set_put(KzgSetWords c, int nw, u32* __restrict__ dst) {
-  for (int i = threadIdx.x; i < nw; i += blockDim.x) dst[i] = c.w[i];
-}
 static void kzg_set_upload(const uint8_t* host, size_t count, u32* dst, hipStream_t st) {
   for (size_t at = 0; at < count; at += KZG_SET_PUT) {
     const size_t m = count - at < (size_t)KZG_SET_PUT ? count - at : (size_t)KZG_SET_PUT;
-    KzgSetWords c;
+    FrWords<KZG_SET_PUT> c;
     memcpy(c.w, host + at * 32, m * 32);
-    hipLaunchKernelGGL(k_kzg_set_put, dim3(1), dim3(256), 0, st, c, (int)(m * 8), dst + at * 8);
+    hipLaunchKernelGGL(k_fr_put<KZG_SET_PUT>, dim3(1), dim3(256), 0, st, c, (int)(m * 8), dst + at * 8);
   }
 }
 
 // ---- coefficient form ----
-struct KzgSetPows {   // z^(KZG_L 2^d), d < KZG_SCAN_STEPS: the scan's multipliers; Montgomery form, canonical
-  u32 m[KZG_SCAN_STEPS][8];
-};
 // one wave per row, lane i its point i: the constants of section 22 (so that k_kzg_open_carries serves a row and point
 // as it serves a row), the scan's multipliers and the point's entries of the table
 __global__ void __launch_bounds__(64) k_kzg_set_consts(const u32* __restrict__ points, int t, KzgRow* __restrict__ rows,
@@ -175,45 +155,22 @@ __global__ void __launch_bounds__(64) k_kzg_set_consts(const u32* __restrict__ p
   if (i < t) {
     const size_t g = y * t + i;
     const auto z = ElemTraits<Fe<FrP, 17>>::from_wire(points + g * 8);
-    E16::store(canonical(z), rows[g].z);
     E16::store(canonical(z), zs + g * 8);
-    KzgV m = fe_pow_u32(z, KZG_L);
-    E16::store(canonical(m), rows[g].zl);
-#pragma unroll 1
-    for (int d = 0; d < KZG_SCAN_STEPS; d++) {
-      E16::store(canonical(m), pows[g].m[d]);
-      m = KzgV(sqr(m));
-    }
-    E16::store(canonical(m), rows[g].zt);
+    kzg_row_consts(z, rows + g, pows + g);
   }
   __threadfence_block();
   block_sync();
   if (i < t) kzg_set_table_lane(zs + y * t * 8, t, i, tab + y * (size_t)kzg_set_tab_at(t, 0) * 8);
 }
 
-// kzg_wg_scan with the multipliers of every step read from the table
-__device__ __forceinline__ KzgV kzg_set_wg_scan(KzgV a, const KzgSetPows* __restrict__ pw, u32* part) {
-  using E16 = ElemTraits<Fe<FrP, 16>>;
-  const int l = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < 9; i++) part[i * KZG_WG + l] = a.l[i];
-  block_sync();
-#pragma unroll 1
-  for (int step = 0; step < KZG_SCAN_STEPS; step++) {
-    const int d = 1 << step;
-    KzgV s = KzgV(fe_zero<FrP>());
-    if (l + d < KZG_WG) {
-#pragma unroll
-      for (int i = 0; i < 9; i++) s.l[i] = part[i * KZG_WG + l + d];
-    }
-    block_sync();
-    a = kzg_compose(a, KzgV(E16::load(pw->m[step])), s);
-#pragma unroll
-    for (int i = 0; i < 9; i++) part[i * KZG_WG + l] = a.l[i];
-    block_sync();
+// S_l = a_l + m S_{l+1} as FrScanAffine, with the multiplier of every step read from the row's table
+struct KzgSetScan {
+  const KzgSetPows* pw;
+  __device__ __forceinline__ static KzgV neutral() { return KzgV(fe_zero<FrP>()); }
+  __device__ __forceinline__ KzgV apply(const KzgV& a, const KzgV& s, int step) const {
+    return kzg_compose(a, KzgV(ElemTraits<Fe<FrP, 16>>::load(pw->m[step])), s);
   }
-  return a;
-}
+};
 
 // first pass: the value of tile tl of row y at point i, to agg[(y t + i) nt + tl]; the tile is read once
 __global__ void __launch_bounds__(KZG_WG) k_kzg_set_tiles(const u32* __restrict__ coeffs, size_t poly_cs, int len, int nt,
@@ -230,7 +187,7 @@ __global__ void __launch_bounds__(KZG_WG) k_kzg_set_tiles(const u32* __restrict_
   for (int i = 0; i < t; i++) {
     const size_t g = y * t + i;
     const KzgV a = kzg_piece<KZG_L, false>(p, KZG_L, E16::load(rows[g].z), KzgV(fe_zero<FrP>()), nullptr);
-    const KzgV s = kzg_set_wg_scan(a, pows + g, part);
+    const KzgV s = fr_wg_scan<KZG_WG, true>(a, KzgSetScan{pows + g}, part);
     if (threadIdx.x == 0) fr_store(canonical(s), agg + (g * nt + tl) * 8);
   }
 }
@@ -241,7 +198,6 @@ __global__ void __launch_bounds__(256) k_kzg_set_mix(const u32* __restrict__ agg
                                                      long long total, const KzgRow* __restrict__ rows,
                                                      const u32* __restrict__ tab, u32* __restrict__ mixed,
                                                      u32* __restrict__ values) {
-  using E16 = ElemTraits<Fe<FrP, 16>>;
   const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= total) return;
   const int s = (int)(g % t);
@@ -251,10 +207,7 @@ __global__ void __launch_bounds__(256) k_kzg_set_mix(const u32* __restrict__ agg
   const KzgV c = kzg_set_carry(row_tab + 8 * kzg_set_tab_at(s, 0), s, tails + (y * t * nt + tl) * 8, (size_t)nt * 8);
   const size_t at = (y * t + s) * nt + tl;
   fr_store(canonical(c), mixed + at * 8);
-  if (tl == 0)
-    fr_store(canonical(kzg_compose(KzgV(fr_load<16>(agg + at * 8)), KzgV(E16::load(rows[y * t + s].zt)),
-                                   KzgV(fr_load<16>(tails + at * 8)))),
-             values + (y * t + s) * 8);
+  if (tl == 0) kzg_row_value(agg + at * 8, tails + at * 8, rows[y * t + s], values + (y * t + s) * 8);
 }
 // the tile pass: t stages on the lane's registers, one store t places down; the last tile of a row also writes the
 // zeros that close it
@@ -281,31 +234,17 @@ __global__ void __launch_bounds__(KZG_WG) k_kzg_set_apply(const u32* __restrict_
     const KzgV above = KzgV(fr_load<16>(mixed + (g * nt + tl) * 8));
     KzgV a = kzg_set_piece<KZG_L, false>(v, KZG_L, z, KzgV(fe_zero<FrP>()));
     if (l == KZG_WG - 1) a = kzg_compose(a, KzgV(E16::load(pows[g].m[0])), above);
-    kzg_set_wg_scan(a, pows + g, part);
-    const KzgV next = kzg_scan_next(part, above);
+    fr_wg_scan<KZG_WG, true>(a, KzgSetScan{pows + g}, part);
+    const KzgV next = fr_scan_neighbour<KZG_WG, true>(part, above);
     block_sync();   // (the next stage's scan overwrites `part`)
     kzg_set_piece<KZG_L, true>(v, KZG_L, z, next);
   }
-  // (a lane overwrites the elements it alone has read)
+  // (a lane overwrites the elements it alone has read); q_(j-t) = h_j: element e of the tile goes t places down
 #pragma unroll
-  for (int i = 0; i < KZG_L; i++) {
-    u32 o[8];
-    pack(canonical(v[i]), o);
-#pragma unroll
-    for (int w = 0; w < 8; w++) tile[kzg_at(l * KZG_L + i, w)] = o[w];
-  }
+  for (int i = 0; i < KZG_L; i++) fr_tile_put(tile, l * KZG_L + i, canonical(v[i]));
   block_sync();
   u32* qrow = quot + y * quot_cs;
-#pragma unroll
-  for (int i = 0; i < KZG_L; i++) {
-    const int e = i * KZG_WG + l;
-    const long long j = (long long)tl * KZG_TILE + e;
-    if (j >= len || j < t) continue;
-    u32 o[8];
-#pragma unroll
-    for (int w = 0; w < 8; w++) o[w] = tile[kzg_at(e, w)];
-    fr_store_words(o, qrow + (size_t)(j - t) * 8);
-  }
+  fr_tile_store<KZG_WG, KZG_L>(tile, tl, len, 0, nullptr, t, qrow);
   if (tl == nt - 1 && l < t && len - t + l >= 0) {
     const u32 o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     fr_store_words(o, qrow + (size_t)(len - t + l) * 8);
@@ -515,15 +454,14 @@ int ozk_fr_poly_open_set_dev(const void* d_coeffs, int32_t npolys, int32_t len, 
   if ((poly_stride != 0 && poly_stride < len) || quot_stride < len)
     return fail(OZK_E_INVALID, "bad strides: poly_stride %lld (0 or >= len), quot_stride %lld (>= len), len %d",
                 (long long)poly_stride, (long long)quot_stride, len);
-  if (!d_coeffs || !points_host || !d_quot || !d_values || !d_workspace) return fail(OZK_E_INVALID, "null pointer argument");
-  if (kzg_misaligned16(d_coeffs) || kzg_misaligned16(d_quot) || kzg_misaligned16(d_values))
-    return fail(OZK_E_INVALID, "elements must be 16-byte aligned");
+  if (int rc = fr_check_pointers(d_coeffs, points_host, d_quot, d_values, d_workspace)) return rc;
+  if (int rc = fr_check_aligned16(d_coeffs, d_quot, d_values)) return rc;
   if (kzg_overlap(d_coeffs, kzg_span(npolys, len, poly_stride), d_quot, kzg_span(npolys, len, quot_stride)))
     return fail(OZK_E_INVALID, "d_quot overlaps d_coeffs");
   if (!kzg_set_rows_distinct(points_host, npolys, t))
     return fail(OZK_E_INVALID, "the %d points of a row are not pairwise distinct mod r", t);
   const KzgSetLayout L = kzg_set_layout(npolys, len, t, d_workspace);
-  if (workspace_bytes < L.bytes) return fail(OZK_E_INVALID, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+  if (int rc = fr_check_workspace(L.bytes, workspace_bytes)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const u32* c = (const u32*)d_coeffs;
   const size_t pcs = (size_t)poly_stride * 8, qcs = (size_t)quot_stride * 8;
@@ -561,43 +499,25 @@ int ozk_fr_evals_open_set_dev(const void* d_evals, int32_t npolys, int32_t n, in
   if ((evals_stride != 0 && evals_stride < n) || quot_stride < n)
     return fail(OZK_E_INVALID, "bad strides: evals_stride %lld (0 or >= n), quot_stride %lld (>= n), n %d",
                 (long long)evals_stride, (long long)quot_stride, n);
-  if (!d_evals || !omega_host32 || !points_host || !d_quot || !d_values || !d_workspace)
-    return fail(OZK_E_INVALID, "null pointer argument");
-  if (kzg_misaligned16(d_evals) || kzg_misaligned16(d_quot) || kzg_misaligned16(d_values))
-    return fail(OZK_E_INVALID, "elements must be 16-byte aligned");
+  if (int rc = fr_check_pointers(d_evals, omega_host32, points_host, d_quot, d_values, d_workspace)) return rc;
+  if (int rc = fr_check_aligned16(d_evals, d_quot, d_values)) return rc;
   if (kzg_overlap(d_evals, kzg_span(npolys, n, evals_stride), d_quot, kzg_span(npolys, n, quot_stride)))
     return fail(OZK_E_INVALID, "d_quot overlaps d_evals");
-  BaceWords om;
-  memset(om.w, 0, sizeof(om.w));
-  memcpy(om.w, omega_host32, 32);
-  {
-    // omega has order exactly n when omega^(n / 2) = -1
-    u32 w[8];
-    memcpy(w, omega_host32, 32);
-    Fe<FrP, 32> x = Fe<FrP, 32>(to_mont<FrP>(w));
-    for (int k = n; k > 2; k >>= 1) x = Fe<FrP, 32>(sqr(x));
-    if (!is_zero(canonical(add(x, fe_one<FrP>()))))
-      return fail(OZK_E_INVALID, "omega does not have order %d (omega^(n/2) != -1)", n);
-  }
+  if (!fr_omega_has_order(omega_host32, n))
+    return fail(OZK_E_INVALID, "omega does not have order %d (omega^(n/2) != -1)", n);
   if (!kzg_set_rows_distinct(points_host, npolys, t))
     return fail(OZK_E_INVALID, "the %d points of a row are not pairwise distinct mod r", t);
-  for (size_t g = 0; g < (size_t)npolys * t; g++) {
-    // z in the domain when z^n = 1
-    u32 w[8];
-    memcpy(w, points_host + g * 32, 32);
-    Fe<FrP, 32> x = Fe<FrP, 32>(to_mont<FrP>(w));
-    for (int k = n; k > 1; k >>= 1) x = Fe<FrP, 32>(sqr(x));
-    if (is_zero(canonical(sub(x, fe_one<FrP>()))))
+  for (size_t g = 0; g < (size_t)npolys * t; g++)
+    if (fr_in_domain(points_host + g * 32, n))
       return fail(OZK_E_INVALID, "point %zu of row %zu lies in the domain (z^n = 1): open such a set in coefficient form",
                   g % t, g / t);
-  }
   const KzgSetEvLayout L = kzg_set_ev_layout(npolys, n, t, d_workspace);
-  if (workspace_bytes < L.bytes) return fail(OZK_E_INVALID, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+  if (int rc = fr_check_workspace(L.bytes, workspace_bytes)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const u32* f = (const u32*)d_evals;
   const size_t ecs = (size_t)evals_stride * 8, qcs = (size_t)quot_stride * 8;
   const size_t np = (size_t)npolys * t;
-  hipLaunchKernelGGL(k_bace_put, dim3(1), dim3(64), 0, st, om, 8, L.omega);
+  fr_put_element(omega_host32, L.omega, st);
   const PowTable pt = PowTable::upto(n);
   pt.build(L.omega, L.pw, st);
   kzg_set_upload(points_host, np, L.pts, st);

@@ -1,6 +1,7 @@
 // The Fr kernels of the PLONK prover: rows scaled by the powers of a coset shift, the permutation
 // grand product, and the quotient pointwise on the coset of four times the domain.  Included at the end of fft.hip
-// after kzg_multi.cuh: it uses that unit's element I/O and kzg.cuh's staged tile, chunked inversion and layout checks.
+// after kzg_multi.cuh: it uses that unit's element I/O and the staged tile, scan, chunked inversion and entry checks of
+// fr_rows.cuh.
 //
 // Every value in HBM is 32 bytes LE, plain (non-Montgomery); inputs are taken mod r, outputs are canonical.  The
 // scalars of a call arrive in host memory and travel in the kernel arguments, already in the form the kernel
@@ -36,17 +37,15 @@ constexpr int PLONK_WG = 128;                           // lanes of a grand-prod
 constexpr int PLONK_L = KZG_INV_BATCH;                  // consecutive rows of a lane: one inversion
 constexpr int PLONK_TILE = PLONK_WG * PLONK_L;          // two staged tiles (66 KiB of LDS) + 4.5 KiB of scan
 constexpr int PLONK_SCAN_WG = 256;                      // tile products scanned at a time
-static_assert(PLONK_TILE == KZG_TILE, "the staged tile is kzg.cuh's (kzg_at)");
+static_assert(PLONK_TILE == KZG_TILE, "the staged tile is fr_rows.cuh's (kzg_at)");
 
 #if defined(__HIPCC__)
-struct PlonkWords {   // one element in the kernel arguments: canonical, packed
-  u32 w[8];
-};
-__device__ __forceinline__ Fe<FrP, 16> plonk_arg(const PlonkWords& c) { return unpack<FrP, 16>(c.w); }
+// one element in the kernel arguments (FrArg): canonical, packed
+__device__ __forceinline__ Fe<FrP, 16> plonk_arg(const FrArg& c) { return unpack<FrP, 16>(c.w); }
 
 // tab[l] = base^(l step) for l < ntab (plain when tab_plain, else Montgomery form); start[t] = c base^(t tile) for
 // t < nt (Montgomery form).  base, c: Montgomery form.
-__global__ void __launch_bounds__(64) k_plonk_pows(PlonkWords base, PlonkWords c, int ntab, unsigned step, int tab_plain,
+__global__ void __launch_bounds__(64) k_plonk_pows(FrArg base, FrArg c, int ntab, unsigned step, int tab_plain,
                                                    int nt, unsigned tile, u32* __restrict__ tab, u32* __restrict__ start) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= ntab + nt) return;
@@ -63,7 +62,7 @@ __global__ void __launch_bounds__(64) k_plonk_pows(PlonkWords base, PlonkWords c
 }
 
 // ---- rows by powers: tile blockIdx.x % nt of row blockIdx.x / nt.  out may be rows (a lane writes what it alone read)
-__global__ void __launch_bounds__(PLONK_CO_WG) k_fr_rows_coset(const u32* rows, int len, size_t row_cs, int nt, PlonkWords s_wg,
+__global__ void __launch_bounds__(PLONK_CO_WG) k_fr_rows_coset(const u32* rows, int len, size_t row_cs, int nt, FrArg s_wg,
                                                               const u32* __restrict__ tab, const u32* __restrict__ start,
                                                               u32* out, int out_len, size_t out_cs) {
   const int y = blockIdx.x / nt, t = blockIdx.x % nt, l = threadIdx.x;
@@ -89,28 +88,9 @@ __global__ void __launch_bounds__(PLONK_CO_WG) k_fr_rows_coset(const u32* rows, 
 
 // ---- grand product
 struct PlonkPermArgs {
-  PlonkWords omega, beta, bk[3];   // Montgomery form: omega, beta, beta k_j
-  PlonkWords gamma;                // plain
+  FrArg omega, beta, bk[3];   // Montgomery form: omega, beta, beta k_j
+  FrArg gamma;                // plain
 };
-
-// the tile's elements of one row (canonical; zero beyond len) into LDS; the caller's barrier follows
-__device__ __forceinline__ void plonk_stage(const u32* __restrict__ row, int len, int t, u32* tile) {
-#pragma unroll
-  for (int i = 0; i < PLONK_L; i++) {
-    const int e = i * PLONK_WG + threadIdx.x;
-    const long long j = (long long)t * PLONK_TILE + e;
-    u32 o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (j < len) pack(canonical(fr_load<85>(row + (size_t)j * 8)), o);
-#pragma unroll
-    for (int w = 0; w < 8; w++) tile[kzg_at(e, w)] = o[w];
-  }
-}
-__device__ __forceinline__ Fe<FrP, 16> plonk_staged(const u32* tile, int e) {
-  u32 o[8];
-#pragma unroll
-  for (int w = 0; w < 8; w++) o[w] = tile[kzg_at(e, w)];
-  return unpack<FrP, 16>(o);
-}
 
 // Column j of the six rows folded into the lane's running numerators f and denominators d: both tiles are staged,
 // read and free again on return.  label: beta k_j omega^i at the lane's first row, plain.
@@ -119,15 +99,15 @@ __device__ __forceinline__ void plonk_column(const u32* __restrict__ w_row, cons
                                              KzgV label, const Fe<FrP, 16>& omega, const Fe<FrP, 16>& beta,
                                              const Fe<FrP, 16>& gamma, u32* tile_w, u32* tile_s, KzgV (&f)[PLONK_L],
                                              KzgV (&d)[PLONK_L]) {
-  plonk_stage(w_row, len, t, tile_w);
-  plonk_stage(s_row, len, t, tile_s);
+  fr_tile_fill<PLONK_WG, PLONK_L>(w_row, len, t, tile_w);
+  fr_tile_fill<PLONK_WG, PLONK_L>(s_row, len, t, tile_s);
   block_sync();
 #pragma unroll
   for (int k = 0; k < PLONK_L; k++) {
     const int e = threadIdx.x * PLONK_L + k;
-    const auto wg = add(plonk_staged(tile_w, e), gamma);
+    const auto wg = add(fr_tile_get(tile_w, e), gamma);
     const auto num = add(wg, label);
-    const auto den = add(wg, mul(plonk_staged(tile_s, e), beta));
+    const auto den = add(wg, mul(fr_tile_get(tile_s, e), beta));
     if (FIRST) {
       f[k] = KzgV(reduce_to<32>(num));
       d[k] = KzgV(reduce_to<32>(den));
@@ -178,38 +158,6 @@ __device__ __forceinline__ KzgV plonk_lane_product(const KzgV (&f)[PLONK_L]) {
   for (int k = 1; k < PLONK_L; k++) a = KzgV(mul(a, f[k]));
   return a;
 }
-// S_l = a_0 a_1 .. a_l over the WG lanes of the workgroup.  Returns the lane's S_l and leaves every S in `part`
-// (limb-major, 9 x WG words) behind a barrier.
-template <int WG>
-__device__ __forceinline__ KzgV plonk_wg_scan(KzgV a, u32* part) {
-  const int l = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < 9; i++) part[i * WG + l] = a.l[i];
-  block_sync();
-  for (int d = 1; d < WG; d <<= 1) {
-    KzgV s = KzgV(fe_one<FrP>());
-    if (l >= d) {
-#pragma unroll
-      for (int i = 0; i < 9; i++) s.l[i] = part[i * WG + l - d];
-    }
-    block_sync();
-    a = KzgV(mul(a, s));
-#pragma unroll
-    for (int i = 0; i < 9; i++) part[i * WG + l] = a.l[i];
-    block_sync();
-  }
-  return a;
-}
-// what lies below lane l after the scan: S_{l-1}, or `below` (what lies below the workgroup) for lane 0
-template <int WG>
-__device__ __forceinline__ KzgV plonk_scan_prev(const u32* part, const KzgV& below) {
-  KzgV s = below;
-  if (threadIdx.x > 0) {
-#pragma unroll
-    for (int i = 0; i < 9; i++) s.l[i] = part[i * WG + threadIdx.x - 1];
-  }
-  return s;
-}
 
 // first pass (several tiles): the product of tile t, Montgomery form, to agg[t]
 __global__ void __launch_bounds__(PLONK_WG) k_plonk_perm_tiles(const u32* __restrict__ wires, const u32* __restrict__ sigma,
@@ -221,26 +169,13 @@ __global__ void __launch_bounds__(PLONK_WG) k_plonk_perm_tiles(const u32* __rest
   __shared__ u32 part[9 * PLONK_WG];
   KzgV f[PLONK_L];
   plonk_factors(wires, sigma, len, cs, blockIdx.x, a, tab, start, tile_w, tile_s, f);
-  const KzgV s = plonk_wg_scan<PLONK_WG>(plonk_lane_product(f), part);
+  const KzgV s = fr_wg_scan<PLONK_WG, false>(plonk_lane_product(f), FrScanProduct{}, part);
   if (threadIdx.x == PLONK_WG - 1) fr_store(canonical(s), agg + (size_t)blockIdx.x * 8);
 }
 // second pass, one workgroup: carry[t] = the product of the tiles below t, PLONK_SCAN_WG tiles at a time from the bottom
 __global__ void __launch_bounds__(PLONK_SCAN_WG) k_plonk_perm_carries(const u32* __restrict__ agg, int nt, u32* __restrict__ carry) {
   __shared__ u32 part[9 * PLONK_SCAN_WG];
-  const int l = threadIdx.x;
-  KzgV below = KzgV(fe_one<FrP>());
-  for (int base = 0; base < nt; base += PLONK_SCAN_WG) {
-    const int t = base + l;
-    KzgV a = KzgV(fe_one<FrP>());
-    if (t < nt) a = KzgV(fr_load<16>(agg + (size_t)t * 8));
-    if (l == 0) a = KzgV(mul(a, below));
-    plonk_wg_scan<PLONK_SCAN_WG>(a, part);
-    const KzgV c = plonk_scan_prev<PLONK_SCAN_WG>(part, below);
-    if (t < nt) fr_store(canonical(c), carry + (size_t)t * 8);
-#pragma unroll
-    for (int i = 0; i < 9; i++) below.l[i] = part[i * PLONK_SCAN_WG + PLONK_SCAN_WG - 1];
-    block_sync();
-  }
+  fr_carries_scan<PLONK_SCAN_WG, false>(agg, nt, FrScanProduct{}, carry, part);
 }
 // the tile pass: z, the count of zero denominators and, from the last tile, the product of all rows.  carry: null
 // when the row is one tile.
@@ -260,7 +195,7 @@ __global__ void __launch_bounds__(PLONK_WG) k_plonk_perm_apply(const u32* __rest
   if (carry) below = KzgV(fr_load<16>(carry + (size_t)t * 8));
   KzgV prod = plonk_lane_product(f);
   if (l == 0) prod = KzgV(mul(prod, below));
-  const KzgV s = plonk_wg_scan<PLONK_WG>(prod, part);
+  const KzgV s = fr_wg_scan<PLONK_WG, false>(prod, FrScanProduct{}, part);
   if (t == nt - 1 && l == PLONK_WG - 1) {
     u32 o[8];
     from_mont(s, o);
@@ -269,34 +204,22 @@ __global__ void __launch_bounds__(PLONK_WG) k_plonk_perm_apply(const u32* __rest
   // the product below the lane's first row, out of Montgomery form; a plain value times f stays plain
   Fe<FrP, 1> one = fe_zero<FrP>();
   one.l[0] = 1;
-  KzgV run = KzgV(mul(plonk_scan_prev<PLONK_WG>(part, below), one));
+  KzgV run = KzgV(mul(fr_scan_neighbour<PLONK_WG, false>(part, below), one));
 #pragma unroll
   for (int k = 0; k < PLONK_L; k++) {
-    u32 o[8];
-    pack(canonical(run), o);
-#pragma unroll
-    for (int w = 0; w < 8; w++) tile_w[kzg_at(l * PLONK_L + k, w)] = o[w];
+    fr_tile_put(tile_w, l * PLONK_L + k, canonical(run));
     if (k + 1 < PLONK_L) run = KzgV(mul(run, f[k]));
   }
   block_sync();
-#pragma unroll
-  for (int i = 0; i < PLONK_L; i++) {
-    const int e = i * PLONK_WG + l;
-    const long long j = (long long)t * PLONK_TILE + e;
-    if (j >= len) continue;
-    u32 o[8];
-#pragma unroll
-    for (int w = 0; w < 8; w++) o[w] = tile_w[kzg_at(e, w)];
-    fr_store_words(o, z + (size_t)j * 8);
-  }
+  fr_tile_store<PLONK_WG, PLONK_L>(tile_w, t, len, 0, nullptr, 0, z);
 }
 
 // ---- quotient
 struct PlonkQuotArgs {
-  PlonkWords alpha_r, alpha2_r2;   // alpha R, alpha^2 R^2
-  PlonkWords beta_r2, bk_r2[3];    // beta R^2, beta k_j R^2
-  PlonkWords gamma_r;              // gamma R
-  PlonkWords zh_r[4];              // R / (g^n i4^m - 1), m < 4
+  FrArg alpha_r, alpha2_r2;   // alpha R, alpha^2 R^2
+  FrArg beta_r2, bk_r2[3];    // beta R^2, beta k_j R^2
+  FrArg gamma_r;              // gamma R
+  FrArg zh_r[4];              // R / (g^n i4^m - 1), m < 4
 };
 enum { PLONK_A, PLONK_B, PLONK_C, PLONK_Z, PLONK_PI, PLONK_WIT_ROWS };
 enum { PLONK_QL, PLONK_QR, PLONK_QO, PLONK_QM, PLONK_QC, PLONK_S1, PLONK_S2, PLONK_S3, PLONK_L1, PLONK_X, PLONK_KEY_ROWS };
@@ -343,8 +266,8 @@ __global__ void __launch_bounds__(256) k_plonk_quotient(const u32* __restrict__ 
 
 // ---- host side ----
 template <int B>
-static PlonkWords plonk_words(const Fe<FrP, B>& v) {
-  PlonkWords o;
+static FrArg plonk_words(const Fe<FrP, B>& v) {
+  FrArg o;
   pack(canonical(v), o.w);
   return o;
 }
@@ -353,7 +276,7 @@ static Fe<FrP, 17> plonk_mont(const uint8_t* host32) {
   memcpy(w, host32, 32);
   return to_mont<FrP>(w);
 }
-static PlonkWords plonk_plain(const uint8_t* host32) {
+static FrArg plonk_plain(const uint8_t* host32) {
   u32 w[8];
   memcpy(w, host32, 32);
   return plonk_words(unpack<FrP, 85>(w));
@@ -418,13 +341,13 @@ int ozk_fr_rows_coset_dev(const void* d_rows, int32_t k, int32_t len, int64_t ro
   if (row_stride < len || out_stride < out_len)
     return fail(OZK_E_INVALID, "bad strides: row_stride %lld (>= len %d), out_stride %lld (>= out_len %d)",
                 (long long)row_stride, len, (long long)out_stride, out_len);
-  if (!d_rows || !s_host32 || !c_host32 || !d_out || !d_workspace) return fail(OZK_E_INVALID, "null pointer argument");
-  if (kzg_misaligned16(d_rows) || kzg_misaligned16(d_out)) return fail(OZK_E_INVALID, "elements must be 16-byte aligned");
+  if (int rc = fr_check_pointers(d_rows, s_host32, c_host32, d_out, d_workspace)) return rc;
+  if (int rc = fr_check_aligned16(d_rows, d_out)) return rc;
   const bool in_place = d_out == d_rows && out_len == len && out_stride == row_stride;
   if (!in_place && kzg_overlap(d_rows, kzg_span(k, len, row_stride), d_out, kzg_span(k, out_len, out_stride)))
     return fail(OZK_E_INVALID, "d_out overlaps d_rows (it may only be d_rows itself, with out_len = len and equal strides)");
   const PlonkPowLayout L = plonk_coset_layout(out_len, d_workspace);
-  if (workspace_bytes < L.bytes) return fail(OZK_E_INVALID, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+  if (int rc = fr_check_workspace(L.bytes, workspace_bytes)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const auto s = plonk_mont(s_host32);
   hipLaunchKernelGGL(k_plonk_pows, dim3((PLONK_CO_WG + L.nt + 63) / 64), dim3(64), 0, st, plonk_words(s),
@@ -447,11 +370,10 @@ int ozk_fr_perm_product_dev(const void* d_wires, const void* d_sigma, int32_t le
   hip_clear_stale();
   if (!plonk_perm_shape_ok(len)) return fail(OZK_E_INVALID, "bad shape: %d rows (1 <= len <= 2^28)", len);
   if (stride < len) return fail(OZK_E_INVALID, "bad stride: %lld (>= len %d)", (long long)stride, len);
-  if (!d_wires || !d_sigma || !omega_host32 || !k_host96 || !beta_host32 || !gamma_host32 || !d_z || !d_total ||
-      !d_zero_dens || !d_workspace)
-    return fail(OZK_E_INVALID, "null pointer argument");
-  if (kzg_misaligned16(d_wires) || kzg_misaligned16(d_sigma) || kzg_misaligned16(d_z) || kzg_misaligned16(d_total))
-    return fail(OZK_E_INVALID, "elements must be 16-byte aligned");
+  if (int rc = fr_check_pointers(d_wires, d_sigma, omega_host32, k_host96, beta_host32, gamma_host32, d_z, d_total,
+                                 d_zero_dens, d_workspace))
+    return rc;
+  if (int rc = fr_check_aligned16(d_wires, d_sigma, d_z, d_total)) return rc;
   if (((uintptr_t)d_zero_dens & 3) != 0) return fail(OZK_E_INVALID, "d_zero_dens must be 4-byte aligned");
   const size_t span = kzg_span(3, len, stride);
   if (kzg_overlap(d_wires, span, d_z, (size_t)len * 32) || kzg_overlap(d_sigma, span, d_z, (size_t)len * 32))
@@ -463,7 +385,7 @@ int ozk_fr_perm_product_dev(const void* d_wires, const void* d_sigma, int32_t le
       kzg_overlap(d_z, (size_t)len * 32, d_zero_dens, 4) || kzg_overlap(d_total, 32, d_zero_dens, 4))
     return fail(OZK_E_INVALID, "d_zero_dens overlaps d_wires, d_sigma, d_z or d_total");
   const PlonkPermLayout L = plonk_perm_layout(len, d_workspace);
-  if (workspace_bytes < L.bytes) return fail(OZK_E_INVALID, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+  if (int rc = fr_check_workspace(L.bytes, workspace_bytes)) return rc;
   hipStream_t st = (hipStream_t)stream;
   PlonkPermArgs a;
   const auto omega = plonk_mont(omega_host32), beta = plonk_mont(beta_host32);
@@ -498,10 +420,9 @@ int ozk_plonk_quotient_dev(const void* d_wit, int64_t wit_stride, const void* d_
   if (wit_stride < n4 || key_stride < n4)
     return fail(OZK_E_INVALID, "bad strides: wit_stride %lld, key_stride %lld (both >= 4 n = %d)", (long long)wit_stride,
                 (long long)key_stride, n4);
-  if (!d_wit || !d_key || !alpha_host32 || !beta_host32 || !gamma_host32 || !k_host96 || !zh_inv_host128 || !d_out)
-    return fail(OZK_E_INVALID, "null pointer argument");
-  if (kzg_misaligned16(d_wit) || kzg_misaligned16(d_key) || kzg_misaligned16(d_out))
-    return fail(OZK_E_INVALID, "elements must be 16-byte aligned");
+  if (int rc = fr_check_pointers(d_wit, d_key, alpha_host32, beta_host32, gamma_host32, k_host96, zh_inv_host128, d_out))
+    return rc;
+  if (int rc = fr_check_aligned16(d_wit, d_key, d_out)) return rc;
   if (kzg_overlap(d_wit, kzg_span(PLONK_WIT_ROWS, n4, wit_stride), d_out, (size_t)n4 * 32) ||
       kzg_overlap(d_key, kzg_span(PLONK_KEY_ROWS, n4, key_stride), d_out, (size_t)n4 * 32))
     return fail(OZK_E_INVALID, "d_out overlaps d_wit or d_key");
