@@ -628,6 +628,58 @@ int ozk_plonk_quotient_dev(const void* d_wit, int64_t wit_stride, const void* d_
                            const uint8_t* alpha_host32, const uint8_t* beta_host32, const uint8_t* gamma_host32,
                            const uint8_t* k_host96, const uint8_t* zh_inv_host128, void* d_out, void* stream);
 
+/* The lookup argument of the PLONK prover (csrc/plonk_lookup.cuh): logUp as a running sum over
+ * one table of three-column tuples.  Conventions are those of the PLONK block above: plain 32-byte elements, reduced
+ * on load, canonical outputs, strides in elements, scalars 32-byte little-endian in HOST memory.  A table is three
+ * rows T1, T2, T3 at table_stride, of which the first n_rows elements count.
+ *   ozk_plonk_lookup_index_dev  Built once per table.  d_index receives an open-addressing table of uint32 row
+ *                              numbers (0xffffffff: empty) over the n_rows tuples; its capacity is the power of two
+ *                              >= 2 n_rows, ozk_plonk_lookup_index_bytes(n_rows) bytes.  The key is the canonical
+ *                              tuple; the slot of a tuple that several rows hold ends on the LOWEST of them, whatever
+ *                              the order of arrival.  1 <= n_rows <= 2^28.  d_index must not overlap d_table.
+ *   ozk_plonk_lookup_counts_dev Run once per proof.  d_wires: the rows a, b, c of len elements at `stride`; d_qk: one
+ *                              row of len.  d_m (m_len >= n_rows elements) is zeroed, and every row i < len with
+ *                              qK_i != 0 mod r adds 1 to the element d_m[row] of the first table row equal to
+ *                              (a_i, b_i, c_i) mod r: later copies of a table row and the elements from n_rows to
+ *                              m_len stay 0.  Counts stay below 2^28, so an element is its count in word 0.
+ *                              *d_missing (int32) is the number of such rows whose tuple is in no table row and
+ *                              *d_first_missing (int32) the lowest of them, 0x7fffffff when there is none.  Integer
+ *                              atomics only: the result is bitwise reproducible.  1 <= len <= 2^28; the outputs
+ *                              must not overlap the inputs or one another (rejected).
+ *   ozk_plonk_lookup_sum_dev   d_s[0] = 0 and, with f = a + eta b + eta^2 c and t = T1 + eta T2 + eta^2 T3,
+ *                                d_s[i + 1] = d_s[i] + m_i / (theta + t_i) - qK_i / (theta + f_i);
+ *                              *d_total (one element) is the sum over all len rows and *d_zero_dens (int32) the
+ *                              number of zero denominators among the 2 len: such a fraction counts as 0, the others
+ *                              stay exact.  d_key4: the four rows qK, T1, T2, T3 of len elements at key_stride; d_m:
+ *                              one row of len.  1 <= len <= 2^28, a power of two or not.  The outputs must not
+ *                              overlap the inputs or one another, nor the workspace the inputs or the outputs
+ *                              (rejected).  Every input element is read twice
+ *                              (once when len <= 1024), d_s written once.
+ *                              Workspace: ozk_plonk_lookup_sum_workspace_bytes(len).
+ *   ozk_plonk_quotient_lookup_dev  ozk_plonk_quotient_dev with two more terms in the numerator,
+ *                                alpha^3 ((S(omega X) - S)(theta + t)(theta + f) - m (theta + f) + qK (theta + t))
+ *                                + alpha^4 S L_1.
+ *                              d_wit: the seven rows a, b, c, Z, PI, m, S on the coset; d_key: the fourteen rows
+ *                              qL, qR, qO, qM, qC, s1, s2, s3, L_1, X, qK, T1, T2, T3.  S(omega X) is S at index
+ *                              (i + 4) mod 4 n.  The vanilla terms are the very code of ozk_plonk_quotient_dev: with
+ *                              qK = m = S = 0 the outputs agree byte for byte.  No workspace.
+ * Size functions and rejections as above: 0 and OZK_E_INVALID before any launch, the shape before the pointers.
+ * Asynchronous on `stream`; nothing is allocated or synchronised. */
+size_t ozk_plonk_lookup_index_bytes(int32_t n_rows);
+int ozk_plonk_lookup_index_dev(const void* d_table, int32_t n_rows, int64_t table_stride, void* d_index, size_t index_bytes,
+                               void* stream);
+int ozk_plonk_lookup_counts_dev(const void* d_wires, const void* d_qk, int32_t len, int64_t stride, const void* d_table,
+                                int32_t n_rows, int64_t table_stride, const void* d_index, size_t index_bytes, void* d_m,
+                                int32_t m_len, int32_t* d_missing, int32_t* d_first_missing, void* stream);
+size_t ozk_plonk_lookup_sum_workspace_bytes(int32_t len);
+int ozk_plonk_lookup_sum_dev(const void* d_wires, int64_t stride, const void* d_key4, int64_t key_stride, const void* d_m,
+                             int32_t len, const uint8_t* eta_host32, const uint8_t* theta_host32, void* d_s, void* d_total,
+                             int32_t* d_zero_dens, void* d_workspace, size_t workspace_bytes, void* stream);
+int ozk_plonk_quotient_lookup_dev(const void* d_wit, int64_t wit_stride, const void* d_key, int64_t key_stride, int32_t n,
+                                  const uint8_t* alpha_host32, const uint8_t* beta_host32, const uint8_t* gamma_host32,
+                                  const uint8_t* k_host96, const uint8_t* zh_inv_host128, const uint8_t* eta_host32,
+                                  const uint8_t* theta_host32, void* d_out, void* stream);
+
 /* ---- batched MSM over shared bases (msm_multi.hip; no counterpart in the reference, whose verifier runs one
  * variable-base MSM per proof): out_i = sum_{j < n} s_ij P_j for k scalar rows over the SAME n bases, G1 only.
  * A window table of every base is built once (ozk_multi_msm_prepare_dev); a run is table gathers and mixed

@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, "libozk_hip.so")
 
 HIP_SOURCES = ["msm_var.hip", "msm_var_g2.hip", "msm_fixed.hip", "fft.hip", "host_ctx.hip", "pairing.hip", "msm_multi.hip",
                "point_codec.hip", "points_scale.hip", "ec_fft.hip", "points_mul.hip", "points_mac.hip"]
-HEADERS = ["consts_gen.h", "mad_chain_gen.h", "fp29.cuh", "fq2.cuh", "fq12.cuh", "batch_verify.cuh", "point_codec.cuh", "points_scale.cuh", "points_mul.cuh", "points_mac.cuh", "ec_fft.cuh", "bace.cuh", "kzg.cuh", "kzg_set.cuh", "kzg_multi.cuh", "plonk.cuh", "pairing_consts_gen.h", "ec.cuh", "quad.cuh", "curve.cuh", "msm_var.cuh", "msm_var_driver.cuh", "msm_multi.cuh", "glv.cuh", "l1_whole.h", "wsum_rc.h", "ozk_common.h", "knobs.h", "host_ctx.h", "pin_cache.h",
+HEADERS = ["consts_gen.h", "mad_chain_gen.h", "fp29.cuh", "fq2.cuh", "fq12.cuh", "batch_verify.cuh", "point_codec.cuh", "points_scale.cuh", "points_mul.cuh", "points_mac.cuh", "ec_fft.cuh", "bace.cuh", "kzg.cuh", "kzg_set.cuh", "kzg_multi.cuh", "plonk.cuh", "plonk_lookup.cuh", "pairing_consts_gen.h", "ec.cuh", "quad.cuh", "curve.cuh", "msm_var.cuh", "msm_var_driver.cuh", "msm_multi.cuh", "glv.cuh", "l1_whole.h", "wsum_rc.h", "ozk_common.h", "knobs.h", "host_ctx.h", "pin_cache.h",
            os.path.join("..", "..", "include", "ozk.h")]
 # hipcc flags of every device translation unit (after the hipcc path); the test harness tests/native/devcheck.hip
 # is compiled with the same list, so that it runs the arithmetic exactly as the library compiles it

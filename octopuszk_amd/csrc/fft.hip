@@ -1351,3 +1351,4 @@ int ozk_fft_compact_host(const uint8_t* in, int32_t n, const uint8_t* omega, int
 #include "kzg_set.cuh"
 #include "kzg_multi.cuh"
 #include "plonk.cuh"
+#include "plonk_lookup.cuh"

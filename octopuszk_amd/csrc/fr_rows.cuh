@@ -206,6 +206,11 @@ struct FrScanProduct {
   __device__ __forceinline__ static KzgV neutral() { return KzgV(fe_one<FrP>()); }
   __device__ __forceinline__ KzgV apply(const KzgV& a, const KzgV& s, int) const { return KzgV(mul(a, s)); }
 };
+// S_l = a_0 + a_1 + .. + a_l, in whichever form the a_l share
+struct FrScanSum {
+  __device__ __forceinline__ static KzgV neutral() { return KzgV(fe_zero<FrP>()); }
+  __device__ __forceinline__ KzgV apply(const KzgV& a, const KzgV& s, int) const { return KzgV(reduce_to<32>(add(a, s))); }
+};
 
 // One workgroup scans the nt per-tile aggregates of a row, WG tiles at a time starting from the far end:
 // carry[t] = what the tiles above t (UP) or below t combine to.  `op` is the operation between neighbouring tiles.

@@ -228,17 +228,19 @@ enum { PLONK_QL, PLONK_QR, PLONK_QO, PLONK_QM, PLONK_QC, PLONK_S1, PLONK_S2, PLO
 __device__ __forceinline__ KzgV plonk_in(const u32* __restrict__ rows, size_t cs, int row, unsigned i) {
   return KzgV(reduce_to<32>(fr_load<85>(rows + (size_t)row * cs + (size_t)i * 8)));
 }
+// gate + alpha P1 + alpha^2 P2 at point i of the coset, plain, not yet divided by Z_H: the identity of the vanilla
+// circuit, stated here once for k_plonk_quotient and for the lookup quotient of plonk_lookup.cuh.  a, b, c leave in
+// Montgomery form for the caller's further terms.
 // Plain operands: a product with an operand carrying R (or R^2) comes out plain (or in Montgomery form), so a, b, c
 // are brought into Montgomery form once and every term of the sum below is a plain value.
-__global__ void __launch_bounds__(256) k_plonk_quotient(const u32* __restrict__ wit, size_t wit_cs, const u32* __restrict__ key,
-                                                        size_t key_cs, unsigned n4, PlonkQuotArgs q, u32* __restrict__ out) {
-  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n4) return;
+__device__ __forceinline__ auto plonk_vanilla_terms(const u32* __restrict__ wit, size_t wit_cs, const u32* __restrict__ key,
+                                                    size_t key_cs, unsigned n4, unsigned i, const PlonkQuotArgs& q, KzgV& a,
+                                                    KzgV& b, KzgV& c) {
   const auto r2 = fe_const<FrP, 16>(FrP::R2);
   const auto gamma_r = plonk_arg(q.gamma_r);
-  const KzgV a = KzgV(mul(plonk_in(wit, wit_cs, PLONK_A, i), r2));
-  const KzgV b = KzgV(mul(plonk_in(wit, wit_cs, PLONK_B, i), r2));
-  const KzgV c = KzgV(mul(plonk_in(wit, wit_cs, PLONK_C, i), r2));
+  a = KzgV(mul(plonk_in(wit, wit_cs, PLONK_A, i), r2));
+  b = KzgV(mul(plonk_in(wit, wit_cs, PLONK_B, i), r2));
+  c = KzgV(mul(plonk_in(wit, wit_cs, PLONK_C, i), r2));
   // qL a + qR b + qO c + qM a b + qC + PI
   const auto qma = mul(plonk_in(key, key_cs, PLONK_QM, i), a);
   const auto gate = add(add(mul2(plonk_in(key, key_cs, PLONK_QL, i), a, plonk_in(key, key_cs, PLONK_QR, i), b),
@@ -260,7 +262,14 @@ __global__ void __launch_bounds__(256) k_plonk_quotient(const u32* __restrict__ 
   Fe<FrP, 1> one = fe_zero<FrP>();
   one.l[0] = 1;
   const auto p2 = mul(sub(zv, one), plonk_in(key, key_cs, PLONK_L1, i));
-  const auto sum = add(gate, mul2(sub(left, right), plonk_arg(q.alpha_r), p2, plonk_arg(q.alpha2_r2)));
+  return add(gate, mul2(sub(left, right), plonk_arg(q.alpha_r), p2, plonk_arg(q.alpha2_r2)));
+}
+__global__ void __launch_bounds__(256) k_plonk_quotient(const u32* __restrict__ wit, size_t wit_cs, const u32* __restrict__ key,
+                                                        size_t key_cs, unsigned n4, PlonkQuotArgs q, u32* __restrict__ out) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n4) return;
+  KzgV a, b, c;
+  const auto sum = plonk_vanilla_terms(wit, wit_cs, key, key_cs, n4, i, q, a, b, c);
   fr_store(canonical(mul(sum, plonk_arg(q.zh_r[i & 3]))), out + (size_t)i * 8);
 }
 
@@ -319,6 +328,37 @@ static PlonkPermLayout plonk_perm_layout(int len, void* wsp) {
   return L;
 }
 static bool plonk_perm_shape_ok(int len) { return len >= 1 && (long long)len <= KZG_MAX_ELEMS; }
+// the checks and the scalars that the quotient's two entry points (this one and plonk_lookup.cuh's) share
+static int plonk_quot_shape(int n, long long wit_stride, long long key_stride) {
+  if (n < 2 || (n & (n - 1)) || n > (1 << 26))
+    return fail(OZK_E_INVALID, "n = %d is not a power of two in [2, 2^26] (the coset has 4 n <= 2^28 points)", n);
+  if (wit_stride < 4 * n || key_stride < 4 * n)
+    return fail(OZK_E_INVALID, "bad strides: wit_stride %lld, key_stride %lld (both >= 4 n = %d)", wit_stride, key_stride,
+                4 * n);
+  return OZK_OK;
+}
+static int plonk_quot_buffers(const void* d_wit, int wit_rows, long long wit_stride, const void* d_key, int key_rows,
+                              long long key_stride, int n, const void* d_out) {
+  if (int rc = fr_check_aligned16(d_wit, d_key, d_out)) return rc;
+  const int n4 = 4 * n;
+  if (kzg_overlap(d_wit, kzg_span(wit_rows, n4, wit_stride), d_out, (size_t)n4 * 32) ||
+      kzg_overlap(d_key, kzg_span(key_rows, n4, key_stride), d_out, (size_t)n4 * 32))
+    return fail(OZK_E_INVALID, "d_out overlaps d_wit or d_key");
+  return OZK_OK;
+}
+static PlonkQuotArgs plonk_quot_args(const uint8_t* alpha_host32, const uint8_t* beta_host32, const uint8_t* gamma_host32,
+                                     const uint8_t* k_host96, const uint8_t* zh_inv_host128) {
+  PlonkQuotArgs q;
+  const auto r2 = fe_const<FrP, 16>(FrP::R2);
+  const auto alpha = plonk_mont(alpha_host32), beta = plonk_mont(beta_host32);
+  q.alpha_r = plonk_words(alpha);
+  q.alpha2_r2 = plonk_words(mul(sqr(alpha), r2));
+  q.beta_r2 = plonk_words(mul(beta, r2));
+  for (int j = 0; j < 3; j++) q.bk_r2[j] = plonk_words(mul(mul(beta, plonk_mont(k_host96 + 32 * j)), r2));
+  q.gamma_r = plonk_words(plonk_mont(gamma_host32));
+  for (int m = 0; m < 4; m++) q.zh_r[m] = plonk_words(plonk_mont(zh_inv_host128 + 32 * m));
+  return q;
+}
 #endif  // __HIPCC__
 
 }  // namespace ozk
@@ -414,27 +454,12 @@ int ozk_plonk_quotient_dev(const void* d_wit, int64_t wit_stride, const void* d_
                            const uint8_t* alpha_host32, const uint8_t* beta_host32, const uint8_t* gamma_host32,
                            const uint8_t* k_host96, const uint8_t* zh_inv_host128, void* d_out, void* stream) {
   hip_clear_stale();
-  if (n < 2 || (n & (n - 1)) || n > (1 << 26))
-    return fail(OZK_E_INVALID, "n = %d is not a power of two in [2, 2^26] (the coset has 4 n <= 2^28 points)", n);
-  const int n4 = 4 * n;
-  if (wit_stride < n4 || key_stride < n4)
-    return fail(OZK_E_INVALID, "bad strides: wit_stride %lld, key_stride %lld (both >= 4 n = %d)", (long long)wit_stride,
-                (long long)key_stride, n4);
+  if (int rc = plonk_quot_shape(n, wit_stride, key_stride)) return rc;
   if (int rc = fr_check_pointers(d_wit, d_key, alpha_host32, beta_host32, gamma_host32, k_host96, zh_inv_host128, d_out))
     return rc;
-  if (int rc = fr_check_aligned16(d_wit, d_key, d_out)) return rc;
-  if (kzg_overlap(d_wit, kzg_span(PLONK_WIT_ROWS, n4, wit_stride), d_out, (size_t)n4 * 32) ||
-      kzg_overlap(d_key, kzg_span(PLONK_KEY_ROWS, n4, key_stride), d_out, (size_t)n4 * 32))
-    return fail(OZK_E_INVALID, "d_out overlaps d_wit or d_key");
-  PlonkQuotArgs q;
-  const auto r2 = fe_const<FrP, 16>(FrP::R2);
-  const auto alpha = plonk_mont(alpha_host32), beta = plonk_mont(beta_host32);
-  q.alpha_r = plonk_words(alpha);
-  q.alpha2_r2 = plonk_words(mul(sqr(alpha), r2));
-  q.beta_r2 = plonk_words(mul(beta, r2));
-  for (int j = 0; j < 3; j++) q.bk_r2[j] = plonk_words(mul(mul(beta, plonk_mont(k_host96 + 32 * j)), r2));
-  q.gamma_r = plonk_words(plonk_mont(gamma_host32));
-  for (int m = 0; m < 4; m++) q.zh_r[m] = plonk_words(plonk_mont(zh_inv_host128 + 32 * m));
+  if (int rc = plonk_quot_buffers(d_wit, PLONK_WIT_ROWS, wit_stride, d_key, PLONK_KEY_ROWS, key_stride, n, d_out)) return rc;
+  const int n4 = 4 * n;
+  const PlonkQuotArgs q = plonk_quot_args(alpha_host32, beta_host32, gamma_host32, k_host96, zh_inv_host128);
   hipLaunchKernelGGL(k_plonk_quotient, dim3((n4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const u32*)d_wit,
                      (size_t)wit_stride * 8, (const u32*)d_key, (size_t)key_stride * 8, (unsigned)n4, q, (u32*)d_out);
   OZK_HIP(hipGetLastError());

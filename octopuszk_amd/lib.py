@@ -121,6 +121,15 @@ _SIGS = {
     "ozk_fr_perm_product_workspace_bytes": (sz, [i32]),
     "ozk_fr_perm_product_dev": (ctypes.c_int, [vp, vp, i32, ctypes.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "ozk_plonk_quotient_dev": (ctypes.c_int, [vp, ctypes.c_int64, vp, ctypes.c_int64, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "ozk_plonk_lookup_index_bytes": (sz, [i32]),
+    "ozk_plonk_lookup_index_dev": (ctypes.c_int, [vp, i32, ctypes.c_int64, vp, sz, vp]),
+    "ozk_plonk_lookup_counts_dev": (ctypes.c_int, [vp, vp, i32, ctypes.c_int64, vp, i32, ctypes.c_int64, vp, sz, vp, i32, vp,
+                                                   vp, vp]),
+    "ozk_plonk_lookup_sum_workspace_bytes": (sz, [i32]),
+    "ozk_plonk_lookup_sum_dev": (ctypes.c_int, [vp, ctypes.c_int64, vp, ctypes.c_int64, vp, i32, vp, vp, vp, vp, vp, vp, sz,
+                                                vp]),
+    "ozk_plonk_quotient_lookup_dev": (ctypes.c_int, [vp, ctypes.c_int64, vp, ctypes.c_int64, i32, vp, vp, vp, vp, vp, vp, vp,
+                                                     vp, vp]),
     "ozk_multi_msm_table_bytes": (sz, [i32, i32]),
     "ozk_multi_msm_prepare_dev": (ctypes.c_int, [vp, i32, i32, vp, sz, vp, sz, vp]),
     "ozk_multi_msm_workspace_bytes": (sz, [i32, i32, i32]),

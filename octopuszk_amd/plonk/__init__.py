@@ -15,10 +15,25 @@ simplifications: there is NO linearisation polynomial (the proof opens all fourt
 product at z and z omega with one CommitKey.open_multi call, eight field elements more than the paper's proof), and
 there is NO blinding (the KZG layer is non-hiding: proofs are sound, not zero-knowledge).
 
-Out of scope: blinding, the linearisation polynomial, custom gates, lookups, import of R1CS.  There is no CPU path.
-"""
-from .circuit import Builder, Circuit
-from .protocol import PROOF_BYTES, Proof, ProvingKey, VerifyingKey, challenges, prove, setup, verify
+Lookups: one table of three-column tuples, logUp as a running sum beside the grand product.
 
-__all__ = ["Builder", "Circuit", "PROOF_BYTES", "Proof", "ProvingKey", "VerifyingKey", "challenges", "prove", "setup",
-           "verify"]
+    b.table([(x, y, x ^ y) for x in range(16) for y in range(16)])      # once per builder
+    b.lookup(u, v, w)                                # (u, v, w) is a row of the table: one row, every selector 0
+    circuit = b.build()                              # a plonk.LookupCircuit; n is also at least the table's length
+    pk, vk = plonk.setup(circuit, commit_key)        # 12 commitments, 392 bytes; pk keeps a 14 x 4n coset table
+    proof = plonk.prove(pk, assignment)              # a LookupProof, 1088 bytes; ValueError names a row not in the table
+    assert plonk.verify(vk, kzg_vk, public_inputs, proof)
+
+setup, prove and verify dispatch on the type of the circuit or key; the transcript of a proof with lookups has tags of
+its own, so neither kind of proof can be read as the other.
+
+Out of scope: blinding, the linearisation polynomial, custom gates, several tables, tables wider than three columns,
+import of R1CS.  There is no CPU path.
+"""
+from .circuit import Builder, Circuit, LookupCircuit
+from .protocol import (LOOKUP_PROOF_BYTES, LOOKUP_STAGES, LOOKUP_VK_BYTES, PROOF_BYTES, LookupProof, LookupProvingKey,
+                       LookupVerifyingKey, Proof, ProvingKey, VerifyingKey, challenges, lookup_challenges, prove, setup, verify)
+
+__all__ = ["Builder", "Circuit", "LookupCircuit", "LOOKUP_PROOF_BYTES", "LOOKUP_STAGES", "LOOKUP_VK_BYTES", "LookupProof",
+           "LookupProvingKey", "LookupVerifyingKey", "PROOF_BYTES", "Proof", "ProvingKey", "VerifyingKey", "challenges",
+           "lookup_challenges", "prove", "setup", "verify"]

@@ -75,12 +75,38 @@ class Circuit:
         return self._index
 
 
+class LookupCircuit(Circuit):
+    """A Circuit with one lookup table.  q_lookup: a column of n values in {0, 1}; table:
+    1 <= n_table <= n rows (T1, T2, T3) of ints, taken mod r.  In a row with q_lookup = 1 the tuple (a, b, c) must be a
+    row of the table; the row's arithmetic gate holds as in any other row."""
+
+    def __init__(self, n, selectors, wires, n_public, q_lookup, table):
+        super().__init__(n, selectors, wires, n_public)
+        self.q_lookup = [int(v) for v in q_lookup]
+        if len(self.q_lookup) != self.n or any(v not in (0, 1) for v in self.q_lookup):
+            raise ValueError("q_lookup: n = %d values in {0, 1}" % self.n)
+        rows = [tuple(row) for row in table]
+        if not 1 <= len(rows) <= self.n:
+            raise ValueError("the table has %d rows: at least 1 and at most n = %d" % (len(rows), self.n))
+        if any(len(row) != 3 for row in rows):
+            raise ValueError("a table row is three values")
+        self.table = [tuple(int(v) % FR for v in row) for row in rows]
+        self.n_table = len(self.table)
+
+    def table_columns(self):
+        """the three columns T1, T2, T3 of n values: the table, then its last row repeated"""
+        rows = self.table + [self.table[-1]] * (self.n - self.n_table)
+        return [[row[j] for row in rows] for j in range(3)]
+
+
 class Builder:
     """Collects variables and gates; build() puts the public inputs first and pads with empty gates to a power of two.
-    A variable used in several cells is copy-constrained by that alone."""
+    A variable used in several cells is copy-constrained by that alone.  table() and lookup() make it a circuit with
+    lookups: build() then returns a LookupCircuit."""
 
     def __init__(self):
         self._n_vars, self._public, self._gates = 0, [], []
+        self._table, self._lookups = None, set()
 
     def var(self) -> int:
         self._n_vars += 1
@@ -115,16 +141,37 @@ class Builder:
         """u = v, as the gate u - v = 0"""
         self.gate(1, -1, 0, 0, 0, u, v, u)
 
+    def table(self, rows):
+        """the circuit's lookup table: rows of three ints, once per builder"""
+        if self._table is not None:
+            raise ValueError("the table is already set")
+        rows = [tuple(int(v) for v in row) for row in rows]
+        if not rows or any(len(row) != 3 for row in rows):
+            raise ValueError("a table is at least one row of three values")
+        self._table = rows
+
+    def lookup(self, a, b, c):
+        """(a, b, c) is a row of the table: a row with every selector 0"""
+        if self._table is None:
+            raise ValueError("lookup needs a table: call table(rows) first")
+        self._known(a, b, c)
+        self._lookups.add(len(self._gates))
+        self._gates.append(((0, 0, 0, 0, 0), (a, b, c)))
+
     def build(self) -> Circuit:
         rows = [((1, 0, 0, 0, 0), (v, v, v)) for v in self._public] + self._gates
         if self._n_vars == 0:
             raise ValueError("a circuit needs a variable")
         n = 2
-        while n < len(rows):
+        while n < len(rows) or (self._table is not None and n < len(self._table)):
             n *= 2
         rows += [((0, 0, 0, 0, 0), (0, 0, 0))] * (n - len(rows))
-        circuit = Circuit(n, [[q[k] for q, _ in rows] for k in range(5)], [[w[k] for _, w in rows] for k in range(3)],
-                          len(self._public))
+        selectors, wires = [[q[k] for q, _ in rows] for k in range(5)], [[w[k] for _, w in rows] for k in range(3)]
+        if self._table is None:
+            circuit = Circuit(n, selectors, wires, len(self._public))
+        else:
+            q_lookup = [int(i - len(self._public) in self._lookups) for i in range(n)]
+            circuit = LookupCircuit(n, selectors, wires, len(self._public), q_lookup, self._table)
         if circuit.n_vars != self._n_vars:
             raise ValueError("variable %d is in no gate" % circuit.n_vars)
         return circuit

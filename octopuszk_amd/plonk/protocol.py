@@ -1,6 +1,7 @@
 """Setup, prover and verifier of the PLONK package: the transcript, the byte formats and the order
 of the device calls.  The group side is CommitKey.commit, CommitKey.open_multi and verify_multi; the field side is the
-transform and the three kernels of csrc/plonk.cuh."""
+transform and the three kernels of csrc/plonk.cuh.  A circuit with a lookup table has its own key,
+proof and transcript tags; its field side adds the kernels of csrc/plonk_lookup.cuh."""
 import time
 
 import numpy as np
@@ -9,9 +10,10 @@ import torch
 from .. import kzg as _kzg
 from .. import transcript as _transcript
 from ..fft import FR, FR_MULT_GEN, root_of_unity
-from ..vectors import fr_fft, fr_perm_product, fr_rows_coset, plonk_quotient
+from ..vectors import (fr_fft, fr_perm_product, fr_rows_coset, plonk_lookup_counts, plonk_lookup_index, plonk_lookup_sum,
+                       plonk_quotient, plonk_quotient_lookup)
 from ..wire import dev_bytes, ints32, le32, upload
-from .circuit import K, N_MAX, Circuit
+from .circuit import K, N_MAX, Circuit, LookupCircuit
 
 PROOF_BYTES = 7 * 32 + 16 * 32 + 64
 VK_BYTES = 8 + 8 * 32
@@ -19,9 +21,18 @@ _BETA_TAG, _GAMMA_TAG, _ALPHA_TAG, _Z_TAG = b"OZK-plonk-beta", b"OZK-plonk-gamma
 _COMMITMENTS = ("[a]", "[b]", "[c]", "[Z]", "[t_lo]", "[t_mid]", "[t_hi]")
 _KEY_COMMITMENTS = ("[qL]", "[qR]", "[qO]", "[qM]", "[qC]", "[s1]", "[s2]", "[s3]")
 _VALUES = ("a", "b", "c", "t_lo", "t_mid", "t_hi", "qL", "qR", "qO", "qM", "qC", "s1", "s2", "s3", "Z", "Z at z omega")
-STAGES = ("witness upload", "witness transforms", "grand product", "coset transforms", "quotient kernel", "commitments",
-          "multi-opening")
-_UPLOAD, _WITNESS, _PRODUCT, _COSET, _QUOTIENT, _COMMIT, _OPEN = STAGES
+LOOKUP_PROOF_BYTES = 9 * 32 + 23 * 32 + 64
+LOOKUP_VK_BYTES = 8 + 12 * 32
+_LK_TAGS = {name: b"OZK-plookup-" + name for name in (b"beta", b"gamma", b"eta", b"theta", b"alpha", b"z")}
+_LK_COMMITMENTS = ("[a]", "[b]", "[c]", "[m]", "[Z]", "[S]", "[t_lo]", "[t_mid]", "[t_hi]")
+_LK_KEY_COMMITMENTS = _KEY_COMMITMENTS + ("[qK]", "[T1]", "[T2]", "[T3]")
+_LK_VALUES = ("a", "b", "c", "m", "t_lo", "t_mid", "t_hi", "qL", "qR", "qO", "qM", "qC", "s1", "s2", "s3", "qK", "T1", "T2",
+              "T3", "Z", "Z at z omega", "S", "S at z omega")
+_UPLOAD, _WITNESS, _PRODUCT, _COSET, _QUOTIENT, _COMMIT, _OPEN, _COUNTS, _SUM = (
+    "witness upload", "witness transforms", "grand product", "coset transforms", "quotient kernel", "commitments",
+    "multi-opening", "lookup counts", "lookup sum")
+STAGES = (_UPLOAD, _WITNESS, _PRODUCT, _COSET, _QUOTIENT, _COMMIT, _OPEN)
+LOOKUP_STAGES = STAGES + (_COUNTS, _SUM)
 
 
 def _inv(v):
@@ -90,7 +101,85 @@ class Proof:
         return Proof(cs, values, b[736:768], b[768:])
 
 
+class LookupVerifyingKey:
+    """n uint32 LE | n_public uint32 LE | [qL] [qR] [qO] [qM] [qC] [s1] [s2] [s3] [qK] [T1] [T2] [T3], compressed: 392
+    bytes"""
+
+    def __init__(self, n, n_public, commitments):
+        self.n, self.n_public = int(n), int(n_public)
+        if self.n < 2 or self.n & (self.n - 1) or self.n > N_MAX:
+            raise ValueError("lookup verifying key: n = %d is not a power of two in [2, 2^26]" % self.n)
+        if not 0 <= self.n_public <= self.n:
+            raise ValueError("lookup verifying key: n_public = %d, not in [0, n = %d]" % (self.n_public, self.n))
+        self.commitments = tuple(bytes(c) for c in commitments)
+        if len(self.commitments) != 12 or any(len(c) != 32 for c in self.commitments):
+            raise ValueError("lookup verifying key: twelve commitments of 32 bytes")
+
+    def to_bytes(self) -> bytes:
+        return self.n.to_bytes(4, "little") + self.n_public.to_bytes(4, "little") + b"".join(self.commitments)
+
+    @staticmethod
+    def from_bytes(b) -> "LookupVerifyingKey":
+        """Strict and host-only, as VerifyingKey.from_bytes"""
+        b = bytes(b)
+        if len(b) != LOOKUP_VK_BYTES:
+            raise ValueError("lookup verifying key: length %d, not %d" % (len(b), LOOKUP_VK_BYTES))
+        cs = [b[8 + 32 * i:40 + 32 * i] for i in range(12)]
+        vk = LookupVerifyingKey(int.from_bytes(b[:4], "little"), int.from_bytes(b[4:8], "little"), cs)
+        _kzg.require_g1(zip(_LK_KEY_COMMITMENTS, cs), "lookup verifying key")
+        return vk
+
+
+class LookupProof:
+    """[a] [b] [c] [m] [Z] [S] [t_lo] [t_mid] [t_hi] | the 23 values a, b, c, m, t_lo, t_mid, t_hi, qL, qR, qO, qM, qC,
+    s1, s2, s3, qK, T1, T2, T3 at z, then Z at z, Z at z omega, S at z, S at z omega | W | W': 1088 bytes"""
+
+    def __init__(self, commitments, values, w, w2):
+        self.commitments = tuple(bytes(c) for c in commitments)
+        self.values = tuple(int(v) for v in values)
+        self.w, self.w2 = bytes(w), bytes(w2)
+        if len(self.commitments) != 9 or any(len(c) != 32 for c in self.commitments + (self.w, self.w2)):
+            raise ValueError("lookup proof: nine commitments, W and W' of 32 bytes")
+        if len(self.values) != 23 or any(not 0 <= v < FR for v in self.values):
+            raise ValueError("lookup proof: twenty-three values in [0, r)")
+
+    def to_bytes(self) -> bytes:
+        return b"".join(self.commitments) + le32(self.values) + self.w + self.w2
+
+    @staticmethod
+    def from_bytes(b) -> "LookupProof":
+        """Strict and host-only, as Proof.from_bytes"""
+        b = bytes(b)
+        if len(b) != LOOKUP_PROOF_BYTES:
+            raise ValueError("lookup proof: length %d, not %d" % (len(b), LOOKUP_PROOF_BYTES))
+        values = ints32(b[288:1024])
+        for name, v in zip(_LK_VALUES, values):
+            if v >= FR:
+                raise ValueError("lookup proof: the value %s is not below r" % name)
+        cs = [b[32 * i:32 * i + 32] for i in range(9)]
+        _kzg.require_g1(list(zip(_LK_COMMITMENTS, cs)) + [("W", b[1024:1056]), ("W'", b[1056:])], "lookup proof")
+        return LookupProof(cs, values, b[1024:1056], b[1056:])
+
+
 # ---------------------------------------------------------------------------- the transcript
+def lookup_challenges(vk_bytes, public_inputs, abcm, zs_commitments=None, t_commitments=None) -> tuple:
+    """(beta, gamma, eta, theta[, alpha[, z]]) of a proof with lookups, under tags of their own.  With D1 =
+    SHA-256("OZK-plookup-beta" | the verifying key's bytes | the public inputs | [a] [b] [c] [m]) and D2 =
+    SHA-256("OZK-plookup-alpha" | D1 | [Z] [S]): beta is drawn from D1, gamma, eta and theta from SHA-256 of their tag
+    and D1, alpha from D2 and z from SHA-256("OZK-plookup-z" | D2 | [t_lo] [t_mid] [t_hi])."""
+    parts = (bytes(vk_bytes), le32(public_inputs), b"".join(abcm))
+    d1 = _transcript.digest(_LK_TAGS[b"beta"], *parts)
+    out = [_transcript.challenge128(_LK_TAGS[b"beta"], *parts)]
+    out += [_transcript.challenge128(_LK_TAGS[name], d1) for name in (b"gamma", b"eta", b"theta")]
+    if zs_commitments is not None:
+        zs = b"".join(zs_commitments)
+        d2 = _transcript.digest(_LK_TAGS[b"alpha"], d1, zs)
+        out.append(_transcript.challenge128(_LK_TAGS[b"alpha"], d1, zs))
+        if t_commitments is not None:
+            out.append(_transcript.challenge128(_LK_TAGS[b"z"], d2, b"".join(t_commitments)))
+    return tuple(out)
+
+
 def challenges(vk_bytes, public_inputs, abc, z_commitment=None, t_commitments=None) -> tuple:
     """(beta, gamma[, alpha[, z]]), as far as the commitments given reach.  With D1 = SHA-256("OZK-plonk-beta" | the
     verifying key's bytes | the public inputs, 32 bytes each | [a] [b] [c]) and D2 = SHA-256("OZK-plonk-alpha" | D1 |
@@ -154,8 +243,35 @@ class ProvingKey:
         self.circuit, self.commit_key, self.coeffs, self.sigma, self.table, self.vk = circuit, commit_key, coeffs, sigma, table, vk
 
 
+class LookupProvingKey(ProvingKey):
+    """The proving key of a LookupCircuit: coeffs holds twelve rows (qK, T1, T2, T3 after the eight), table fourteen
+    (14 x 4 n x 32 bytes: qK, T1, T2, T3 after the ten); lookup_rows holds qK, T1, T2, T3 on the domain and index the
+    table's index (ozk_plonk_lookup_index_dev), both on the device."""
+
+    def __init__(self, circuit, commit_key, coeffs, sigma, table, vk, lookup_rows, index):
+        super().__init__(circuit, commit_key, coeffs, sigma, table, vk)
+        self.lookup_rows, self.index = lookup_rows, index
+
+
+def _setup_lookup(circuit, commit_key):
+    n = circuit.n
+    if commit_key.n != n:
+        raise ValueError("the circuit has n = %d gates, the commit key n = %d bases" % (n, commit_key.n))
+    sigma = _rows(circuit.sigma_labels())
+    lookup_rows = _rows([circuit.q_lookup] + circuit.table_columns())
+    coeffs = _interpolate(torch.cat([_rows(circuit.selectors), sigma, lookup_rows]), 12, n)
+    vk = LookupVerifyingKey(n, circuit.n_public, commit_key.commit(coeffs))
+    extra = _rows([[_inv(n)] * n, [0, 1] + [0] * (n - 2)])
+    table = _onto_coset(torch.cat([coeffs[:8], extra, coeffs[8:]]), 14, n)
+    index = plonk_lookup_index(lookup_rows[1:], circuit.n_table, n)
+    return LookupProvingKey(circuit, commit_key, coeffs, sigma, table, vk, lookup_rows, index), vk
+
+
 def setup(circuit, commit_key):
-    """(ProvingKey, VerifyingKey) of a circuit over a CommitKey of n bases: eight commitments, no secret"""
+    """(ProvingKey, VerifyingKey) of a circuit over a CommitKey of n bases: eight commitments, no secret; for a
+    LookupCircuit (LookupProvingKey, LookupVerifyingKey), twelve commitments"""
+    if isinstance(circuit, LookupCircuit):
+        return _setup_lookup(circuit, commit_key)
     if not isinstance(circuit, Circuit):
         raise TypeError("setup takes a plonk.Circuit")
     n = circuit.n
@@ -189,19 +305,9 @@ class _Clock:
         self.at = now
 
 
-def prove(pk, assignment=None, timings=None, wire_values=None) -> Proof:
-    """The proof of one assignment (one Fr value per variable: a list of ints, or their 32-byte little-endian records
-    back to back as bytes, which are taken mod r), or of a witness produced elsewhere and given cell by cell
-    (wire_values: the three columns a, b, c of n values).  ValueError, before any commitment to t, when the
-    grand product does not close (a copy constraint is violated) or the quotient is no polynomial (a gate is violated,
-    seen as a nonzero top quarter of its 4 n coefficients by one reduction on the device); RuntimeError when a
-    denominator of the grand product is zero.  timings: a dict that receives the seconds of every stage of STAGES."""
-    circuit, ck, n = pk.circuit, pk.commit_key, pk.circuit.n
-    omega = root_of_unity(n)
-    vk_bytes = pk.vk.to_bytes()
-    if (assignment is None) == (wire_values is None):
-        raise ValueError("prove takes an assignment or the three columns of wire values")
-    clock = _Clock(timings)
+def _host_witness(circuit, assignment, wire_values):
+    """(the three wire columns as a [3, 32 n] array of bytes, the public inputs) of an assignment or of wire values"""
+    n = circuit.n
     if wire_values is None:
         # one 32-byte record per variable, gathered into the three columns by the circuit's index
         if isinstance(assignment, (bytes, bytearray)):
@@ -219,24 +325,80 @@ def prove(pk, assignment=None, timings=None, wire_values=None) -> Proof:
             raise ValueError("wire_values: three columns of n = %d values in [0, r)" % n)
         host = np.frombuffer(le32(v for col in values for v in col), dtype=np.uint8).reshape(3, 32 * n)
         public = values[0][:circuit.n_public]
+    return host, public
+
+
+def _witness_on_device(circuit, assignment, timings, wire_values):
+    """(the clock, the public inputs, the three wire columns on the device, their coefficient rows): how both
+    provers begin"""
+    if (assignment is None) == (wire_values is None):
+        raise ValueError("prove takes an assignment or the three columns of wire values")
+    clock = _Clock(timings)
+    host, public = _host_witness(circuit, assignment, wire_values)
     wires = upload(host)
     clock.lap(_UPLOAD)
-    wire_coeffs = _interpolate(wires, 3, n)
+    wire_coeffs = _interpolate(wires, 3, circuit.n)
     clock.lap(_WITNESS)
-    abc = ck.commit(wire_coeffs)
-    clock.lap(_COMMIT)
-    beta, gamma = challenges(vk_bytes, public, abc)
-    z_evals, total, zero_dens = fr_perm_product(wires, pk.sigma, n, n, omega, K, beta, gamma)
+    return clock, public, wires, wire_coeffs
+
+
+def _grand_product(wires, sigma, n, beta, gamma, clock):
+    """Z on the domain; RuntimeError for a zero denominator, ValueError when the product does not close"""
+    z_evals, total, zero_dens = fr_perm_product(wires, sigma, n, n, root_of_unity(n), K, beta, gamma)
     if zero_dens:
         raise RuntimeError("the grand product met %d zero denominator(s) under these challenges" % zero_dens)
     if total != 1:
         raise ValueError("a copy constraint is violated: the grand product does not close")
     clock.lap(_PRODUCT)
-    z_coeffs = _interpolate(z_evals.unsqueeze(0), 1, n)
-    pi_evals = torch.zeros((1, 32 * n), dtype=torch.uint8, device=wires.device)
+    return z_evals
+
+
+def _public_input_row(public, n, device):
+    """the coefficients of PI: -x_i in row i of the domain"""
+    pi_evals = torch.zeros((1, 32 * n), dtype=torch.uint8, device=device)
     if public:
         pi_evals[0, :32 * len(public)] = dev_bytes(le32((FR - x) % FR for x in public))
-    pi_coeffs = _interpolate(pi_evals, 1, n)
+    return _interpolate(pi_evals, 1, n)
+
+
+def _quotient_parts(t_evals, n, ck, clock):
+    """(t_lo, t_mid, t_hi as three coefficient rows, their commitments) of the quotient's values on the coset;
+    ValueError when its top quarter is not zero"""
+    t = _off_coset(t_evals, n)
+    if bool(t[32 * 3 * n:].any().item()):
+        raise ValueError("a gate is violated: the quotient is no polynomial")
+    clock.lap(_COSET)
+    t_rows = t[:32 * 3 * n].view(3, 32 * n)
+    t_commitments = ck.commit(t_rows)
+    clock.lap(_COMMIT)
+    return t_rows, t_commitments
+
+
+def _outside_domain(z, n):
+    if pow(z, n, FR) == 1:
+        raise RuntimeError("the evaluation challenge fell into the domain")
+    return z
+
+
+def prove(pk, assignment=None, timings=None, wire_values=None) -> Proof:
+    """The proof of one assignment (one Fr value per variable: a list of ints, or their 32-byte little-endian records
+    back to back as bytes, which are taken mod r), or of a witness produced elsewhere and given cell by cell
+    (wire_values: the three columns a, b, c of n values).  ValueError, before any commitment to t, when the
+    grand product does not close (a copy constraint is violated) or the quotient is no polynomial (a gate is violated,
+    seen as a nonzero top quarter of its 4 n coefficients by one reduction on the device); RuntimeError when a
+    denominator of the grand product is zero.  timings: a dict that receives the seconds of every stage of STAGES.
+    With a LookupProvingKey the proof is a LookupProof (_prove_lookup)."""
+    if isinstance(pk, LookupProvingKey):
+        return _prove_lookup(pk, assignment, timings, wire_values)
+    circuit, ck, n = pk.circuit, pk.commit_key, pk.circuit.n
+    vk_bytes = pk.vk.to_bytes()
+    clock, public, wires, wire_coeffs = _witness_on_device(circuit, assignment, timings, wire_values)
+    abc = ck.commit(wire_coeffs)
+    clock.lap(_COMMIT)
+    beta, gamma = challenges(vk_bytes, public, abc)
+    z_evals = _grand_product(wires, pk.sigma, n, beta, gamma, clock)
+    z_coeffs = _interpolate(z_evals.unsqueeze(0), 1, n)
+    pi_coeffs = _public_input_row(public, n, wires.device)
     clock.lap(_WITNESS)
     z_commitment = ck.commit(z_coeffs)[0]
     clock.lap(_COMMIT)
@@ -245,16 +407,8 @@ def prove(pk, assignment=None, timings=None, wire_values=None) -> Proof:
     clock.lap(_COSET)
     t_evals = plonk_quotient(wit, 4 * n, pk.table, 4 * n, n, alpha, beta, gamma, K, zh_inverses(n))
     clock.lap(_QUOTIENT)
-    t = _off_coset(t_evals, n)
-    if bool(t[32 * 3 * n:].any().item()):
-        raise ValueError("a gate is violated: the quotient is no polynomial")
-    clock.lap(_COSET)
-    t_rows = t[:32 * 3 * n].view(3, 32 * n)
-    t_commitments = ck.commit(t_rows)
-    clock.lap(_COMMIT)
-    z = challenges(vk_bytes, public, abc, z_commitment, t_commitments)[3]
-    if pow(z, n, FR) == 1:
-        raise RuntimeError("the evaluation challenge fell into the domain")
+    t_rows, t_commitments = _quotient_parts(t_evals, n, ck, clock)
+    z = _outside_domain(challenges(vk_bytes, public, abc, z_commitment, t_commitments)[3], n)
     rows = torch.cat([wire_coeffs, t_rows, pk.coeffs, z_coeffs])
     mo = ck.open_multi(rows, _point_sets(n, z), abc + t_commitments + list(pk.vk.commitments) + [z_commitment])
     clock.lap(_OPEN)
@@ -263,6 +417,52 @@ def prove(pk, assignment=None, timings=None, wire_values=None) -> Proof:
 
 def _point_sets(n, z):
     return [[z]] * 14 + [[z, z * root_of_unity(n) % FR]]
+
+
+def _prove_lookup(pk, assignment, timings, wire_values) -> LookupProof:
+    """The proof of a circuit with lookups.  As prove, and: ValueError naming the first offending row, before any
+    commitment, when a row with qK = 1 holds a tuple that is in no table row; RuntimeError when a denominator of the
+    lookup sum is zero or the sum does not close after a clean count.  timings receives LOOKUP_STAGES."""
+    circuit, ck, n = pk.circuit, pk.commit_key, pk.circuit.n
+    vk_bytes = pk.vk.to_bytes()
+    clock, public, wires, wire_coeffs = _witness_on_device(circuit, assignment, timings, wire_values)
+    m_evals, missing, first = plonk_lookup_counts(wires, pk.lookup_rows[0], n, n, pk.lookup_rows[1:], circuit.n_table, n,
+                                                  pk.index, n)
+    if missing:
+        raise ValueError("row %d looks up a tuple that is in no row of the table (%d such row(s))" % (first, missing))
+    clock.lap(_COUNTS)
+    m_coeffs = _interpolate(m_evals.view(1, -1), 1, n)
+    clock.lap(_WITNESS)
+    abcm = ck.commit(torch.cat([wire_coeffs, m_coeffs]))
+    clock.lap(_COMMIT)
+    beta, gamma, eta, theta = lookup_challenges(vk_bytes, public, abcm)
+    z_evals = _grand_product(wires, pk.sigma, n, beta, gamma, clock)
+    s_evals, s_total, zero_dens = plonk_lookup_sum(wires, n, pk.lookup_rows, n, m_evals, n, eta, theta)
+    if zero_dens:
+        raise RuntimeError("the lookup sum met %d zero denominator(s) under these challenges" % zero_dens)
+    if s_total != 0:
+        raise RuntimeError("the lookup sum does not close after a clean count")
+    clock.lap(_SUM)
+    zs_coeffs = _interpolate(torch.stack([z_evals, s_evals]), 2, n)
+    pi_coeffs = _public_input_row(public, n, wires.device)
+    clock.lap(_WITNESS)
+    zs_commitments = ck.commit(zs_coeffs)
+    clock.lap(_COMMIT)
+    alpha = lookup_challenges(vk_bytes, public, abcm, zs_commitments)[4]
+    wit = _onto_coset(torch.cat([wire_coeffs, zs_coeffs[:1], pi_coeffs, m_coeffs, zs_coeffs[1:]]), 7, n)
+    clock.lap(_COSET)
+    t_evals = plonk_quotient_lookup(wit, 4 * n, pk.table, 4 * n, n, alpha, beta, gamma, K, zh_inverses(n), eta, theta)
+    clock.lap(_QUOTIENT)
+    t_rows, t_commitments = _quotient_parts(t_evals, n, ck, clock)
+    z = _outside_domain(lookup_challenges(vk_bytes, public, abcm, zs_commitments, t_commitments)[5], n)
+    rows = torch.cat([wire_coeffs, m_coeffs, t_rows, pk.coeffs, zs_coeffs])
+    mo = ck.open_multi(rows, _lookup_point_sets(n, z), abcm + t_commitments + list(pk.vk.commitments) + zs_commitments)
+    clock.lap(_OPEN)
+    return LookupProof(abcm + zs_commitments + t_commitments, [y for row in mo.values for y in row], mo.w, mo.w2)
+
+
+def _lookup_point_sets(n, z):
+    return [[z]] * 19 + [[z, z * root_of_unity(n) % FR]] * 2
 
 
 # ---------------------------------------------------------------------------- the verifier
@@ -286,10 +486,58 @@ def identity_holds(vk, public_inputs, values, beta, gamma, alpha, z) -> bool:
     return (gate + alpha * p1 + alpha * alpha * p2 - t * (zn - 1)) % FR == 0
 
 
+def lookup_identity_holds(vk, public_inputs, values, beta, gamma, eta, theta, alpha, z) -> bool:
+    """gate + alpha P1 + alpha^2 (Z - 1) L_1 + alpha^3 L1 + alpha^4 S L_1 = t Z_H at z, on the 23 opened values, with
+    L1 = (S(omega z) - S)(theta + t)(theta + f) - m (theta + f) + qK (theta + t)"""
+    a, b, c, m, t_lo, t_mid, t_hi, ql, qr, qo, qm, qc, s1, s2, s3, qk, t1, t2, t3, zz, zw, ss, sw = values
+    n = vk.n
+    zn = pow(z, n, FR)
+    if zn == 1:
+        return False
+    omega, w, lagrange = root_of_unity(n), 1, []
+    for _ in range(max(1, len(public_inputs))):
+        lagrange.append(w * (zn - 1) * _inv(n * (z - w)) % FR)
+        w = w * omega % FR
+    pi = -sum(x * l for x, l in zip(public_inputs, lagrange)) % FR
+    gate = ql * a + qr * b + qo * c + qm * a * b + qc + pi
+    p1 = (zz * (a + beta * z + gamma) * (b + beta * K[1] * z + gamma) * (c + beta * K[2] * z + gamma)
+          - zw * (a + beta * s1 + gamma) * (b + beta * s2 + gamma) * (c + beta * s3 + gamma))
+    p2 = (zz - 1) * lagrange[0]
+    df, dt = theta + a + eta * b + eta * eta * c, theta + t1 + eta * t2 + eta * eta * t3
+    l1 = (sw - ss) * dt * df - m * df + qk * dt
+    l2 = ss * lagrange[0]
+    t = t_lo + zn * (t_mid + zn * t_hi)
+    return (gate + alpha * p1 + alpha ** 2 * p2 + alpha ** 3 * l1 + alpha ** 4 * l2 - t * (zn - 1)) % FR == 0
+
+
+def _verify_lookup(vk, kzg_vk, public_inputs, proof) -> bool:
+    try:
+        proof = proof if isinstance(proof, LookupProof) else LookupProof.from_bytes(proof)
+        public = [int(x) for x in public_inputs]
+    except (ValueError, TypeError):
+        return False
+    if len(public) != vk.n_public or any(not 0 <= x < FR for x in public):
+        return False
+    cs = list(proof.commitments)
+    beta, gamma, eta, theta, alpha, z = lookup_challenges(vk.to_bytes(), public, cs[:4], cs[4:6], cs[6:])
+    if not lookup_identity_holds(vk, public, proof.values, beta, gamma, eta, theta, alpha, z):
+        return False
+    values = [[v] for v in proof.values[:19]] + [list(proof.values[19:21]), list(proof.values[21:])]
+    try:
+        mo = _kzg.MultiOpening(cs[:4] + cs[6:] + list(vk.commitments) + cs[4:6], _lookup_point_sets(vk.n, z), values,
+                               proof.w, proof.w2)
+    except ValueError:
+        return False
+    return _kzg.verify_multi(kzg_vk, mo)
+
+
 def verify(vk, kzg_vk, public_inputs, proof) -> bool:
     """Whether `proof` (a Proof or its 800 bytes) proves the circuit of `vk` on these public inputs: the proof's form,
     then the identity on the opened values, then verify_multi over the MultiOpening rebuilt from the verifying key, the
-    proof and z.  False, never an exception, for a malformed proof of the right size."""
+    proof and z.  False, never an exception, for a malformed proof of the right size.  With a LookupVerifyingKey the
+    proof is a LookupProof or its 1088 bytes."""
+    if isinstance(vk, LookupVerifyingKey):
+        return _verify_lookup(vk, kzg_vk, public_inputs, proof)
     try:
         proof = proof if isinstance(proof, Proof) else Proof.from_bytes(proof)
         public = [int(x) for x in public_inputs]

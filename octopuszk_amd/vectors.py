@@ -233,3 +233,55 @@ def plonk_quotient(wit, wit_stride, key, key_stride, n, alpha, beta, gamma, ks, 
     _lib.check(L.ozk_plonk_quotient_dev(_ptr(wit), wit_stride, _ptr(key), key_stride, n, le([alpha]), le([beta]),
                                         le([gamma]), le(ks), le(zh_inv), _ptr(out), _stream()))
     return out
+
+
+def plonk_lookup_index(table, n_rows, table_stride):
+    """The index of a lookup table's first n_rows tuples (ozk_plonk_lookup_index_dev; table: the rows T1, T2, T3 at
+    table_stride): uint32 row numbers on the device, built once per key.  Asynchronous on the current stream."""
+    L = _lib.load()
+    index = torch.empty(max(int(L.ozk_plonk_lookup_index_bytes(n_rows)), 16), dtype=torch.uint8, device=table.device)
+    _lib.check(L.ozk_plonk_lookup_index_dev(_ptr(table), n_rows, table_stride, _ptr(index), index.numel(), _stream()))
+    return index
+
+
+def plonk_lookup_counts(wires, qk, length, stride, table, n_rows, table_stride, index, m_len):
+    """How often the rows with qK != 0 name each table row (ozk_plonk_lookup_counts_dev): (m, m_len x 32 bytes on the
+    device; the number of rows whose tuple is in no table row; the first of them, or None).  Synchronises."""
+    L = _lib.load()
+    m = torch.empty(32 * m_len, dtype=torch.uint8, device=wires.device)
+    tail = torch.empty(16, dtype=torch.uint8, device=wires.device)         # missing, then first_missing
+    _lib.check(L.ozk_plonk_lookup_counts_dev(_ptr(wires), _ptr(qk), length, stride, _ptr(table), n_rows, table_stride,
+                                             _ptr(index), index.numel(), _ptr(m), m_len, _ptr(tail), _ptr(tail[4:]),
+                                             _stream()))
+    host = _wire.host_bytes(tail)
+    missing = int.from_bytes(host[:4], "little", signed=True)
+    return m, missing, int.from_bytes(host[4:8], "little", signed=True) if missing else None
+
+
+def plonk_lookup_sum(wires, stride, key4, key_stride, m, length, eta, theta):
+    """The running sum of the lookup argument over three wire rows, the key rows qK, T1, T2, T3 and the counts m
+    (ozk_plonk_lookup_sum_dev): (S, `length` x 32 bytes on the device with S[0] = 0; the sum over all rows as an int;
+    the number of zero denominators).  Synchronises."""
+    L = _lib.load()
+    s = torch.empty(32 * length, dtype=torch.uint8, device=wires.device)
+    tail = torch.empty(48, dtype=torch.uint8, device=wires.device)         # the total, then the count
+    ws = torch.empty(max(int(L.ozk_plonk_lookup_sum_workspace_bytes(length)), 256), dtype=torch.uint8, device=wires.device)
+    le = lambda vs: _wire.vp(_wire.le32([int(v) % FR for v in vs]))
+    _lib.check(L.ozk_plonk_lookup_sum_dev(_ptr(wires), stride, _ptr(key4), key_stride, _ptr(m), length, le([eta]),
+                                          le([theta]), _ptr(s), _ptr(tail), _ptr(tail[32:]), _ptr(ws), ws.numel(),
+                                          _stream()))
+    host = _wire.host_bytes(tail)
+    return s, int.from_bytes(host[:32], "little"), int.from_bytes(host[32:36], "little", signed=True)
+
+
+def plonk_quotient_lookup(wit, wit_stride, key, key_stride, n, alpha, beta, gamma, ks, zh_inv, eta, theta, out=None):
+    """t on the coset of 4 n points from the seven witness rows and the fourteen key rows of a circuit with lookups
+    (ozk_plonk_quotient_lookup_dev): 4 n x 32 bytes on the device.  Asynchronous on the current stream."""
+    L = _lib.load()
+    if out is None:
+        out = torch.empty(32 * 4 * n, dtype=torch.uint8, device=wit.device)
+    le = lambda vs: _wire.vp(_wire.le32([int(v) % FR for v in vs]))
+    _lib.check(L.ozk_plonk_quotient_lookup_dev(_ptr(wit), wit_stride, _ptr(key), key_stride, n, le([alpha]), le([beta]),
+                                               le([gamma]), le(ks), le(zh_inv), le([eta]), le([theta]), _ptr(out),
+                                               _stream()))
+    return out

@@ -11,7 +11,14 @@ feeds every third gate, padded to 2^k rows.  The string is built from a known ta
 (c) the grand-product and quotient entry points alone under device events, with the bytes per second of their counted
     traffic: 32 len (12 reads + 1 write) and 32 (4 n) (16 reads + 1 write).
 
-    python tools/plonk_prove.py [--log-n 16] [--reps 5] [--public 3]
+With --lookups FRACTION a second circuit of the same n is proved in the same run, in which that
+share of the rows are lookups into a table of --table-rows rows (x, y, x xor y):
+(d) every stage of its proof, the two lookup stages among them, beside the vanilla proof's;
+(e) the four entry points of csrc/plonk_lookup.cuh alone under device events with their counted traffic, the counts
+    also against a 256-row table (the most contended one), and against numpy on the host (np.unique over the 96-byte
+    records, and the upload of m).
+
+    python tools/plonk_prove.py [--log-n 16] [--reps 5] [--public 3] [--lookups 0.5 --table-rows 256]
 """
 import argparse
 import ctypes
@@ -26,6 +33,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import kzg_bench as kb  # noqa: E402
@@ -36,16 +44,16 @@ from octopuszk_amd.plonk import protocol  # noqa: E402
 from octopuszk_amd.plonk.circuit import K  # noqa: E402
 
 
-def chain(n, n_public):
-    """(circuit, assignment): n_public inputs, n - n_public - 1 gates alternating addition and multiplication, one
-    padding row"""
+def chain_columns(n, n_public, end):
+    """(selector columns, wire columns, assignment) of n rows: n_public inputs, then gates alternating addition and
+    multiplication in the rows up to `end`; the rows from `end` on are empty"""
     values = [(0x9e3779b97f4a7c15f39cc0605cedc835 * (i + 1)) % FR for i in range(n_public)]
     sel, wires = [[0] * n for _ in range(5)], [[0] * n for _ in range(3)]
     for v in range(n_public):
         sel[0][v] = 1
         wires[0][v] = wires[1][v] = wires[2][v] = v
     prev = 0
-    for row in range(n_public, n - 1):
+    for row in range(n_public, end):
         other = 0 if row % 3 == 0 else prev
         new = len(values)
         if row % 2:
@@ -56,14 +64,155 @@ def chain(n, n_public):
             sel[0][row], sel[1][row], sel[2][row] = 1, 1, FR - 1
         wires[0][row], wires[1][row], wires[2][row] = prev, other, new
         prev = new
+    return sel, wires, values
+
+
+def chain(n, n_public):
+    """(circuit, assignment): n_public inputs, n - n_public - 1 gates, one padding row"""
+    sel, wires, values = chain_columns(n, n_public, n - 1)
     return plonk.Circuit(n, sel, wires, n_public), values
+
+
+def xor_table(rows):
+    """rows (x, y, x xor y) over x, y < 2^k: the first `rows` of them"""
+    side = 1
+    while side * side < rows:
+        side *= 2
+    return [(i // side, i % side, (i // side) ^ (i % side)) for i in range(rows)]
+
+
+def chain_with_lookups(n, n_public, share, table):
+    """(circuit, assignment): the chain over the first rows, then round(n * share) lookup rows (at least one, and at
+    least one gate of the chain stays); the lookups of one table row share three variables"""
+    lookups = max(1, min(int(round(n * share)), n - n_public - 1))
+    sel, wires, values = chain_columns(n, n_public, n - lookups)
+    q_lookup, cells = [0] * (n - lookups) + [1] * lookups, {}
+    for k in range(lookups):
+        at = (k * 2654435761) % len(table)
+        if at not in cells:
+            cells[at] = len(values)
+            values += list(table[at])
+        for j in range(3):
+            wires[j][n - lookups + k] = cells[at] + j
+    return plonk.LookupCircuit(n, sel, wires, n_public, q_lookup, table), values
+
+
+def run_lookup(log_n, reps, n_public, share, table_rows, ck, kvk):
+    n = 1 << log_n
+    L = _lib.load()
+    circuit, as_ints = chain_with_lookups(n, n_public, share, xor_table(table_rows))
+    public = as_ints[:n_public]
+    t0 = time.perf_counter()
+    pk, vk = plonk.setup(circuit, ck)
+    torch.cuda.synchronize()
+    res = {"lookups": sum(circuit.q_lookup), "table_rows": table_rows, "setup_s": time.perf_counter() - t0,
+           "proving_key_table_bytes": pk.table.numel(), "index_bytes": pk.index.numel()}
+    assignment = wire.le32(as_ints)
+    proof = plonk.prove(pk, assignment)
+    assert plonk.verify(vk, kvk, public, proof)
+    stages, whole, verify = {name: [] for name in plonk.LOOKUP_STAGES}, [], []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        plonk.prove(pk, assignment)
+        torch.cuda.synchronize()
+        whole.append(time.perf_counter() - t0)
+    for _ in range(reps):
+        timings = {}
+        proof = plonk.prove(pk, assignment, timings)
+        for name in stages:
+            stages[name].append(timings.get(name, 0.0))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        assert plonk.verify(vk, kvk, public, proof)
+        torch.cuda.synchronize()
+        verify.append(time.perf_counter() - t0)
+    res["stages_ms"] = {name: _median_ms(v) for name, v in stages.items()}
+    res["stages_ms"]["verification"] = _median_ms(verify)
+    res["prove_ms"] = _median_ms(whole)
+    res["proof_bytes"] = len(proof.to_bytes())
+
+    # (e) the entry points alone
+    host_wires = np.frombuffer(wire.le32(v for col in circuit.wire_values(as_ints) for v in col), dtype=np.uint8).reshape(3, n, 32)
+    wires = wire.upload(host_wires.reshape(3, 32 * n))
+    keep = [wire.le32([c + n]) for c in (0x2468ace, 0x13579bd, 0x1357, 0x1234567, 0x7654321)]
+    keep += [wire.le32(K), wire.le32(protocol.zh_inverses(n))]
+    eta, theta, alpha, beta, gamma, ks, zh = (ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in keep)
+    tail = torch.empty(64, dtype=torch.uint8, device="cuda")
+
+    def counts_of(wires, rows4, n_rows):
+        index = vectors.plonk_lookup_index(rows4[1:], n_rows, n)
+        m = torch.empty(32 * n, dtype=torch.uint8, device="cuda")
+
+        def build():
+            _lib.check(L.ozk_plonk_lookup_index_dev(_ptr(rows4[1:]), n_rows, n, _ptr(index), index.numel(), _stream()))
+
+        def count():
+            _lib.check(L.ozk_plonk_lookup_counts_dev(_ptr(wires), _ptr(rows4[0]), n, n, _ptr(rows4[1:]), n_rows, n,
+                                                     _ptr(index), index.numel(), _ptr(m), n, _ptr(tail), _ptr(tail[4:]),
+                                                     _stream()))
+
+        return kb._event_ms(build, reps), kb._event_ms(count, reps), m
+
+    index_ms, counts_ms, m = counts_of(wires, pk.lookup_rows, table_rows)
+    looked = res["lookups"]
+    res["index"] = {"ms": index_ms, "counted_bytes": 100 * table_rows}
+    bytes_counts = 32 * n + 96 * looked + 100 * looked
+    res["counts"] = {"ms": counts_ms, "counted_bytes": bytes_counts, "bytes_per_s": bytes_counts / (counts_ms * 1e-3)}
+    if table_rows != 256:
+        small, small_ints = chain_with_lookups(n, n_public, share, xor_table(256))
+        rows4 = protocol._rows([small.q_lookup] + small.table_columns())
+        res["counts_256_row_table_ms"] = counts_of(protocol._rows(small.wire_values(small_ints)), rows4, 256)[1]
+
+    def host_count():
+        records = np.ascontiguousarray(host_wires[:, n - looked:, :].transpose(1, 0, 2)).reshape(looked, 96)
+        keys = np.ascontiguousarray(records).view(np.dtype((np.void, 96))).ravel()
+        uniq, cnt = np.unique(keys, return_counts=True)
+        table = np.frombuffer(wire.le32(v for row in circuit.table for v in row), dtype=np.uint8).reshape(-1, 96)
+        order = {bytes(row): i for i, row in reversed(list(enumerate(table)))}
+        out = np.zeros((n, 4), dtype=np.uint64)
+        for key, c in zip(uniq, cnt):
+            out[order[bytes(key)], 0] = c
+        return wire.upload(out.view(np.uint8).reshape(-1))
+
+    samples = []
+    for _ in range(max(1, min(reps, 3))):
+        t0 = time.perf_counter()
+        host_m = host_count()
+        torch.cuda.synchronize()
+        samples.append(time.perf_counter() - t0)
+    assert torch.equal(host_m, m)
+    res["counts_host_numpy_ms"] = _median_ms(samples)
+
+    s_out = torch.empty(32 * n, dtype=torch.uint8, device="cuda")
+    ws = torch.empty(max(int(L.ozk_plonk_lookup_sum_workspace_bytes(n)), 256), dtype=torch.uint8, device="cuda")
+
+    def lookup_sum():
+        _lib.check(L.ozk_plonk_lookup_sum_dev(_ptr(wires), n, _ptr(pk.lookup_rows), n, _ptr(m), n, eta, theta, _ptr(s_out),
+                                              _ptr(tail), _ptr(tail[32:]), _ptr(ws), ws.numel(), _stream()))
+
+    ms = kb._event_ms(lookup_sum, reps)
+    res["lookup_sum"] = {"ms": ms, "counted_bytes": 32 * n * 17, "bytes_per_s": 32 * n * 17 / (ms * 1e-3),
+                         "products_per_s": 23 * n / (ms * 1e-3)}
+    rows = kb._random_rows(1, 4 * n, log_n)
+    wit = torch.cat([rows[0].view(1, -1)] * 7)
+    out = torch.empty(32 * 4 * n, dtype=torch.uint8, device="cuda")
+
+    def quotient():
+        _lib.check(L.ozk_plonk_quotient_lookup_dev(_ptr(wit), 4 * n, _ptr(pk.table), 4 * n, n, alpha, beta, gamma, ks, zh,
+                                                   eta, theta, _ptr(out), _stream()))
+
+    ms = kb._event_ms(quotient, reps)
+    res["quotient_lookup"] = {"ms": ms, "counted_bytes": 32 * 4 * n * 24, "bytes_per_s": 32 * 4 * n * 24 / (ms * 1e-3),
+                              "products_per_s": 38 * 4 * n / (ms * 1e-3)}
+    return res
 
 
 def _median_ms(samples):
     return statistics.median(samples) * 1e3
 
 
-def run(log_n, reps, n_public):
+def run(log_n, reps, n_public, share=0.0, table_rows=256):
     n = 1 << log_n
     L = _lib.load()
     t0 = time.perf_counter()
@@ -142,6 +291,9 @@ def run(log_n, reps, n_public):
 
     ms = kb._event_ms(quotient, reps)
     res["quotient"] = {"ms": ms, "counted_bytes": 32 * 4 * n * 17, "bytes_per_s": 32 * 4 * n * 17 / (ms * 1e-3)}
+    if share > 0:
+        del pk, wit, wires
+        res["lookup"] = run_lookup(log_n, reps, n_public, share, table_rows, ck, kvk)
     return res
 
 
@@ -150,12 +302,16 @@ def main():
     ap.add_argument("--log-n", type=int, default=16)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--public", type=int, default=3)
+    ap.add_argument("--lookups", type=float, default=0.0, help="the share of rows that are lookups (0: none)")
+    ap.add_argument("--table-rows", type=int, default=256)
     a = ap.parse_args()
     if not 2 <= a.log_n <= 22 or not 1 <= a.public < (1 << a.log_n) - 1:
         ap.error("2 <= --log-n <= 22 and 1 <= --public < 2^log-n - 1")
+    if not 0 <= a.lookups <= 1 or not 1 <= a.table_rows <= 1 << a.log_n:
+        ap.error("0 <= --lookups <= 1 and 1 <= --table-rows <= 2^log-n")
     torch.cuda.set_device(0)
     out = {"bench": "plonk_prove", "device": torch.cuda.get_device_name(0), "reps": a.reps,
-           "result": run(a.log_n, a.reps, a.public)}
+           "result": run(a.log_n, a.reps, a.public, a.lookups, a.table_rows)}
     print(json.dumps(out))
 
 
