@@ -462,9 +462,11 @@ int ozk_groth16_verify_rlc_dev(const void* d_alpha_beta, const void* d_gamma_pre
  *   ozk_bace_result_dev       Verifier.getResult: d_out[i] = proof(omega_N^i), i < N (N x 32 B) for a proof of D
  *                             coefficients: the proof folded mod z^N - 1, then one transform of size N.
  *                             Workspace: ozk_bace_workspace_bytes(1, N, N, 0, 0, 0).
- *   ozk_fr_poly_eval_dev      d_out[y] = sum_i c_yi r^i for npolys polynomials of len coefficients each (canonical,
- *                             32-byte LE), polynomial y at d_coeffs + 32 y poly_stride bytes.  Workspace:
- *                             ozk_fr_poly_eval_workspace_bytes(npolys).
+ *   ozk_fr_poly_eval_dev      d_out[y] = sum_i c_yi r^i (canonical) for npolys polynomials of len coefficients each
+ *                             (32-byte LE, any 256-bit word: reduced mod r on load, like the rows of the KZG blocks
+ *                             below, whose callers pass theirs here), polynomial y at d_coeffs + 32 y poly_stride
+ *                             bytes; poly_stride is 0 (npolys = 1 only) or >= len, 1 <= npolys <= 65535, 1 <= len.
+ *                             r: 32-byte LE host value.  Workspace: ozk_fr_poly_eval_workspace_bytes(npolys).
  * A size function returns 0 for a shape it rejects; the entry points return OZK_E_INVALID for it (N not a power of two,
  * D < N, D > 2^28, a malformed program, a short workspace).  All calls are asynchronous on `stream`. */
 size_t ozk_bace_workspace_bytes(int32_t n, int32_t N, int32_t D, int32_t n_ops, int32_t n_slots, int32_t n_consts);

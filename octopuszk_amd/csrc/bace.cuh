@@ -170,7 +170,8 @@ __global__ void __launch_bounds__(BACE_WG) k_bace_circuit(BaceEval e) {
 // ---- polynomial evaluation at a point ----
 // Lane g of polynomial y (S = gridDim.x x 256 lanes per polynomial) runs Horner in r^S over the coefficients
 // c[g], c[g + S], ... (consecutive lanes read consecutive coefficients), multiplies by r^g, and the workgroup's sum
-// goes to partial[y gridDim.x + blockIdx.x]; k_bace_sum_partials adds each polynomial's partials.
+// goes to partial[y gridDim.x + blockIdx.x]; k_bace_sum_partials adds each polynomial's partials.  The coefficients are
+// any 256-bit words, reduced mod r on load (the KZG callers pass their rows as they got them); the partials are canonical.
 __global__ void __launch_bounds__(256) k_fr_poly_eval(const u32* __restrict__ c, size_t poly_cs, int len,
                                                       const u32* __restrict__ r_mont, u32* __restrict__ partial) {
   __shared__ u32 part[9 * 256];
@@ -181,9 +182,12 @@ __global__ void __launch_bounds__(256) k_fr_poly_eval(const u32* __restrict__ c,
   FrAcc acc = FrAcc(fe_zero<FrP>());
   if (g < (u32)len) {
     const BaceV rS = fe_pow_u32(r, S);
-    for (long long k = ((u32)len - 1 - g) / S; k >= 0; k--)   // plain: (acc rS R) / R
-      acc = FrAcc(reduce_to<32>(add(mul(acc, rS), fr_load<16>(cp + ((size_t)g + (size_t)k * S) * 8))));
-    acc = FrAcc(mul(acc, fe_pow_u32(r, g)));
+    // No reduction inside the loop: the product is below 18/16 r, a coefficient as loaded below 85/16 r, and the
+    // multiplier takes their sum (below 103/16 r) as it is.  The bounds are the types': a wider one does not compile.
+    Fe<FrP, 103> h = Fe<FrP, 103>(fe_zero<FrP>());
+    for (long long k = ((u32)len - 1 - g) / S; k >= 0; k--)   // plain: (h rS R) / R
+      h = add(mul(h, rS), fr_load<85>(cp + ((size_t)g + (size_t)k * S) * 8));
+    acc = FrAcc(mul(h, fe_pow_u32(r, g)));
   }
   const FrAcc sum = r1cs_block_sum(acc, part);
   if (threadIdx.x == 0) fr_store(canonical(sum), partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8);

@@ -175,7 +175,7 @@ def fr_fft(values, n, omega, out=None):
 
 def fr_poly_eval(coeffs, r, npolys=1):
     """sum_i c_yi r^i for npolys polynomials of equal length stored back to back in a uint8 CUDA tensor (32-byte LE
-    canonical coefficients): a CUDA tensor of npolys x 32 bytes."""
+    coefficients, any 256-bit word: reduced mod r on load): a CUDA tensor of npolys x 32 canonical bytes."""
     L = _lib.load()
     total = coeffs.numel() // 32
     if coeffs.numel() % 32 or total % npolys or total == 0:

@@ -1,5 +1,6 @@
-"""BACE on the GPU against tests/bace_ref.py: proof bytes, the HBM slot path, the verifier, getResult and the naive
-evaluator, a D = 2^18 consistency check, repeatability."""
+"""BACE on the GPU against tests/bace_ref.py: proof bytes, inputs taken mod r, the HBM slot path and the LDS slot caps,
+the interpreter past one launch of lanes, the verifier, getResult and the naive evaluator, a D = 2^18 consistency
+check, repeatability."""
 import os
 import random
 import secrets
@@ -23,10 +24,16 @@ def _ints(t):
     return [int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(len(raw) // 32)]
 
 
+def _dev_words(values):
+    """32-byte LE words on the device as written (a list of ints goes through the package mod r)"""
+    return torch.tensor(list(b"".join(v.to_bytes(32, "little") for v in values)), dtype=torch.uint8).cuda()
+
+
 def _check_against_oracle(circ, inputs, N):
     n = circ.input_size
-    D, proof = bace.Prover(circ, inputs, N).compute_proof()
-    D_ref, want = ref.prove(bu.to_ref(circ), inputs, n, N)
+    as_written = _dev_words(inputs) if any(v >= R for v in inputs) else inputs
+    D, proof = bace.Prover(circ, as_written, N).compute_proof()
+    D_ref, want = ref.prove(bu.to_ref(circ), [v % R for v in inputs], n, N)
     assert D == D_ref
     assert _ints(proof) == want
     return D, proof
@@ -59,10 +66,10 @@ def test_small_cases_bit_exact(case):
     elif case == "chain32":              # x^32: D = 32 N
         circ, N = bu.power_chain(5), 8
         inputs = _random_inputs(1, N, 4)
-    else:                                # inputs 0, 1, r - 1 (and r, 2^256 - 1: taken mod r)
+    else:                                # inputs 0, 1, r - 1 and r, r + 1, 2^256 - 1: taken mod r
         y = bace.InputGate(1)
         circ, N = bace.Circuit([x, y], (x * y) * (x + y)), 4
-        inputs = [0, 1, R - 1, 0, 1, R - 1, R - 1, R - 1]
+        inputs = [0, 1, R - 1, R, R + 1, (1 << 256) - 1, R - 1, R - 1]
     _check_against_oracle(circ, inputs, N)
 
 
@@ -98,12 +105,44 @@ def test_hbm_slot_path_same_bytes():
     L = _lib.load()
     old = os.environ.get("OZK_BACE_LDS_SLOTS")
     try:
-        for cap in ("0", "3"):
+        for cap in ("0", "3", "28", "64"):   # all in HBM, three in LDS, the most LDS a workgroup may take, clamped to it
             os.environ["OZK_BACE_LDS_SLOTS"] = cap
             L.ozk_tuning_reload()
             _, b = bace.Prover(circ, inputs, 32).compute_proof()
             assert torch.equal(a, b)
             assert _ints(bace.NaiveEvaluator(circ, inputs, 32).get_result()) == ref.naive(bu.to_ref(circ), inputs, 6, 32)
+    finally:
+        if old is None:
+            os.environ.pop("OZK_BACE_LDS_SLOTS", None)
+        else:
+            os.environ["OZK_BACE_LDS_SLOTS"] = old
+        L.ozk_tuning_reload()
+
+
+def test_interpreter_past_one_launch_of_lanes():
+    """65536 + 65 rows: a launch has 65536 lanes, and 65 of them (one whole wave and one lane) take a second trip of the
+    loop over points; with three slots in LDS the spilled slots of that trip are indexed by the lane, not the row"""
+    rows, n = 65536 + 65, 2
+    circ = bu.random_dag(n, 70, 4, seed=25, const_rate=0.05)        # (34 of its gates reach the result)
+    prog, n_slots, _ = circ.compile()
+    assert n_slots > 3 and 30 <= prog.shape[0] <= 60
+    inputs = _random_inputs(n, rows, 24)
+    for k, row in enumerate((0, 65535, 65536, rows - 1)):          # written as x + k r, k = 2 .. 5 where it fits
+        for j in range(n):
+            v, m = inputs[n * row + j], 2 + k
+            while v + m * R >= 1 << 256:
+                m -= 1
+            inputs[n * row + j] = v + m * R
+    assert all(inputs[n * row] >= 2 * R for row in (0, 65535, 65536, rows - 1))
+    want = [circ.compute(inputs[n * i:n * i + n]) for i in range(rows)]
+    d_inputs = _dev_words(inputs)
+    assert _ints(bace.NaiveEvaluator._evaluate(circ, d_inputs, rows)) == want
+    L = _lib.load()
+    old = os.environ.get("OZK_BACE_LDS_SLOTS")
+    try:
+        os.environ["OZK_BACE_LDS_SLOTS"] = "3"
+        L.ozk_tuning_reload()
+        assert _ints(bace.NaiveEvaluator._evaluate(circ, d_inputs, rows)) == want
     finally:
         if old is None:
             os.environ.pop("OZK_BACE_LDS_SLOTS", None)

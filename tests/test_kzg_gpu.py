@@ -9,6 +9,8 @@ import torch
 
 import kzg_ref as kr
 import srs_gpu_util as u
+from fr_gpu_util import evals_open as _evals_open
+from fr_gpu_util import poly_open as _poly_open
 from oracle import bn254 as o
 
 pytestmark = pytest.mark.gpu
@@ -40,25 +42,6 @@ def _dev_ints(values):
 
 def _ws(nbytes):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device="cuda")
-
-
-def _poly_open(coeffs, npolys, length, stride, points, quot_stride):
-    """the entry point on host ints: coeffs a flat list laid out at `stride`; -> (rows of the quotient, values, the
-    bytes of the gaps between quotient rows)"""
-    L = _lib()
-    d_c, d_p = _dev_ints(coeffs), _dev_ints(points)
-    quot = torch.full((npolys * quot_stride * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-    vals = torch.full((npolys * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-    wsb = L.ozk_fr_poly_open_workspace_bytes(npolys, length)
-    assert wsb > 0
-    ws = _ws(wsb)
-    rc = L.ozk_fr_poly_open_dev(_ptr(d_c), npolys, length, stride, _ptr(d_p), _ptr(quot), quot_stride, _ptr(vals),
-                                _ptr(ws), wsb, _stream())
-    assert rc == 0, L.ozk_last_error()
-    q = kr.ints(u.host(quot))
-    rows = [q[y * quot_stride:y * quot_stride + length] for y in range(npolys)]
-    gaps = [v for y in range(npolys) for v in q[y * quot_stride + length:(y + 1) * quot_stride]]
-    return rows, kr.ints(u.host(vals)), gaps
 
 
 LENGTHS = [1, 2, 3, T - 1, T, T + 1, 2 * T + 1, 3 * T + 5]
@@ -105,22 +88,6 @@ def test_poly_open_across_the_chunk_of_tile_carries():
     got_q, got_y, _ = _poly_open(p, 1, length, length, [z], length)
     q, y = kr.div_linear(p, z)
     assert got_y == [y] and got_q[0] == q
-
-
-def _evals_open(evals, npolys, n, stride, omega, points, quot_stride, expect=0):
-    L = _lib()
-    d_f, d_p = _dev_ints(evals), _dev_ints(points)
-    quot = torch.full((npolys * quot_stride * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-    vals = torch.full((npolys * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-    wsb = L.ozk_fr_evals_open_workspace_bytes(npolys, n)
-    assert wsb > 0
-    ws = _ws(wsb)
-    om = ctypes.create_string_buffer(kr.le(omega), 32)
-    rc = L.ozk_fr_evals_open_dev(_ptr(d_f), npolys, n, stride, ctypes.cast(om, ctypes.c_void_p), _ptr(d_p), _ptr(quot),
-                                 quot_stride, _ptr(vals), _ptr(ws), wsb, _stream())
-    assert rc == expect, L.ozk_last_error()
-    q = kr.ints(u.host(quot))
-    return [q[y * quot_stride:y * quot_stride + n] for y in range(npolys)], kr.ints(u.host(vals)), quot, vals
 
 
 @pytest.mark.parametrize("n", [2, 4, 64, T, 2 * T, 4 * T])

@@ -10,6 +10,7 @@ import torch
 import kzg_multi_ref as km
 import kzg_ref as kr
 import srs_gpu_util as u
+from fr_gpu_util import poly_eval_set as _eval_set
 from oracle import bn254 as o
 
 pytestmark = pytest.mark.gpu
@@ -122,20 +123,6 @@ def test_rows_combine_groups_of_one_group_is_rows_combine(length):
 
 
 # ---------------------------------------------------------------------------- the values at a set
-def _eval_set(flat, npolys, length, stride, t, points):
-    """the entry point on host ints -> (the values, their bytes)"""
-    L = _lib()
-    d_c = _dev_ints(flat)
-    keep, p_host = _host_ints(points)
-    vals = torch.full((npolys * t * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-    wsb = L.ozk_fr_poly_eval_set_workspace_bytes(npolys, length, t)
-    assert wsb > 0
-    ws = _ws(wsb)
-    rc = L.ozk_fr_poly_eval_set_dev(_ptr(d_c), npolys, length, stride, t, p_host, _ptr(vals), _ptr(ws), wsb, _stream())
-    assert rc == 0, L.ozk_last_error()
-    return kr.ints(u.host(vals)), u.host(vals)
-
-
 def _open_set_values(flat, npolys, length, stride, t, points):
     """the value bytes ozk_fr_poly_open_set_dev writes on the same inputs"""
     L = _lib()

@@ -10,6 +10,8 @@ import torch
 import kzg_ref as kr
 import kzg_set_ref as ks
 import srs_gpu_util as u
+from fr_gpu_util import evals_open_set as _evals_open_set
+from fr_gpu_util import poly_open_set as _poly_open_set
 from oracle import bn254 as o
 
 pytestmark = pytest.mark.gpu
@@ -57,26 +59,6 @@ def _points(rng, t, special=()):
         if z not in out:
             out.append(z)
     return out
-
-
-def _poly_open_set(coeffs, npolys, length, stride, t, points, quot_stride):
-    """the entry point on host ints: coeffs a flat list laid out at `stride`, points npolys t of them; -> (rows of the
-    quotient, values, the elements of the gaps between quotient rows)"""
-    L = _lib()
-    d_c = _dev_ints(coeffs)
-    keep, p_host = _host_ints(points)
-    quot = torch.full((npolys * quot_stride * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-    vals = torch.full((npolys * t * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-    wsb = L.ozk_fr_poly_open_set_workspace_bytes(npolys, length, t)
-    assert wsb > 0
-    ws = _ws(wsb)
-    rc = L.ozk_fr_poly_open_set_dev(_ptr(d_c), npolys, length, stride, t, p_host, _ptr(quot), quot_stride, _ptr(vals),
-                                    _ptr(ws), wsb, _stream())
-    assert rc == 0, L.ozk_last_error()
-    q = kr.ints(u.host(quot))
-    rows = [q[y * quot_stride:y * quot_stride + length] for y in range(npolys)]
-    gaps = [v for y in range(npolys) for v in q[y * quot_stride + length:(y + 1) * quot_stride]]
-    return rows, kr.ints(u.host(vals)), gaps, quot, vals
 
 
 def _poly_open(coeffs, length, z):
@@ -134,23 +116,6 @@ def test_poly_open_set_across_the_chunk_of_tile_carries():
     got_q, got_y, _, _, _ = _poly_open_set(p, 1, length, length, 2, pts, length)
     q, values = ks.div_set(p, pts)
     assert got_y == values and got_q[0] == q
-
-
-def _evals_open_set(evals, npolys, n, stride, omega, t, points, quot_stride, expect=0):
-    L = _lib()
-    d_f = _dev_ints(evals)
-    keep, p_host = _host_ints(points)
-    quot = torch.full((npolys * quot_stride * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-    vals = torch.full((npolys * t * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-    wsb = L.ozk_fr_evals_open_set_workspace_bytes(npolys, n, t)
-    assert wsb > 0
-    ws = _ws(wsb)
-    om = ctypes.create_string_buffer(kr.le(omega), 32)
-    rc = L.ozk_fr_evals_open_set_dev(_ptr(d_f), npolys, n, stride, ctypes.cast(om, ctypes.c_void_p), t, p_host, _ptr(quot),
-                                     quot_stride, _ptr(vals), _ptr(ws), wsb, _stream())
-    assert rc == expect, L.ozk_last_error()
-    q = kr.ints(u.host(quot))
-    return [q[y * quot_stride:y * quot_stride + n] for y in range(npolys)], kr.ints(u.host(vals)), quot, vals
 
 
 @pytest.mark.parametrize("n", [2, 4, 64, T, 2 * T, 4 * T])

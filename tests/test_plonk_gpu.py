@@ -10,6 +10,9 @@ import torch
 import kzg_ref as kr
 import plonk_ref as pm
 import srs_gpu_util as u
+from fr_gpu_util import perm_product as _perm_product
+from fr_gpu_util import plonk_quotient as _quotient
+from fr_gpu_util import rows_coset as _rows_coset
 from oracle import bn254 as o
 
 pytestmark = pytest.mark.gpu
@@ -38,10 +41,6 @@ def _stream():
     return ctypes.c_void_p(int(torch.cuda.current_stream().cuda_stream))
 
 
-def _dev_ints(values):
-    return u.dev(b"".join(kr.le(v) for v in values))
-
-
 def _host_ints(values):
     buf = ctypes.create_string_buffer(b"".join(kr.le(v) for v in values), 32 * len(values))
     return buf, ctypes.cast(buf, ctypes.c_void_p)
@@ -59,25 +58,6 @@ def _flat(rows, stride, fill=7):
 
 
 # ---------------------------------------------------------------------------- rows by powers
-def _rows_coset(flat, k, length, stride, s, c, out_len, out_stride, in_place=False):
-    """the entry point on host ints -> (the output rows, the elements of the gaps between them)"""
-    L = _lib()
-    d_r = _dev_ints(flat)
-    keep_s, p_s = _host_ints([s])
-    keep_c, p_c = _host_ints([c])
-    out = d_r if in_place else torch.full((k * out_stride * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-    wsb = L.ozk_fr_rows_coset_workspace_bytes(k, length, out_len)
-    assert wsb > 0
-    ws = _ws(wsb)
-    rc = L.ozk_fr_rows_coset_dev(_ptr(d_r), k, length, stride, p_s, p_c, _ptr(out), out_len, out_stride, _ptr(ws), wsb,
-                                 _stream())
-    assert rc == 0, L.ozk_last_error()
-    got = kr.ints(u.host(out))
-    rows = [got[y * out_stride:y * out_stride + out_len] for y in range(k)]
-    gaps = [v for y in range(k) for v in got[y * out_stride + out_len:(y + 1) * out_stride]]
-    return rows, gaps
-
-
 @pytest.mark.parametrize("k", [1, 3])
 @pytest.mark.parametrize("length", [1, 255, T, T + 1, 2 * T + 1])
 def test_rows_coset_matches_the_model(k, length):
@@ -100,24 +80,6 @@ def test_rows_coset_matches_the_model(k, length):
 
 
 # ---------------------------------------------------------------------------- the grand product
-def _perm_product(wires, sigma, length, stride, omega, beta, gamma):
-    """the entry point on host ints -> (z, the elements behind it, the total, the count)"""
-    L = _lib()
-    d_w, d_s = _dev_ints(_flat(wires, stride)), _dev_ints(_flat(sigma, stride))
-    keep = [_host_ints(v) for v in ([omega], list(pm.KS), [beta], [gamma])]
-    z = torch.full(((length + 2) * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-    tail = torch.full((64,), SENTINEL, dtype=torch.uint8, device="cuda")
-    wsb = L.ozk_fr_perm_product_workspace_bytes(length)
-    assert wsb > 0
-    ws = _ws(wsb)
-    rc = L.ozk_fr_perm_product_dev(_ptr(d_w), _ptr(d_s), length, stride, keep[0][1], keep[1][1], keep[2][1], keep[3][1],
-                                   _ptr(z), _ptr(tail), _ptr(tail[32:]), _ptr(ws), wsb, _stream())
-    assert rc == 0, L.ozk_last_error()
-    got, t = kr.ints(u.host(z)), u.host(tail)
-    assert t[36:] == bytes([SENTINEL]) * 28
-    return got[:length], got[length:], int.from_bytes(t[:32], "little"), int.from_bytes(t[32:36], "little", signed=True)
-
-
 def _random_rows(rng, length):
     return [[rng.getrandbits(253) for _ in range(length)] for _ in range(3)]
 
@@ -206,20 +168,6 @@ def _quotient_inputs(n, break_gate=False):
     wit = [kr.intt(col, omega) for col in wires] + [kr.intt(zs, omega), kr.intt(pm.pi_evals(n, public), omega)]
     key = pm.key_polys(circuit) + [[pm.inv(n)] * n, [0, 1] + [0] * (n - 2)]
     return _coset_rows(wit, n), _coset_rows(key, n), (alpha, beta, gamma)
-
-
-def _quotient(wit, key, n, challenges_, wit_stride, key_stride):
-    L = _lib()
-    alpha, beta, gamma = challenges_
-    d_w, d_k = _dev_ints(_flat(wit, wit_stride)), _dev_ints(_flat(key, key_stride))
-    keep = [_host_ints(v) for v in ([alpha], [beta], [gamma], list(pm.KS), pm.zh_inverses(n))]
-    out = torch.full(((4 * n + 2) * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-    rc = L.ozk_plonk_quotient_dev(_ptr(d_w), wit_stride, _ptr(d_k), key_stride, n, keep[0][1], keep[1][1], keep[2][1],
-                                  keep[3][1], keep[4][1], _ptr(out), _stream())
-    assert rc == 0, L.ozk_last_error()
-    got = kr.ints(u.host(out))
-    assert got[4 * n:] == [SENTINEL_INT] * 2
-    return got[:4 * n]
 
 
 @pytest.mark.parametrize("n", [2, 4, 256, 1024])

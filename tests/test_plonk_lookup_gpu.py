@@ -11,6 +11,9 @@ import kzg_ref as kr
 import plonk_lookup_ref as lm
 import plonk_ref as pm
 import srs_gpu_util as u
+from fr_gpu_util import lookup_counts as _counts
+from fr_gpu_util import lookup_sum as _sum
+from fr_gpu_util import plonk_quotient as _plonk_quotient
 from oracle import bn254 as o
 
 pytestmark = pytest.mark.gpu
@@ -40,10 +43,6 @@ def _stream():
     return ctypes.c_void_p(int(torch.cuda.current_stream().cuda_stream))
 
 
-def _dev_ints(values):
-    return u.dev(b"".join(kr.le(v) for v in values))
-
-
 def _host_ints(values):
     buf = ctypes.create_string_buffer(b"".join(kr.le(v) for v in values), 32 * len(values))
     return buf, ctypes.cast(buf, ctypes.c_void_p)
@@ -53,49 +52,11 @@ def _ws(nbytes):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device="cuda")
 
 
-def _flat(rows, stride, fill=7):
-    out = []
-    for row in rows:
-        out += list(row) + [fill] * (stride - len(row))
-    return out
-
-
 def _columns(table):
     return [[row[j] for row in table] for j in range(3)]
 
 
 # ---------------------------------------------------------------------------- index and counts
-def _index(d_table, n_rows, table_stride):
-    L = _lib()
-    nbytes = L.ozk_plonk_lookup_index_bytes(n_rows)
-    cap = nbytes // 4
-    assert cap >= 2 * n_rows and cap & (cap - 1) == 0 and (cap < 4 * n_rows or cap == 2)
-    index = torch.full((nbytes + 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-    rc = L.ozk_plonk_lookup_index_dev(_ptr(d_table), n_rows, table_stride, _ptr(index), nbytes, _stream())
-    assert rc == 0, L.ozk_last_error()
-    return index, nbytes
-
-
-def _counts(wires, qk, table, m_len, stride=None, table_stride=None):
-    """the two entry points on host ints -> (m, the elements behind it, missing, first_missing, the index's slots)"""
-    L = _lib()
-    length, n_rows = len(qk), len(table)
-    stride, table_stride = stride or length, table_stride or n_rows
-    d_w, d_q = _dev_ints(_flat(wires, stride)), _dev_ints(qk)
-    d_t = _dev_ints(_flat(_columns(table), table_stride))
-    index, nbytes = _index(d_t, n_rows, table_stride)
-    m = torch.full(((m_len + 2) * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-    tail = torch.full((16,), SENTINEL, dtype=torch.uint8, device="cuda")
-    rc = L.ozk_plonk_lookup_counts_dev(_ptr(d_w), _ptr(d_q), length, stride, _ptr(d_t), n_rows, table_stride, _ptr(index),
-                                       nbytes, _ptr(m), m_len, _ptr(tail), _ptr(tail[4:]), _stream())
-    assert rc == 0, L.ozk_last_error()
-    got, t, slots = kr.ints(u.host(m)), u.host(tail), u.host(index)
-    assert t[8:] == bytes([SENTINEL]) * 8 and slots[nbytes:] == bytes([SENTINEL]) * 32
-    slots = [int.from_bytes(slots[i:i + 4], "little") for i in range(0, nbytes, 4)]
-    return (got[:m_len], got[m_len:], int.from_bytes(t[:4], "little", signed=True),
-            int.from_bytes(t[4:8], "little", signed=True), slots)
-
-
 def _special_tuples(rng):
     """one tuple and its near misses: word 7 of the third column, word 0 of the first, two column permutations"""
     x = [rng.getrandbits(220) for _ in range(3)]
@@ -175,24 +136,6 @@ def test_two_runs_give_the_same_bytes():
 
 
 # ---------------------------------------------------------------------------- the running sum
-def _sum(wires, key4, m, length, stride, key_stride, eta, theta):
-    """the entry point on host ints -> (S, the elements behind it, the total, the count)"""
-    L = _lib()
-    d_w, d_k, d_m = _dev_ints(_flat(wires, stride)), _dev_ints(_flat(key4, key_stride)), _dev_ints(m)
-    keep = [_host_ints([eta]), _host_ints([theta])]
-    s = torch.full(((length + 2) * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-    tail = torch.full((64,), SENTINEL, dtype=torch.uint8, device="cuda")
-    wsb = L.ozk_plonk_lookup_sum_workspace_bytes(length)
-    assert wsb > 0
-    ws = _ws(wsb)
-    rc = L.ozk_plonk_lookup_sum_dev(_ptr(d_w), stride, _ptr(d_k), key_stride, _ptr(d_m), length, keep[0][1], keep[1][1],
-                                    _ptr(s), _ptr(tail), _ptr(tail[32:]), _ptr(ws), wsb, _stream())
-    assert rc == 0, L.ozk_last_error()
-    got, t = kr.ints(u.host(s)), u.host(tail)
-    assert t[36:] == bytes([SENTINEL]) * 28
-    return got[:length], got[length:], int.from_bytes(t[:32], "little"), int.from_bytes(t[32:36], "little", signed=True)
-
-
 def _consistent(length, seed, n_rows=None):
     """(wires, the rows qK, T1, T2, T3, m) of `length` rows that look up a table of n_rows, padded to `length`"""
     rng = random.Random(seed)
@@ -302,21 +245,7 @@ def _quotient_inputs(n, spoil=None):
 
 
 def _quotient(wit, key, n, ch, wit_stride, key_stride, vanilla=False):
-    L = _lib()
-    alpha, beta, gamma, eta, theta = ch
-    d_w, d_k = _dev_ints(_flat(wit, wit_stride)), _dev_ints(_flat(key, key_stride))
-    keep = [_host_ints(v) for v in ([alpha], [beta], [gamma], list(pm.KS), pm.zh_inverses(n), [eta], [theta])]
-    out = torch.full(((4 * n + 2) * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-    if vanilla:
-        rc = L.ozk_plonk_quotient_dev(_ptr(d_w), wit_stride, _ptr(d_k), key_stride, n, *[k[1] for k in keep[:5]], _ptr(out),
-                                      _stream())
-    else:
-        rc = L.ozk_plonk_quotient_lookup_dev(_ptr(d_w), wit_stride, _ptr(d_k), key_stride, n, *[k[1] for k in keep],
-                                             _ptr(out), _stream())
-    assert rc == 0, L.ozk_last_error()
-    got = kr.ints(u.host(out))
-    assert got[4 * n:] == [SENTINEL_INT] * 2
-    return got[:4 * n]
+    return _plonk_quotient(wit, key, n, ch[:3] if vanilla else ch, wit_stride, key_stride)
 
 
 def _top_quarter(got, n):

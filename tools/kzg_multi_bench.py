@@ -9,7 +9,10 @@
     verify_set_combined calls that cover the same statement, by wall clock with a synchronise, and the lone G1 MSM of
     the same n for scale.
 
-    python tools/kzg_multi_bench.py [--log 20] [--reps 5] [--k 16]
+    python tools/kzg_multi_bench.py [--log 20] [--reps 5] [--k 16] [--parts combine,eval,protocol]
+
+--parts names the measurements to make (all three by default); (b) reports the three alternated rounds beside the
+middle one.
 
 The string is built from a known tau, so every opening verifies.
 """
@@ -44,12 +47,25 @@ def _points(t, salt=0):
     return [(0x123456789abcdef0123456789 * (i + 1) + salt) % FR for i in range(t)]
 
 
-def run(log, reps, k):
+PARTS = ("combine", "eval", "protocol")
+
+
+def run(log, reps, k, parts=PARTS):
     n = 1 << log
     L = _lib.load()
     rows = kb._random_rows(k, n, log)
     res = {"n": n, "k": k}
 
+    if "combine" in parts:
+        _combine(L, rows, k, n, reps, res)
+    if "eval" in parts:
+        _eval(L, rows, k, n, reps, res)
+    if "protocol" in parts:
+        _protocol(rows, k, n, reps, res)
+    return res
+
+
+def _combine(L, rows, k, n, reps, res):
     # (a) the grouped combine
     group_of = [i % 2 for i in range(k)]
     weights = [(0xabcdef0123456789 * (i + 3)) % FR for i in range(k)]
@@ -76,6 +92,8 @@ def run(log, reps, k):
                       "rows_combine_groups_rounds_ms": a_ms, "two_rows_combine_zero_weights_rounds_ms": b_ms,
                       "bytes_read_grouped": k * n * 32, "bytes_read_zero_weights": 2 * k * n * 32}
 
+
+def _eval(L, rows, k, n, reps, res):
     # (b) the values
     res["eval"] = {}
     d_val = torch.empty(k * 8 * 32, dtype=torch.uint8, device="cuda")
@@ -100,8 +118,11 @@ def run(log, reps, k):
         for _ in range(3):
             a_ms.append(kb._event_ms(eval_set, reps))
             b_ms.append(kb._event_ms(eval_calls, reps))
-        res["eval"][str(t)] = {"poly_eval_set_ms": sorted(a_ms)[1], "t_poly_eval_calls_ms": sorted(b_ms)[1]}
+        res["eval"][str(t)] = {"poly_eval_set_ms": sorted(a_ms)[1], "t_poly_eval_calls_ms": sorted(b_ms)[1],
+                               "t_poly_eval_calls_rounds_ms": b_ms}
 
+
+def _protocol(rows, k, n, reps, res):
     # (c) the protocol
     s = _String(n // 2)
     ck = kzg.CommitKey.from_srs(s, n)
@@ -138,7 +159,6 @@ def run(log, reps, k):
                     "verify_key": len(vk.to_bytes()), "set_verify_key_t2": len(svk.to_bytes()),
                     "statement_values": values}
     res["pairings"] = {"verify_multi": 2, "two_verify_set_combined": 4}
-    return res
 
 
 def main():
@@ -146,9 +166,13 @@ def main():
     ap.add_argument("--log", type=int, default=20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--k", type=int, default=16)
+    ap.add_argument("--parts", default=",".join(PARTS))
     a = ap.parse_args()
+    parts = tuple(a.parts.split(","))
+    if not parts or any(p not in PARTS for p in parts):
+        ap.error("--parts takes a comma-separated subset of %s" % ", ".join(PARTS))
     torch.cuda.set_device(0)
-    out = {"bench": "kzg_multi", "device": torch.cuda.get_device_name(0), "reps": a.reps, "result": run(a.log, a.reps, a.k)}
+    out = {"bench": "kzg_multi", "device": torch.cuda.get_device_name(0), "reps": a.reps, "result": run(a.log, a.reps, a.k, parts)}
     print(json.dumps(out))
 
 
