@@ -288,8 +288,20 @@ int ozk_fixed_double_batch_msm_host(int32_t outerc1, int32_t window_size1, int32
  * in: (n+1) x 32 B LE, element n is the multiplier; out: n x 64 B BE, x_i * b mod r. */
 int ozk_field_batch_mul_host(const uint8_t* in, int32_t n, int32_t task_id, uint8_t* out);
 
+/* Scalars are any 256-bit words.  When the caller's windows cover a whole Fr scalar (outerc * window_size >= 254) the
+ * result is (s mod r) B in every form of the kernels; with fewer bits of windows it is (s mod 2^(outerc *
+ * window_size)) B for the word as written, the reference's rule (FixedBaseMSM.java:146-164). */
 size_t ozk_fixed_batch_msm_workspace_bytes(int32_t outerc, int32_t window_size, int32_t n,
                                            int32_t bn_type);
+/* The plan a call of this shape runs under the tuning knobs in force, for tests and profiles (host only, no device
+ * work): *form = 0 plain windows over the word (outerc * window_size < 254, or OZK_MSM_GLV=0), 1 GLV split with the
+ * Jacobian gather-add (OZK_FB_AFFINE=0), 2 GLV split over affine table records (the default); *table_window = the
+ * window bits of the table that is built (the caller's in the plain form; in the GLV forms the cost model's choice
+ * or OZK_FB_WS, never more than the caller's: a forced value outside [1, window_size] gives window_size);
+ * *windows = the windows gathered per digit string (outerc, or ceil(128 / *table_window)).  Any of the three
+ * pointers may be null.  OZK_E_INVALID for a shape the entry points reject. */
+int ozk_fixed_batch_msm_plan(int32_t outerc, int32_t window_size, int32_t n, int32_t* form, int32_t* table_window,
+                             int32_t* windows);
 int ozk_fixed_batch_msm_dev(int32_t outerc, int32_t window_size, int32_t n, const void* d_base,
                             const void* d_scalars, int32_t bn_type, void* d_out,
                             void* d_workspace, size_t workspace_bytes, void* stream);

@@ -86,6 +86,11 @@ __global__ void __launch_bounds__(256) k_fb_main(const u32* __restrict__ scalars
   const uint4 a = sp[0], b = sp[1];
   s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w;
   s[4] = b.x; s[5] = b.y; s[6] = b.z; s[7] = b.w;
+  // windows that cover a whole Fr scalar: the word is reduced mod r first, as the GLV forms do (glv_decompose), so
+  // that every form returns (s mod r) B for every 256-bit word; with 254 or 255 bits of windows the bits of a word
+  // >= 2^(outerc ws) would be dropped instead.  Fewer bits: the truncation of the word as written
+  // (FixedBaseMSM.java:146-164).
+  if (outerc * ws >= 254) reduce_mod_r(s);
   Jac<CV> acc = jac_infinity<CV>();
   for (int w = 0; w < outerc; w++) {
     // digit = bits [w*ws, w*ws + ws) (testBit loop, FixedBaseMSM.java:153-159); ws may exceed 16
@@ -548,6 +553,18 @@ size_t ozk_fixed_batch_msm_workspace_bytes(int32_t outerc, int32_t ws, int32_t n
   if (fb_check_args(outerc, ws, n)) return 0;
   return bn_type == OZK_G1 ? fb_layout<G1Cfg>(outerc, ws, n, nullptr, 0).bytes
                            : fb_layout<G2Cfg>(outerc, ws, n, nullptr, 0).bytes;
+}
+
+// the plan of a call of this shape under the knobs in force (fb_choose): host only, no device work
+int ozk_fixed_batch_msm_plan(int32_t outerc, int32_t ws, int32_t n, int32_t* form, int32_t* table_window,
+                             int32_t* windows) {
+  const int rc = fb_check_args(outerc, ws, n);
+  if (rc) return rc;
+  const FbPlan fp = fb_choose(outerc, ws, n);
+  if (form) *form = fp.affine ? 2 : fp.glv ? 1 : 0;
+  if (table_window) *table_window = fp.wt;
+  if (windows) *windows = fp.oc;
+  return OZK_OK;
 }
 
 int ozk_fixed_batch_msm_dev(int32_t outerc, int32_t ws, int32_t n, const void* d_base, const void* d_scalars,

@@ -63,6 +63,8 @@ _SIGS = {
     "ozk_fixed_double_batch_msm_host": (ctypes.c_int, [i32] * 9 + [vp, vp, vp, i32, vp]),
     "ozk_field_batch_mul_host": (ctypes.c_int, [vp, i32, i32, vp]),
     "ozk_fixed_batch_msm_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "ozk_fixed_batch_msm_plan": (ctypes.c_int, [i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32),
+                                                ctypes.POINTER(i32)]),
     "ozk_fixed_batch_msm_dev": (ctypes.c_int, [i32, i32, i32, vp, vp, i32, vp, vp, sz, vp]),
     "ozk_field_batch_mul_dev": (ctypes.c_int, [vp, i32, vp, vp]),
     "ozk_fixed_batch_msm_compact_dev": (ctypes.c_int, [i32, i32, i32, vp, vp, i32, vp, vp, sz, vp]),

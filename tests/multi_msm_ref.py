@@ -132,3 +132,32 @@ def edge_scalars():
             0xfedcba9876543210, r - 0xfedcba9876543210,          # the Fp.random shapes: 64 bits, r minus 64 bits
             (carry_k - carry_k * LAM) % r,                       # halves (+carry_k, -carry_k): opposite signs, all carries
             (3 + (1 << 100) * LAM) % r]
+
+
+def carry_patterns(ws):
+    """(never, always): magnitudes whose raw digit is `half` in every window wholly below bit 125 (the recoding never
+    carries there) and `half + 1` in every such window (it always carries), as test_multi_msm_cpu.test_recode_exact
+    builds them, with bit 125 set above: a half below 2^124.4 is not sure to come back from the split as written"""
+    half = 1 << (ws - 1)
+    whole = 125 // ws
+    return tuple(sum(d << (ws * w) for w in range(whole)) | 1 << 125 for d in (half, half + 1))
+
+
+def carry_pattern_scalars(ws):
+    """[(s, k1, k2)]: s = k1 + k2 LAM mod r with the patterns of carry_patterns(ws) as halves, each in both places"""
+    never, always = carry_patterns(ws)
+    return [((k1 + k2 * LAM) % o.R, k1, k2) for k1, k2 in ((never, -always), (always, -never), (never, -never),
+                                                           (always, -always))]
+
+
+def assert_carry_patterns_realised(ws):
+    """the split gives back the halves the scalars were built from, and their recoding is what the names say"""
+    half = 1 << (ws - 1)
+    whole = 125 // ws
+    never, always = carry_patterns(ws)
+    d, c = recode(never, ws)
+    assert c == 0 and d[:whole] == [half] * whole
+    d, c = recode(always, ws)
+    assert c == 0 and d[0] == half + 1 - (1 << ws) and d[1:whole] == [half + 2 - (1 << ws)] * (whole - 1)
+    for s, k1, k2 in carry_pattern_scalars(ws):
+        assert glv_split(s) == (k1, k2), (ws, hex(s))

@@ -71,6 +71,17 @@ def test_recode_exact(ws):
         assert sum(d << (ws * w) for w, d in enumerate(digits)) == m
 
 
+@pytest.mark.parametrize("ws", [4, 5, 6, 7, 8])
+def test_carry_patterns_come_back_from_the_split(ws):
+    """the scalars test_multi_msm_windows_gpu.py builds from the never-carries / always-carries magnitudes: the split
+    gives back exactly those halves, and the model agrees with the naive MSM on them"""
+    ref.assert_carry_patterns_realised(ws)
+    bases = _bases(2, 13)
+    rows = [[s, 0] for s, _, _ in ref.carry_pattern_scalars(ws)][:2] + [[s for s, _, _ in ref.carry_pattern_scalars(ws)][2:]]
+    for row, g in zip(rows, ref.model_msm(rows, bases, ws)):
+        assert g == _naive(row, bases), (ws, row)
+
+
 @pytest.mark.parametrize("ws", [8, 7, 5])
 def test_model_matches_naive_msm_on_edge_scalars(ws):
     bases = _bases(3, 11)
