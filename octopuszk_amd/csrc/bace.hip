@@ -1,7 +1,7 @@
 // BACE on the GPU: Williams' Merlin-Arthur proof for batch arithmetic-circuit evaluation (the reference's bace/
 // package: Prover.computeProof, Verifier.verifyProof / getResult, NaiveEvaluator.getResult, Common.getInputPolynomials).
-// Included at the end of fft.hip: it reuses that unit's twiddle plans (domain_tables), its tiled pass kernel (fft_core,
-// batched through PassArgs::in_cs / out_cs) and its block sum (r1cs_block_sum).  DESIGN.md section 11.
+// A unit of its own: from fft.hip it takes the twiddle plans (domain_tables) and the tiled transform (fft_core, batched
+// through in_cs / out_cs), declared in fft_plan.h; the evaluation at a point is fr_tables.cuh's.  DESIGN.md section 11.
 //
 //   n inputs per instance, N instances (a power of two), circuit degree deg, D = lowestPowerOfTwo(deg N).
 //   prove:  beta_j = iFFT_N(column j); evaluations beta_j(omega_D^k) = FFT_D(beta_j zero-padded); R_k = C(beta(omega_D^k));
@@ -10,6 +10,9 @@
 //   result: FFT_D(proof) at every (D/N)-th point = FFT_N(proof folded mod z^N - 1).
 //
 // Every value in HBM is 32 bytes LE, plain (non-Montgomery) and canonical unless stated otherwise.
+#include "fft_plan.h"
+#include "fr_tables.cuh"
+
 namespace ozk {
 
 constexpr int BACE_LDS_FFT_MAX = 2048;      // transforms up to this size: one workgroup per column, column in LDS (64 KiB)
@@ -165,40 +168,6 @@ __global__ void __launch_bounds__(BACE_WG) k_bace_circuit(BaceEval e) {
     }
     fr_store(canonical(mul(last, ko)), e.out + (size_t)p * 8);   // Montgomery x plain = plain
   }
-}
-
-// ---- polynomial evaluation at a point ----
-// Lane g of polynomial y (S = gridDim.x x 256 lanes per polynomial) runs Horner in r^S over the coefficients
-// c[g], c[g + S], ... (consecutive lanes read consecutive coefficients), multiplies by r^g, and the workgroup's sum
-// goes to partial[y gridDim.x + blockIdx.x]; k_bace_sum_partials adds each polynomial's partials.  The coefficients are
-// any 256-bit words, reduced mod r on load (the KZG callers pass their rows as they got them); the partials are canonical.
-__global__ void __launch_bounds__(256) k_fr_poly_eval(const u32* __restrict__ c, size_t poly_cs, int len,
-                                                      const u32* __restrict__ r_mont, u32* __restrict__ partial) {
-  __shared__ u32 part[9 * 256];
-  const u32 S = gridDim.x * 256u;
-  const u32 g = blockIdx.x * 256u + threadIdx.x;
-  const u32* cp = c + (size_t)blockIdx.y * poly_cs;
-  const auto r = ElemTraits<Fe<FrP, 16>>::load(r_mont);
-  FrAcc acc = FrAcc(fe_zero<FrP>());
-  if (g < (u32)len) {
-    const BaceV rS = fe_pow_u32(r, S);
-    // No reduction inside the loop: the product is below 18/16 r, a coefficient as loaded below 85/16 r, and the
-    // multiplier takes their sum (below 103/16 r) as it is.  The bounds are the types': a wider one does not compile.
-    Fe<FrP, 103> h = Fe<FrP, 103>(fe_zero<FrP>());
-    for (long long k = ((u32)len - 1 - g) / S; k >= 0; k--)   // plain: (h rS R) / R
-      h = add(mul(h, rS), fr_load<85>(cp + ((size_t)g + (size_t)k * S) * 8));
-    acc = FrAcc(mul(h, fe_pow_u32(r, g)));
-  }
-  const FrAcc sum = r1cs_block_sum(acc, part);
-  if (threadIdx.x == 0) fr_store(canonical(sum), partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8);
-}
-__global__ void __launch_bounds__(256) k_bace_sum_partials(const u32* __restrict__ partial, int per, u32* __restrict__ out) {
-  __shared__ u32 part[9 * 256];
-  FrAcc acc = FrAcc(fe_zero<FrP>());
-  for (int i = threadIdx.x; i < per; i += 256)
-    acc = FrAcc(reduce_to<32>(add(acc, fr_load<16>(partial + ((size_t)blockIdx.x * per + i) * 8))));
-  const FrAcc sum = r1cs_block_sum(acc, part);
-  if (threadIdx.x == 0) fr_store(canonical(sum), out + (size_t)blockIdx.x * 8);
 }
 
 // ---- result extraction: f[i] = sum_k proof[i + k N], k < D / N (the proof folded mod z^N - 1) ----
@@ -375,16 +344,9 @@ static int bace_check_shape(int n, int N, int D) {
   return OZK_OK;
 }
 
-// the batched polynomial evaluation: npolys polynomials of len coefficients at c + y poly_cs (words); r_mont: device
-static void bace_poly_eval(const u32* c, size_t poly_cs, int len, int npolys, const u32* r_mont, u32* partial, u32* out,
-                           hipStream_t st) {
-  int nb = (len + 256 * 32 - 1) / (256 * 32);
-  if (nb > 256) nb = 256;
-  hipLaunchKernelGGL(k_fr_poly_eval, dim3(nb, npolys), dim3(256), 0, st, c, poly_cs, len, r_mont, partial);
-  hipLaunchKernelGGL(k_bace_sum_partials, dim3(npolys), dim3(256), 0, st, (const u32*)partial, nb, out);
-}
-
 }  // namespace ozk
+
+using namespace ozk;
 
 extern "C" {
 
@@ -452,26 +414,7 @@ int ozk_bace_columns_at_dev(const void* d_inputs, int32_t n, int32_t N, const ui
   if ((rc = bace_upload_consts(L, N, N, r_host32, st))) return rc;
   PlanPin pin;
   if ((rc = bace_columns(L, d_inputs, n, N, (size_t)N * 8, pin, st))) return rc;
-  bace_poly_eval(L.lde, (size_t)N * 8, N, n, L.cst + 24, L.partial, (u32*)d_out, st);
-  OZK_HIP(hipGetLastError());
-  return OZK_OK;
-}
-
-size_t ozk_fr_poly_eval_workspace_bytes(int32_t npolys) { return npolys > 0 ? pad256((size_t)npolys * 256 * 32) + 512 : 0; }
-
-int ozk_fr_poly_eval_dev(const void* d_coeffs, int32_t npolys, int32_t len, int64_t poly_stride, const uint8_t* r_host32,
-                         void* d_out, void* d_workspace, size_t workspace_bytes, void* stream) {
-  hip_clear_stale();
-  if (!d_coeffs || !r_host32 || !d_out || !d_workspace) return fail(OZK_E_INVALID, "null pointer argument");
-  if (npolys <= 0 || npolys > BACE_MAX_N || len <= 0 || poly_stride < 0 || (npolys > 1 && poly_stride < len))
-    return fail(OZK_E_INVALID, "bad shape: %d polynomials of %d coefficients, stride %lld", npolys, len, (long long)poly_stride);
-  if (workspace_bytes < ozk_fr_poly_eval_workspace_bytes(npolys)) return fail(OZK_E_INVALID, "workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  u32* partial = (u32*)d_workspace;
-  u32* r = (u32*)((uint8_t*)d_workspace + pad256((size_t)npolys * 256 * 32));
-  fr_put_element(r_host32, r, st);
-  hipLaunchKernelGGL(k_to_mont_inplace, dim3(1), dim3(64), 0, st, r, 1);
-  bace_poly_eval((const u32*)d_coeffs, (size_t)poly_stride * 8, len, npolys, r, partial, (u32*)d_out, st);
+  fr_poly_eval(L.lde, (size_t)N * 8, N, n, L.cst + 24, L.partial, (u32*)d_out, st);
   OZK_HIP(hipGetLastError());
   return OZK_OK;
 }

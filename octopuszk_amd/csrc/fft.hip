@@ -22,6 +22,7 @@
 #include <new>
 #include <vector>
 
+#include "fft_plan.h"
 #include "fr_tables.cuh"
 #include "host_ctx.h"
 #include "pin_cache.h"
@@ -78,7 +79,7 @@ struct PassArgs {
   int pyr;          // 1: twiddles from the pyramid's levels (default), 0: from level 0 with a stride
   const u32* scale; // LAST pass only, or null: out[i] is multiplied by scale[i] (n x 8 words, Montgomery form) on its
                     // way out — the coset / 1-over-m scalings of the witness map ride on the transform before them
-  size_t in_cs, out_cs;   // batched transforms (bace.cuh): column blockIdx.y reads at in + y in_cs, writes at
+  size_t in_cs, out_cs;   // batched transforms (bace.hip): column blockIdx.y reads at in + y in_cs, writes at
                           // out + y out_cs (words); one column (gridDim.y = 1) reads and writes at offset 0
 };
 
@@ -528,13 +529,14 @@ static const PassKernel FFT_PASS[2][3][2] = {
 // through the two ping-pong buffers (d_out may be one of them only if it is not read by the last pass)
 // batch > 1 (the tiled transform only): `batch` independent columns, column c from d_in + c in_cs to d_out + c out_cs
 // (words), one launch per pass for all of them; the ping-pong buffers then hold batch x n x 8 words each
-static int fft_core(const u32* d_in, int n, const u32* tw, u32* d_out, int out_stride, u32* buf0, u32* buf1,
-                    hipStream_t st, const u32* scale = nullptr, int batch = 1, size_t in_cs = 0, size_t out_cs = 0) {
+// (declared in fft_plan.h: bace.hip runs its columns through it)
+int fft_core(const u32* d_in, int n, const u32* tw, u32* d_out, int out_stride, u32* buf0, u32* buf1, hipStream_t st,
+             const u32* scale, int batch, size_t in_cs, size_t out_cs) {
   hip_clear_stale();   // (ozk_common.h: a stale error of the calling thread is not this call's)
   const int logn = ilog2((uint32_t)n);
   if (n < FFT_TILE) {
     if (scale) return fail(OZK_E_INTERNAL, "output scaling needs the tiled transform");
-    if (batch != 1) return fail(OZK_E_INTERNAL, "batched transforms below %d elements go through bace.cuh", FFT_TILE);
+    if (batch != 1) return fail(OZK_E_INTERNAL, "batched transforms below %d elements go through bace.hip", FFT_TILE);
     hipLaunchKernelGGL(k_fft_small, dim3(1), dim3(FFT_THREADS), 0, st, d_in, d_out, tw, n, logn, buf0, out_stride);
     OZK_HIP(hipGetLastError());
     return OZK_OK;
@@ -629,12 +631,9 @@ static void plan_release(FftPlan* p) {
   g_plans.release(p, plan_limits(), &dead);
   plans_free(dead);
 }
-struct PlanPin {
-  FftPlan* p = nullptr;
-  ~PlanPin() {
-    if (p) plan_release(p);
-  }
-};
+PlanPin::~PlanPin() {   // (fft_plan.h)
+  if (p) plan_release(p);
+}
 
 // ---------------------------------------------------------------------------------------------
 // QAP witness map: the caller of the FFT path.
@@ -820,8 +819,8 @@ static int plan_get(int n, const uint8_t* omega, const uint8_t* g, hipStream_t s
 // has enqueued the last kernel that reads them, else the caller's own `*t` (carved from its workspace) with their
 // build enqueued on `st` — OZK_FFT_PLAN_CACHE=0, a plan beyond the cache's byte budget, or n = 1 (one element has no
 // plan).  by_value: omega is a temporary of the caller and goes up as a kernel argument, not as an asynchronous copy.
-static int domain_tables(int n, const uint8_t* omega, const uint8_t* g, bool by_value, DomainTables* t, PlanPin& pin,
-                         hipStream_t st) {
+int domain_tables(int n, const uint8_t* omega, const uint8_t* g, bool by_value, DomainTables* t, PlanPin& pin,
+                  hipStream_t st) {
   if (n >= 2 && knob(K_FFT_PLAN_CACHE)) {
     int rc = plan_get(n, omega, g, st, &pin.p);
     if (rc) return rc;
@@ -888,7 +887,6 @@ static int qap_witness_dev(const void* d_A, const void* d_B, const void* d_C, in
 // One lane per row; rows longer than R1CS_LONG terms (the closing constraint of the reference's synthetic
 // circuits sums every variable, R1CSConstruction.java:87-96) are left to one workgroup each.
 constexpr int R1CS_LONG = 64;
-using FrAcc = Fe<FrP, 32>;
 
 // value of one term (plain, < 2r): z[j], times its coefficient when there is a coefficient array
 // ONE0: LinearCombination.evaluate's rule for the variable "one" (constraint evaluation); without it the kernels
@@ -926,31 +924,9 @@ __global__ void __launch_bounds__(256) k_r1cs_eval(const u32* __restrict__ ptr, 
 }
 
 // a long row is cut into R1CS_SPLIT slices, one workgroup each: strided partial sums per thread, a tree over the
-// 256 partials in LDS, one 32-byte partial per slice; k_r1cs_eval_long2 then adds the slices of every long row
+// 256 partials in LDS (fr_block_sum of fr_tables.cuh), one 32-byte partial per slice; k_r1cs_eval_long2 then adds the
+// slices of every long row
 constexpr int R1CS_SPLIT = 64;
-__device__ __forceinline__ FrAcc r1cs_block_sum(FrAcc acc, u32* part) {
-#pragma unroll
-  for (int i = 0; i < 9; i++) part[i * 256 + threadIdx.x] = acc.l[i];
-  block_sync();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      FrAcc x, y;
-#pragma unroll
-      for (int i = 0; i < 9; i++) {
-        x.l[i] = part[i * 256 + threadIdx.x];
-        y.l[i] = part[i * 256 + threadIdx.x + o];
-      }
-      const FrAcc s = FrAcc(reduce_to<32>(add(x, y)));
-#pragma unroll
-      for (int i = 0; i < 9; i++) part[i * 256 + threadIdx.x] = s.l[i];
-    }
-    block_sync();
-  }
-  FrAcc r;
-#pragma unroll
-  for (int i = 0; i < 9; i++) r.l[i] = part[i * 256];
-  return r;
-}
 template <bool ONE0>
 __global__ void __launch_bounds__(256) k_r1cs_eval_long1(const u32* __restrict__ ptr, const u32* __restrict__ idx,
                                                          const u32* __restrict__ coeff, const u32* __restrict__ z,
@@ -964,7 +940,7 @@ __global__ void __launch_bounds__(256) k_r1cs_eval_long1(const u32* __restrict__
   const u32 hi = (lo + per < e) ? lo + per : e;
   FrAcc acc = FrAcc(fe_zero<FrP>());
   for (u32 t = lo + threadIdx.x; t < hi; t += 256) acc = FrAcc(reduce_to<32>(add(acc, r1cs_term<ONE0>(idx, coeff, z, t))));
-  const FrAcc r = r1cs_block_sum(acc, part);
+  const FrAcc r = fr_block_sum(acc, part);
   if (threadIdx.x == 0) {
     u32 o[8];
     pack(canonical(r), o);
@@ -983,7 +959,7 @@ __global__ void __launch_bounds__(256) k_r1cs_eval_long2(const u32* __restrict__
     for (int i = 0; i < 8; i++) w[i] = partial[((size_t)blockIdx.x * R1CS_SPLIT + threadIdx.x) * 8 + i];
     acc = FrAcc(reduce_to<32>(unpack<FrP, 16>(w)));
   }
-  const FrAcc r = r1cs_block_sum(acc, part);
+  const FrAcc r = fr_block_sum(acc, part);
   if (threadIdx.x == 0) {
     u32 o[8];
     pack(canonical(r), o);
@@ -1081,12 +1057,6 @@ __global__ void __launch_bounds__(256) k_lincomb3(const u32* __restrict__ a, con
   const auto x = ET::load(a + (size_t)i * 8), y = ET::load(b + (size_t)i * 8), z = ET::load(c + (size_t)i * 8);
   const auto s = add(add(mul(x, ET::load(k3)), mul(y, ET::load(k3 + 8))), z);   // plain
   fr_store(canonical(mul(reduce_to<32>(s), ET::load(k3 + 16))), out + (size_t)i * 8);
-}
-// wire (plain canonical) constants -> Montgomery form, in place: one lane per 8-word element
-__global__ void k_to_mont_inplace(u32* __restrict__ v, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  ElemTraits<Fe<FrP, 16>>::store(canonical(ElemTraits<Fe<FrP, 17>>::from_wire(v + (size_t)i * 8)), v + (size_t)i * 8);
 }
 
 void fft_plan_cache_release() {
@@ -1345,10 +1315,3 @@ int ozk_fft_compact_host(const uint8_t* in, int32_t n, const uint8_t* omega, int
 }
 
 }  // extern "C"
-
-#include "bace.cuh"
-#include "kzg.cuh"
-#include "kzg_set.cuh"
-#include "kzg_multi.cuh"
-#include "plonk.cuh"
-#include "plonk_lookup.cuh"

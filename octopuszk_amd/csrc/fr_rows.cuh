@@ -1,7 +1,7 @@
 // What the Fr kernels that walk rows of 32-byte elements share: kzg.cuh, kzg_set.cuh,
-// kzg_multi.cuh and plonk.cuh build on it.  Included by kzg.cuh.  The per-lane pieces compile for the host too
-// (tests/native/kzg_hostcheck.cpp, kzg_set_hostcheck.cpp); the device parts use the element I/O of fr_tables.cuh and
-// the barrier of curve.cuh, which fft.hip has included by then.
+// kzg_multi.cuh (the kzg.hip unit) and plonk.cuh, plonk_lookup.cuh (the plonk.hip unit) build on it.  Stands alone.
+// The per-lane pieces compile for the host too (tests/native/kzg_hostcheck.cpp, kzg_set_hostcheck.cpp); the device
+// parts use the element I/O of fr_tables.cuh and the barrier of curve.cuh, included below for the device compiler.
 //
 //   - the per-lane pieces: Horner's recurrence over a piece, the composition of carries, the chunk inversion;
 //   - a row's constants (KzgRow, KzgSetPows) and its value from tile 0 and the tail above it;
@@ -11,6 +11,9 @@
 //   - the checks every entry point makes on the host.
 #pragma once
 #include "fp29.cuh"
+#if defined(__HIPCC__)
+#include "fr_tables.cuh"
+#endif
 
 namespace ozk {
 

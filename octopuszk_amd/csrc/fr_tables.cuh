@@ -1,6 +1,8 @@
-// What the Fr kernels of fft.hip and bace.cuh share: element I/O, host words in kernel arguments, exponentiation by a
-// word, the two-level power table, and the description of one domain's tables.  Included by
-// fft.hip only.
+// What the Fr units (fft.hip, bace.hip, kzg.hip, plonk.hip) share: element I/O, host words in kernel arguments,
+// exponentiation by a word, the two-level power table, the description of one domain's tables, the workgroup sum and
+// the small kernels that more than one unit launches (DESIGN.md sections 19 and 34).  Stands alone.  A kernel here
+// that is no template is `static` (hipcc ignores `inline` on a kernel): under -fno-gpu-rdc each unit that launches it
+// compiles and registers its own copy.
 #pragma once
 #include "curve.cuh"
 #include "ozk_common.h"
@@ -73,8 +75,8 @@ OZK_HD Fe<FrP, 32> fe_pow_u32(const Fe<FrP, B>& base, unsigned e) {
 // pw[j] = base^j for j < lo, pw[lo + j] = base^(j lo) for j < hi; Montgomery form, packed 8 words: base^i for every
 // i < lo hi is ONE product of two entries (pow_at), and the table is built by lo + hi independent lanes.
 constexpr int TW_LO = 2048;
-__global__ void __launch_bounds__(256) k_tw_small(const u32* __restrict__ base_wire, int lo, int hi,
-                                                  u32* __restrict__ pw) {
+static __global__ void __launch_bounds__(256) k_tw_small(const u32* __restrict__ base_wire, int lo, int hi,
+                                                         u32* __restrict__ pw) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= lo + hi) return;
   const auto base = ElemTraits<Fe<FrP, 32>>::from_wire(base_wire);
@@ -139,6 +141,84 @@ inline DomainTables carve(Bump& b, int n, bool qap, bool roomy = false) {
     t.sc_gi = b.take<u32>((size_t)n * 8);
   }
   return t;
+}
+
+// ---- the workgroup sum ------------------------------------------------------------------------------------------
+// The sum of the 256 lanes' accumulators: a tree over the partials in LDS (part: 9 x 256 words, limb-major)
+using FrAcc = Fe<FrP, 32>;
+__device__ __forceinline__ FrAcc fr_block_sum(FrAcc acc, u32* part) {
+#pragma unroll
+  for (int i = 0; i < 9; i++) part[i * 256 + threadIdx.x] = acc.l[i];
+  block_sync();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      FrAcc x, y;
+#pragma unroll
+      for (int i = 0; i < 9; i++) {
+        x.l[i] = part[i * 256 + threadIdx.x];
+        y.l[i] = part[i * 256 + threadIdx.x + o];
+      }
+      const FrAcc s = FrAcc(reduce_to<32>(add(x, y)));
+#pragma unroll
+      for (int i = 0; i < 9; i++) part[i * 256 + threadIdx.x] = s.l[i];
+    }
+    block_sync();
+  }
+  FrAcc r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.l[i] = part[i * 256];
+  return r;
+}
+
+// ---- small kernels that more than one unit launches --------------------------------------------------------------
+// wire (plain canonical) constants -> Montgomery form, in place: one lane per 8-word element
+static __global__ void k_to_mont_inplace(u32* __restrict__ v, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  ElemTraits<Fe<FrP, 16>>::store(canonical(ElemTraits<Fe<FrP, 17>>::from_wire(v + (size_t)i * 8)), v + (size_t)i * 8);
+}
+
+// Polynomial evaluation at a point (ozk_fr_poly_eval_dev of kzg.hip, ozk_bace_columns_at_dev of bace.hip).
+// Lane g of polynomial y (S = gridDim.x x 256 lanes per polynomial) runs Horner in r^S over the coefficients
+// c[g], c[g + S], ... (consecutive lanes read consecutive coefficients), multiplies by r^g, and the workgroup's sum
+// goes to partial[y gridDim.x + blockIdx.x]; k_fr_sum_partials adds each polynomial's partials.  The coefficients are
+// any 256-bit words, reduced mod r on load (the KZG callers pass their rows as they got them); the partials are canonical.
+static __global__ void __launch_bounds__(256) k_fr_poly_eval(const u32* __restrict__ c, size_t poly_cs, int len,
+                                                             const u32* __restrict__ r_mont, u32* __restrict__ partial) {
+  __shared__ u32 part[9 * 256];
+  const u32 S = gridDim.x * 256u;
+  const u32 g = blockIdx.x * 256u + threadIdx.x;
+  const u32* cp = c + (size_t)blockIdx.y * poly_cs;
+  const auto r = ElemTraits<Fe<FrP, 16>>::load(r_mont);
+  FrAcc acc = FrAcc(fe_zero<FrP>());
+  if (g < (u32)len) {
+    const FrAcc rS = fe_pow_u32(r, S);
+    // No reduction inside the loop: the product is below 18/16 r, a coefficient as loaded below 85/16 r, and the
+    // multiplier takes their sum (below 103/16 r) as it is.  The bounds are the types': a wider one does not compile.
+    Fe<FrP, 103> h = Fe<FrP, 103>(fe_zero<FrP>());
+    for (long long k = ((u32)len - 1 - g) / S; k >= 0; k--)   // plain: (h rS R) / R
+      h = add(mul(h, rS), fr_load<85>(cp + ((size_t)g + (size_t)k * S) * 8));
+    acc = FrAcc(mul(h, fe_pow_u32(r, g)));
+  }
+  const FrAcc sum = fr_block_sum(acc, part);
+  if (threadIdx.x == 0) fr_store(canonical(sum), partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8);
+}
+static __global__ void __launch_bounds__(256) k_fr_sum_partials(const u32* __restrict__ partial, int per, u32* __restrict__ out) {
+  __shared__ u32 part[9 * 256];
+  FrAcc acc = FrAcc(fe_zero<FrP>());
+  for (int i = threadIdx.x; i < per; i += 256)
+    acc = FrAcc(reduce_to<32>(add(acc, fr_load<16>(partial + ((size_t)blockIdx.x * per + i) * 8))));
+  const FrAcc sum = fr_block_sum(acc, part);
+  if (threadIdx.x == 0) fr_store(canonical(sum), out + (size_t)blockIdx.x * 8);
+}
+// the batched polynomial evaluation: npolys polynomials of len coefficients at c + y poly_cs (words); r_mont: device
+constexpr int FR_POLY_EVAL_MAX = 65535;   // polynomials of one call: gridDim.y
+static void fr_poly_eval(const u32* c, size_t poly_cs, int len, int npolys, const u32* r_mont, u32* partial, u32* out,
+                         hipStream_t st) {
+  int nb = (len + 256 * 32 - 1) / (256 * 32);
+  if (nb > 256) nb = 256;
+  hipLaunchKernelGGL(k_fr_poly_eval, dim3(nb, npolys), dim3(256), 0, st, c, poly_cs, len, r_mont, partial);
+  hipLaunchKernelGGL(k_fr_sum_partials, dim3(npolys), dim3(256), 0, st, (const u32*)partial, nb, out);
 }
 
 // n is a power of two in [lo, 2^28]; `what` names it in the message

@@ -1,7 +1,8 @@
 // The Fr kernels of KZG openings: the quotient (p(X) - p(z)) / (X - z) with the value p(z),
-// in coefficient form and in evaluation form, and a weighted sum of rows.  Included at the end of fft.hip (it uses that
-// unit's element I/O, power table and block sum).  The per-lane pieces, the staged tile, the scan and the entry checks
-// are fr_rows.cuh's; the pieces compile for the host too (tests/native/kzg_hostcheck.cpp).
+// in coefficient form and in evaluation form, and a weighted sum of rows.  A section of the kzg.hip unit, which alone
+// includes it for the device: kernels, layouts and entry points.  The per-lane pieces, the staged tile, the scan and the
+// entry checks are fr_rows.cuh's, element I/O, power table and block sum fr_tables.cuh's; what is outside __HIPCC__
+// compiles for the host too (tests/native/kzg_hostcheck.cpp).
 //
 // Every value in HBM is 32 bytes LE, plain (non-Montgomery); inputs are taken mod r, outputs are canonical.
 //
@@ -153,7 +154,7 @@ __global__ void __launch_bounds__(KZG_WG) k_kzg_ev_inv(const u32* __restrict__ e
       }
     }
   }
-  const FrAcc sum = r1cs_block_sum(acc, part);
+  const FrAcc sum = fr_block_sum(acc, part);
   if (threadIdx.x == 0) fr_store(canonical(sum), partial + (size_t)blockIdx.x * 8);
 }
 // one workgroup per row: y = -c sum, or f_k for z = omega^k
@@ -165,7 +166,7 @@ __global__ void __launch_bounds__(256) k_kzg_ev_value(const u32* __restrict__ pa
   FrAcc acc = FrAcc(fe_zero<FrP>());
   for (int i = threadIdx.x; i < nb; i += 256)
     acc = FrAcc(reduce_to<32>(add(acc, fr_load<16>(partial + ((size_t)y * nb + i) * 8))));
-  const FrAcc sum = r1cs_block_sum(acc, part);
+  const FrAcc sum = fr_block_sum(acc, part);
   if (threadIdx.x != 0) return;
   u32 o[8];
   const u32 k1 = flags[y];
@@ -195,7 +196,7 @@ __global__ void __launch_bounds__(KZG_WG) k_kzg_ev_quot(const u32* __restrict__ 
     if (inside) acc = FrAcc(reduce_to<32>(add(acc, mul(v, pow_at(pw, lo, i)))));
   }
   if (!inside) return;
-  const FrAcc sum = r1cs_block_sum(acc, part);
+  const FrAcc sum = fr_block_sum(acc, part);
   if (threadIdx.x == 0) fr_store(canonical(sum), partial + (size_t)blockIdx.x * 8);
 }
 // z = omega^k: q_k = -omega^(n - k) sum_i q_i omega^i, one workgroup per row
@@ -209,7 +210,7 @@ __global__ void __launch_bounds__(256) k_kzg_ev_inside(const u32* __restrict__ p
   FrAcc acc = FrAcc(fe_zero<FrP>());
   for (int i = threadIdx.x; i < nb; i += 256)
     acc = FrAcc(reduce_to<32>(add(acc, fr_load<16>(partial + ((size_t)y * nb + i) * 8))));
-  const FrAcc sum = r1cs_block_sum(acc, part);
+  const FrAcc sum = fr_block_sum(acc, part);
   if (threadIdx.x != 0) return;
   const int k = (int)(k1 - 1);
   fr_store(canonical(neg(mul(sum, pow_at(pw, lo, n - k)))), quot + (size_t)y * quot_cs + (size_t)k * 8);
@@ -273,6 +274,8 @@ static KzgEvLayout kzg_ev_layout(int npolys, int n, void* wsp) {
 }  // namespace ozk
 
 #if defined(__HIPCC__)
+using namespace ozk;
+
 extern "C" {
 
 size_t ozk_fr_poly_open_workspace_bytes(int32_t npolys, int32_t len) {

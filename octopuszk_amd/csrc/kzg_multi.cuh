@@ -1,6 +1,7 @@
 // The Fr kernels of the KZG multi-opening: a weighted sum of rows per GROUP of rows, the groups
-// any partition of the rows, and the values of every row at its own t points without a quotient.  Included at the end
-// of fft.hip after kzg_set.cuh, whose first pass and scan it runs as they are.
+// any partition of the rows, and the values of every row at its own t points without a quotient.  A section of the
+// kzg.hip unit, which alone includes it: kernels, layouts and entry points, after kzg_set.cuh, whose first pass and scan
+// it runs as they are.
 //
 // Grouped combine.  out[g][j] = sum_{i : id[i] = g} w_i rows[i][j].  One lane per column, the group on the grid's
 // second dimension; the ids travel in the kernel arguments, so that `id[i] == g` is uniform over the wave and a row
@@ -92,6 +93,8 @@ static bool kzg_eval_set_shape_ok(int npolys, int len, int t) {
 }  // namespace ozk
 
 #if defined(__HIPCC__)
+using namespace ozk;
+
 extern "C" {
 
 int ozk_fr_rows_combine_groups_dev(const void* d_rows, int32_t k, int32_t len, int64_t row_stride, const void* d_weights,

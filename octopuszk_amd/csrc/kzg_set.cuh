@@ -1,7 +1,8 @@
 // The Fr kernels of KZG set openings: the quotient (p - I) / Z_S for S = (z_0 .. z_{t-1}),
 // Z_S = prod (X - z_i) and I the interpolant of p on S, with the values p(z_i), in coefficient form and in evaluation
-// form.  Included at the end of fft.hip after kzg.cuh; it builds on the tiles, scan and chunk inversion of
-// fr_rows.cuh.  The per-lane pieces above the kernels compile for the host too (tests/native/kzg_set_hostcheck.cpp).
+// form.  A section of the kzg.hip unit, which alone includes it for the device: kernels, layouts and entry points, after
+// kzg.cuh, whose tile load and carries kernel it uses; it builds on the tiles, scan and chunk inversion of fr_rows.cuh.
+// The per-lane pieces above the kernels compile for the host too (tests/native/kzg_set_hostcheck.cpp).
 //
 // Coefficient form.  Dividing by (X - z_0), .., (X - z_{t-1}) in turn is t runs of the recurrence of section 22,
 // stage s over the output of stage s - 1: h^s_j = h^(s-1)_j + z_s h^s_(j+1), h^(-1) = p.  Position j holds h_j at
@@ -334,7 +335,7 @@ __global__ void __launch_bounds__(KZG_WG) k_kzg_set_ev_inv(const u32* __restrict
 #pragma unroll
   for (int j = 0; j < KZG_SET_EV_T; j++) {
     if (j < t) {   // (uniform over the workgroup)
-      const FrAcc sum = r1cs_block_sum(acc[j], part);
+      const FrAcc sum = fr_block_sum(acc[j], part);
       if (threadIdx.x == 0) fr_store(canonical(sum), partial + ((size_t)blockIdx.x * t + j) * 8);
       block_sync();
     }
@@ -350,7 +351,7 @@ __global__ void __launch_bounds__(256) k_kzg_set_ev_value(const u32* __restrict_
   FrAcc acc = FrAcc(fe_zero<FrP>());
   for (int i = threadIdx.x; i < nb; i += 256)
     acc = FrAcc(reduce_to<32>(add(acc, fr_load<16>(partial + ((y * nb + i) * t + j) * 8))));
-  const FrAcc sum = r1cs_block_sum(acc, part);
+  const FrAcc sum = fr_block_sum(acc, part);
   if (threadIdx.x != 0) return;
   KzgSetEv& e = ev[blockIdx.x];
   const Fe<FrP, 16> val = canonical(neg(mul(sum, E16::load(e.c))));
@@ -436,6 +437,8 @@ static bool kzg_set_rows_distinct(const uint8_t* points_host, int npolys, int t)
 }  // namespace ozk
 
 #if defined(__HIPCC__)
+using namespace ozk;
+
 extern "C" {
 
 size_t ozk_fr_poly_open_set_workspace_bytes(int32_t npolys, int32_t len, int32_t t) {

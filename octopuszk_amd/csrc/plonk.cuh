@@ -1,7 +1,7 @@
 // The Fr kernels of the PLONK prover: rows scaled by the powers of a coset shift, the permutation
-// grand product, and the quotient pointwise on the coset of four times the domain.  Included at the end of fft.hip
-// after kzg_multi.cuh: it uses that unit's element I/O and the staged tile, scan, chunked inversion and entry checks of
-// fr_rows.cuh.
+// grand product, and the quotient pointwise on the coset of four times the domain.  A section of the plonk.hip unit,
+// which alone includes it: kernels, layouts and entry points.  It uses the element I/O and kernel-argument words of
+// fr_tables.cuh and the staged tile, scan, chunked inversion and entry checks of fr_rows.cuh; no KZG kernel.
 //
 // Every value in HBM is 32 bytes LE, plain (non-Montgomery); inputs are taken mod r, outputs are canonical.  The
 // scalars of a call arrive in host memory and travel in the kernel arguments, already in the form the kernel
@@ -26,7 +26,7 @@
 // rows and of Z four places on.  Z_H takes four values on the coset; their inverses come with the call.
 //   products per point: 26 (3 conversions, the gate 7, P1 12, P2 2, the weights 2); bytes: 16 x 32 read + 32 written.
 #pragma once
-#include "kzg_multi.cuh"
+#include "fr_rows.cuh"
 
 namespace ozk {
 
@@ -364,6 +364,8 @@ static PlonkQuotArgs plonk_quot_args(const uint8_t* alpha_host32, const uint8_t*
 }  // namespace ozk
 
 #if defined(__HIPCC__)
+using namespace ozk;
+
 extern "C" {
 
 size_t ozk_fr_rows_coset_workspace_bytes(int32_t k, int32_t len, int32_t out_len) {

@@ -1,7 +1,7 @@
 // The lookup argument of the PLONK prover: logUp in its univariate running-sum form over one
-// table of three-column tuples.  Included at the end of fft.hip after plonk.cuh: it uses that unit's element I/O,
-// scalars in kernel arguments, the vanilla terms of the quotient, and the staged tile, scan, chunked inversion and entry
-// checks of fr_rows.cuh.  Values in HBM are 32 bytes LE, plain; inputs are taken mod r, outputs are canonical.
+// table of three-column tuples.  A section of the plonk.hip unit, which alone includes it, after plonk.cuh: it uses that
+// file's scalars in kernel arguments and vanilla terms of the quotient, the element I/O of fr_tables.cuh and the staged
+// tile, scan, chunked inversion and entry checks of fr_rows.cuh.  Values in HBM are 32 bytes LE, plain; inputs are taken mod r, outputs are canonical.
 //
 // Index.  An open-addressing table of uint32 row numbers over the first n_rows table rows, capacity the power of two
 // >= 2 n_rows, empty = 0xffffffff.  The key is the 24 words of the canonical tuple.  A row claims an empty slot with a
@@ -352,6 +352,8 @@ static bool lookup_misaligned4(const void* p) { return ((uintptr_t)p & 3) != 0; 
 }  // namespace ozk
 
 #if defined(__HIPCC__)
+using namespace ozk;
+
 extern "C" {
 
 size_t ozk_plonk_lookup_index_bytes(int32_t n_rows) {

@@ -1,5 +1,5 @@
 """The transforms with their tables built per call in the caller's workspace (csrc/fft.hip fft_layout, qap_layout,
-qap_build_tables; csrc/bace.cuh bace_twiddles), and the knobs beside them: OZK_FFT_PLAN_CACHE=0, the byte-budget
+qap_build_tables; csrc/bace.hip bace_twiddles), and the knobs beside them: OZK_FFT_PLAN_CACHE=0, the byte-budget
 fallback OZK_FFT_PLAN_CACHE_MB (a plan larger than the budget is not cached: production domains above 4 GiB),
 OZK_FFT_TW_PYRAMID=0 and OZK_QAP_FOLD_SCALE=0 (k_coset_scale as a kernel of its own, at sizes where it reads the
 second level of its power table).  Every result is compared byte for byte with the oracle.

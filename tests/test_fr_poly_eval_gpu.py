@@ -1,4 +1,4 @@
-"""ozk_fr_poly_eval_dev (k_fr_poly_eval and k_bace_sum_partials of csrc/bace.cuh) through the C ABI, against plain
+"""ozk_fr_poly_eval_dev (k_fr_poly_eval and k_fr_sum_partials of csrc/fr_tables.cuh) through the C ABI, against plain
 Horner in Python integers (kzg_ref.horner), byte for byte.  The kernel runs nb = min(ceil(len / 8192), 256) workgroups a
 polynomial, S = 256 nb lanes, lane g over the coefficients g, g + S, ..: the lengths below take one workgroup with idle
 lanes (len < 256), the first split (8193: nb = 2, 17 trips of the lane loop), nb = 4, and the cap (len > 2^21).  Every
