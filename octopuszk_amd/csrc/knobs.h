@@ -28,6 +28,8 @@ constexpr int KNOB_STRING = KNOB_COMPUTED + 1;  // a string, read with knob_str(
   X(MSM_C, "OZK_MSM_C", KNOB_COMPUTED, "window bits, 1..16 (default: the cost model's choice)")                          \
   X(MSM_L1, "OZK_MSM_L1", KNOB_COMPUTED, "sorted entries per level-1 lane (default: from the bucket size; 0 as unset)")   \
   X(MSM_L1_WHOLE, "OZK_MSM_L1_WHOLE", 1, "G1 level 1 by whole buckets on lane groups: 0 never, 1 on every plan that can take it (unset: where it pays)") \
+  X(MSM_L1_ORDER, "OZK_MSM_L1_ORDER", 1, "item order of the whole-bucket level 1: 0 by rank inside the sort bin, 1 by part length over the whole MSM") \
+  X(MSM_L1_DENSE, "OZK_MSM_L1_DENSE", 1, "0: every workgroup of the whole-bucket level 1 merges lane groups by quad permutes, none densely through LDS") \
   X(MSM_L1_ROUNDS, "OZK_MSM_L1_ROUNDS", 2, "most rounds of resident workgroups level 1 is rounded up to; 0: no rounding") \
   X(MSM_TAIL_MODE, "OZK_MSM_TAIL_MODE", -1, "0 / 1: force the latency / throughput shape of the window sums")            \
   X(MSM_TAIL_RC, "OZK_MSM_TAIL_RC", -1, "1: G1 throughput window sums by bucket rows and columns wherever the buffers take them (0 / unset: the serial levels)") \

@@ -87,4 +87,85 @@ OZK_HD void whole_part(uint32_t count, uint32_t g, uint32_t G, uint32_t* first, 
   *len = b - a;
 }
 
+// ---------------------------------------------------------------- items ordered by part length (OZK_MSM_L1_ORDER=1)
+// The rank order above makes a wave run "the r-th largest bucket of 32 neighbouring bins": the longest of its 64 parts
+// sets its trip count, 4 % above the mean at the workload's shape.  Here an item's KEY is the trip count of its lane 0,
+// ceil(count / G) clamped to WHOLE_KEYS - 1 (longer buckets share the last class: only balance suffers), key 0 is the
+// empty bucket, and the items of a REGION descend by key over all windows.  Region 0 holds the ordinary windows' items
+// (G = 2), region 1 the top window's where g_top is not 2; lane u of a region serves item u / G, and a region's end is
+// padded to a whole wave.  A class table T[region][key] (items per key, summed by k_bin_sums) gives every class its
+// first item; inside a class the order is free.  The workgroups of region 1 (and the one that straddles the regions)
+// are spread among region 0's in proportion, so that the grid as a whole still runs longest-first.
+constexpr int WHOLE_KEYS = 128;
+constexpr int WHOLE_WAVE = 64, WHOLE_TB = 256;          // lanes per wave and per workgroup of k_l1_whole
+constexpr int WHOLE_TABLE_WORDS = 2 * 2 * WHOLE_KEYS;   // T[2][KEYS], then the cursors C[2][KEYS] k_bucket_items takes slots from
+OZK_HD uint32_t whole_key(uint32_t count, uint32_t G) {
+  const uint32_t k = (count + G - 1) / G;
+  return k < (uint32_t)(WHOLE_KEYS - 1) ? k : (uint32_t)(WHOLE_KEYS - 1);
+}
+OZK_HD int whole_regions(const WholeGeom& g) { return g.g_top == WHOLE_G ? 1 : 2; }
+OZK_HD int whole_bin_region(const WholeGeom& g, int bin) { return (whole_regions(g) == 2 && bin / g.NH == g.W - 1) ? 1 : 0; }
+OZK_HD uint32_t whole_region_group(const WholeGeom& g, int r) { return r == 0 ? (uint32_t)WHOLE_G : (uint32_t)g.g_top; }
+OZK_HD uint32_t whole_region_items(const WholeGeom& g, int r) {
+  const uint32_t top = (uint32_t)(g.NH * g.nb), all = (uint32_t)(g.W * g.NH * g.nb);
+  if (whole_regions(g) == 1) return r == 0 ? all : 0u;
+  return r == 0 ? all - top : top;
+}
+OZK_HD uint32_t whole_region_lanes(const WholeGeom& g, int r) {
+  const uint32_t l = whole_region_group(g, r) * whole_region_items(g, r);
+  return (l + (uint32_t)(WHOLE_WAVE - 1)) & ~(uint32_t)(WHOLE_WAVE - 1);
+}
+OZK_HD long long whole_lanes_len(const WholeGeom& g) { return (long long)whole_region_lanes(g, 0) + whole_region_lanes(g, 1); }
+// class bases of one region: base[k] = items with a key above k (the classes descend by key; T has WHOLE_KEYS words)
+OZK_HD uint32_t whole_class_base(const uint32_t* T, uint32_t key) {
+  uint32_t s = 0;
+  for (uint32_t k = (uint32_t)WHOLE_KEYS - 1; k > key; k--) s += T[k];
+  return s;
+}
+OZK_HD void whole_class_bases(const uint32_t* T, uint32_t* base) {
+  for (uint32_t k = 0; k < (uint32_t)WHOLE_KEYS; k++) base[k] = whole_class_base(T, k);
+}
+// the workgroups: nb0 lie wholly in region 0, the other nb1 (the straddling one first) follow in lane order
+OZK_HD void whole_len_blocks(const WholeGeom& g, uint32_t* nb0, uint32_t* nb1) {
+  const uint32_t all = (uint32_t)((whole_lanes_len(g) + WHOLE_TB - 1) / WHOLE_TB);
+  *nb0 = whole_region_lanes(g, 0) / (uint32_t)WHOLE_TB;
+  *nb1 = all - *nb0;
+}
+// launch order -> lane order: workgroup p of the grid runs lanes [b * WHOLE_TB, (b + 1) * WHOLE_TB), the nb1 late
+// workgroups spread evenly among the nb0 early ones (a bijection of [0, nb0 + nb1))
+OZK_HD uint32_t whole_block_interleave(uint32_t p, uint32_t nb0, uint32_t nb1) {
+  const unsigned long long n = (unsigned long long)nb0 + nb1;
+  const uint32_t before = (uint32_t)((unsigned long long)p * nb1 / n), upto = (uint32_t)(((unsigned long long)p + 1) * nb1 / n);
+  return upto > before ? nb0 + before : p - before;
+}
+// lane u (lane order) -> its item (WHOLE_NO_ITEM for a padding lane), place g in the lane group, group size G
+OZK_HD void whole_lane_map_len(const WholeGeom& geo, uint32_t u, uint32_t* item, uint32_t* g, uint32_t* G) {
+  const uint32_t l0 = whole_region_lanes(geo, 0), n0 = whole_region_items(geo, 0);
+  if (u < l0) {
+    *G = (uint32_t)WHOLE_G;
+    *g = u % (uint32_t)WHOLE_G;
+    const uint32_t i = u / (uint32_t)WHOLE_G;
+    *item = i < n0 ? i : WHOLE_NO_ITEM;
+  } else {
+    const uint32_t q = u - l0, gt = (uint32_t)geo.g_top;
+    *G = gt;
+    *g = q % gt;
+    const uint32_t i = q / gt;
+    *item = i < whole_region_items(geo, 1) ? n0 + i : WHOLE_NO_ITEM;
+  }
+}
+
+// ---------------------------------------------------------------- dense merges
+// A workgroup all of whose lanes are pairs (G = 2) merges its 128 buckets on two full waves through LDS, not on four
+// half-used ones by quad permutes.  Whether workgroup `block` (lane order) is such a one, from the geometry alone:
+// uniform over the workgroup.  order 1: it lies wholly in region 0; order 0: wholly in one rank's ordinary section.
+OZK_HD bool whole_block_dense(const WholeGeom& geo, int order, uint32_t block, uint32_t n_lanes) {
+  const unsigned long long t0 = (unsigned long long)block * WHOLE_TB;
+  if (t0 + WHOLE_TB > n_lanes) return false;
+  if (order == 1) return t0 + WHOLE_TB <= whole_region_lanes(geo, 0);
+  const uint32_t per_rank = (uint32_t)whole_lanes_per_rank(geo);
+  const uint32_t q0 = (uint32_t)(t0 % per_rank);
+  return q0 + (uint32_t)WHOLE_TB <= (uint32_t)whole_pad4(WHOLE_G * geo.NH * (geo.W - 1));
+}
+
 }  // namespace ozk

@@ -60,6 +60,8 @@ struct MsmPlan {
   int tail_rc;     // 1: G1 throughput window sums by bucket rows and columns wherever they fit the tail buffers (wsum_rc.h)
   int l1_whole;    // 1: level 1 by whole buckets on lane groups where the data allow it (G1; k_bucket_items, k_l1_whole)
   int l1_gtop;     // lanes per bucket of the top window on that path (l1_whole.h WholeGeom::g_top)
+  int l1_order;    // item order of that path: 0 by rank inside the sort bin, 1 by part length over the whole MSM (l1_whole.h)
+  int l1_dense;    // 1: workgroups of lane pairs merge their buckets on two full waves through LDS (k_l1_whole)
 };
 
 OZK_HD u32 scalar_digit(const u32 (&s)[8], int w, int c) {
@@ -1355,38 +1357,85 @@ __device__ __forceinline__ u32 items_block_sum(u32 v, u32* wsum) {   // sum over
   return wsum[0] + wsum[1];
 }
 static __global__ void __launch_bounds__(ITEMS_BLOCK)
-k_bin_sums(const u32* __restrict__ hist, WholeGeom geo, int cb, int lo_bits, u32* __restrict__ binsum) {
-  static_assert(ITEMS_BLOCK == 128, "two waves");
+k_bin_sums(const u32* __restrict__ hist, WholeGeom geo, int cb, int lo_bits, u32* __restrict__ binsum, int order,
+           u32* __restrict__ table) {
+  static_assert(ITEMS_BLOCK == 128 && WHOLE_KEYS == ITEMS_BLOCK, "two waves; one thread per key class");
   __shared__ u32 wsum[2];
-  const int t = threadIdx.x, bin = blockIdx.x;
-  const int w = bin / geo.NH, h = bin - w * geo.NH;
-  const u32 bucket0 = ((u32)w << cb) | ((u32)h << lo_bits);
-  const u32 sum = items_block_sum(t < geo.nb ? hist[bucket0 + t] : 0u, wsum);
-  if (t == 0) binsum[bin] = sum;
-}
-static __global__ void __launch_bounds__(ITEMS_BLOCK)
-k_bucket_items(const u32* __restrict__ hist, const u32* __restrict__ binsum, WholeGeom geo, int cb, int lo_bits,
-               u32 big_thresh, uint4* __restrict__ items, u32* __restrict__ bad) {
-  __shared__ u32 cnt[WHOLE_NB_MAX];
-  __shared__ u32 wsum[2];
+  __shared__ u32 keys[WHOLE_KEYS];
   const int t = threadIdx.x, bin = blockIdx.x;
   const int w = bin / geo.NH, h = bin - w * geo.NH;
   const u32 bucket0 = ((u32)w << cb) | ((u32)h << lo_bits);
   const u32 c = t < geo.nb ? hist[bucket0 + t] : 0u;
+  if (order == 1) {   // the bin's buckets per key class (l1_whole.h whole_key)
+    keys[t] = 0u;
+    block_sync();
+    if (t < geo.nb) atomicAdd(&keys[whole_key(c, (u32)whole_group(geo, bin))], 1u);
+  }
+  const u32 sum = items_block_sum(c, wsum);   // (its barrier also publishes keys[])
+  if (t == 0) binsum[bin] = sum;
+  if (order == 1) {   // integer sums commute: the class table is the same every run
+    const u32 v = keys[t];
+    if (v != 0u) atomicAdd(&table[whole_bin_region(geo, bin) * WHOLE_KEYS + t], v);
+  }
+}
+// order 1 (items by part length): a bucket's item goes to  first item of its region + class base of its key (the
+// table k_bin_sums summed, scanned in descending key order) + a slot inside the class.  The slots of a class are
+// handed out by a cursor beside the table, one returning atomic per block and distinct key; the block's buckets of
+// one key take consecutive slots in bucket order.  Which slot a block gets differs from run to run; the items'
+// contents, and so the bucket records, do not.  A slot outside the region (a table that was not zeroed: never with
+// this driver) raises *bad and writes nothing.
+static __global__ void __launch_bounds__(ITEMS_BLOCK)
+k_bucket_items(const u32* __restrict__ hist, const u32* __restrict__ binsum, WholeGeom geo, int cb, int lo_bits,
+               u32 big_thresh, uint4* __restrict__ items, u32* __restrict__ bad, int order, u32* __restrict__ table) {
+  __shared__ u32 cnt[WHOLE_NB_MAX];
+  __shared__ u32 wsum[2];
+  __shared__ u32 keyv[WHOLE_NB_MAX], cls[WHOLE_KEYS], slot0[WHOLE_KEYS];
+  const int t = threadIdx.x, bin = blockIdx.x;
+  const int w = bin / geo.NH, h = bin - w * geo.NH;
+  const u32 bucket0 = ((u32)w << cb) | ((u32)h << lo_bits);
+  const u32 c = t < geo.nb ? hist[bucket0 + t] : 0u;
+  const u32 G = (u32)whole_group(geo, bin);
+  const int region = whole_bin_region(geo, bin);
+  const u32 key = whole_key(c, G);
   cnt[t] = c;
+  if (order == 1) {
+    keyv[t] = key;
+    cls[t] = table[region * WHOLE_KEYS + t];
+  }
   u32 before = 0;
   for (int j = t; j < bin; j += ITEMS_BLOCK) before += binsum[j];
-  const u32 base = items_block_sum(before, wsum);   // (its barrier also publishes cnt[])
-  if (t >= geo.nb) return;
+  const u32 base = items_block_sum(before, wsum);   // (its barrier also publishes cnt[], keyv[], cls[])
+  const bool live = t < geo.nb;
   u32 excl = 0, sum = 0;
   for (int j = 0; j < geo.nb; j++) {
     const u32 cj = cnt[j];
     sum += cj;
     excl += j < t ? cj : 0u;
   }
-  const u32 rank = whole_rank(cnt, geo.nb, t);
-  items[whole_item_index(rank, (u32)bin, (u32)whole_nbins(geo))] = make_uint4(base + excl, c, bucket0 + (u32)t, 0u);
-  if (c > whole_limit(whole_group(geo, bin)) || sum > big_thresh) *bad = 1u;
+  const uint4 it = make_uint4(base + excl, c, bucket0 + (u32)t, G);
+  if (order != 1) {
+    if (!live) return;
+    const u32 rank = whole_rank(cnt, geo.nb, t);
+    items[whole_item_index(rank, (u32)bin, (u32)whole_nbins(geo))] = it;
+    if (c > whole_limit((int)G) || sum > big_thresh) *bad = 1u;
+    return;
+  }
+  u32 same = 0, same_before = 0;
+  for (int j = 0; j < geo.nb; j++) {
+    const bool e = keyv[j] == key;
+    same += e ? 1u : 0u;
+    same_before += (e && j < t) ? 1u : 0u;
+  }
+  const u32 cbase = whole_class_base(cls, key);
+  if (live && same_before == 0u) slot0[key] = atomicAdd(&table[(2 + region) * WHOLE_KEYS + key], same);
+  block_sync();
+  if (!live) return;
+  const u32 slot = cbase + slot0[key] + same_before;
+  if (slot < whole_region_items(geo, region))
+    items[(region == 1 ? whole_region_items(geo, 0) : 0u) + slot] = it;
+  else
+    *bad = 1u;
+  if (c > whole_limit((int)G) || sum > big_thresh) *bad = 1u;
 }
 
 // partner lane's value across a quad permute (lane ^ 1: 0xB1 = [1,0,3,2]; lane ^ 2: 0x4E = [2,3,0,1])
@@ -1409,20 +1458,31 @@ __device__ __forceinline__ Xyzz<CV> xyzz_quad_swap(const Xyzz<CV>& a) {
   return b;
 }
 
-// k_l1_whole: lane t serves part g of G of one item (l1_whole.h whole_lane_map / whole_part) with the software-
-// pipelined gather of the chunked loop (segreduce_lane: record one entry ahead through the buffer resource, index
-// word two ahead, look-ahead unconditional and clamped) and xyzz_madd_lazy, the first two entries peeled (a copy, then
-// the affine + affine xyzz_add_affine2_lazy): no bucket id is read, nothing is compared.  Then log2 G steps of the complete xyzz_add over the group (an empty part, a
-// doubling and P + (-P) included), and lane 0 of the group stores the bucket.  Count 0 writes nothing: the window
-// sums skip such buckets by their count.  Lanes past the grid's end stay in the kernel as empty parts, so that every
-// lane of a wave is active at the exchange.  `clk`: as k_segreduce.
+// k_l1_whole: lane t serves part g of G of one item (l1_whole.h whole_lane_map / whole_lane_map_len, whole_part) with
+// the software-pipelined gather of the chunked loop (segreduce_lane: record one entry ahead through the buffer
+// resource, index word two ahead, look-ahead unconditional and clamped) and xyzz_madd_lazy, the first two entries
+// peeled (a copy, then the affine + affine xyzz_add_affine2_lazy): no bucket id is read, nothing is compared.  Then the
+// parts of a bucket meet under the complete xyzz_add (an empty part, a doubling and P + (-P) included):
+//   dense (a workgroup of pairs only, whole_block_dense: uniform over the workgroup, decided before the barrier):
+//     every lane leaves its accumulator in LDS, word-major (word k of lane l at k * 256 + l: conflict-free), lane 2 j
+//     also its bucket id; after ONE barrier lane j of waves 0 and 1 reads the words of lanes 2 j and 2 j + 1 as one
+//     64-bit load each, adds them and stores bucket j; waves 2 and 3 leave.  Two full waves add where four half-used
+//     ones did.
+//   otherwise (a four-lane group or a padding tail in the workgroup): log2 G steps over quad permutes, and lane 0 of
+//     the group stores the bucket.
+// Count 0 writes nothing: the window sums skip such buckets by their count.  Lanes past the grid's end stay in the
+// kernel as empty parts, so that every lane of a wave is active at the exchange.  `clk`: as k_segreduce.
+// order 1: workgroup blockIdx.x runs the lanes of workgroup whole_block_interleave(blockIdx.x, nb0, nb1).
 template <class CV>
 __global__ void __launch_bounds__(256)
 k_l1_whole(const uint4* __restrict__ items, const uint2* __restrict__ sent, const u32* __restrict__ pts_in,
            const u32* __restrict__ bad, WholeGeom geo, u32 n_lanes, u32* __restrict__ buckets,
-           unsigned long long* __restrict__ clk) {
+           unsigned long long* __restrict__ clk, int order, int dense_on, u32 nb0, u32 nb1) {
   using IO = CurveIO<CV>;
   using Acc = RunAcc<CV, true>;
+  constexpr int RW = IO::RW;
+  static_assert(WHOLE_TB == 256, "the launch bound, the LDS layout");
+  static_assert(WHOLE_G >= 2, "the first merge step below is unconditional: every lane group has a partner lane");
   if (*bad != 0u) return;   // the chunked kernels run instead
   unsigned long long w0 = 0, c0 = 0;
   if (clk != nullptr && threadIdx.x == 0) {
@@ -1430,9 +1490,24 @@ k_l1_whole(const uint4* __restrict__ items, const uint2* __restrict__ sent, cons
     c0 = (unsigned long long)clock64();
     atomicMax(&clk[0], ~w0);
   }
-  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  auto stamp_end = [&]() {
+    if (clk != nullptr && (threadIdx.x & 63) == 0) {
+      const unsigned long long w1 = (unsigned long long)wall_clock64();
+      atomicMax(&clk[1], w1);
+      if (threadIdx.x == 0) {
+        atomicAdd(&clk[2], (unsigned long long)clock64() - c0);
+        atomicAdd(&clk[3], w1 - w0);
+      }
+    }
+  };
+  const u32 block = order == 1 ? whole_block_interleave(blockIdx.x, nb0, nb1) : blockIdx.x;
+  const bool dense = dense_on != 0 && whole_block_dense(geo, order, block, n_lanes);
+  const u32 t = block * blockDim.x + threadIdx.x;
   u32 item, g, G;
-  whole_lane_map(geo, t < n_lanes ? t : 0u, &item, &g, &G);
+  if (order == 1)
+    whole_lane_map_len(geo, t < n_lanes ? t : 0u, &item, &g, &G);
+  else
+    whole_lane_map(geo, t < n_lanes ? t : 0u, &item, &g, &G);
   const bool valid = t < n_lanes && item != WHOLE_NO_ITEM;   // (a padding lane: an empty part of no bucket)
   uint4 it = items[valid ? item : 0u];
   if (!valid) it.y = 0u;
@@ -1470,23 +1545,55 @@ k_l1_whole(const uint4* __restrict__ items, const uint2* __restrict__ sent, cons
       a = xyzz_madd_lazy(a, q, negate);
     }
   }
-  if (__ballot(G > 1u) != 0ull) {
-    const Xyzz<CV> b = xyzz_quad_swap<0xB1, CV>(a);
-    if (G > 1u) a = xyzz_add(a, b);
-  }
-  if (__ballot(G > 2u) != 0ull) {
-    const Xyzz<CV> b = xyzz_quad_swap<0x4E, CV>(a);
-    if (G > 2u) a = xyzz_add(a, b);
-  }
-  if (g == 0u && it.y != 0u) IO::store_rec_xyzz(a, buckets + (size_t)it.z * IO::REC_WORDS);
-  if (clk != nullptr && (threadIdx.x & 63) == 0) {
-    const unsigned long long w1 = (unsigned long long)wall_clock64();
-    atomicMax(&clk[1], w1);
-    if (threadIdx.x == 0) {
-      atomicAdd(&clk[2], (unsigned long long)clock64() - c0);
-      atomicAdd(&clk[3], w1 - w0);
+  extern __shared__ __attribute__((aligned(16))) u32 ozk_whole_lds[];   // 4 RW words of 256 lanes, then 128 bucket ids
+  if (dense) {
+    {
+      u32 w[4 * RW];
+      ElemTraits<typename CV::XX>::store_raw(a.X, w);
+      ElemTraits<typename CV::XY>::store_raw(a.Y, w + RW);
+      ElemTraits<typename CV::XZZ>::store_raw(a.ZZ, w + 2 * RW);
+      ElemTraits<typename CV::XZZZ>::store_raw(a.ZZZ, w + 3 * RW);
+#pragma unroll
+      for (int k = 0; k < 4 * RW; k++) ozk_whole_lds[k * WHOLE_TB + threadIdx.x] = w[k];
+      if (g == 0u) ozk_whole_lds[4 * RW * WHOLE_TB + (threadIdx.x >> 1)] = it.y != 0u ? it.z : WHOLE_NO_ITEM;
+    }
+    block_sync();
+    if (threadIdx.x >= WHOLE_TB / 2) {
+      stamp_end();
+      return;
     }
   }
+  // first step: the partner's sum from LDS (dense; then `a` too: lanes 2 j and 2 j + 1) or across the pair
+  Xyzz<CV> b;
+  u32 store_id;
+  if (dense) {
+    u32 wa[4 * RW], wb[4 * RW];
+#pragma unroll
+    for (int k = 0; k < 4 * RW; k++) {
+      const uint2 p = reinterpret_cast<const uint2*>(ozk_whole_lds + k * WHOLE_TB)[threadIdx.x];
+      wa[k] = p.x;
+      wb[k] = p.y;
+    }
+    a.X = ElemTraits<typename CV::XX>::load_raw(wa);
+    a.Y = ElemTraits<typename CV::XY>::load_raw(wa + RW);
+    a.ZZ = ElemTraits<typename CV::XZZ>::load_raw(wa + 2 * RW);
+    a.ZZZ = ElemTraits<typename CV::XZZZ>::load_raw(wa + 3 * RW);
+    b.X = ElemTraits<typename CV::XX>::load_raw(wb);
+    b.Y = ElemTraits<typename CV::XY>::load_raw(wb + RW);
+    b.ZZ = ElemTraits<typename CV::XZZ>::load_raw(wb + 2 * RW);
+    b.ZZZ = ElemTraits<typename CV::XZZZ>::load_raw(wb + 3 * RW);
+    store_id = ozk_whole_lds[4 * RW * WHOLE_TB + threadIdx.x];
+  } else {
+    b = xyzz_quad_swap<0xB1, CV>(a);
+    store_id = (g == 0u && it.y != 0u) ? it.z : WHOLE_NO_ITEM;
+  }
+  a = xyzz_add(a, b);   // (every group has at least two lanes)
+  if (!dense && __ballot(G > 2u) != 0ull) {
+    b = xyzz_quad_swap<0x4E, CV>(a);
+    if (G > 2u) a = xyzz_add(a, b);
+  }
+  if (store_id != WHOLE_NO_ITEM) IO::store_rec_xyzz(a, buckets + (size_t)store_id * IO::REC_WORDS);
+  stamp_end();
 }
 
 // ------------------------------------------------------------------ window sums

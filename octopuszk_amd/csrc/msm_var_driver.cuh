@@ -183,6 +183,8 @@ static MsmPlan make_plan(int n) {
   if (p.tail_rc != 1) p.tail_rc = 0;
   p.l1_whole = 0;   // (plan_for: G1 only)
   p.l1_gtop = WHOLE_G;
+  p.l1_order = knob(K_MSM_L1_ORDER) != 0 ? 1 : 0;
+  p.l1_dense = knob(K_MSM_L1_DENSE) != 0 ? 1 : 0;
   return p;
 }
 
@@ -528,8 +530,10 @@ int var_msm_accum(const MsmPlan& p, void* sorted, size_t sorted_bytes, void* acc
   if (tneed > tail_bytes) return fail(OZK_E_INVALID, "tail buffer too small: need %zu bytes, got %zu", tneed, tail_bytes);
   const int TB = 256;
   // whole-bucket level 1 where the plan asks for it and the items (16 bytes per bucket, 4 per sort bin) fit the accumulate scratch
+  // (and, under the length order only, its class table: 2 KiB more, l1_whole.h WHOLE_TABLE_WORDS)
+  const size_t whole_table_words = p.l1_order == 1 ? (size_t)WHOLE_TABLE_WORDS : 0;
   const bool whole = !CV::LDS_ACC && p.l1_whole && (1 << L.lo_bits) <= WHOLE_NB_MAX &&
-                     L.NB * sizeof(uint4) + (size_t)p.W * L.NH * sizeof(u32) <= rb.accum_ws;
+                     L.NB * sizeof(uint4) + ((size_t)p.W * L.NH + whole_table_words) * sizeof(u32) <= rb.accum_ws;
   u32* whole_bad = L.total + 2;
   g_l1_path_last.planned = whole ? 1 : 0;
   g_l1_path_last.d_bad = whole_bad;
@@ -573,16 +577,24 @@ int var_msm_accum(const MsmPlan& p, void* sorted, size_t sorted_bytes, void* acc
       const WholeGeom geo{p.W, L.NH, 1 << L.lo_bits, p.l1_gtop};
       const u32 big_thresh = (u32)(p.n / 64) > SORT_BIG ? (u32)(p.n / 64) : SORT_BIG;   // as var_msm_sort
       uint4* items = (uint4*)accum_ws;
-      u32* binsum = (u32*)(items + L.NB);
+      u32* table = (u32*)(items + L.NB);   // class table and slot cursors of the length order, then the bin sums
+      u32* binsum = table + whole_table_words;
+      static_assert(TB == WHOLE_TB && ((size_t)4 * CurveIO<CV>::RW * WHOLE_TB + WHOLE_TB / 2) * sizeof(u32) <= (size_t)L1_LDS_G1,
+                    "the dense merge's LDS lies inside what the launch asks for anyway");
+      // The table is summed by atomics, so it starts from zero: no launch of this stage precedes k_bin_sums, and the
+      // scratch is the caller's, so this memset is the one node the length order adds to the stream.
+      if (p.l1_order == 1) OZK_HIP(hipMemsetAsync(table, 0, WHOLE_TABLE_WORDS * sizeof(u32), st));
       hipLaunchKernelGGL(k_bin_sums, dim3((unsigned)whole_nbins(geo)), dim3(ITEMS_BLOCK), 0, st, (const u32*)L.hist, geo,
-                         p.cb, L.lo_bits, binsum);
+                         p.cb, L.lo_bits, binsum, p.l1_order, table);
       hipLaunchKernelGGL(k_bucket_items, dim3((unsigned)whole_nbins(geo)), dim3(ITEMS_BLOCK), 0, st, (const u32*)L.hist,
-                         (const u32*)binsum, geo, p.cb, L.lo_bits, big_thresh, items, whole_bad);
-      const long long wl = whole_lanes(geo);
+                         (const u32*)binsum, geo, p.cb, L.lo_bits, big_thresh, items, whole_bad, p.l1_order, table);
+      const long long wl = p.l1_order == 1 ? whole_lanes_len(geo) : whole_lanes(geo);
+      u32 nb0 = 0, nb1 = 0;
+      whole_len_blocks(geo, &nb0, &nb1);
       hipExtLaunchKernelGGL((k_l1_whole<CV>), dim3((unsigned)((wl + TB - 1) / TB)), dim3(TB), (uint32_t)acc_lds, st,
                             prof ? prof_e0 : (hipEvent_t) nullptr, prof ? prof_e1 : (hipEvent_t) nullptr, 0u,
                             (const uint4*)items, (const uint2*)L.sent, (const u32*)L.aff, (const u32*)whole_bad, geo,
-                            (u32)wl, L.buckets, clk);
+                            (u32)wl, L.buckets, clk, p.l1_order, p.l1_dense, nb0, nb1);
     }
   }
   // the lazily carried mixed addition (ec.cuh xyzz_madd_lazy) where the curve has it

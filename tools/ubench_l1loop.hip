@@ -298,7 +298,7 @@ int main() {
     const double ms_w = timeit([&] {
       hipLaunchKernelGGL((k_l1_whole<G1Cfg>), dim3((unsigned)((wl + 255) / 256)), dim3(256), lds, 0, (const uint4*)d_items,
                          (const uint2*)d_ent_p, (const u32*)d_pts, (const u32*)d_bad, geo, (u32)wl, d_buckets,
-                         (unsigned long long*)nullptr);
+                         (unsigned long long*)nullptr, 0, 0, 0u, 0u);   // (items in rank order, quad-permute merges)
     });
     printf("%-52s %.3f ms for %.2f M additions + %d merges -> %.3f ms per 16.78 M  (%lld lanes, %u blocks)\n",
            "W whole buckets on lane pairs (k_l1_whole)", ms_w, (double)NE * 1e-6, nruns, ms_w * 16.777216e6 / (double)NE, wl,
