@@ -694,6 +694,39 @@ int ozk_plonk_quotient_lookup_dev(const void* d_wit, int64_t wit_stride, const v
                                   const uint8_t* k_host96, const uint8_t* zh_inv_host128, const uint8_t* eta_host32,
                                   const uint8_t* theta_host32, void* d_out, void* stream);
 
+/* The witness of the PLONK prover built on the device (csrc/plonk_r1cs.cuh).  Conventions are
+ * those of the PLONK block above: plain 32-byte elements, reduced on load, canonical outputs, strides in elements.
+ *   ozk_fr_term_sums_dev       d_out[t] = sum_{u <= t} coeff[u] vec[index[u]] for t < terms: the inclusive running sum
+ *                              over the WHOLE stream, not segmented (the sum over terms t0 .. t is
+ *                              d_out[t] - d_out[t0 - 1], which ozk_plonk_wires_dev takes).  d_index: `terms` uint32;
+ *                              d_vec: n_vec elements; d_coeff: `terms` elements, or NULL when every coefficient is
+ *                              one.  A coefficient is stored in the form the kernel multiplies by: the word at
+ *                              d_coeff[u] is c_u 2^261 mod r (any 256-bit word is accepted and reduced on load, as
+ *                              every element is), so that its product with a plain element is plain.  A term whose
+ *                              index is >= n_vec is never read: it counts as zero and adds 1 to *d_bad (int32, zeroed
+ *                              by the call); no index makes the call read outside d_vec.  1 <= terms <= 2^28,
+ *                              1 <= n_vec < 2^32.  d_index, d_coeff, d_vec and d_out are 16-byte aligned.  The
+ *                              outputs must not overlap the inputs or one another, nor the workspace any of them
+ *                              (rejected).  No atomics on field data: bitwise reproducible.  Every input is read
+ *                              twice (once when terms <= 1024): 4 + 32 bytes a term and pass, + 32 with coefficients;
+ *                              d_out is written once.  Workspace: ozk_fr_term_sums_workspace_bytes(terms).
+ *   ozk_plonk_wires_dev        d_cells: k rows of len descriptors (hi, lo), two uint32 each, row y at
+ *                              d_cells + 8 y cell_stride.  d_out[y][i] = src[hi] - src[lo] mod r, or src[hi] alone when
+ *                              lo = 0xFFFFFFFF; output row y at d_out + 32 y out_stride (elements of a row beyond len
+ *                              are not touched).  A descriptor whose hi or lo (other than 0xFFFFFFFF) is >= n_src is
+ *                              not followed: its element is written as zero and adds 1 to *d_bad (int32, zeroed by
+ *                              the call).  1 <= k, 1 <= len, k len <= 2^28, 1 <= n_src < 2^32, both strides >= len.
+ *                              d_cells is 8-byte aligned.  d_out must not overlap d_src or d_cells, nor d_bad any of
+ *                              them (rejected).  With every descriptor (v, 0xFFFFFFFF) this is the gather of a
+ *                              circuit's wire columns from one value per variable.  No workspace.
+ * Size functions and rejections as above: 0 and OZK_E_INVALID before any launch, the shape before the pointers.
+ * Asynchronous on `stream`; nothing is allocated or synchronised. */
+size_t ozk_fr_term_sums_workspace_bytes(int32_t terms);
+int ozk_fr_term_sums_dev(const void* d_index, const void* d_coeff, const void* d_vec, int64_t n_vec, int32_t terms,
+                         void* d_out, int32_t* d_bad, void* d_workspace, size_t workspace_bytes, void* stream);
+int ozk_plonk_wires_dev(const void* d_src, int64_t n_src, const void* d_cells, int32_t k, int32_t len, int64_t cell_stride,
+                        void* d_out, int64_t out_stride, int32_t* d_bad, void* stream);
+
 /* ---- batched MSM over shared bases (msm_multi.hip; no counterpart in the reference, whose verifier runs one
  * variable-base MSM per proof): out_i = sum_{j < n} s_ij P_j for k scalar rows over the SAME n bases, G1 only.
  * A window table of every base is built once (ozk_multi_msm_prepare_dev); a run is table gathers and mixed

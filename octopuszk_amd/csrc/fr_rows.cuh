@@ -1,6 +1,6 @@
 // What the Fr kernels that walk rows of 32-byte elements share: kzg.cuh, kzg_set.cuh,
-// kzg_multi.cuh (the kzg.hip unit) and plonk.cuh, plonk_lookup.cuh (the plonk.hip unit) build on it.  Stands alone.
-// The per-lane pieces compile for the host too (tests/native/kzg_hostcheck.cpp, kzg_set_hostcheck.cpp); the device
+// kzg_multi.cuh (the kzg.hip unit) and plonk.cuh, plonk_lookup.cuh, plonk_r1cs.cuh (the plonk.hip unit) build on it.
+// Stands alone.  The per-lane pieces compile for the host too (tests/native/kzg_hostcheck.cpp, kzg_set_hostcheck.cpp); the device
 // parts use the element I/O of fr_tables.cuh and the barrier of curve.cuh, included below for the device compiler.
 //
 //   - the per-lane pieces: Horner's recurrence over a piece, the composition of carries, the chunk inversion;

@@ -27,13 +27,26 @@ Lookups: one table of three-column tuples, logUp as a run
 setup, prove and verify dispatch on the type of the circuit or key; the transcript of a proof with lookups has tags of
 its own, so neither kind of proof can be read as the other.
 
+Import of R1CS: an R1CS in CSR form (A, B, C with ptr, index, value; num_inputs, num_auxiliary:
+the shape of zksnark.R1CSRelation) compiles to a vanilla circuit, one gate a constraint and one addition gate for
+every term of a linear combination past its first.
+
+    circuit = plonk.from_r1cs(r1cs)                  # a plonk.R1CSCircuit; n_public = num_inputs, the leading one included
+    pk, vk = plonk.setup(circuit, commit_key)        # a plonk.R1CSProvingKey and an ordinary VerifyingKey
+    proof = plonk.prove(pk, full)                    # the R1CS assignment: ints, bytes, or a uint8 CUDA tensor
+    assert plonk.verify(vk, kzg_vk, primary, proof)
+
+An assignment that is already on the device (a uint8 CUDA tensor of 32-byte records, for any circuit) never visits the
+host: the wire columns are gathered there, and for an imported R1CS the chains' running sums are computed there.
+
 Out of scope: blinding, the linearisation polynomial, custom gates, several tables, tables wider than three columns,
-import of R1CS.  There is no CPU path.
+lookups in an imported R1CS.  There is no CPU path.
 """
-from .circuit import Builder, Circuit, LookupCircuit
+from .circuit import Builder, Circuit, LookupCircuit, R1CSCircuit, from_r1cs
 from .protocol import (LOOKUP_PROOF_BYTES, LOOKUP_STAGES, LOOKUP_VK_BYTES, PROOF_BYTES, LookupProof, LookupProvingKey,
-                       LookupVerifyingKey, Proof, ProvingKey, VerifyingKey, challenges, lookup_challenges, prove, setup, verify)
+                       LookupVerifyingKey, Proof, ProvingKey, R1CSProvingKey, VerifyingKey, challenges, lookup_challenges,
+                       prove, setup, verify)
 
 __all__ = ["Builder", "Circuit", "LookupCircuit", "LOOKUP_PROOF_BYTES", "LOOKUP_STAGES", "LOOKUP_VK_BYTES", "LookupProof",
-           "LookupProvingKey", "LookupVerifyingKey", "PROOF_BYTES", "Proof", "ProvingKey", "VerifyingKey", "challenges",
-           "lookup_challenges", "prove", "setup", "verify"]
+           "LookupProvingKey", "LookupVerifyingKey", "PROOF_BYTES", "Proof", "ProvingKey", "R1CSCircuit", "R1CSProvingKey",
+           "VerifyingKey", "challenges", "from_r1cs", "lookup_challenges", "prove", "setup", "verify"]

@@ -175,3 +175,105 @@ class Builder:
         if circuit.n_vars != self._n_vars:
             raise ValueError("variable %d is in no gate" % circuit.n_vars)
         return circuit
+
+
+class R1CSCircuit(Circuit):
+    """The circuit that from_r1cs compiles of an R1CS.  Variables 0 .. num_variables - 1 are the
+    R1CS's own, variable 0 the constant one; variable num_variables + t is the accumulator after position t of the term
+    stream: term_index (T variable numbers) and term_coeff (T ints in [0, r), or None when every one is 1) hold the
+    non-constant terms of every chained combination in row order, chain_start and chain_length where each chain lies
+    in the stream.  The slot of a chain's first term is in no cell.  n_vars = num_variables + T."""
+
+    def __init__(self, n, selectors, wires, n_public, num_variables, term_index, term_coeff, chain_start, chain_length):
+        super().__init__(n, selectors, wires, n_public)
+        self.num_variables = int(num_variables)
+        self.term_index, self.term_coeff = list(term_index), None if term_coeff is None else list(term_coeff)
+        self.chain_start, self.chain_length = list(chain_start), list(chain_length)
+        self.n_vars = self.num_variables + len(self.term_index)
+
+    def extend(self, full):
+        """the n_vars values of an R1CS assignment (num_variables ints in [0, r), full[0] = 1): the assignment, then
+        the running sum of every chain"""
+        values = [int(v) for v in full]
+        if len(values) != self.num_variables:
+            raise ValueError("%d values for %d variables" % (len(values), self.num_variables))
+        if any(not 0 <= v < FR for v in values):
+            raise ValueError("a value does not lie in [0, r)")
+        index, coeff = self.term_index, self.term_coeff
+        for start, length in zip(self.chain_start, self.chain_length):
+            acc = 0
+            for t in range(start, start + length):
+                acc = (acc + (values[index[t]] if coeff is None else coeff[t] * values[index[t]])) % FR
+                values.append(acc)
+        return values
+
+
+def _column_terms(lc, nv):
+    """(the number of rows, a function row -> its (index, coefficient) pairs) of one side of an R1CS"""
+    ptr, index = [int(p) for p in lc.ptr], [int(v) for v in lc.index]
+    value = None if lc.value is None else [int(c) % FR for c in lc.value]
+    if not ptr or ptr[0] != 0 or ptr[-1] != len(index) or any(a > b for a, b in zip(ptr, ptr[1:])):
+        raise ValueError("ptr does not split the %d terms into rows" % len(index))
+    if value is not None and len(value) != len(index):
+        raise ValueError("%d coefficients for %d terms" % (len(value), len(index)))
+    if any(not 0 <= v < nv for v in index):
+        raise ValueError("a term names a variable outside [0, %d)" % nv)
+    return len(ptr) - 1, lambda i: [(index[t], 1 if value is None else value[t]) for t in range(ptr[i], ptr[i + 1])]
+
+
+def from_r1cs(r1cs) -> R1CSCircuit:
+    """An R1CS as a vanilla circuit.  r1cs has A, B, C with ptr, index, value (CSR; value None: every coefficient is
+    one), num_inputs and num_auxiliary.  A term with index 0 contributes one whatever its coefficient, every other
+    term coefficient * variable; terms are neither merged nor reordered.  With k index-0 terms and p others a
+    combination is s x + k: s = 0 (p = 0), its one coefficient and variable (p = 1), or 1 and the last accumulator of
+    a chain of p - 1 addition gates (qL = c_1 or 1, qR = c_j, qO = -1).  The constraint is then the one gate
+    qM = sA sB, qL = sA kB, qR = sB kA, qO = -sC, qC = kA kB - kC over (xA, xB, xC).  Rows: the num_inputs public rows,
+    then per constraint the chains of A, B, C and its gate, then empty gates to a power of two."""
+    ni, nv = int(r1cs.num_inputs), int(r1cs.num_inputs) + int(r1cs.num_auxiliary)
+    if not 0 <= ni <= nv or nv < 1:
+        raise ValueError("num_inputs = %d of %d variables" % (ni, nv))
+    sides = [_column_terms(lc, nv) for lc in (r1cs.A, r1cs.B, r1cs.C)]
+    nc = sides[0][0]
+    if any(rows != nc for rows, _ in sides):
+        raise ValueError("A, B and C have %s rows" % ", ".join(str(rows) for rows, _ in sides))
+    unit = all(lc.value is None for lc in (r1cs.A, r1cs.B, r1cs.C))
+    sel, wires = [[1] * ni, [0] * ni, [0] * ni, [0] * ni, [0] * ni], [list(range(ni)) for _ in range(3)]
+    term_index, term_coeff, chain_start, chain_length = [], [], [], []
+
+    def gate(q, cells):
+        for col, v in zip(sel, q):
+            col.append(v)
+        for col, v in zip(wires, cells):
+            col.append(v)
+
+    def normal_form(terms):
+        """(s, x, k) with the combination = s x + k, after the chain gates it needs"""
+        k = sum(1 for v, _ in terms if v == 0)
+        rest = [(v, c) for v, c in terms if v != 0]
+        if len(rest) < 2:
+            return (rest[0][1], rest[0][0], k) if rest else (0, 0, k)
+        start = len(term_index)
+        chain_start.append(start)
+        chain_length.append(len(rest))
+        term_index.extend(v for v, _ in rest)
+        term_coeff.extend(c for _, c in rest)
+        gate((rest[0][1], rest[1][1], -1, 0, 0), (rest[0][0], rest[1][0], nv + start + 1))
+        for j in range(2, len(rest)):
+            gate((1, rest[j][1], -1, 0, 0), (nv + start + j - 1, rest[j][0], nv + start + j))
+        return 1, nv + start + len(rest) - 1, k
+
+    for i in range(nc):
+        (sa, xa, ka), (sb, xb, kb), (sc, xc, kc) = (normal_form(terms(i)) for _, terms in sides)
+        gate((sa * kb, sb * ka, -sc, sa * sb, ka * kb - kc), (xa, xb, xc))
+        if len(sel[0]) > N_MAX:
+            raise ValueError("the circuit has more than N_MAX = 2^26 rows")
+    if nv + len(term_index) >= (1 << 32) - 1:
+        raise ValueError("%d variables and %d chain terms: their sum must stay below 2^32 - 1" % (nv, len(term_index)))
+    if len(sel[0]) > N_MAX:
+        raise ValueError("the circuit has more than N_MAX = 2^26 rows")
+    n = 2
+    while n < len(sel[0]):
+        n *= 2
+    for _ in range(n - len(sel[0])):
+        gate((0, 0, 0, 0, 0), (0, 0, 0))
+    return R1CSCircuit(n, sel, wires, ni, nv, term_index, None if unit else term_coeff, chain_start, chain_length)

@@ -1,19 +1,22 @@
 """Setup, prover and verifier of the PLONK package: the transcript, the byte formats and the order
 of the device calls.  The group side is CommitKey.commit, CommitKey.open_multi and verify_multi; the field side is the
 transform and the three kernels of csrc/plonk.cuh.  A circuit with a lookup table has its own key,
-proof and transcript tags; its field side adds the kernels of csrc/plonk_lookup.cuh."""
+proof and transcript tags; its field side adds the kernels of csrc/plonk_lookup.cuh.  An imported R1CS (DESIGN.md section
+36) is a vanilla circuit with a key of its own kind, which holds what builds the witness on the device
+(csrc/plonk_r1cs.cuh)."""
 import time
 
 import numpy as np
 import torch
 
 from .. import kzg as _kzg
+from .. import lib as _lib
 from .. import transcript as _transcript
 from ..fft import FR, FR_MULT_GEN, root_of_unity
-from ..vectors import (fr_fft, fr_perm_product, fr_rows_coset, plonk_lookup_counts, plonk_lookup_index, plonk_lookup_sum,
-                       plonk_quotient, plonk_quotient_lookup)
-from ..wire import dev_bytes, ints32, le32, upload
-from .circuit import K, N_MAX, Circuit, LookupCircuit
+from ..vectors import (fr_fft, fr_perm_product, fr_rows_coset, fr_term_sums, plonk_lookup_counts, plonk_lookup_index,
+                       plonk_lookup_sum, plonk_quotient, plonk_quotient_lookup, plonk_wires)
+from ..wire import dev_bytes, host_bytes, ints32, le32, upload
+from .circuit import K, N_MAX, Circuit, LookupCircuit, R1CSCircuit
 
 PROOF_BYTES = 7 * 32 + 16 * 32 + 64
 VK_BYTES = 8 + 8 * 32
@@ -33,6 +36,8 @@ _UPLOAD, _WITNESS, _PRODUCT, _COSET, _QUOTIENT, _COMMIT, _OPEN, _COUNTS, _SUM = 
     "multi-opening", "lookup counts", "lookup sum")
 STAGES = (_UPLOAD, _WITNESS, _PRODUCT, _COSET, _QUOTIENT, _COMMIT, _OPEN)
 LOOKUP_STAGES = STAGES + (_COUNTS, _SUM)
+_NO_CELL = 0xFFFFFFFF                  # the `lo` of a cell descriptor that names one element (ozk_plonk_wires_dev)
+_MONT_R = 1 << 261                     # a coefficient c of the term stream is kept as c R mod r (ozk_fr_term_sums_dev)
 
 
 def _inv(v):
@@ -237,10 +242,13 @@ def zh_inverses(n):
 class ProvingKey:
     """What the prover keeps of one circuit: the circuit, the CommitKey, the eight coefficient rows qL .. s3 and the
     three rows of sigma labels on the device, the table of qL, qR, qO, qM, qC, s1, s2, s3, L_1 and the points
-    themselves on the coset of 4 n points (10 x 4 n x 32 bytes on the device), and the verifying key."""
+    themselves on the coset of 4 n points (10 x 4 n x 32 bytes on the device), and the verifying key.  cells: the
+    [3, n] cell descriptors (hi, lo) of ozk_plonk_wires_dev on the device, built on the first proof from an assignment
+    that is already there."""
 
     def __init__(self, circuit, commit_key, coeffs, sigma, table, vk):
         self.circuit, self.commit_key, self.coeffs, self.sigma, self.table, self.vk = circuit, commit_key, coeffs, sigma, table, vk
+        self.cells = None
 
 
 class LookupProvingKey(ProvingKey):
@@ -251,6 +259,50 @@ class LookupProvingKey(ProvingKey):
     def __init__(self, circuit, commit_key, coeffs, sigma, table, vk, lookup_rows, index):
         super().__init__(circuit, commit_key, coeffs, sigma, table, vk)
         self.lookup_rows, self.index = lookup_rows, index
+
+
+class R1CSProvingKey(ProvingKey):
+    """The proving key of an R1CSCircuit: a vanilla key that also holds, on the device, the term stream (term_index:
+    T uint32; term_coeff: T elements c R mod r, or None when every coefficient is one), the cell descriptors, in which
+    an accumulator is the difference of two running sums, and the workspace of the sums."""
+
+    def __init__(self, circuit, commit_key, coeffs, sigma, table, vk, term_index, term_coeff, cells, workspace):
+        super().__init__(circuit, commit_key, coeffs, sigma, table, vk)
+        self.term_index, self.term_coeff, self.cells, self.workspace = term_index, term_coeff, cells, workspace
+
+
+def _plain_cells(circuit):
+    """every cell names its variable alone: [3, n] descriptors (v, none)"""
+    hi = circuit.wire_index().astype(np.uint32)
+    return upload(np.stack([hi, np.full_like(hi, _NO_CELL)], axis=-1).view(np.uint8).reshape(-1))
+
+
+def _r1cs_cells(circuit):
+    """over src = [assignment | term sums]: variable v < nv is (v, none); the accumulator nv + t of a chain that starts
+    at stream position t0 is (nv + t, nv + t0 - 1), and (nv + t, none) when t0 = 0"""
+    nv = circuit.num_variables
+    hi = circuit.wire_index()
+    lo = np.full(hi.shape, _NO_CELL, dtype=np.int64)
+    if circuit.term_index:
+        starts = np.repeat(np.array(circuit.chain_start, dtype=np.int64), circuit.chain_length)
+        below = np.where(starts == 0, _NO_CELL, nv + starts - 1)
+        chained = hi >= nv
+        lo[chained] = below[hi[chained] - nv]
+    return upload(np.stack([hi, lo], axis=-1).astype(np.uint32).view(np.uint8).reshape(-1))
+
+
+def _r1cs_key(key, device):
+    circuit = key.circuit
+    terms = len(circuit.term_index)
+    index = coeff = workspace = None
+    if terms:
+        index = upload(np.array(circuit.term_index, dtype=np.uint32).view(np.uint8))
+        if circuit.term_coeff is not None:
+            coeff = dev_bytes(le32(c * _MONT_R % FR for c in circuit.term_coeff))
+        need = int(_lib.load().ozk_fr_term_sums_workspace_bytes(terms))
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+    return R1CSProvingKey(circuit, key.commit_key, key.coeffs, key.sigma, key.table, key.vk, index, coeff,
+                          _r1cs_cells(circuit), workspace)
 
 
 def _setup_lookup(circuit, commit_key):
@@ -269,7 +321,8 @@ def _setup_lookup(circuit, commit_key):
 
 def setup(circuit, commit_key):
     """(ProvingKey, VerifyingKey) of a circuit over a CommitKey of n bases: eight commitments, no secret; for a
-    LookupCircuit (LookupProvingKey, LookupVerifyingKey), twelve commitments"""
+    LookupCircuit (LookupProvingKey, LookupVerifyingKey), twelve commitments; for an R1CSCircuit (R1CSProvingKey,
+    VerifyingKey): the circuit is a vanilla one"""
     if isinstance(circuit, LookupCircuit):
         return _setup_lookup(circuit, commit_key)
     if not isinstance(circuit, Circuit):
@@ -283,7 +336,8 @@ def setup(circuit, commit_key):
     # L_1 = (X^n - 1) / (n (X - 1)) has every coefficient 1 / n; the points of the coset are the values of X
     extra = _rows([[_inv(n)] * n, [0, 1] + [0] * (n - 2)])
     table = _onto_coset(torch.cat([coeffs, extra]), 10, n)
-    return ProvingKey(circuit, commit_key, coeffs, sigma, table, vk), vk
+    key = ProvingKey(circuit, commit_key, coeffs, sigma, table, vk)
+    return (_r1cs_key(key, table.device) if isinstance(circuit, R1CSCircuit) else key), vk
 
 
 # ---------------------------------------------------------------------------- the prover
@@ -328,14 +382,56 @@ def _host_witness(circuit, assignment, wire_values):
     return host, public
 
 
-def _witness_on_device(circuit, assignment, timings, wire_values):
+def _device_witness(pk, assignment):
+    """(the three wire columns on the device, the public inputs) of an assignment that is on the device: for an
+    R1CSProvingKey the running sums of the term stream are written behind a copy of it; then the cells are gathered"""
+    circuit, n = pk.circuit, pk.circuit.n
+    if not assignment.is_cuda or assignment.dtype != torch.uint8:
+        raise TypeError("an assignment on the device is a uint8 CUDA tensor")
+    r1cs = isinstance(pk, R1CSProvingKey)
+    given = circuit.num_variables if r1cs else circuit.n_vars
+    if assignment.numel() != 32 * given:
+        raise ValueError("%d bytes for %d variables of 32 bytes" % (assignment.numel(), given))
+    src = assignment.contiguous().view(-1)
+    bad = torch.zeros(8, dtype=torch.uint8, device=src.device)             # two int32: of the cells, of the terms
+    if r1cs and pk.term_index is not None:
+        src = torch.empty(32 * circuit.n_vars, dtype=torch.uint8, device=src.device)
+        src[:32 * given].copy_(assignment.reshape(-1))
+        fr_term_sums(pk.term_index, pk.term_coeff, src, given, circuit.n_vars - given, src[32 * given:], bad[4:],
+                     pk.workspace)
+    if pk.cells is None:
+        pk.cells = _plain_cells(circuit)
+    wires = plonk_wires(src, circuit.n_vars, pk.cells, 3, n, n, bad)
+    host = host_bytes(torch.cat([bad, wires[0, :32 * circuit.n_public]]))
+    wrong = int.from_bytes(host[:4], "little") + int.from_bytes(host[4:8], "little")
+    if wrong:
+        raise RuntimeError("%d cell(s) or term(s) of the key point outside the assignment" % wrong)
+    return wires, [v % FR for v in ints32(host[8:])]
+
+
+def _r1cs_values(circuit, assignment):
+    """the n_vars values of an R1CS assignment given as ints or as their 32-byte records (taken mod r)"""
+    if isinstance(assignment, (bytes, bytearray)):
+        if len(assignment) != 32 * circuit.num_variables:
+            raise ValueError("%d bytes for %d variables of 32 bytes" % (len(assignment), circuit.num_variables))
+        assignment = [v % FR for v in ints32(bytes(assignment))]
+    return circuit.extend(assignment)
+
+
+def _witness_on_device(pk, assignment, timings, wire_values):
     """(the clock, the public inputs, the three wire columns on the device, their coefficient rows): how both
     provers begin"""
+    circuit = pk.circuit
     if (assignment is None) == (wire_values is None):
         raise ValueError("prove takes an assignment or the three columns of wire values")
     clock = _Clock(timings)
-    host, public = _host_witness(circuit, assignment, wire_values)
-    wires = upload(host)
+    if isinstance(assignment, torch.Tensor):
+        wires, public = _device_witness(pk, assignment)
+    else:
+        if assignment is not None and isinstance(circuit, R1CSCircuit):
+            assignment = _r1cs_values(circuit, assignment)
+        host, public = _host_witness(circuit, assignment, wire_values)
+        wires = upload(host)
     clock.lap(_UPLOAD)
     wire_coeffs = _interpolate(wires, 3, circuit.n)
     clock.lap(_WITNESS)
@@ -382,8 +478,11 @@ def _outside_domain(z, n):
 
 def prove(pk, assignment=None, timings=None, wire_values=None) -> Proof:
     """The proof of one assignment (one Fr value per variable: a list of ints, or their 32-byte little-endian records
-    back to back as bytes, which are taken mod r), or of a witness produced elsewhere and given cell by cell
-    (wire_values: the three columns a, b, c of n values).  ValueError, before any commitment to t, when the
+    back to back as bytes or as a uint8 CUDA tensor, which are taken mod r; the tensor's wire columns are gathered on
+    the device, and RuntimeError is raised if the key points outside it), or of a witness produced elsewhere and given
+    cell by cell (wire_values: the three columns a, b, c of n values).  With an R1CSProvingKey the assignment is the
+    R1CS's, num_variables values with the leading one: the accumulators of its chains are computed here, on the device
+    for a tensor.  ValueError, before any commitment to t, when the
     grand product does not close (a copy constraint is violated) or the quotient is no polynomial (a gate is violated,
     seen as a nonzero top quarter of its 4 n coefficients by one reduction on the device); RuntimeError when a
     denominator of the grand product is zero.  timings: a dict that receives the seconds of every stage of STAGES.
@@ -392,7 +491,7 @@ def prove(pk, assignment=None, timings=None, wire_values=None) -> Proof:
         return _prove_lookup(pk, assignment, timings, wire_values)
     circuit, ck, n = pk.circuit, pk.commit_key, pk.circuit.n
     vk_bytes = pk.vk.to_bytes()
-    clock, public, wires, wire_coeffs = _witness_on_device(circuit, assignment, timings, wire_values)
+    clock, public, wires, wire_coeffs = _witness_on_device(pk, assignment, timings, wire_values)
     abc = ck.commit(wire_coeffs)
     clock.lap(_COMMIT)
     beta, gamma = challenges(vk_bytes, public, abc)
@@ -425,7 +524,7 @@ def _prove_lookup(pk, assignment, timings, wire_values) -> LookupProof:
     lookup sum is zero or the sum does not close after a clean count.  timings receives LOOKUP_STAGES."""
     circuit, ck, n = pk.circuit, pk.commit_key, pk.circuit.n
     vk_bytes = pk.vk.to_bytes()
-    clock, public, wires, wire_coeffs = _witness_on_device(circuit, assignment, timings, wire_values)
+    clock, public, wires, wire_coeffs = _witness_on_device(pk, assignment, timings, wire_values)
     m_evals, missing, first = plonk_lookup_counts(wires, pk.lookup_rows[0], n, n, pk.lookup_rows[1:], circuit.n_table, n,
                                                   pk.index, n)
     if missing:

@@ -285,3 +285,33 @@ def plonk_quotient_lookup(wit, wit_stride, key, key_stride, n, alpha, beta, gamm
                                                le([gamma]), le(ks), le(zh_inv), le([eta]), le([theta]), _ptr(out),
                                                _stream()))
     return out
+
+
+def fr_term_sums(index, coeff, vec, n_vec, terms, out, bad, workspace=None):
+    """out[t] = sum_{u <= t} coeff[u] vec[index[u]], t < terms (ozk_fr_term_sums_dev): index `terms` uint32 on the
+    device, coeff their coefficients in the form c 2^261 mod r or None (every one is 1), vec n_vec elements, out
+    `terms` x 32 bytes, bad an int32 on the device that receives the number of indices >= n_vec.  Asynchronous on the
+    current stream over a `workspace` of the caller's; without one, synchronises (the workspace dies here)."""
+    L = _lib.load()
+    ws = workspace
+    if ws is None:
+        ws = torch.empty(max(int(L.ozk_fr_term_sums_workspace_bytes(terms)), 256), dtype=torch.uint8, device=vec.device)
+    _lib.check(L.ozk_fr_term_sums_dev(_ptr(index), None if coeff is None else _ptr(coeff), _ptr(vec), n_vec, terms,
+                                      _ptr(out), _ptr(bad), _ptr(ws), ws.numel(), _stream()))
+    if workspace is None:
+        torch.cuda.current_stream().synchronize()
+    return out
+
+
+def plonk_wires(src, n_src, cells, k, length, cell_stride, bad, out=None, out_stride=None):
+    """out[y][i] = src[hi] - src[lo], or src[hi] where lo = 0xFFFFFFFF, for k rows of `length` descriptors (hi, lo) of
+    two uint32 at cell_stride (ozk_plonk_wires_dev): k rows at out_stride (default length), a new tensor unless `out`
+    is given; bad an int32 on the device that receives the number of descriptors pointing outside src.  Asynchronous
+    on the current stream."""
+    L = _lib.load()
+    out_stride = length if out_stride is None else int(out_stride)
+    if out is None:
+        out = torch.empty((k, 32 * out_stride), dtype=torch.uint8, device=src.device)
+    _lib.check(L.ozk_plonk_wires_dev(_ptr(src), n_src, _ptr(cells), k, length, cell_stride, _ptr(out), out_stride,
+                                     _ptr(bad), _stream()))
+    return out

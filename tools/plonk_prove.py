@@ -18,7 +18,16 @@ share of the rows are lookups into a table of --table-rows rows (x, y, x xor y):
     also against a 256-row table (the most contended one), and against numpy on the host (np.unique over the 96-byte
     records, and the upload of m).
 
+With --r1cs LOG_NC [--inputs NI] the circuit is the import of the synthetic R1CS that
+tools/groth16_prove.py proves, serial_construct(2^LOG_NC, NI): about NI + 3.5 2^LOG_NC rows, so --r1cs 18 is n = 2^20.
+With --device-assignment the assignment of any circuit is a uint8 CUDA tensor, and the wire columns are built on the
+device.  The stage table is the same one; in both cases the run also reports
+(f) the compile time of the import, and ozk_fr_term_sums_dev and ozk_plonk_wires_dev alone under device events with
+    their counted traffic: per term and pass 4 + 32 bytes read (+ 32 with coefficients) and 32 written once; per cell
+    8 + 32 read (+ 32 where the cell is a difference) and 32 written.
+
     python tools/plonk_prove.py [--log-n 16] [--reps 5] [--public 3] [--lookups 0.5 --table-rows 256]
+    python tools/plonk_prove.py --r1cs 18 [--inputs 1023] [--device-assignment]
 """
 import argparse
 import ctypes
@@ -212,12 +221,64 @@ def _median_ms(samples):
     return statistics.median(samples) * 1e3
 
 
-def run(log_n, reps, n_public, share=0.0, table_rows=256):
-    n = 1 << log_n
+def witness_kernels(pk, d_assignment, reps):
+    """(f): the two entry points of csrc/plonk_r1cs.cuh alone, over the key's own term stream and cells"""
+    L = _lib.load()
+    circuit, n = pk.circuit, pk.circuit.n
+    res = {}
+    given = d_assignment.numel() // 32
+    src = torch.zeros(32 * circuit.n_vars, dtype=torch.uint8, device="cuda")
+    src[:32 * given].copy_(d_assignment)
+    bad = torch.zeros(8, dtype=torch.uint8, device="cuda")
+    terms = circuit.n_vars - given
+    if terms:
+        ws = pk.workspace
+
+        def sums():
+            _lib.check(L.ozk_fr_term_sums_dev(_ptr(pk.term_index), None if pk.term_coeff is None else _ptr(pk.term_coeff),
+                                              _ptr(src), given, terms, _ptr(src[32 * given:]), _ptr(bad[4:]), _ptr(ws),
+                                              ws.numel(), _stream()))
+
+        ms = kb._event_ms(sums, reps)
+        per_pass = 4 + 32 + (0 if pk.term_coeff is None else 32)
+        counted = terms * ((2 if terms > 1024 else 1) * per_pass + 32)
+        res["term_sums"] = {"terms": terms, "ms": ms, "counted_bytes": counted, "bytes_per_s": counted / (ms * 1e-3)}
+    if pk.cells is None:
+        pk.cells = protocol._plain_cells(circuit)
+    out = torch.empty((3, 32 * n), dtype=torch.uint8, device="cuda")
+
+    def gather():
+        _lib.check(L.ozk_plonk_wires_dev(_ptr(src), circuit.n_vars, _ptr(pk.cells), 3, n, n, _ptr(out), n, _ptr(bad),
+                                         _stream()))
+
+    ms = kb._event_ms(gather, reps)
+    differences = int((circuit.wire_index() >= given).sum()) if terms else 0
+    counted = 3 * n * (8 + 32 + 32) + 32 * differences
+    res["wires"] = {"cells": 3 * n, "differences": differences, "ms": ms, "counted_bytes": counted,
+                    "bytes_per_s": counted / (ms * 1e-3)}
+    assert not bad.any().item()
+    return res
+
+
+def run(log_n, reps, n_public, share=0.0, table_rows=256, r1cs_log=None, device_assignment=False):
     L = _lib.load()
     t0 = time.perf_counter()
-    circuit, assignment = chain(n, n_public)
-    public = assignment[:n_public]
+    imported = {}
+    if r1cs_log is None:
+        n = 1 << log_n
+        circuit, assignment = chain(n, n_public)
+        public = assignment[:n_public]
+    else:
+        from octopuszk_amd import zksnark
+        r1cs, public, auxiliary = zksnark.serial_construct(1 << r1cs_log, n_public)
+        assignment = public + auxiliary
+        t_compile = time.perf_counter()
+        circuit = plonk.from_r1cs(r1cs)
+        n = circuit.n
+        log_n = n.bit_length() - 1
+        imported = {"constraints": 1 << r1cs_log, "variables": circuit.num_variables, "chain_terms": len(circuit.term_index),
+                    "rows": sum(1 for i in range(n) if any(col[i] for col in circuit.selectors)),
+                    "compile_s": time.perf_counter() - t_compile}
     s = kb._String(n // 2)
     ck = kzg.CommitKey.from_srs(s, n)
     kvk = kzg.VerifyKey.from_srs(s)
@@ -227,13 +288,28 @@ def run(log_n, reps, n_public, share=0.0, table_rows=256):
     pk, vk = plonk.setup(circuit, ck)
     torch.cuda.synchronize()
     res = {"n": n, "n_public": n_public, "circuit_and_string_s": t1 - t0, "setup_s": time.perf_counter() - t1,
-           "proving_key_table_bytes": pk.table.numel()}
+           "proving_key_table_bytes": pk.table.numel(), "device_assignment": device_assignment}
+    if imported:
+        res["r1cs"] = imported
 
     # (a), (b): whole proofs
     as_ints = assignment
     assignment = wire.le32(as_ints)                                      # the 32-byte records: no per-value host work
+    d_assignment = wire.dev_bytes(assignment)
+    pk_device = pk
+    if device_assignment:
+        assignment = d_assignment                                        # already in HBM: the wires are built there
+    elif imported:
+        t_extend = time.perf_counter()
+        extended = circuit.extend(as_ints)
+        res["r1cs"]["extend_host_s"] = time.perf_counter() - t_extend     # what prove(pk, ints or bytes) adds per proof
+        assignment = wire.le32(extended)                                 # the host path with the chains summed once
+        plain = plonk.Circuit(n, circuit.selectors, circuit.wires, circuit.n_public)   # the same gates, every variable given
+        pk_host = plonk.ProvingKey(plain, ck, pk.coeffs, pk.sigma, pk.table, vk)
+        assert plonk.prove(pk_host, assignment).to_bytes() == plonk.prove(pk, d_assignment).to_bytes()
+        pk = pk_host
     proof = plonk.prove(pk, assignment)                                  # the warm-up
-    assert proof.to_bytes() == plonk.prove(pk, as_ints).to_bytes()
+    assert proof.to_bytes() == plonk.prove(pk_device, as_ints).to_bytes()
     assert plonk.verify(vk, kvk, public, proof)
     stages, whole, verify = {name: [] for name in plonk.protocol.STAGES}, [], []
     for _ in range(reps):
@@ -267,8 +343,12 @@ def run(log_n, reps, n_public, share=0.0, table_rows=256):
     res["fft_4n_ms"] = kb._median_ms(lambda: vectors.fr_fft(rows[0], 4 * n, root_of_unity(4 * n), out), reps)
     res["msm_and_fft_calls_ms"] = 9 * res["msm_n_ms"] + 5 * res["fft_n_ms"] + 6 * res["fft_4n_ms"]
 
+    # (f) the witness kernels alone
+    if imported or device_assignment:
+        res["witness_kernels"] = witness_kernels(pk_device, d_assignment, reps)
+
     # (c) the two kernels alone
-    wires = protocol._rows(circuit.wire_values(as_ints))
+    wires = protocol._rows(circuit.wire_values(circuit.extend(as_ints) if imported else as_ints))
     z = torch.empty(32 * n, dtype=torch.uint8, device="cuda")
     tail = torch.empty(48, dtype=torch.uint8, device="cuda")
     ws = torch.empty(max(int(L.ozk_fr_perm_product_workspace_bytes(n)), 256), dtype=torch.uint8, device="cuda")
@@ -292,7 +372,7 @@ def run(log_n, reps, n_public, share=0.0, table_rows=256):
     ms = kb._event_ms(quotient, reps)
     res["quotient"] = {"ms": ms, "counted_bytes": 32 * 4 * n * 17, "bytes_per_s": 32 * 4 * n * 17 / (ms * 1e-3)}
     if share > 0:
-        del pk, wit, wires
+        del pk, pk_device, wit, wires
         res["lookup"] = run_lookup(log_n, reps, n_public, share, table_rows, ck, kvk)
     return res
 
@@ -304,14 +384,25 @@ def main():
     ap.add_argument("--public", type=int, default=3)
     ap.add_argument("--lookups", type=float, default=0.0, help="the share of rows that are lookups (0: none)")
     ap.add_argument("--table-rows", type=int, default=256)
+    ap.add_argument("--r1cs", type=int, default=None, metavar="LOG_NC",
+                    help="prove the import of serial_construct(2^LOG_NC, --inputs) instead of the generated chain")
+    ap.add_argument("--inputs", type=int, default=None, help="the R1CS's num_inputs (default: min(1023, 2^LOG_NC))")
+    ap.add_argument("--device-assignment", action="store_true", help="hand prove the assignment as a CUDA tensor")
     a = ap.parse_args()
+    if a.r1cs is not None:
+        if not 1 <= a.r1cs <= 20 or a.lookups:
+            ap.error("1 <= --r1cs <= 20, without --lookups")
+        a.public = min(1023, 1 << a.r1cs) if a.inputs is None else a.inputs
+        if not 1 <= a.public <= (1 << a.r1cs) + 1:
+            ap.error("1 <= --inputs <= 2^LOG_NC + 1")
+        a.log_n = 16
     if not 2 <= a.log_n <= 22 or not 1 <= a.public < (1 << a.log_n) - 1:
         ap.error("2 <= --log-n <= 22 and 1 <= --public < 2^log-n - 1")
     if not 0 <= a.lookups <= 1 or not 1 <= a.table_rows <= 1 << a.log_n:
         ap.error("0 <= --lookups <= 1 and 1 <= --table-rows <= 2^log-n")
     torch.cuda.set_device(0)
     out = {"bench": "plonk_prove", "device": torch.cuda.get_device_name(0), "reps": a.reps,
-           "result": run(a.log_n, a.reps, a.public, a.lookups, a.table_rows)}
+           "result": run(a.log_n, a.reps, a.public, a.lookups, a.table_rows, a.r1cs, a.device_assignment)}
     print(json.dumps(out))
 
 
