@@ -727,6 +727,33 @@ int ozk_fr_term_sums_dev(const void* d_index, const void* d_coeff, const void* d
 int ozk_plonk_wires_dev(const void* d_src, int64_t n_src, const void* d_cells, int32_t k, int32_t len, int64_t cell_stride,
                         void* d_out, int64_t out_stride, int32_t* d_bad, void* stream);
 
+/* What makes a PLONK proof zero-knowledge (csrc/plonk_zk.cuh).  Conventions are those of the
+ * PLONK block above: plain 32-byte elements, reduced on load, canonical outputs, strides in elements, scalars 32-byte
+ * little-endian in HOST memory, taken mod r and read before the call returns.
+ *   ozk_fr_rows_blind_dev      In place on k coefficient rows, row y at d_rows + 32 y stride.  Row y takes
+ *                              counts_host[y] blinders r_0, r_1, .. (int32 in host memory, 0 .. 4 each) from
+ *                              blinders_host, where the blinders of all rows lie back to back in row order:
+ *                                row[j] = row[j] - r_j mod r and row[n + j] = r_j, j < counts_host[y],
+ *                              which adds (r_0 + r_1 X + ..)(X^n - 1) to the row's polynomial.  What row[n + j] held is
+ *                              not read; no other element is touched.  1 <= k <= 8, 4 <= n, stride >= n + 4,
+ *                              k stride <= 2^28.  One launch, no workspace.
+ *   ozk_plonk_quotient_split_dev  d_t: the 4 n coefficients of the quotient.  d_out receives three rows at out_stride
+ *                              (>= n + 8), each written up to the stride; with blinders_host128 = (u_0, u_1, v_0, v_1):
+ *                                t_lo'  = t[0 : n]        + (u_0 + u_1 X) X^n,
+ *                                t_mid' = t[n : 2 n]      - (u_0 + u_1 X) + (v_0 + v_1 X) X^n,
+ *                                t_hi'  = t[2 n : 3 n + 6] - (v_0 + v_1 X),
+ *                              zero beyond, so that t_lo' + X^n t_mid' + X^2n t_hi' = t[0 : 3 n + 6].  *d_nonzero (int32,
+ *                              zeroed by the call) is the number of coefficients t[i], 3 n + 6 <= i < 4 n, that are not
+ *                              zero mod r: they are in no output row.  n a power of two, 8 <= n <= 2^26,
+ *                              3 out_stride <= 2^28.  d_out must not overlap d_t, nor d_nonzero either (rejected).
+ *                              Every coefficient is read once, every output element written once.  No workspace.
+ * Rejections as above: OZK_E_INVALID before any launch, the shape before the pointers.  Asynchronous on `stream`;
+ * nothing is allocated or synchronised. */
+int ozk_fr_rows_blind_dev(void* d_rows, int32_t k, int32_t n, int64_t stride, const uint8_t* blinders_host,
+                          const int32_t* counts_host, void* stream);
+int ozk_plonk_quotient_split_dev(const void* d_t, int32_t n, void* d_out, int64_t out_stride, const uint8_t* blinders_host128,
+                                 int32_t* d_nonzero, void* stream);
+
 /* ---- batched MSM over shared bases (msm_multi.hip; no counterpart in the reference, whose verifier runs one
  * variable-base MSM per proof): out_i = sum_{j < n} s_ij P_j for k scalar rows over the SAME n bases, G1 only.
  * A window table of every base is built once (ozk_multi_msm_prepare_dev); a run is table gathers and mixed

@@ -135,6 +135,8 @@ _SIGS = {
     "ozk_fr_term_sums_workspace_bytes": (sz, [i32]),
     "ozk_fr_term_sums_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_int64, i32, vp, vp, vp, sz, vp]),
     "ozk_plonk_wires_dev": (ctypes.c_int, [vp, ctypes.c_int64, vp, i32, i32, ctypes.c_int64, vp, ctypes.c_int64, vp, vp]),
+    "ozk_fr_rows_blind_dev": (ctypes.c_int, [vp, i32, i32, ctypes.c_int64, vp, vp, vp]),
+    "ozk_plonk_quotient_split_dev": (ctypes.c_int, [vp, i32, vp, ctypes.c_int64, vp, vp, vp]),
     "ozk_multi_msm_table_bytes": (sz, [i32, i32]),
     "ozk_multi_msm_prepare_dev": (ctypes.c_int, [vp, i32, i32, vp, sz, vp, sz, vp]),
     "ozk_multi_msm_workspace_bytes": (sz, [i32, i32, i32]),

@@ -13,7 +13,7 @@ Vanilla PLONK over BN254 Fr: three wire columns, the gate qL a + qR b + qO c + q
 through one permutation of the 3 n cells (identity labels x, k1 x, k2 x with k1 = 5, k2 = 25).  Two deliberate
 simplifications: there is NO linearisation polynomial (the proof opens all fourteen polynomials at z and the grand
 product at z and z omega with one CommitKey.open_multi call, eight field elements more than the paper's proof), and
-there is NO blinding (the KZG layer is non-hiding: proofs are sound, not zero-knowledge).
+a proof is zero-knowledge only under a key of setup(zk=True) (below; the KZG layer itself is non-hiding).
 
 Lookups: one table of three-column tuples, logUp as a running sum beside the grand product.
 
@@ -39,14 +39,21 @@ every term of a linear combination past its first.
 An assignment that is already on the device (a uint8 CUDA tensor of 32-byte records, for any circuit) never visits the
 host: the wire columns are gathered there, and for an imported R1CS the chains' running sums are computed there.
 
-Out of scope: blinding, the linearisation polynomial, custom gates, several tables, tables wider than three columns,
+Zero knowledge: a key over ZK_PAD = 8 more bases blinds every polynomial the prover commits to by
+a multiple of Z_H, and the quotient's parts by terms that cancel; verifying key, proof bytes and verifier are the same.
+
+    pk, vk = plonk.setup(circuit, kzg.CommitKey.from_srs(srs, circuit.n + plonk.ZK_PAD), zk=True)     # n >= 8
+    proof = plonk.prove(pk, assignment)              # 13 blinders (18 with lookups) from secrets.randbelow
+    assert plonk.verify(vk, kzg_vk, public_inputs, proof)               # vk: byte for byte the one of zk=False
+
+Out of scope: the linearisation polynomial, custom gates, several tables, tables wider than three columns,
 lookups in an imported R1CS.  There is no CPU path.
 """
 from .circuit import Builder, Circuit, LookupCircuit, R1CSCircuit, from_r1cs
 from .protocol import (LOOKUP_PROOF_BYTES, LOOKUP_STAGES, LOOKUP_VK_BYTES, PROOF_BYTES, LookupProof, LookupProvingKey,
-                       LookupVerifyingKey, Proof, ProvingKey, R1CSProvingKey, VerifyingKey, challenges, lookup_challenges,
-                       prove, setup, verify)
+                       LookupVerifyingKey, Proof, ProvingKey, R1CSProvingKey, VerifyingKey, ZK_BLINDERS, ZK_LOOKUP_BLINDERS,
+                       ZK_PAD, challenges, lookup_challenges, prove, setup, verify)
 
 __all__ = ["Builder", "Circuit", "LookupCircuit", "LOOKUP_PROOF_BYTES", "LOOKUP_STAGES", "LOOKUP_VK_BYTES", "LookupProof",
            "LookupProvingKey", "LookupVerifyingKey", "PROOF_BYTES", "Proof", "ProvingKey", "R1CSCircuit", "R1CSProvingKey",
-           "VerifyingKey", "challenges", "from_r1cs", "lookup_challenges", "prove", "setup", "verify"]
+           "VerifyingKey", "ZK_BLINDERS", "ZK_LOOKUP_BLINDERS", "ZK_PAD", "challenges", "from_r1cs", "lookup_challenges", "prove", "setup", "verify"]

@@ -3,7 +3,9 @@ of the device calls.  The group side is CommitKey.commit, CommitKey.open_multi a
 transform and the three kernels of csrc/plonk.cuh.  A circuit with a lookup table has its own key,
 proof and transcript tags; its field side adds the kernels of csrc/plonk_lookup.cuh.  An imported R1CS (DESIGN.md section
 36) is a vanilla circuit with a key of its own kind, which holds what builds the witness on the device
-(csrc/plonk_r1cs.cuh)."""
+(csrc/plonk_r1cs.cuh).  A key of setup(zk=True) makes zero-knowledge proofs: its rows have
+ZK_PAD coefficients more, the prover blinds what it commits to (csrc/plonk_zk.cuh), and the verifier is the same."""
+import secrets
 import time
 
 import numpy as np
@@ -13,8 +15,9 @@ from .. import kzg as _kzg
 from .. import lib as _lib
 from .. import transcript as _transcript
 from ..fft import FR, FR_MULT_GEN, root_of_unity
-from ..vectors import (fr_fft, fr_perm_product, fr_rows_coset, fr_term_sums, plonk_lookup_counts, plonk_lookup_index,
-                       plonk_lookup_sum, plonk_quotient, plonk_quotient_lookup, plonk_wires)
+from ..vectors import (fr_fft, fr_perm_product, fr_rows_blind, fr_rows_coset, fr_term_sums, plonk_lookup_counts,
+                       plonk_lookup_index, plonk_lookup_sum, plonk_quotient, plonk_quotient_lookup, plonk_quotient_split,
+                       plonk_wires)
 from ..wire import dev_bytes, host_bytes, ints32, le32, upload
 from .circuit import K, N_MAX, Circuit, LookupCircuit, R1CSCircuit
 
@@ -38,6 +41,10 @@ STAGES = (_UPLOAD, _WITNESS, _PRODUCT, _COSET, _QUOTIENT, _COMMIT, _OPEN)
 LOOKUP_STAGES = STAGES + (_COUNTS, _SUM)
 _NO_CELL = 0xFFFFFFFF                  # the `lo` of a cell descriptor that names one element (ozk_plonk_wires_dev)
 _MONT_R = 1 << 261                     # a coefficient c of the term stream is kept as c R mod r (ozk_fr_term_sums_dev)
+ZK_PAD = 8                             # a row of a zero-knowledge key and proof has n + ZK_PAD coefficients
+ZK_N_MIN = 8                           # the quotient of blinded rows has up to 3 n + 6 <= 4 n coefficients
+ZK_BLINDERS = 13                       # a0 a1 b0 b1 c0 c1 Z0 Z1 Z2 u0 u1 v0 v1
+ZK_LOOKUP_BLINDERS = 18                # a0 a1 b0 b1 c0 c1 m0 m1 Z0 Z1 Z2 S0 S1 S2 u0 u1 v0 v1
 
 
 def _inv(v):
@@ -207,18 +214,22 @@ def _rows(values):
     return dev_bytes(le32(v for row in values for v in row)).view(len(values), -1)
 
 
-def _interpolate(evals, k, n):
-    """k rows of values on the domain of omega_n -> their coefficient rows (a new tensor)"""
+def _interpolate(evals, k, n, out_len=None):
+    """k rows of values on the domain of omega_n -> their coefficient rows (a new tensor), zero-extended to out_len
+    elements when that is given"""
     out = torch.empty_like(evals)
     w_inv = _inv(root_of_unity(n))
     for y in range(k):
         fr_fft(evals[y], n, w_inv, out[y])
-    return fr_rows_coset(out, k, n, n, 1, _inv(n), out)
+    if out_len is None:
+        return fr_rows_coset(out, k, n, n, 1, _inv(n), out)
+    return fr_rows_coset(out, k, n, n, 1, _inv(n), None, out_len)
 
 
-def _onto_coset(coeffs, k, n):
-    """k coefficient rows of n -> their values at g omega_4n^i, i < 4 n (a new tensor)"""
-    scaled = fr_rows_coset(coeffs, k, n, n, FR_MULT_GEN, 1, None, 4 * n)
+def _onto_coset(coeffs, k, n, length=None):
+    """k coefficient rows of n (of `length` <= 4 n when given) -> their values at g omega_4n^i, i < 4 n (a new tensor)"""
+    length = n if length is None else length
+    scaled = fr_rows_coset(coeffs, k, length, length, FR_MULT_GEN, 1, None, 4 * n)
     out = torch.empty_like(scaled)
     w4 = root_of_unity(4 * n)
     for y in range(k):
@@ -244,7 +255,9 @@ class ProvingKey:
     three rows of sigma labels on the device, the table of qL, qR, qO, qM, qC, s1, s2, s3, L_1 and the points
     themselves on the coset of 4 n points (10 x 4 n x 32 bytes on the device), and the verifying key.  cells: the
     [3, n] cell descriptors (hi, lo) of ozk_plonk_wires_dev on the device, built on the first proof from an assignment
-    that is already there."""
+    that is already there.  zk: the key is setup(zk=True)'s; its coefficient rows, and every row its prover commits to,
+    have commit_key.n = n + ZK_PAD elements."""
+    zk = False
 
     def __init__(self, circuit, commit_key, coeffs, sigma, table, vk):
         self.circuit, self.commit_key, self.coeffs, self.sigma, self.table, self.vk = circuit, commit_key, coeffs, sigma, table, vk
@@ -305,39 +318,59 @@ def _r1cs_key(key, device):
                           _r1cs_cells(circuit), workspace)
 
 
-def _setup_lookup(circuit, commit_key):
+def _key_row_len(circuit, commit_key, zk):
+    """the length of the key's coefficient rows: None for n itself (interpolated in place), n + ZK_PAD for a
+    zero-knowledge key; ValueError when the commit key has another number of bases"""
     n = circuit.n
-    if commit_key.n != n:
-        raise ValueError("the circuit has n = %d gates, the commit key n = %d bases" % (n, commit_key.n))
+    if not zk:
+        if commit_key.n != n:
+            raise ValueError("the circuit has n = %d gates, the commit key n = %d bases" % (n, commit_key.n))
+        return None
+    if n < ZK_N_MIN or commit_key.n != n + ZK_PAD:
+        raise ValueError("a zero-knowledge key takes a circuit of n >= %d gates and a commit key of n + %d bases: the "
+                         "circuit has n = %d, the commit key n = %d" % (ZK_N_MIN, ZK_PAD, n, commit_key.n))
+    return n + ZK_PAD
+
+
+def _setup_lookup(circuit, commit_key, zk):
+    n = circuit.n
+    row_len = _key_row_len(circuit, commit_key, zk)
     sigma = _rows(circuit.sigma_labels())
     lookup_rows = _rows([circuit.q_lookup] + circuit.table_columns())
-    coeffs = _interpolate(torch.cat([_rows(circuit.selectors), sigma, lookup_rows]), 12, n)
+    coeffs = _interpolate(torch.cat([_rows(circuit.selectors), sigma, lookup_rows]), 12, n, row_len)
     vk = LookupVerifyingKey(n, circuit.n_public, commit_key.commit(coeffs))
     extra = _rows([[_inv(n)] * n, [0, 1] + [0] * (n - 2)])
-    table = _onto_coset(torch.cat([coeffs[:8], extra, coeffs[8:]]), 14, n)
+    table = _onto_coset(torch.cat([coeffs[:8, :32 * n], extra, coeffs[8:, :32 * n]]), 14, n)
     index = plonk_lookup_index(lookup_rows[1:], circuit.n_table, n)
-    return LookupProvingKey(circuit, commit_key, coeffs, sigma, table, vk, lookup_rows, index), vk
+    key = LookupProvingKey(circuit, commit_key, coeffs, sigma, table, vk, lookup_rows, index)
+    key.zk = bool(zk)
+    return key, vk
 
 
-def setup(circuit, commit_key):
+def setup(circuit, commit_key, zk=False):
     """(ProvingKey, VerifyingKey) of a circuit over a CommitKey of n bases: eight commitments, no secret; for a
     LookupCircuit (LookupProvingKey, LookupVerifyingKey), twelve commitments; for an R1CSCircuit (R1CSProvingKey,
-    VerifyingKey): the circuit is a vanilla one"""
+    VerifyingKey): the circuit is a vanilla one.  zk: the proving key makes zero-knowledge proofs.
+    It takes n >= 8 and a CommitKey of n + ZK_PAD bases (ValueError otherwise) and keeps its coefficient rows
+    zero-extended to that length; the verifying key is the one of zk=False over n bases of the same string, byte for
+    byte."""
     if isinstance(circuit, LookupCircuit):
-        return _setup_lookup(circuit, commit_key)
+        return _setup_lookup(circuit, commit_key, zk)
     if not isinstance(circuit, Circuit):
         raise TypeError("setup takes a plonk.Circuit")
     n = circuit.n
-    if commit_key.n != n:
-        raise ValueError("the circuit has n = %d gates, the commit key n = %d bases" % (n, commit_key.n))
+    row_len = _key_row_len(circuit, commit_key, zk)
     sigma = _rows(circuit.sigma_labels())
-    coeffs = _interpolate(torch.cat([_rows(circuit.selectors), sigma]), 8, n)
+    coeffs = _interpolate(torch.cat([_rows(circuit.selectors), sigma]), 8, n, row_len)
     vk = VerifyingKey(n, circuit.n_public, commit_key.commit(coeffs))
     # L_1 = (X^n - 1) / (n (X - 1)) has every coefficient 1 / n; the points of the coset are the values of X
     extra = _rows([[_inv(n)] * n, [0, 1] + [0] * (n - 2)])
-    table = _onto_coset(torch.cat([coeffs, extra]), 10, n)
+    table = _onto_coset(torch.cat([coeffs[:, :32 * n], extra]), 10, n)
     key = ProvingKey(circuit, commit_key, coeffs, sigma, table, vk)
-    return (_r1cs_key(key, table.device) if isinstance(circuit, R1CSCircuit) else key), vk
+    if isinstance(circuit, R1CSCircuit):
+        key = _r1cs_key(key, table.device)
+    key.zk = bool(zk)
+    return key, vk
 
 
 # ---------------------------------------------------------------------------- the prover
@@ -418,9 +451,26 @@ def _r1cs_values(circuit, assignment):
     return circuit.extend(assignment)
 
 
-def _witness_on_device(pk, assignment, timings, wire_values):
+def _drawn_blinders(pk, blinders, count):
+    """None for a key without zk (which takes no blinders: ValueError); else the `count` blinders of one proof, drawn
+    here unless given (ValueError for another number of them or one outside [0, r))"""
+    if not pk.zk:
+        if blinders is not None:
+            raise ValueError("blinders are for a key of setup(zk=True): this key makes no zero-knowledge proofs")
+        return None
+    if blinders is None:
+        return [secrets.randbelow(FR) for _ in range(count)]
+    blinders = list(blinders)
+    if len(blinders) != count:
+        raise ValueError("%d blinders: a proof under this key takes %d" % (len(blinders), count))
+    if any(not isinstance(r, int) or not 0 <= r < FR for r in blinders):
+        raise ValueError("blinders are ints in [0, r)")
+    return blinders
+
+
+def _witness_on_device(pk, assignment, timings, wire_values, blinders=None):
     """(the clock, the public inputs, the three wire columns on the device, their coefficient rows): how both
-    provers begin"""
+    provers begin.  blinders: a0 a1 b0 b1 c0 c1 of a zero-knowledge key, whose rows have commit_key.n coefficients"""
     circuit = pk.circuit
     if (assignment is None) == (wire_values is None):
         raise ValueError("prove takes an assignment or the three columns of wire values")
@@ -433,7 +483,12 @@ def _witness_on_device(pk, assignment, timings, wire_values):
         host, public = _host_witness(circuit, assignment, wire_values)
         wires = upload(host)
     clock.lap(_UPLOAD)
-    wire_coeffs = _interpolate(wires, 3, circuit.n)
+    if blinders is None:
+        wire_coeffs = _interpolate(wires, 3, circuit.n)
+    else:
+        row_len = pk.commit_key.n
+        wire_coeffs = _interpolate(wires, 3, circuit.n, row_len)
+        fr_rows_blind(wire_coeffs, 3, circuit.n, row_len, [blinders[0:2], blinders[2:4], blinders[4:6]])
     clock.lap(_WITNESS)
     return clock, public, wires, wire_coeffs
 
@@ -449,22 +504,28 @@ def _grand_product(wires, sigma, n, beta, gamma, clock):
     return z_evals
 
 
-def _public_input_row(public, n, device):
+def _public_input_row(public, n, device, out_len=None):
     """the coefficients of PI: -x_i in row i of the domain"""
     pi_evals = torch.zeros((1, 32 * n), dtype=torch.uint8, device=device)
     if public:
         pi_evals[0, :32 * len(public)] = dev_bytes(le32((FR - x) % FR for x in public))
-    return _interpolate(pi_evals, 1, n)
+    return _interpolate(pi_evals, 1, n, out_len)
 
 
-def _quotient_parts(t_evals, n, ck, clock):
+def _quotient_parts(t_evals, n, ck, clock, blinders=None):
     """(t_lo, t_mid, t_hi as three coefficient rows, their commitments) of the quotient's values on the coset;
-    ValueError when its top quarter is not zero"""
+    ValueError when its top quarter is not zero.  blinders: u0 u1 v0 v1 of a zero-knowledge key: the rows have ck.n
+    coefficients and are blinded, and the quotient may reach 3 n + 6 coefficients, zero from there on"""
     t = _off_coset(t_evals, n)
-    if bool(t[32 * 3 * n:].any().item()):
-        raise ValueError("a gate is violated: the quotient is no polynomial")
+    if blinders is None:
+        if bool(t[32 * 3 * n:].any().item()):
+            raise ValueError("a gate is violated: the quotient is no polynomial")
+        t_rows = t[:32 * 3 * n].view(3, 32 * n)
+    else:
+        t_rows, nonzero = plonk_quotient_split(t, n, ck.n, blinders)
+        if nonzero:
+            raise ValueError("a gate is violated: the quotient is no polynomial")
     clock.lap(_COSET)
-    t_rows = t[:32 * 3 * n].view(3, 32 * n)
     t_commitments = ck.commit(t_rows)
     clock.lap(_COMMIT)
     return t_rows, t_commitments
@@ -476,7 +537,7 @@ def _outside_domain(z, n):
     return z
 
 
-def prove(pk, assignment=None, timings=None, wire_values=None) -> Proof:
+def prove(pk, assignment=None, timings=None, wire_values=None, blinders=None) -> Proof:
     """The proof of one assignment (one Fr value per variable: a list of ints, or their 32-byte little-endian records
     back to back as bytes or as a uint8 CUDA tensor, which are taken mod r; the tensor's wire columns are gathered on
     the device, and RuntimeError is raised if the key points outside it), or of a witness produced elsewhere and given
@@ -486,27 +547,37 @@ def prove(pk, assignment=None, timings=None, wire_values=None) -> Proof:
     grand product does not close (a copy constraint is violated) or the quotient is no polynomial (a gate is violated,
     seen as a nonzero top quarter of its 4 n coefficients by one reduction on the device); RuntimeError when a
     denominator of the grand product is zero.  timings: a dict that receives the seconds of every stage of STAGES.
-    With a LookupProvingKey the proof is a LookupProof (_prove_lookup)."""
+    With a LookupProvingKey the proof is a LookupProof (_prove_lookup).
+    Under a key of setup(zk=True) the proof is zero-knowledge: every polynomial the prover
+    commits to is blinded by a multiple of Z_H (the quotient's parts by terms that cancel in t), with 13 scalars, 18
+    for a proof with lookups, drawn here from secrets.randbelow.  blinders: those scalars given instead, ints in
+    [0, r) in the section's order, for tests and models (ValueError for another number of them, one out of range, or
+    any under a key without zk); all zero, they give the proof of the key without zk.  Inputs, errors, bytes and the
+    verifier are the same."""
     if isinstance(pk, LookupProvingKey):
-        return _prove_lookup(pk, assignment, timings, wire_values)
+        return _prove_lookup(pk, assignment, timings, wire_values, blinders)
     circuit, ck, n = pk.circuit, pk.commit_key, pk.circuit.n
+    zk = _drawn_blinders(pk, blinders, ZK_BLINDERS)
+    row_len = ck.n if zk else None
     vk_bytes = pk.vk.to_bytes()
-    clock, public, wires, wire_coeffs = _witness_on_device(pk, assignment, timings, wire_values)
+    clock, public, wires, wire_coeffs = _witness_on_device(pk, assignment, timings, wire_values, zk)
     abc = ck.commit(wire_coeffs)
     clock.lap(_COMMIT)
     beta, gamma = challenges(vk_bytes, public, abc)
     z_evals = _grand_product(wires, pk.sigma, n, beta, gamma, clock)
-    z_coeffs = _interpolate(z_evals.unsqueeze(0), 1, n)
-    pi_coeffs = _public_input_row(public, n, wires.device)
+    z_coeffs = _interpolate(z_evals.unsqueeze(0), 1, n, row_len)
+    if zk:
+        fr_rows_blind(z_coeffs, 1, n, row_len, [zk[6:9]])
+    pi_coeffs = _public_input_row(public, n, wires.device, row_len)
     clock.lap(_WITNESS)
     z_commitment = ck.commit(z_coeffs)[0]
     clock.lap(_COMMIT)
     alpha = challenges(vk_bytes, public, abc, z_commitment)[2]
-    wit = _onto_coset(torch.cat([wire_coeffs, z_coeffs, pi_coeffs]), 5, n)
+    wit = _onto_coset(torch.cat([wire_coeffs, z_coeffs, pi_coeffs]), 5, n, row_len)
     clock.lap(_COSET)
     t_evals = plonk_quotient(wit, 4 * n, pk.table, 4 * n, n, alpha, beta, gamma, K, zh_inverses(n))
     clock.lap(_QUOTIENT)
-    t_rows, t_commitments = _quotient_parts(t_evals, n, ck, clock)
+    t_rows, t_commitments = _quotient_parts(t_evals, n, ck, clock, zk[9:] if zk else None)
     z = _outside_domain(challenges(vk_bytes, public, abc, z_commitment, t_commitments)[3], n)
     rows = torch.cat([wire_coeffs, t_rows, pk.coeffs, z_coeffs])
     mo = ck.open_multi(rows, _point_sets(n, z), abc + t_commitments + list(pk.vk.commitments) + [z_commitment])
@@ -518,19 +589,23 @@ def _point_sets(n, z):
     return [[z]] * 14 + [[z, z * root_of_unity(n) % FR]]
 
 
-def _prove_lookup(pk, assignment, timings, wire_values) -> LookupProof:
+def _prove_lookup(pk, assignment, timings, wire_values, blinders=None) -> LookupProof:
     """The proof of a circuit with lookups.  As prove, and: ValueError naming the first offending row, before any
     commitment, when a row with qK = 1 holds a tuple that is in no table row; RuntimeError when a denominator of the
     lookup sum is zero or the sum does not close after a clean count.  timings receives LOOKUP_STAGES."""
     circuit, ck, n = pk.circuit, pk.commit_key, pk.circuit.n
+    zk = _drawn_blinders(pk, blinders, ZK_LOOKUP_BLINDERS)
+    row_len = ck.n if zk else None
     vk_bytes = pk.vk.to_bytes()
-    clock, public, wires, wire_coeffs = _witness_on_device(pk, assignment, timings, wire_values)
+    clock, public, wires, wire_coeffs = _witness_on_device(pk, assignment, timings, wire_values, zk)
     m_evals, missing, first = plonk_lookup_counts(wires, pk.lookup_rows[0], n, n, pk.lookup_rows[1:], circuit.n_table, n,
                                                   pk.index, n)
     if missing:
         raise ValueError("row %d looks up a tuple that is in no row of the table (%d such row(s))" % (first, missing))
     clock.lap(_COUNTS)
-    m_coeffs = _interpolate(m_evals.view(1, -1), 1, n)
+    m_coeffs = _interpolate(m_evals.view(1, -1), 1, n, row_len)
+    if zk:
+        fr_rows_blind(m_coeffs, 1, n, row_len, [zk[6:8]])
     clock.lap(_WITNESS)
     abcm = ck.commit(torch.cat([wire_coeffs, m_coeffs]))
     clock.lap(_COMMIT)
@@ -542,17 +617,19 @@ def _prove_lookup(pk, assignment, timings, wire_values) -> LookupProof:
     if s_total != 0:
         raise RuntimeError("the lookup sum does not close after a clean count")
     clock.lap(_SUM)
-    zs_coeffs = _interpolate(torch.stack([z_evals, s_evals]), 2, n)
-    pi_coeffs = _public_input_row(public, n, wires.device)
+    zs_coeffs = _interpolate(torch.stack([z_evals, s_evals]), 2, n, row_len)
+    if zk:
+        fr_rows_blind(zs_coeffs, 2, n, row_len, [zk[8:11], zk[11:14]])
+    pi_coeffs = _public_input_row(public, n, wires.device, row_len)
     clock.lap(_WITNESS)
     zs_commitments = ck.commit(zs_coeffs)
     clock.lap(_COMMIT)
     alpha = lookup_challenges(vk_bytes, public, abcm, zs_commitments)[4]
-    wit = _onto_coset(torch.cat([wire_coeffs, zs_coeffs[:1], pi_coeffs, m_coeffs, zs_coeffs[1:]]), 7, n)
+    wit = _onto_coset(torch.cat([wire_coeffs, zs_coeffs[:1], pi_coeffs, m_coeffs, zs_coeffs[1:]]), 7, n, row_len)
     clock.lap(_COSET)
     t_evals = plonk_quotient_lookup(wit, 4 * n, pk.table, 4 * n, n, alpha, beta, gamma, K, zh_inverses(n), eta, theta)
     clock.lap(_QUOTIENT)
-    t_rows, t_commitments = _quotient_parts(t_evals, n, ck, clock)
+    t_rows, t_commitments = _quotient_parts(t_evals, n, ck, clock, zk[14:] if zk else None)
     z = _outside_domain(lookup_challenges(vk_bytes, public, abcm, zs_commitments, t_commitments)[5], n)
     rows = torch.cat([wire_coeffs, m_coeffs, t_rows, pk.coeffs, zs_coeffs])
     mo = ck.open_multi(rows, _lookup_point_sets(n, z), abcm + t_commitments + list(pk.vk.commitments) + zs_commitments)

@@ -315,3 +315,33 @@ def plonk_wires(src, n_src, cells, k, length, cell_stride, bad, out=None, out_st
     _lib.check(L.ozk_plonk_wires_dev(_ptr(src), n_src, _ptr(cells), k, length, cell_stride, _ptr(out), out_stride,
                                      _ptr(bad), _stream()))
     return out
+
+
+def fr_rows_blind(rows, k, n, stride, blinders):
+    """In place on k coefficient rows at `stride` >= n + 4 elements (ozk_fr_rows_blind_dev): row y takes the blinders
+    blinders[y] (a sequence of up to four ints), row[j] -= r_j and row[n + j] = r_j, which leaves its values on the
+    domain of n points as they are.  Returns `rows`.  Asynchronous on the current stream."""
+    L = _lib.load()
+    if len(blinders) != k:
+        raise ValueError("%d sequences of blinders for %d rows" % (len(blinders), k))
+    counts = (ctypes.c_int32 * k)(*[len(row) for row in blinders])
+    flat = _wire.le32([int(r) % FR for row in blinders for r in row]) or bytes(32)
+    _lib.check(L.ozk_fr_rows_blind_dev(_ptr(rows), k, n, stride, _wire.vp(flat), ctypes.cast(counts, ctypes.c_void_p),
+                                       _stream()))
+    return rows
+
+
+def plonk_quotient_split(t, n, out_stride, blinders, out=None):
+    """The 4 n coefficients of a quotient -> (its three parts t_lo', t_mid', t_hi' as rows at out_stride >= n + 8
+    elements, zero up to the stride and blinded by blinders = (u0, u1, v0, v1), a new [3, 32 out_stride] tensor unless
+    `out` is given; how many of the coefficients from 3 n + 6 are not zero) (ozk_plonk_quotient_split_dev).
+    Synchronises."""
+    L = _lib.load()
+    if len(blinders) != 4:
+        raise ValueError("%d blinders of the quotient's parts, not 4" % len(blinders))
+    if out is None:
+        out = torch.empty((3, 32 * out_stride), dtype=torch.uint8, device=t.device)
+    count = torch.empty(16, dtype=torch.uint8, device=t.device)
+    _lib.check(L.ozk_plonk_quotient_split_dev(_ptr(t), n, _ptr(out), out_stride,
+                                              _wire.vp(_wire.le32([int(r) % FR for r in blinders])), _ptr(count), _stream()))
+    return out, int.from_bytes(_wire.host_bytes(count[:4]), "little", signed=True)

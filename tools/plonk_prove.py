@@ -26,8 +26,13 @@ device.  The stage table is the same one; in both cases the run also reports
     their counted traffic: per term and pass 4 + 32 bytes read (+ 32 with coefficients) and 32 written once; per cell
     8 + 32 read (+ 32 where the cell is a difference) and 32 written.
 
-    python tools/plonk_prove.py [--log-n 16] [--reps 5] [--public 3] [--lookups 0.5 --table-rows 256]
-    python tools/plonk_prove.py --r1cs 18 [--inputs 1023] [--device-assignment]
+With --zk every circuit of the run is also set up with zk=True over n + 8 bases of the same
+string and proved with drawn blinders, after its proof without zk and in the same process:
+(g) the stage table and the rounds of whole proofs under the zero-knowledge key ("zk" beside the figures without), and
+    the zero-knowledge proof verified under the verifying key of the key without zk.
+
+    python tools/plonk_prove.py [--log-n 16] [--reps 5] [--public 3] [--lookups 0.5 --table-rows 256] [--zk]
+    python tools/plonk_prove.py --r1cs 18 [--inputs 1023] [--device-assignment] [--zk]
 """
 import argparse
 import ctypes
@@ -106,20 +111,10 @@ def chain_with_lookups(n, n_public, share, table):
     return plonk.LookupCircuit(n, sel, wires, n_public, q_lookup, table), values
 
 
-def run_lookup(log_n, reps, n_public, share, table_rows, ck, kvk):
-    n = 1 << log_n
-    L = _lib.load()
-    circuit, as_ints = chain_with_lookups(n, n_public, share, xor_table(table_rows))
-    public = as_ints[:n_public]
-    t0 = time.perf_counter()
-    pk, vk = plonk.setup(circuit, ck)
-    torch.cuda.synchronize()
-    res = {"lookups": sum(circuit.q_lookup), "table_rows": table_rows, "setup_s": time.perf_counter() - t0,
-           "proving_key_table_bytes": pk.table.numel(), "index_bytes": pk.index.numel()}
-    assignment = wire.le32(as_ints)
-    proof = plonk.prove(pk, assignment)
-    assert plonk.verify(vk, kvk, public, proof)
-    stages, whole, verify = {name: [] for name in plonk.LOOKUP_STAGES}, [], []
+def prove_rounds(pk, vk, kvk, public, assignment, reps, stage_names):
+    """(a): `reps` whole proofs by the host clock, then `reps` proofs stage by stage, each verified.  pk has proved
+    once already (the warm-up)."""
+    stages, whole, verify = {name: [] for name in stage_names}, [], []
     for _ in range(reps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -136,10 +131,48 @@ def run_lookup(log_n, reps, n_public, share, table_rows, ck, kvk):
         assert plonk.verify(vk, kvk, public, proof)
         torch.cuda.synchronize()
         verify.append(time.perf_counter() - t0)
-    res["stages_ms"] = {name: _median_ms(v) for name, v in stages.items()}
+    res = {"stages_ms": {name: _median_ms(v) for name, v in stages.items()}}
     res["stages_ms"]["verification"] = _median_ms(verify)
     res["prove_ms"] = _median_ms(whole)
+    res["prove_rounds_ms"] = [x * 1e3 for x in whole]
     res["proof_bytes"] = len(proof.to_bytes())
+    return res
+
+
+def zk_rounds(circuit, zk_ck, pk, vk, kvk, public, assignment, reps, stage_names):
+    """(g): the circuit under a key of setup(zk=True), proved as `pk`, the key without zk, was: a ProvingKey over the
+    same rows when `pk` is one of a plain circuit (the host path of an imported R1CS)"""
+    t0 = time.perf_counter()
+    zk_pk, zk_vk = plonk.setup(circuit, zk_ck, zk=True)
+    torch.cuda.synchronize()
+    res = {"row_length": zk_ck.n, "setup_s": time.perf_counter() - t0}
+    assert zk_vk.to_bytes() == vk.to_bytes()
+    if type(pk) is plonk.ProvingKey and type(zk_pk) is not plonk.ProvingKey:
+        zk_pk = plonk.ProvingKey(pk.circuit, zk_ck, zk_pk.coeffs, zk_pk.sigma, zk_pk.table, zk_vk)
+        zk_pk.zk = True
+    proof = plonk.prove(zk_pk, assignment)                               # the warm-up
+    assert plonk.verify(vk, kvk, public, proof)
+    assert proof.to_bytes() != plonk.prove(zk_pk, assignment).to_bytes()
+    res.update(prove_rounds(zk_pk, vk, kvk, public, assignment, reps, stage_names))
+    return res
+
+
+def run_lookup(log_n, reps, n_public, share, table_rows, ck, kvk, zk_ck=None):
+    n = 1 << log_n
+    L = _lib.load()
+    circuit, as_ints = chain_with_lookups(n, n_public, share, xor_table(table_rows))
+    public = as_ints[:n_public]
+    t0 = time.perf_counter()
+    pk, vk = plonk.setup(circuit, ck)
+    torch.cuda.synchronize()
+    res = {"lookups": sum(circuit.q_lookup), "table_rows": table_rows, "setup_s": time.perf_counter() - t0,
+           "proving_key_table_bytes": pk.table.numel(), "index_bytes": pk.index.numel()}
+    assignment = wire.le32(as_ints)
+    proof = plonk.prove(pk, assignment)
+    assert plonk.verify(vk, kvk, public, proof)
+    res.update(prove_rounds(pk, vk, kvk, public, assignment, reps, plonk.LOOKUP_STAGES))
+    if zk_ck is not None:
+        res["zk"] = zk_rounds(circuit, zk_ck, pk, vk, kvk, public, assignment, reps, plonk.LOOKUP_STAGES)
 
     # (e) the entry points alone
     host_wires = np.frombuffer(wire.le32(v for col in circuit.wire_values(as_ints) for v in col), dtype=np.uint8).reshape(3, n, 32)
@@ -260,7 +293,7 @@ def witness_kernels(pk, d_assignment, reps):
     return res
 
 
-def run(log_n, reps, n_public, share=0.0, table_rows=256, r1cs_log=None, device_assignment=False):
+def run(log_n, reps, n_public, share=0.0, table_rows=256, r1cs_log=None, device_assignment=False, zk=False):
     L = _lib.load()
     t0 = time.perf_counter()
     imported = {}
@@ -279,8 +312,9 @@ def run(log_n, reps, n_public, share=0.0, table_rows=256, r1cs_log=None, device_
         imported = {"constraints": 1 << r1cs_log, "variables": circuit.num_variables, "chain_terms": len(circuit.term_index),
                     "rows": sum(1 for i in range(n) if any(col[i] for col in circuit.selectors)),
                     "compile_s": time.perf_counter() - t_compile}
-    s = kb._String(n // 2)
+    s = kb._String(n // 2 + (plonk.ZK_PAD // 2 if zk else 0))
     ck = kzg.CommitKey.from_srs(s, n)
+    zk_ck = kzg.CommitKey.from_srs(s, n + plonk.ZK_PAD) if zk else None
     kvk = kzg.VerifyKey.from_srs(s)
     ck.bases()
     torch.cuda.synchronize()
@@ -311,28 +345,10 @@ def run(log_n, reps, n_public, share=0.0, table_rows=256, r1cs_log=None, device_
     proof = plonk.prove(pk, assignment)                                  # the warm-up
     assert proof.to_bytes() == plonk.prove(pk_device, as_ints).to_bytes()
     assert plonk.verify(vk, kvk, public, proof)
-    stages, whole, verify = {name: [] for name in plonk.protocol.STAGES}, [], []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        plonk.prove(pk, assignment)
-        torch.cuda.synchronize()
-        whole.append(time.perf_counter() - t0)
-    for _ in range(reps):
-        timings = {}
-        proof = plonk.prove(pk, assignment, timings)
-        for name in stages:
-            stages[name].append(timings.get(name, 0.0))
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        assert plonk.verify(vk, kvk, public, proof)
-        torch.cuda.synchronize()
-        verify.append(time.perf_counter() - t0)
-    res["stages_ms"] = {name: _median_ms(v) for name, v in stages.items()}
-    res["stages_ms"]["verification"] = _median_ms(verify)
-    res["prove_ms"] = _median_ms(whole)
-    res["prove_rounds_ms"] = [x * 1e3 for x in whole]
-    res["proof_bytes"] = len(proof.to_bytes())
+    res.update(prove_rounds(pk, vk, kvk, public, assignment, reps, plonk.protocol.STAGES))
+    if zk:
+        zk_ck.bases()
+        res["zk"] = zk_rounds(circuit, zk_ck, pk, vk, kvk, public, assignment, reps, plonk.protocol.STAGES)
 
     # (b) the MSM and the transforms alone
     rows = kb._random_rows(1, 4 * n, log_n)
@@ -373,7 +389,7 @@ def run(log_n, reps, n_public, share=0.0, table_rows=256, r1cs_log=None, device_
     res["quotient"] = {"ms": ms, "counted_bytes": 32 * 4 * n * 17, "bytes_per_s": 32 * 4 * n * 17 / (ms * 1e-3)}
     if share > 0:
         del pk, pk_device, wit, wires
-        res["lookup"] = run_lookup(log_n, reps, n_public, share, table_rows, ck, kvk)
+        res["lookup"] = run_lookup(log_n, reps, n_public, share, table_rows, ck, kvk, zk_ck)
     return res
 
 
@@ -388,6 +404,7 @@ def main():
                     help="prove the import of serial_construct(2^LOG_NC, --inputs) instead of the generated chain")
     ap.add_argument("--inputs", type=int, default=None, help="the R1CS's num_inputs (default: min(1023, 2^LOG_NC))")
     ap.add_argument("--device-assignment", action="store_true", help="hand prove the assignment as a CUDA tensor")
+    ap.add_argument("--zk", action="store_true", help="also prove every circuit under a key of setup(zk=True)")
     a = ap.parse_args()
     if a.r1cs is not None:
         if not 1 <= a.r1cs <= 20 or a.lookups:
@@ -402,7 +419,7 @@ def main():
         ap.error("0 <= --lookups <= 1 and 1 <= --table-rows <= 2^log-n")
     torch.cuda.set_device(0)
     out = {"bench": "plonk_prove", "device": torch.cuda.get_device_name(0), "reps": a.reps,
-           "result": run(a.log_n, a.reps, a.public, a.lookups, a.table_rows, a.r1cs, a.device_assignment)}
+           "result": run(a.log_n, a.reps, a.public, a.lookups, a.table_rows, a.r1cs, a.device_assignment, a.zk)}
     print(json.dumps(out))
 
 
