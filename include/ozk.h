@@ -754,6 +754,38 @@ int ozk_fr_rows_blind_dev(void* d_rows, int32_t k, int32_t n, int64_t stride, co
 int ozk_plonk_quotient_split_dev(const void* d_t, int32_t n, void* d_out, int64_t out_stride, const uint8_t* blinders_host128,
                                  int32_t* d_nonzero, void* stream);
 
+/* The field side of the batched PLONK verifier (csrc/plonk_verify.cuh): for K proofs under one
+ * verifying key, what plonk.verify computes in host integers, one proof per lane.  Conventions are those of the PLONK
+ * block above: plain 32-byte elements, canonical outputs.  kind: 0 a vanilla proof (800 bytes, key of 264), 1 a proof
+ * with lookups (1088 bytes, key of 392).  d_proofs holds the K proofs back to back, d_public their public inputs,
+ * K x n_public x 32 bytes (not read, and may be null, when n_public = 0); n is the key's.
+ *   ozk_plonk_verify_challenges_dev  d_out receives one record of 8 (kind 1: 12) scalars per proof:
+ *                                kind 0: beta, gamma, alpha, z, the multi-opening's gamma and point, rho_m, 0;
+ *                                kind 1: beta, gamma, eta, theta, alpha, z, those two, rho_m, 0, 0, 0,
+ *                              the challenges of plonk.challenges / lookup_challenges and kzg.multi_challenges over the
+ *                              MultiOpening verify builds, from SHA-256 on the device (csrc/sha256.cuh); rho_m is
+ *                              half m % 2 of SHA-256("OZK-plonk-rho" | seed_host32 | m / 2 as 8 bytes LE), 1 if zero:
+ *                              transcript.weights.  d_vk_bytes: the key's bytes on the device.  One launch.
+ *   ozk_plonk_verify_scalars_dev  d_flags[m] (int32): bit 0 an opened value is >= r, bit 1 a public input is >= r,
+ *                              bit 2 z^n = 1, bit 3 the identity on the opened values fails (evaluated when the
+ *                              other three are clear).  d_scalars: K x NC scalars of the proofs' commitments in the
+ *                              row order of verify's MultiOpening (NC = 7: a b c t_lo t_mid t_hi Z; kind 1, NC = 9:
+ *                              a b c m t_lo t_mid t_hi Z S), each the weight of kzg._multi_terms times rho_m; then K
+ *                              of W, K of W'; then the NKEY = 8 (12) sums over the batch for the key's commitments
+ *                              and the one for g1.  d_rho: the K weights rho_m.  A flagged proof has zero scalars, a
+ *                              zero weight, adds nothing to the sums, and nothing is inverted for it.  Sums are
+ *                              fixed-shape trees: the output is bitwise reproducible.  Three launches.
+ * 1 <= K <= 2^16, K (n_public + 1) <= 2^24, n a power of two in [2, 2^26], 0 <= n_public <= n; every buffer 16-byte
+ * aligned (d_flags 4); outputs and workspace may overlap neither inputs nor each other (rejected).  Rejections as
+ * above: OZK_E_INVALID before any launch, the shape before the pointers; the size function returns 0 for a bad shape.
+ * Asynchronous on `stream`; nothing is allocated or synchronised. */
+int ozk_plonk_verify_challenges_dev(int32_t kind, const void* d_vk_bytes, int32_t n, int32_t n_public, const void* d_proofs,
+                                    const void* d_public, int32_t K, const uint8_t* seed_host32, void* d_out, void* stream);
+size_t ozk_plonk_verify_scalars_workspace_bytes(int32_t kind, int32_t K);
+int ozk_plonk_verify_scalars_dev(int32_t kind, int32_t n, int32_t n_public, const void* d_proofs, const void* d_public,
+                                 const void* d_challenges, int32_t K, void* d_scalars, void* d_rho, int32_t* d_flags,
+                                 void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- batched MSM over shared bases (msm_multi.hip; no counterpart in the reference, whose verifier runs one
  * variable-base MSM per proof): out_i = sum_{j < n} s_ij P_j for k scalar rows over the SAME n bases, G1 only.
  * A window table of every base is built once (ozk_multi_msm_prepare_dev); a run is table gathers and mixed

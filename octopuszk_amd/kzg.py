@@ -465,9 +465,16 @@ def _pairing_holds(lhs_out, neg_weight_pi, pi_is_inf, vk) -> bool:
     return _vectors.pairs_are_one(torch.cat([wire_out_to_in(lhs_out, G1), neg]), vk.points()[1])
 
 
+def decode_g1(encodings):
+    """n x 32 bytes of compressed G1 encodings on the device (a uint8 CUDA tensor) -> (n wire-in points with Z = 1,
+    n int32 codes, 0 where the point decoded): the strict decoder for the byte formats built on this module.  A point
+    with a nonzero code, like infinity, is written as (0, 1, 0).  Asynchronous on the current stream."""
+    return _codec.decompress_g1(encodings.reshape(-1))
+
+
 def _decoded(encs):
     """the wire-in points of compressed G1 encodings, or None when one does not decode"""
-    pts, codes = _codec.decompress_g1(_wire.dev_bytes(b"".join(encs)))
+    pts, codes = decode_g1(_wire.dev_bytes(b"".join(encs)))
     return None if int(codes.any().item()) else pts
 
 

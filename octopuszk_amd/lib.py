@@ -137,6 +137,9 @@ _SIGS = {
     "ozk_plonk_wires_dev": (ctypes.c_int, [vp, ctypes.c_int64, vp, i32, i32, ctypes.c_int64, vp, ctypes.c_int64, vp, vp]),
     "ozk_fr_rows_blind_dev": (ctypes.c_int, [vp, i32, i32, ctypes.c_int64, vp, vp, vp]),
     "ozk_plonk_quotient_split_dev": (ctypes.c_int, [vp, i32, vp, ctypes.c_int64, vp, vp, vp]),
+    "ozk_plonk_verify_challenges_dev": (ctypes.c_int, [i32, vp, i32, i32, vp, vp, i32, vp, vp, vp]),
+    "ozk_plonk_verify_scalars_workspace_bytes": (sz, [i32, i32]),
+    "ozk_plonk_verify_scalars_dev": (ctypes.c_int, [i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
     "ozk_multi_msm_table_bytes": (sz, [i32, i32]),
     "ozk_multi_msm_prepare_dev": (ctypes.c_int, [vp, i32, i32, vp, sz, vp, sz, vp]),
     "ozk_multi_msm_workspace_bytes": (sz, [i32, i32, i32]),

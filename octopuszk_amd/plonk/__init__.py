@@ -46,14 +46,19 @@ a multiple of Z_H, and the quotient's parts by terms that cancel; verifying key,
     proof = plonk.prove(pk, assignment)              # 13 blinders (18 with lookups) from secrets.randbelow
     assert plonk.verify(vk, kzg_vk, public_inputs, proof)               # vk: byte for byte the one of zk=False
 
-Out of scope: the linearisation polynomial, custom gates, several tables, tables wider than three columns,
+Many proofs of one circuit: K proofs under one key, one pairing product whatever K is.
+
+    assert plonk.verify_all(vk, kzg_vk, public_rows, proofs)            # objects, bytes, or K x 800 bytes on the device
+    verdicts = plonk.verify_each(vk, kzg_vk, public_rows, proofs)       # singles only when the batch check fails
+
+Out of scope: the linearisation polynomial, mixed keys in one batch, custom gates, several tables, tables wider than three columns,
 lookups in an imported R1CS.  There is no CPU path.
 """
 from .circuit import Builder, Circuit, LookupCircuit, R1CSCircuit, from_r1cs
-from .protocol import (LOOKUP_PROOF_BYTES, LOOKUP_STAGES, LOOKUP_VK_BYTES, PROOF_BYTES, LookupProof, LookupProvingKey,
+from .protocol import (BATCH_STAGES, LOOKUP_PROOF_BYTES, LOOKUP_STAGES, LOOKUP_VK_BYTES, PROOF_BYTES, LookupProof, LookupProvingKey,
                        LookupVerifyingKey, Proof, ProvingKey, R1CSProvingKey, VerifyingKey, ZK_BLINDERS, ZK_LOOKUP_BLINDERS,
-                       ZK_PAD, challenges, lookup_challenges, prove, setup, verify)
+                       ZK_PAD, challenges, lookup_challenges, prove, setup, verify, verify_all, verify_each)
 
-__all__ = ["Builder", "Circuit", "LookupCircuit", "LOOKUP_PROOF_BYTES", "LOOKUP_STAGES", "LOOKUP_VK_BYTES", "LookupProof",
+__all__ = ["BATCH_STAGES", "Builder", "Circuit", "LookupCircuit", "LOOKUP_PROOF_BYTES", "LOOKUP_STAGES", "LOOKUP_VK_BYTES", "LookupProof",
            "LookupProvingKey", "LookupVerifyingKey", "PROOF_BYTES", "Proof", "ProvingKey", "R1CSCircuit", "R1CSProvingKey",
-           "VerifyingKey", "ZK_BLINDERS", "ZK_LOOKUP_BLINDERS", "ZK_PAD", "challenges", "from_r1cs", "lookup_challenges", "prove", "setup", "verify"]
+           "VerifyingKey", "ZK_BLINDERS", "ZK_LOOKUP_BLINDERS", "ZK_PAD", "challenges", "from_r1cs", "lookup_challenges", "prove", "setup", "verify", "verify_all", "verify_each"]

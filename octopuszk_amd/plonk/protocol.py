@@ -4,7 +4,9 @@ transform and the three kernels of csrc/plonk.cuh.  A circuit with a lookup tabl
 proof and transcript tags; its field side adds the kernels of csrc/plonk_lookup.cuh.  An imported R1CS (DESIGN.md section
 36) is a vanilla circuit with a key of its own kind, which holds what builds the witness on the device
 (csrc/plonk_r1cs.cuh).  A key of setup(zk=True) makes zero-knowledge proofs: its rows have
-ZK_PAD coefficients more, the prover blinds what it commits to (csrc/plonk_zk.cuh), and the verifier is the same."""
+ZK_PAD coefficients more, the prover blinds what it commits to (csrc/plonk_zk.cuh), and the verifier is the same.
+verify_all and verify_each check K proofs under one key with one pairing product: the
+transcripts and the per-proof arithmetic of verify run on the device (csrc/plonk_verify.cuh, csrc/sha256.cuh)."""
 import secrets
 import time
 
@@ -15,10 +17,10 @@ from .. import kzg as _kzg
 from .. import lib as _lib
 from .. import transcript as _transcript
 from ..fft import FR, FR_MULT_GEN, root_of_unity
-from ..vectors import (fr_fft, fr_perm_product, fr_rows_blind, fr_rows_coset, fr_term_sums, plonk_lookup_counts,
+from ..vectors import (fr_fft, fr_perm_product, fr_rows_blind, fr_rows_coset, fr_term_sums, msm, plonk_lookup_counts,
                        plonk_lookup_index, plonk_lookup_sum, plonk_quotient, plonk_quotient_lookup, plonk_quotient_split,
-                       plonk_wires)
-from ..wire import dev_bytes, host_bytes, ints32, le32, upload
+                       plonk_verify_challenges, plonk_verify_scalars, plonk_wires)
+from ..wire import dev_bytes, host_bytes, ints32, is_inf_out, le32, upload, wire_out_to_in
 from .circuit import K, N_MAX, Circuit, LookupCircuit, R1CSCircuit
 
 PROOF_BYTES = 7 * 32 + 16 * 32 + 64
@@ -732,3 +734,188 @@ def verify(vk, kzg_vk, public_inputs, proof) -> bool:
     except ValueError:
         return False
     return _kzg.verify_multi(kzg_vk, mo)
+
+
+# ---------------------------------------------------------------------------- the batched verifier
+BATCH_K_MAX, BATCH_ROWS_MAX = 1 << 16, 1 << 24          # PLONK_VF_K_MAX, PLONK_VF_ROWS_MAX of csrc/plonk_verify.cuh
+_RHO_TAG = b"OZK-plonk-rho"
+_ROW_ORDER = (0, 1, 2, 4, 5, 6, 3)                      # a proof's commitments in the row order of verify's MultiOpening
+_LK_ROW_ORDER = (0, 1, 2, 3, 6, 7, 8, 4, 5)
+_B_UPLOAD, _B_CHALLENGES, _B_SCALARS, _B_DECODE, _B_MSM, _B_PAIRING = (
+    "upload", "challenges", "scalars", "decode", "two MSMs", "pairing product")
+BATCH_STAGES = (_B_UPLOAD, _B_CHALLENGES, _B_SCALARS, _B_DECODE, _B_MSM, _B_PAIRING)
+_OUT_OF_RANGE = b"\xff" * 32                            # stands for a public input that is no int in [0, 2^256): >= r
+
+
+def _batch_kind(vk):
+    """(kind, proof bytes, row order) of the key's kind, as the library numbers them"""
+    if isinstance(vk, LookupVerifyingKey):
+        return 1, LOOKUP_PROOF_BYTES, _LK_ROW_ORDER
+    if isinstance(vk, VerifyingKey):
+        return 0, PROOF_BYTES, _ROW_ORDER
+    raise TypeError("verify_all takes a VerifyingKey or a LookupVerifyingKey")
+
+
+def _is_device_bytes(t, what):
+    if not isinstance(t, torch.Tensor):
+        return False
+    if t.dtype != torch.uint8 or not t.is_cuda:
+        raise TypeError("%s on the device are a uint8 CUDA tensor" % what)
+    return True
+
+
+def _public_row(row, n_public):
+    row = list(row)
+    if len(row) != n_public:
+        raise ValueError("a row of %d public inputs: the key has n_public = %d" % (len(row), n_public))
+    out = []
+    for x in row:
+        try:
+            out.append(int(x).to_bytes(32, "little"))
+        except (TypeError, ValueError, OverflowError):
+            out.append(_OUT_OF_RANGE)
+    return b"".join(out)
+
+
+def _batch_args(vk, public_inputs, proofs):
+    """(kind, K, the proofs and the public inputs, each as bytes or as a uint8 CUDA tensor): every check that needs no
+    device.  proofs: what _sized_objects returns.  ValueError for a buffer of the wrong size, for public inputs of
+    another number of proofs, for K or K (n_public + 1) above the caps."""
+    kind, proof_len, _ = _batch_kind(vk)
+    if _is_device_bytes(proofs, "proofs"):
+        size = proofs.numel()
+    else:
+        proofs = bytes(proofs) if isinstance(proofs, (bytes, bytearray)) else b"".join(proofs)
+        size = len(proofs)
+    if size % proof_len:
+        raise ValueError("%d bytes of proofs are no whole number of %d-byte proofs" % (size, proof_len))
+    k = size // proof_len
+    if k > BATCH_K_MAX:
+        raise ValueError("K = %d proofs: at most 2^16 in one batch" % k)
+    if k * (vk.n_public + 1) > BATCH_ROWS_MAX:
+        raise ValueError("K (n_public + 1) = %d: at most 2^24 in one batch" % (k * (vk.n_public + 1)))
+    if _is_device_bytes(public_inputs, "public inputs"):
+        have = public_inputs.numel()
+    else:
+        if not isinstance(public_inputs, (bytes, bytearray)):
+            rows = list(public_inputs)
+            if len(rows) != k:
+                raise ValueError("%d rows of public inputs for %d proofs" % (len(rows), k))
+            public_inputs = b"".join(_public_row(row, vk.n_public) for row in rows)
+        public_inputs = bytes(public_inputs)
+        have = len(public_inputs)
+    if have != 32 * vk.n_public * k:
+        raise ValueError("%d proofs under this key take %d bytes of public inputs, not %d" % (k, 32 * vk.n_public * k, have))
+    return kind, k, proofs, public_inputs
+
+
+def _sized_objects(vk, proofs):
+    """a sequence of proofs whose members all have the key's size, else ValueError (before they are joined)"""
+    _, proof_len, _ = _batch_kind(vk)
+    if isinstance(proofs, (bytes, bytearray, torch.Tensor)):
+        return proofs
+    out = []
+    for i, p in enumerate(proofs):
+        b = p.to_bytes() if isinstance(p, (Proof, LookupProof)) else bytes(p)
+        if len(b) != proof_len:
+            raise ValueError("proof %d has %d bytes: a proof under this key has %d" % (i, len(b), proof_len))
+        out.append(b)
+    return out
+
+
+class _Batch:
+    """The K proofs and their public inputs on the device, and what the two kernels and the decoder make of them"""
+
+    def __init__(self, vk, kzg_vk, kind, k, d_proofs, d_public, seed, clock):
+        _, proof_len, order = _batch_kind(vk)
+        nc, nkey = len(order), len(vk.commitments)
+        self.k, self.nc, self.total = k, nc, k * (nc + 2) + nkey + 1
+        d_vk = dev_bytes(vk.to_bytes())
+        clock.lap(_B_UPLOAD)
+        records = plonk_verify_challenges(kind, d_vk, vk.n, vk.n_public, d_proofs, d_public, seed)
+        clock.lap(_B_CHALLENGES)
+        self.scalars, self.rho, flags = plonk_verify_scalars(kind, vk.n, vk.n_public, d_proofs, d_public, records)
+        clock.lap(_B_SCALARS)
+        view = d_proofs.view(k, proof_len)
+        own = view[:, :32 * nc].reshape(k, nc, 32)[:, list(order), :]
+        encodings = torch.cat([own.reshape(-1), view[:, proof_len - 64:proof_len - 32].reshape(-1),
+                               view[:, proof_len - 32:].reshape(-1), d_vk[8:]])
+        points, codes = _kzg.decode_g1(encodings)
+        self.points = torch.cat([points, kzg_vk.points()[0]])
+        per_proof = torch.cat([codes[:k * nc].view(k, nc), codes[k * nc:k * (nc + 2)].view(2, k).t()], dim=1)
+        bad = (flags != 0) | (per_proof != 0).any(dim=1)
+        if bool((codes[k * (nc + 2):] != 0).any().item()):
+            bad = torch.ones_like(bad)                       # the key's own commitments do not decode
+        self.bad = bad.cpu().tolist()
+        clock.lap(_B_DECODE)
+
+    def holds(self, kzg_vk, clock) -> bool:
+        """the pairing product over every proof that is not `bad` (their scalars and weights are zero)"""
+        k, nc = self.k, self.nc
+        lhs, ws1 = msm(self.points, self.scalars, self.total)
+        ps, ws2 = msm(self.points[96 * k * (nc + 1):96 * k * (nc + 2)], self.rho, k)
+        torch.cuda.current_stream().synchronize()
+        clock.lap(_B_MSM)
+        ok = _kzg._pairing_holds(lhs, wire_out_to_in(ps, 1), is_inf_out(ps), kzg_vk)
+        clock.lap(_B_PAIRING)
+        del ws1, ws2
+        return ok
+
+
+def _batch(vk, kzg_vk, kind, k, proofs, public, seed, clock):
+    d_proofs = proofs if isinstance(proofs, torch.Tensor) else dev_bytes(proofs)
+    d_public = None
+    if vk.n_public:
+        d_public = public if isinstance(public, torch.Tensor) else dev_bytes(public)
+    return _Batch(vk, kzg_vk, kind, k, d_proofs.reshape(-1), None if d_public is None else d_public.reshape(-1), seed,
+                  clock)
+
+
+def _batch_seed(seed):
+    return secrets.token_bytes(32) if seed is None else _transcript.seed_bytes(seed)
+
+
+def verify_all(vk, kzg_vk, public_inputs, proofs, seed=None, timings=None) -> bool:
+    """Whether every one of K proofs under ONE verifying key verifies on its public inputs, with
+    one pairing product whatever K is.  proofs: a sequence of Proof / LookupProof objects or of their bytes, or one
+    bytes object or uint8 CUDA tensor of K x 800 (K x 1088 under a LookupVerifyingKey) bytes; public_inputs: K
+    sequences of vk.n_public ints, or K x n_public x 32 bytes as bytes or as a uint8 CUDA tensor.  The transcripts and
+    the per-proof arithmetic of verify run on the device (ozk_plonk_verify_challenges_dev, ozk_plonk_verify_scalars_dev),
+    with weights rho_m in [1, 2^128), the stream transcript.weights(seed, K, b"OZK-plonk-rho") drawn there; then
+        e(sum_m rho_m (sum_i w_mi C_mi + s_m g1 + t_m W_m + x_m W'_m), g2) e(-sum_m rho_m W'_m, tau_g2) = 1
+    as one G1 MSM over every commitment, W and W' of the batch, the key's commitments once and g1, one MSM of the K
+    points W'_m, and one product of two pairings.  True exactly when verify is True for every pair, up to the 2^-128 of
+    the weights; True for an empty batch; False, never an exception, for a malformed proof of the right size.
+    ValueError, before any device call, for a buffer of the wrong size, public inputs for another number of proofs,
+    K > 2^16 or K (n_public + 1) > 2^24.  seed: None draws 32 bytes from the system; a given seed is for tests only.
+    timings: a dict that receives the seconds of every stage of BATCH_STAGES."""
+    clock = _Clock(timings)                  # (the upload stage begins with the host's marshalling)
+    kind, k, proofs, public = _batch_args(vk, public_inputs, _sized_objects(vk, proofs))
+    if k == 0:
+        return True
+    batch = _batch(vk, kzg_vk, kind, k, proofs, public, _batch_seed(seed), clock)
+    if any(batch.bad):
+        return False
+    return batch.holds(kzg_vk, clock)
+
+
+def verify_each(vk, kzg_vk, public_inputs, proofs, seed=None) -> list:
+    """One verdict per proof, arguments as verify_all: the batch check over the proofs that pass the per-proof checks
+    (form, ranges, z outside the domain, the identity); verify one by one only when that batch fails"""
+    kind, k, proofs, public = _batch_args(vk, public_inputs, _sized_objects(vk, proofs))
+    if k == 0:
+        return []
+    seed = _batch_seed(seed)
+    clock = _Clock(None)
+    batch = _batch(vk, kzg_vk, kind, k, proofs, public, seed, clock)
+    good = [not b for b in batch.bad]
+    if not any(good):
+        return good
+    if batch.holds(kzg_vk, clock):       # (a proof that is `bad` has zero scalars and a zero weight: it is not in the sum)
+        return good
+    _, proof_len, _ = _batch_kind(vk)
+    proofs = host_bytes(proofs) if isinstance(proofs, torch.Tensor) else proofs
+    public = host_bytes(public) if isinstance(public, torch.Tensor) else public
+    row = 32 * vk.n_public
+    return [ok and verify(vk, kzg_vk, ints32(public[row * m:row * (m + 1)]), proofs[proof_len * m:proof_len * (m + 1)])
+            for m, ok in enumerate(good)]

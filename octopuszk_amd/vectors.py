@@ -345,3 +345,64 @@ def plonk_quotient_split(t, n, out_stride, blinders, out=None):
     _lib.check(L.ozk_plonk_quotient_split_dev(_ptr(t), n, _ptr(out), out_stride,
                                               _wire.vp(_wire.le32([int(r) % FR for r in blinders])), _ptr(count), _stream()))
     return out, int.from_bytes(_wire.host_bytes(count[:4]), "little", signed=True)
+
+
+PLONK_VERIFY_K_MAX, PLONK_VERIFY_ROWS_MAX = 1 << 16, 1 << 24    # PLONK_VF_K_MAX, PLONK_VF_ROWS_MAX of csrc/plonk_verify.cuh
+_PLONK_VERIFY_SHAPES = ((800, 264, 8, 7, 8), (1088, 392, 12, 9, 12))   # proof, key, record, NC, NKEY of kind 0 and 1
+
+
+def _plonk_verify_buffers(kind, vk_bytes, n_public, proofs, public):
+    proof_len, vk_len = _PLONK_VERIFY_SHAPES[kind][:2]
+    if vk_bytes.numel() != vk_len:
+        raise ValueError("a verifying key of %d bytes, not %d" % (vk_len, vk_bytes.numel()))
+    k = _wire.count(proofs, proof_len, "proofs")
+    have = 0 if public is None else public.numel()
+    if have != 32 * n_public * k:
+        raise ValueError("%d proofs need %d bytes of public inputs, not %d" % (k, 32 * n_public * k, have))
+    return k, proofs.contiguous(), (public.contiguous() if have else None)
+
+
+def plonk_verify_challenges(kind, vk_bytes, n, n_public, proofs, public, seed):
+    """The transcripts of K proofs under one key (ozk_plonk_verify_challenges_dev): kind 0 vanilla, 1 with lookups;
+    vk_bytes the key's bytes, proofs K x 800 (1088) bytes and public K x n_public x 32 bytes on the device (None when
+    n_public = 0); seed: 32 bytes.  Returns [K, 8 (12), 32] bytes on the device: beta, gamma, [eta, theta,] alpha, z,
+    the multi-opening's gamma and point, rho_m, zero padding.  Asynchronous on the current stream."""
+    L = _lib.load()
+    k, proofs, public = _plonk_verify_buffers(kind, vk_bytes, n_public, proofs, public)
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("the seed is 32 bytes, not %d" % len(seed))
+    rec = _PLONK_VERIFY_SHAPES[kind][2]
+    out = torch.empty((k, rec, 32), dtype=torch.uint8, device=proofs.device)
+    _lib.check(L.ozk_plonk_verify_challenges_dev(kind, _ptr(vk_bytes.contiguous()), n, n_public, _ptr(proofs),
+                                                 None if public is None else _ptr(public), k, _wire.vp(seed), _ptr(out),
+                                                 _stream()))
+    return out
+
+
+def plonk_verify_scalars(kind, n, n_public, proofs, public, challenges, workspace=None):
+    """The scalars of the batch check of K proofs from their challenge records (ozk_plonk_verify_scalars_dev):
+    (scalars, K x NC + 2 K + NKEY + 1 elements in the order of the MSM's points; rho, K x 32 bytes; flags, K int32)
+    on the device.  Asynchronous on the current stream over a `workspace` of the caller's; without one, synchronises
+    (the workspace dies here)."""
+    L = _lib.load()
+    proof_len, _, rec, nc, nkey = _PLONK_VERIFY_SHAPES[kind]
+    k = _wire.count(proofs, proof_len, "proofs")
+    have = 0 if public is None else public.numel()
+    if have != 32 * n_public * k or challenges.numel() != 32 * rec * k:
+        raise ValueError("%d proofs need %d bytes of public inputs and %d of challenges" % (k, 32 * n_public * k, 32 * rec * k))
+    proofs, challenges = proofs.contiguous(), challenges.contiguous()
+    public = public.contiguous() if have else None
+    dev = proofs.device
+    scalars = torch.empty(32 * (k * (nc + 2) + nkey + 1), dtype=torch.uint8, device=dev)
+    rho = torch.empty(32 * k, dtype=torch.uint8, device=dev)
+    flags = torch.empty(k, dtype=torch.int32, device=dev)
+    ws = workspace
+    if ws is None:
+        ws = torch.empty(max(int(L.ozk_plonk_verify_scalars_workspace_bytes(kind, k)), 256), dtype=torch.uint8, device=dev)
+    _lib.check(L.ozk_plonk_verify_scalars_dev(kind, n, n_public, _ptr(proofs), None if public is None else _ptr(public),
+                                              _ptr(challenges), k, _ptr(scalars), _ptr(rho), _ptr(flags), _ptr(ws),
+                                              ws.numel(), _stream()))
+    if workspace is None:
+        torch.cuda.current_stream().synchronize()
+    return scalars, rho, flags
